@@ -5,7 +5,7 @@ One "step" = one pass of the hot path over one stack: Frangi (all scales) -> J8 
 extraction -> ZNCC seed scoring/filter/sort -> SMC tracing of the first `--seeds` sorted seeds
 (both directions) -> host replay.  The input stack is resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 without WORLD_SIZE in the environment: this process starts N ranks of itself with
 torch.distributed.run (one per GPU, RCCL) BEFORE anything touches a GPU, waits for them and exits
@@ -19,11 +19,15 @@ global seed order: early DENSITY stops as on one GPU, every rank ends with the s
 `--mode stacks` is the replica mode: every rank owns an independent stack (weak scaling, no data-path
 collective, one final gather of the node graphs).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (the whole particle
+Prints ONE JSON line on rank 0 with `ms_per_step`, `value` (Mvox/s) and `roofline` (the whole particle
 evaluation: ph_predict + ph_sample + ph_sums + ph_update, HIP-event times measured live on the kernels'
-streams), `roofline_sample` / `roofline_sums` (its two halves alone), `roofline_frangi`,
-`full_trace_loop` (all sorted seeds until MAX_TRACE_COUNT, untimed extra) and `cpu_baseline` (oracle C
-restatement, 1 core, bounded sample).
+streams during the timed steps), `roofline_sample` / `roofline_sums` (its two halves alone) and `roofline_frangi`.
+A plain run does nothing else: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the line.
+`--full` adds what takes runs of its own, after the timed steps: `roofline_isolated` (one trace group),
+`roofline_full_occupancy` (the sampling kernel over all traces at once), `full_trace_loop` (all sorted seeds
+until MAX_TRACE_COUNT; these three: --no-extra drops them) and `cpu_baseline` (oracle C restatement, 1 core,
+bounded sample; --cpu-baseline picks its sample, --no-cpu-baseline drops it).
+`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy (float64; see dump_outputs).
 Scheduler options for experiments: PNR_BENCH_OPTS="groups=2,window=1024" (pnr_set_option keys).
 """
 import argparse
@@ -44,7 +48,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=1024, help="cubic stack edge (BASELINE configs[2]: 1024)")
     ap.add_argument("--seeds", type=int, default=2000, help="sorted seeds traced per stack (configs[3]: 2000); 0 = ALL sorted seeds until MAX_TRACE_COUNT traces (the reference's full trace loop)")
@@ -53,12 +57,19 @@ def parse():
     ap.add_argument("--mode", choices=["shard", "stacks"], default="shard", help="N > 1: one stack sharded over the ranks (configs[3]) or one stack per rank")
     ap.add_argument("--one-shot", action="store_true", help="trace every seed to its map-free end + one replay (no early DENSITY stops; 1 GPU)")
     ap.add_argument("--cpu-baseline", choices=["default", "survey", "off"], default="default",
-                    help="oracle on one host core: a 32-plane slab + 10 seeds (~1 min), SURVEY 8(d)'s 256-plane slab + 50 seeds (~10 min), or none")
+                    help="with --full: oracle on one host core: a 32-plane slab + 10 seeds (~1 min), SURVEY 8(d)'s 256-plane slab + 50 seeds (~10 min), or none")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed full-occupancy measurement of the sampling kernel")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the untimed one-group, full-occupancy and full-trace-loop runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed extra measurements and the CPU baseline (off: a plain run only sets up, warms up and times)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MiB in all)")
     ap.add_argument("--driver", choices=["phased", "persistent"], default="phased",
                     help="SMC scheduler (pnr_set_smc_driver): one launch per phase (default) or one persistent work-group per trace")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def launch_ranks(a):
@@ -170,9 +181,30 @@ def stash_row_floats(np_):
     return 64 * (n // 64) + (((n % 64) + 15) // 16) * 16
 
 
+DUMP_LIMIT = 64 << 20  # bytes of all .npy payloads of --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as float64 (exact for the f32 / i32 fields it holds) in path/<name>.npy.  Past DUMP_LIMIT in all,
+    every array keeps the same fixed, seeded sample of its rows, and the kept row numbers go to path/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    big = [k for k, v in arrays.items() if v.ndim and len(v) > 1024]  # (the small ones are always written whole)
+    total = sum(v.nbytes for v in arrays.values())
+    rest = total - sum(arrays[k].nbytes for k in big)
+    frac = 1.0 if total <= DUMP_LIMIT else 0.99 * (DUMP_LIMIT - rest) / sum(arrays[k].nbytes + 8.0 * len(arrays[k]) for k in big)
+    for k, v in arrays.items():
+        if frac < 1.0 and k in big:
+            rows = np.sort(np.random.default_rng(12345).choice(len(v), max(1, int(len(v) * frac)), replace=False))
+            v = v[rows]
+            np.save(os.path.join(path, k + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     a = parse()
-    if a.no_cpu_baseline:
+    if a.no_cpu_baseline or not a.full:
         a.cpu_baseline = "off"
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))  # before torch / HIP are even imported
@@ -252,11 +284,13 @@ def main():
             exchange = multigpu.make_exchange(dist, world, coll_dev, staged=(backend != "nccl" and want == "rccl"))
             exchange_kind = "RCCL all_gather_into_tensor" if backend == "nccl" else (backend + (" all_gather_into_tensor, pinned staging (the RCCL exchange's shape)" if want == "rccl" else ""))
 
+    last = {}  # what the step computed, for --dump-outputs (references only: converted after the timed region)
+
     def step():
         st = {}
         t0 = time.perf_counter()
         if shard:  # one stack: z-slabs of Frangi + seeds per rank, 2-float all-reduce, scored seeds all-gathered
-            mine, _, _ = multigpu.frangi_seeds_sharded(ctx, img.data_ptr(), (S, S, S), dist, rank, world, device=coll_dev)
+            mine, jmin, jmax = multigpu.frangi_seeds_sharded(ctx, img.data_ptr(), (S, S, S), dist, rank, world, device=coll_dev)
             t1 = time.perf_counter()
             n_init = len(mine)
             mine = ctx.score_filter(mine)  # znccBBB of this slab's seeds on the whole stack, threshold
@@ -267,7 +301,7 @@ def main():
             t3 = time.perf_counter()
             nodes, links, ntr, iters = ctx.trace_replay_sharded(s, rank, world, exchange)
         else:
-            ctx.frangi()
+            jmin, jmax = ctx.frangi()
             t1 = time.perf_counter()
             s0 = ctx.extract_seeds()
             n_init = len(s0)
@@ -289,6 +323,7 @@ def main():
         else:
             st.update(frangi_ms=1e3 * (t1 - t0), seeds_ms=1e3 * (t2 - t1), score_ms=1e3 * (t3 - t2), trace_replay_gather_ms=1e3 * (t5 - t3))
         st.update(n_seeds_init=n_init, n_seeds=len(s), iters=iters, nodes=len(nodes) - 1, traces_used=int(ntr))
+        last.update(jminmax=(jmin, jmax), seeds=s, nodes=nodes, links=links, traces_used=ntr)
         return st
 
     def barrier():
@@ -317,6 +352,16 @@ def main():
     else:
         iters_all = st["iters"]
     st["iters_all"] = iters_all
+
+    if rank == 0 and a.dump_outputs:
+        # the node graph with the sorted seeds it was traced from (the same on every rank), Frangi's global (Jmin, Jmax), traces used
+        dump_outputs(a.dump_outputs, {
+            "nodes": np.stack([last["nodes"][k] for k in pnr_amd.lib.NODE_DT.names], 1),  # x y z vx vy vz corr sig type
+            "links": np.asarray(last["links"]).reshape(-1, 2),
+            "seeds": np.stack([last["seeds"][k] for k in pnr_amd.lib.SEED_DT.names], 1),  # x y z vx vy vz score corr
+            "jminmax": np.asarray(last["jminmax"]),
+            "traces_used": np.asarray([last["traces_used"]]),
+        })
 
     if rank == 0:
         units = nvox * (world if (world > 1 and a.mode == "stacks") else 1)
@@ -465,7 +510,7 @@ def main():
             "smc_launches_per_step": smc_n / a.steps,
             "Mvox_per_s_frangi": (nvox / (fr_ms * 1e-3) / 1e6) if (fr_vox and fr_ms > 0) else None,
         }
-        if world == 1 and not shard and not a.one_shot and not a.no_extra:
+        if a.full and world == 1 and not shard and not a.one_shot and not a.no_extra:
             s_sorted = ctx.score_filter_sort(ctx.extract_seeds())
             s_all = s_sorted[:a.seeds] if a.seeds > 0 else s_sorted
             if overlapped:

@@ -2,7 +2,9 @@
 # then copy gpurun_out/fin_* / prof_fin* / traffic / frangi_fin / gaps_fin into profiles/ (profiles/README.md says which file is which)
 set -x
 cd $GRAFT_REPO_ROOT
-for i in 1 2 3; do python bench.py > gpurun_out/fin_bench_$i.json 2> gpurun_out/fin_bench_$i.err || exit 1; done
+# three full result lines of the default workload (--full: roofline_isolated, full_trace_loop, cpu_baseline) into $FIN_OUT
+FIN_OUT=${FIN_OUT:-bench_out}; mkdir -p "$FIN_OUT"
+for i in 1 2 3; do python bench.py --full > "$FIN_OUT/fin_bench_$i.json" 2> "$FIN_OUT/fin_bench_$i.err" || exit 1; done
 PNR_BENCH_OPTS=groups=1 bash scripts/prof_traffic.sh > gpurun_out/fin_traffic.log 2>&1 || exit 1
 bash scripts/profile_bench.sh fin2 --steps 2 --no-cpu-baseline --no-extra > gpurun_out/fin_prof2.log 2>&1 || exit 1
 PNR_BENCH_OPTS=groups=1 bash scripts/profile_bench.sh fin1 --steps 2 --no-cpu-baseline --no-extra > gpurun_out/fin_prof1.log 2>&1 || exit 1

@@ -85,5 +85,35 @@ def main():
     print("eigen_kat", len(A))
 
 
+def ref_cases():
+    """ref_cases.npz: the reference's outputs on the inputs of test_oracle_golden.py's reference tests (ragged extents, random seed
+    layers, erosion + u8 Gaussian, 2-D Frangi), one `<case>__<name>` entry per array: the tests compare the oracle with them where
+    oracle/_ref cannot be built, and with the reference live as well where it can"""
+    import test_oracle_golden as t  # the tests' case lists and input generators
+    R = orc.load_ref()
+    L = orc.load_oracle()
+    assert R is not None, "oracle/_ref/libpnr_ref.so missing (needs the reference sources)"
+    out = {}
+
+    def put(key, d):
+        out.update({key + "__" + k: np.asarray(v) for k, v in d.items()})
+
+    for shape, sigs, zdist, tol in t.RAGGED:
+        w, h, l = shape
+        img = synth.synth(w, h, l, seed=3)
+        a = orc.frangi3d(L, img, sigs, zdist)
+        put("ragged_%dx%dx%d" % shape, t.ragged_reference(R, img, sigs, zdist, tol, orc.j8(L, a[0], a[1], a[2])))
+    put("layers", t.random_layers_reference(R))
+    for shape, rad in t.ERODE:
+        put("erode_%dx%dx%d_r%d" % (*shape, rad), t.erode_reference(R, t.erode_input(shape), rad))
+    for shape, sigs in t.F2D:
+        put("f2d_%dx%d_n%d" % (shape[1], shape[2], len(sigs)), t.frangi2d_reference(R, t.frangi2d_input(shape), sigs))
+    np.savez_compressed(os.path.join(HERE, "ref_cases.npz"), **out)
+    print("ref_cases", len(out), "arrays", os.path.getsize(os.path.join(HERE, "ref_cases.npz")) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    main()
+    # python tests/golden/make_golden.py [ref_cases]: every fixture, or ref_cases.npz alone
+    if sys.argv[1:] != ["ref_cases"]:
+        main()
+    ref_cases()

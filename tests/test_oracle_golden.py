@@ -1,13 +1,26 @@
 """CPU: pin oracle/pnr_oracle.c against the golden vectors produced by the reference's own
-frangi.cpp / seed.cpp (tests/golden/make_golden.py) and, when oracle/_ref is built, against
-the reference live on fresh inputs.  Bit-exact: the restatement keeps the reference's
-operation order and precision."""
+frangi.cpp / seed.cpp (tests/golden/make_golden.py) and, on further inputs, against the
+reference's outputs recorded in tests/golden/ref_cases.npz -- and live as well where oracle/_ref
+is built.  Bit-exact: the restatement keeps the reference's operation order and precision."""
 import ctypes as C
 import os
 import numpy as np
 import pytest
 import orc
 import synth
+
+REF_CASES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cases.npz")
+
+
+def references(ref, key, live):
+    """the reference's outputs for case `key`: as recorded in tests/golden/ref_cases.npz (make_golden.py ref_cases), and computed
+    live by `live(ref)` where oracle/_ref is built"""
+    with np.load(REF_CASES) as z:
+        out = [{k.split("__", 1)[1]: z[k] for k in z.files if k.startswith(key + "__")}]
+    assert out[0], f"{key}: not in {REF_CASES}"
+    if ref is not None:
+        out.append(live(ref))
+    return out
 
 
 def test_gaussian_matches_reference(oracle, golden):
@@ -57,38 +70,60 @@ def test_seeds_match_reference(oracle, golden):
     assert np.array_equal(s, golden["seeds"])
 
 
-@pytest.mark.parametrize("shape,sigs,zdist,tol", [((33, 21, 9), [2.0], 2.0, 5.0), ((20, 50, 14), [2.0, 3.0], 1.0, 2.0),
-                                                     ((9, 9, 5), [2.0], 2.0, 5.0)])
+RAGGED = [((33, 21, 9), [2.0], 2.0, 5.0), ((20, 50, 14), [2.0, 3.0], 1.0, 2.0), ((9, 9, 5), [2.0], 2.0, 5.0)]
+
+
+def ragged_reference(R, img, sigs, zdist, tol, J8):
+    img0 = img.copy()
+    J, jmin, jmax, Vx, Vy, Vz = orc.frangi3d(R, img, sigs, zdist, prefix="ref")
+    return dict(img=img0, J=J, Jmin=np.float32(jmin), Jmax=np.float32(jmax), Vx=Vx, Vy=Vy, Vz=Vz,
+                seeds=orc.extract_seeds(R, tol, J8, Vx, Vy, Vz, prefix="ref"))
+
+
+@pytest.mark.parametrize("shape,sigs,zdist,tol", RAGGED)
 def test_live_reference_ragged(oracle, ref, shape, sigs, zdist, tol):
-    """ragged / smaller-than-kernel extents, live against the reference build"""
-    if ref is None:
-        pytest.skip("oracle/_ref not built on this box")
+    """ragged / smaller-than-kernel extents against the reference (recorded, and live where built)"""
     w, h, l = shape
     img = synth.synth(w, h, l, seed=3)
     a = orc.frangi3d(oracle, img, sigs, zdist)
-    b = orc.frangi3d(ref, img, sigs, zdist, prefix="ref")
-    assert np.array_equal(a[0], b[0]) and a[1:3] == b[1:3]
-    for i in (3, 4, 5):
-        assert np.array_equal(a[i], b[i])
     J8 = orc.j8(oracle, a[0], a[1], a[2])
     sa = orc.extract_seeds(oracle, tol, J8, a[3], a[4], a[5])
-    sb = orc.extract_seeds(ref, tol, J8, b[3], b[4], b[5], prefix="ref")
-    assert np.array_equal(sa, sb)
+    for b in references(ref, "ragged_%dx%dx%d" % shape, lambda R: ragged_reference(R, img, sigs, zdist, tol, J8)):
+        assert np.array_equal(b["img"], img)
+        assert np.array_equal(a[0], b["J"]) and a[1:3] == (float(b["Jmin"]), float(b["Jmax"]))
+        for i, k in ((3, "Vx"), (4, "Vy"), (5, "Vz")):
+            assert np.array_equal(a[i], b[k])
+        assert np.array_equal(sa, b["seeds"])
 
 
-def test_seeds_random_layers_live(oracle, ref):
-    """MaximumFinder on random u8 layers: plateaus, ties and tolerance chains."""
-    if ref is None:
-        pytest.skip("oracle/_ref not built on this box")
+TOLS = (0.0, 1.0, 5.0, 40.0)
+
+
+def random_layers():
+    """(tol, J8, [Vx, Vy, Vz]) per tolerance: random u8 layers with plateaus, ties, an empty layer and a low-range layer"""
     rs = np.random.RandomState(11)
-    for tol in (0.0, 1.0, 5.0, 40.0):
+    for tol in TOLS:
         J8 = (rs.randint(0, 6, (4, 31, 37)) * rs.randint(0, 50, (4, 31, 37))).astype(np.uint8)
         J8[1] = 0  # empty layer: globalMax == globalMin
         J8[2] = np.clip(J8[2], 0, 3)
         V = [rs.randint(0, 256, J8.shape).astype(np.uint8) for _ in range(3)]
-        sa = orc.extract_seeds(oracle, tol, J8, *V)
-        sb = orc.extract_seeds(ref, tol, J8, *V, prefix="ref")
-        assert np.array_equal(sa, sb, equal_nan=True), tol
+        yield tol, J8, V
+
+
+def random_layers_reference(R):
+    out = {}
+    for i, (tol, J8, V) in enumerate(random_layers()):
+        out.update({f"J8_{i}": J8, f"Vx_{i}": V[0], f"Vy_{i}": V[1], f"Vz_{i}": V[2], f"seeds_{i}": orc.extract_seeds(R, tol, J8, *V, prefix="ref")})
+    return out
+
+
+def test_seeds_random_layers_live(oracle, ref):
+    """MaximumFinder on random u8 layers: plateaus, ties and tolerance chains."""
+    for b in references(ref, "layers", random_layers_reference):
+        for i, (tol, J8, V) in enumerate(random_layers()):
+            assert np.array_equal(b[f"J8_{i}"], J8) and all(np.array_equal(b[f"V{c}_{i}"], v) for c, v in zip("xyz", V))
+            sa = orc.extract_seeds(oracle, tol, J8, *V)
+            assert np.array_equal(sa, b[f"seeds_{i}"], equal_nan=True), tol
 
 
 def test_glibc_rand_stream(oracle):
@@ -117,22 +152,38 @@ def test_tracker_table_shapes(oracle):
 
 
 # ---- soma path: erosion and the u8 Gaussian are pinned on the reference's own frangi.cpp ----
-@pytest.mark.parametrize("shape,rad", [((24, 40, 48), 3), ((5, 7, 9), 4), ((3, 33, 20), 2), ((1, 16, 16), 1)])
-def test_imerode_imgaussian_u8_vs_reference(oracle, ref, shape, rad):
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+ERODE = [((24, 40, 48), 3), ((5, 7, 9), 4), ((3, 33, 20), 2), ((1, 16, 16), 1)]
+
+
+def erode_input(shape):
     rng = np.random.default_rng(5)
     l, h, w = shape
     img = rng.integers(0, 256, shape, dtype=np.uint8)
     img[:, h // 4: h // 2, w // 4: w // 2] = 200  # a plateau survives the erosion
-    Eo, Er = np.zeros_like(img), np.zeros_like(img)
+    return img
+
+
+def erode_reference(R, img, rad):
+    l, h, w = img.shape
+    E = np.zeros_like(img)
+    R.ref_imerode_xy(img.copy(), w, h, l, float(rad), E)
+    G = E.copy()
+    R.ref_imgaussian_u8_xy(G, w, h, l, float(rad))
+    return dict(img=img.copy(), eroded=E, blurred=G)
+
+
+@pytest.mark.parametrize("shape,rad", ERODE)
+def test_imerode_imgaussian_u8_vs_reference(oracle, ref, shape, rad):
+    l, h, w = shape
+    img = erode_input(shape)
+    Eo = np.zeros_like(img)
     oracle.orc_imerode_xy(img, w, h, l, float(rad), Eo)
-    ref.ref_imerode_xy(img.copy(), w, h, l, float(rad), Er)
-    assert np.array_equal(Eo, Er)
-    Go, Gr = Eo.copy(), Er.copy()
+    Go = Eo.copy()
     oracle.orc_imgaussian_u8_xy(Go, w, h, l, float(rad))
-    ref.ref_imgaussian_u8_xy(Gr, w, h, l, float(rad))
-    assert np.array_equal(Go, Gr) and Go.max() > 0
+    for b in references(ref, "erode_%dx%dx%d_r%d" % (*shape, rad), lambda R: erode_reference(R, img, rad)):
+        assert np.array_equal(b["img"], img)
+        assert np.array_equal(Eo, b["eroded"])
+        assert np.array_equal(Go, b["blurred"]) and Go.max() > 0
 
 
 def test_maxentropy_and_conn3d_properties(oracle):
@@ -168,24 +219,41 @@ def test_maxentropy_and_conn3d_properties(oracle):
 
 
 # ---- 2-D mode: Frangi::frangi2d / hessian2d pinned on the reference's own frangi.cpp ----
-@pytest.mark.parametrize("shape,sigs", [((1, 40, 48), [2.0]), ((1, 33, 21), [2.0, 3.0]), ((1, 64, 64), [1.0, 2.0, 4.0]), ((1, 7, 9), [2.0])])
-def test_frangi2d_vs_reference(oracle, ref, shape, sigs):
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+F2D = [((1, 40, 48), [2.0]), ((1, 33, 21), [2.0, 3.0]), ((1, 64, 64), [1.0, 2.0, 4.0]), ((1, 7, 9), [2.0])]
+
+
+def frangi2d_input(shape):
     _, h, w = shape
-    img = synth.synth(w, h, 9, seed=4)[4:5].copy() if min(h, w) > 16 else np.random.default_rng(3).integers(0, 255, shape, dtype=np.uint8)
-    for sg in sigs:
-        a = [np.zeros(shape, np.float32) for _ in range(3)]
-        b = [np.zeros(shape, np.float32) for _ in range(3)]
-        oracle.orc_hessian2d(img, w, h, sg, *a)
-        ref.ref_hessian2d(img.copy(), w, h, sg, *b)
-        assert all(np.array_equal(x, y) for x, y in zip(a, b))
-    Jo, jmo, jMo, Vxo, Vyo, Vzo = orc.frangi2d(oracle, img, sigs)
-    Jr, jmr, jMr, Vxr, Vyr, Vzr = orc.frangi2d(ref, img.copy(), sigs, prefix="ref")
-    assert np.array_equal(Jo, Jr) and jmo == jmr and jMo == jMr
-    assert np.array_equal(Vxo, Vxr) and np.array_equal(Vyo, Vyr) and np.array_equal(Vzo, Vzr) and not Vzo.any()
-    if min(h, w) > 16:
-        assert jMo > 0.05
+    return synth.synth(w, h, 9, seed=4)[4:5].copy() if min(h, w) > 16 else np.random.default_rng(3).integers(0, 255, shape, dtype=np.uint8)
+
+
+def frangi2d_reference(R, img, sigs):
+    _, h, w = img.shape
+    out = dict(img=img.copy())
+    for i, sg in enumerate(sigs):
+        D = [np.zeros(img.shape, np.float32) for _ in range(3)]
+        R.ref_hessian2d(img.copy(), w, h, sg, *D)
+        out.update({f"D{k}_{i}": d for k, d in enumerate(D)})
+    J, jmin, jmax, Vx, Vy, Vz = orc.frangi2d(R, img.copy(), sigs, prefix="ref")
+    out.update(J=J, Jmin=np.float32(jmin), Jmax=np.float32(jmax), Vx=Vx, Vy=Vy, Vz=Vz)
+    return out
+
+
+@pytest.mark.parametrize("shape,sigs", F2D)
+def test_frangi2d_vs_reference(oracle, ref, shape, sigs):
+    _, h, w = shape
+    img = frangi2d_input(shape)
+    for b in references(ref, "f2d_%dx%d_n%d" % (h, w, len(sigs)), lambda R: frangi2d_reference(R, img, sigs)):
+        assert np.array_equal(b["img"], img)
+        for i, sg in enumerate(sigs):
+            a = [np.zeros(shape, np.float32) for _ in range(3)]
+            oracle.orc_hessian2d(img, w, h, sg, *a)
+            assert all(np.array_equal(a[k], b[f"D{k}_{i}"]) for k in range(3))
+        Jo, jmo, jMo, Vxo, Vyo, Vzo = orc.frangi2d(oracle, img, sigs)
+        assert np.array_equal(Jo, b["J"]) and jmo == float(b["Jmin"]) and jMo == float(b["Jmax"])
+        assert np.array_equal(Vxo, b["Vx"]) and np.array_equal(Vyo, b["Vy"]) and np.array_equal(Vzo, b["Vz"]) and not Vzo.any()
+        if min(h, w) > 16:
+            assert jMo > 0.05
 
 
 # ---- committed fixtures of the reference's 2-D Frangi and soma filters (tests/golden/make_golden.py) ----
