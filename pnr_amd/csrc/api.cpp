@@ -73,8 +73,10 @@ static int load_tables(pnr_ctx *c, bool is2d)
     hipFree(c->d_p); hipFree(c->d_u); hipFree(c->d_w0); hipFree(c->d_w0cws); hipFree(c->d_v); hipFree(c->d_w);
     hipFree(c->d_wcws); hipFree(c->d_tmpl); hipFree(c->d_corrc); hipFree(c->d_sig); hipFree(c->d_M); hipFree(c->d_moff);
     hipFree(c->d_rng); hipFree(c->d_grid); hipFree(c->d_axes); hipFree(c->d_axes_off); hipFree(c->d_wd);
+    hipFree(c->d_share); hipFree(c->d_grows);
     c->d_p = c->d_u = c->d_w0 = c->d_w0cws = c->d_v = c->d_w = c->d_wcws = c->d_tmpl = c->d_corrc = c->d_sig = nullptr;
     c->d_M = c->d_moff = nullptr; c->d_rng = nullptr; c->d_grid = nullptr; c->d_axes = nullptr; c->d_axes_off = nullptr; c->d_wd = nullptr;
+    c->d_share = nullptr; c->d_grows = nullptr;
     pnr::build_tables(c->prm, is2d, c->tab);
     const pnr::Tables &t = c->tab;
     std::vector<float> sig(c->prm.sig, c->prm.sig + c->prm.nsig);
@@ -95,6 +97,8 @@ static int load_tables(pnr_ctx *c, bool is2d)
     if (!rc) rc = upload(&c->d_axes, t.axes, c->stream);
     if (!rc) rc = upload(&c->d_axes_off, t.axes_off, c->stream);
     if (!rc) rc = upload(&c->d_wd, t.wd, c->stream);
+    if (!rc) rc = upload(&c->d_share, t.share_tab, c->stream);
+    if (!rc) rc = upload(&c->d_grows, t.grows, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = PNR_E_HIP;
     return rc;
 }
@@ -207,6 +211,7 @@ void pnr_destroy(pnr_ctx *c)
     hipFree(c->d_p); hipFree(c->d_u); hipFree(c->d_w0); hipFree(c->d_w0cws); hipFree(c->d_v); hipFree(c->d_w);
     hipFree(c->d_wcws); hipFree(c->d_tmpl); hipFree(c->d_corrc); hipFree(c->d_sig); hipFree(c->d_M); hipFree(c->d_moff);
     hipFree(c->d_rng); hipFree(c->d_grid); hipFree(c->d_axes); hipFree(c->d_axes_off); hipFree(c->d_wd);
+    hipFree(c->d_share); hipFree(c->d_grows);
     for (auto &kv : c->scratch) hipFree(kv.second.p);
     c->resolve_timers();
     for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
@@ -855,6 +860,7 @@ const OptEntry OPTS[] = {
     {"sums_deep", &pnr::Options::sums_deep, nullptr, -1, 1},      {"sums_deep_max", &pnr::Options::sums_deep_max, nullptr, 0, 1 << 20},
     {"lag", &pnr::Options::lag, nullptr, -1, 1023},               {"profile_every", &pnr::Options::profile_every, nullptr, 1, 1024},
     {"overfill", &pnr::Options::overfill, nullptr, 0, 1},        {"concentrate", &pnr::Options::concentrate, nullptr, 0, 100},
+    {"share_scales", &pnr::Options::share_scales, nullptr, 0, 1}, {"share_min", &pnr::Options::share_min, nullptr, 0, 1 << 20},
 };
 } // namespace
 

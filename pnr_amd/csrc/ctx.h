@@ -49,10 +49,18 @@ struct Tables {
     std::vector<float> wd;                                // sum(M): wgt - avg
     float ext_v = 0, ext_uw = 0;                          // largest |vv| and |uu|,|ww|
     std::vector<float> ext_vs, ext_uws;                   // the same per sigma
+    // scales whose template grid nests in another's (find_scale_pairs): a GUEST's samples are a subsequence, in order, of its
+    // HOST's, so the phased driver samples the host only and reads the guest's samples from the host's stash
+    struct ScalePair { int guest, host, v0, nv, u0, nu, w0, nw; }; // runs [x0, x0 + nx) of the host's axes that are the guest's
+    std::vector<ScalePair> pairs;
+    std::vector<int> share_tab;                           // device form (TabX::share): [0, 8) host of scale s or -1; [8, 16) s's first entry in grows
+    std::vector<int> grows;                               // per guest: the host's stash row of each of its samples, in its own order
+    int guest_mask = 0;                                   // bit s: scale s is a guest
     std::vector<uint32_t> rng;                            // np + 1 glibc rand() draws
     std::vector<std::vector<float>> gxy, gz;              // Gaussian taps per sigma
 };
 void build_tables(const pnr_params &p, bool is2d, Tables &t);
+void find_scale_pairs(Tables &t); // (part of build_tables; t.pairs and the device tables from t.grid / t.axes / t.wd)
 void glibc_rand_stream(uint32_t seed, int n, uint32_t *out);
 int gaussian_taps(float sig, std::vector<float> &g); // returns radius L
 
@@ -85,6 +93,10 @@ struct Options {
     int tentative = 1;          // streaming scheduler: pause traces that a tentative replay of everything recorded so far cuts (stream_sched.h)
     int gauss_march = 1;        // the fused x-y Gaussian marches down strips of a slice (gauss_xy_u8_m; 0: one 64 x 64 tile per work-group)
     int cube_copy = 1;          // phased driver: the cube of a trace is fetched from the image once per step (ph_cube) and copied by its sampling work-groups (0: each stages it itself)
+    int share_scales = 1;       // phased driver: a scale whose template grid nests in another's is not sampled; its sums read the host's
+                                // stash (tables.cpp find_scale_pairs; 0: every scale samples on its own -- the same results)
+    int share_min = 0;          // ... in steps of at least this many traces (a guest's wave is not the longest of its trace, so small
+                                // steps lose nothing by it: 0, not tuned on a workload of its own)
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host
@@ -134,6 +146,7 @@ struct pnr_ctx {
           *d_wcws = nullptr, *d_tmpl = nullptr, *d_corrc = nullptr, *d_sig = nullptr;
     int *d_M = nullptr, *d_moff = nullptr, *d_grid = nullptr, *d_axes_off = nullptr;
     float *d_axes = nullptr, *d_wd = nullptr;
+    int *d_share = nullptr, *d_grows = nullptr; // nested scales (Tables::share_tab, grows)
     uint32_t *d_rng = nullptr;
 
     // SMC pass-1 sample stash (HBM scratch, sized at the first trace batch)

@@ -800,6 +800,80 @@ __device__ __forceinline__ float zncc_from_stash_deep(const float *__restrict__ 
     return (prod > FLT_MIN) ? corra / sqrtf(prod) : 0.f; // tracker.cpp:1955
 }
 
+// ---- a guest scale's sums from its host's stash (tables.cpp find_scale_pairs) ------------------------------------------------
+// The guest's samples are the host's at the rows `rows[m]` (m in the guest's own sample order; the rows ascend), so the guest is
+// not sampled and its wave reads them from the host's stash region: zncc_from_stash with a wave-uniform row index per value (scalar
+// loads), the same values in the same order.  16 values in flight (the row indices of the next chunk and the weights of this one
+// are scalar registers); a guest's chain is the shortest of its trace, not the one the launch waits for.
+template <int STRIDE = 64, int CH = 16>
+__device__ __forceinline__ float zncc_from_stash_rows(const float *__restrict__ stash_lane, const int *__restrict__ rows, int M, const float *__restrict__ wd,
+                                                      float corrc)
+{
+    const int nfull = M / CH, tail = M - nfull * CH; // wave-uniform
+    float cur[CH], nxt[CH];
+    float ag = 0.f;
+    if (nfull > 0) {
+#pragma unroll
+        for (int j = 0; j < CH; j++) cur[j] = STASH_LD(&stash_lane[(i64)rows[j] * STRIDE]);
+    }
+    for (int c = 0; c < nfull; c++) {
+        if (c + 1 < nfull) {
+            const int *rn = rows + (c + 1) * CH;
+#pragma unroll
+            for (int j = 0; j < CH; j++) nxt[j] = STASH_LD(&stash_lane[(i64)rn[j] * STRIDE]);
+        }
+#pragma unroll
+        for (int j = 0; j < CH; j++) ag += cur[j];
+#pragma unroll
+        for (int j = 0; j < CH; j++) cur[j] = nxt[j];
+    }
+    {
+        const int *rt = rows + nfull * CH;
+#pragma unroll
+        for (int j = 0; j < CH; j++) cur[j] = (j < tail) ? STASH_LD(&stash_lane[(i64)rt[j] * STRIDE]) : 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; j++)
+            if (j < tail) ag += cur[j];
+    }
+    ag /= (float)M;
+    float corra = 0.f, corrb = 0.f;
+    if (nfull > 0) {
+#pragma unroll
+        for (int j = 0; j < CH; j++) cur[j] = STASH_LD(&stash_lane[(i64)rows[j] * STRIDE]);
+    }
+    for (int c = 0; c < nfull; c++) {
+        if (c + 1 < nfull) {
+            const int *rn = rows + (c + 1) * CH;
+#pragma unroll
+            for (int j = 0; j < CH; j++) nxt[j] = STASH_LD(&stash_lane[(i64)rn[j] * STRIDE]);
+        }
+        const float *wk = wd + c * CH; // wave-uniform address: scalar loads
+#pragma unroll
+        for (int j = 0; j < CH; j++) {
+            const float di = cur[j] - ag;
+            corra += di * wk[j];
+            corrb = (float)__builtin_fma((double)di, (double)di, (double)corrb); // (see zncc_from_stash)
+        }
+#pragma unroll
+        for (int j = 0; j < CH; j++) cur[j] = nxt[j];
+    }
+    {
+        const int *rt = rows + nfull * CH;
+        const float *wk = wd + nfull * CH;
+#pragma unroll
+        for (int j = 0; j < CH; j++) cur[j] = (j < tail) ? STASH_LD(&stash_lane[(i64)rt[j] * STRIDE]) : 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; j++)
+            if (j < tail) {
+                const float di = cur[j] - ag;
+                corra += di * wk[j];
+                corrb = (float)__builtin_fma((double)di, (double)di, (double)corrb);
+            }
+    }
+    const float prod = corrb * corrc;
+    return (prod > FLT_MIN) ? corra / sqrtf(prod) : 0.f; // tracker.cpp:1955
+}
+
 struct TabX { // extra template tables for the box kernel
     const Grid *grid;   // per sigma
     const float *axes;  // per sigma: vv[nv] | uu[nu] | ww[nw], at axes_off[s]
@@ -811,6 +885,10 @@ struct TabX { // extra template tables for the box kernel
     int *slot_busy;      // nslots flags, 0 = free
     int nslots;
     long long slot_floats, wave_floats;
+    // nested scales (tables.cpp find_scale_pairs; the phased driver only)
+    const int *share;       // [0, 8) the host of scale s or -1; [8, 16) the first of s's entries in grows
+    const int *grows;       // per guest: the host's stash row of each of its samples
+    int guest_mask;         // bit s: scale s is a guest
 };
 
 

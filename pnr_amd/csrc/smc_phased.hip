@@ -441,7 +441,7 @@ __device__ unsigned long long g_ph_stamps[8];
 #endif
 
 template <int CS, bool IS2D, bool GCUBE>
-__global__ __launch_bounds__(PH_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void ph_sample(Vol V, Tab T, TabX X, PhState P, int np, int ni, int it_arg, int lp, int nslots)
+__global__ __launch_bounds__(PH_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void ph_sample(Vol V, Tab T, TabX X, PhState P, int np, int ni, int it_arg, int lp, int nslots, int share)
 {
     extern __shared__ unsigned char cube[];
     // part-major: the first nslots work-groups are one per trace, the later ones join whatever is left of their trace
@@ -497,8 +497,11 @@ __global__ __launch_bounds__(PH_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5
     // `parts` times (sample_slice_packed) and its item is ROWS rounds of `parts` rows each
     constexpr int ROWS = 5;
     const int parts = rem > 0 ? 64 / rem : 1;
+    // share (decided per step, the same argument as ph_sums'): guest scales are not sampled, their sums come from the host's stash
+    const int skip = share ? X.guest_mask : 0;
     int nchsum = 0, npksum = 0;
     for (int s = 0; s < S; s++) {
+        if (skip >> s & 1) continue;
         const int nv_s = __builtin_amdgcn_readfirstlane(X.grid[s].nv), nu_s = __builtin_amdgcn_readfirstlane(X.grid[s].nu);
         nchsum += nv_s * ((nu_s + ROWS - 1) / ROWS);
         npksum += nv_s * (((nu_s + parts - 1) / parts + ROWS - 1) / ROWS);
@@ -522,8 +525,8 @@ __global__ __launch_bounds__(PH_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5
         int sI = S - 1, r = packed ? item - nfull : item;
         while (sI > 0) {
             const int nv_s = __builtin_amdgcn_readfirstlane(X.grid[sI].nv), nu_s = __builtin_amdgcn_readfirstlane(X.grid[sI].nu);
-            const int c = packed ? nv_s * (((nu_s + parts - 1) / parts + ROWS - 1) / ROWS) : nv_s * ((nu_s + ROWS - 1) / ROWS) * ngf;
-            if (r < c) break;
+            const int c = (skip >> sI & 1) ? 0 : packed ? nv_s * (((nu_s + parts - 1) / parts + ROWS - 1) / ROWS) : nv_s * ((nu_s + ROWS - 1) / ROWS) * ngf;
+            if (r < c) break; // (a skipped scale has no items; one at sI = 0 is never reached: the items of the scales above end first)
             r -= c;
             sI--;
         }
@@ -595,11 +598,12 @@ __global__ __launch_bounds__(PH_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5
 #endif
 }
 
-// one wave per (trace, sigma, chain group): the ordered sums of the chains from the stash
+// one wave per (trace, sigma, chain group): the ordered sums of the chains from the stash.  With `share` (decided per step, the same
+// argument as ph_sample's) a guest scale's wave reads its samples from its host's stash region (they were not sampled on their own).
 constexpr int PH_CH = 32; // stash values in flight per lane (64: 256 VGPRs, slower with many traces, no faster with few)
 // DEEP: zncc_from_stash_deep (four chunk buffers in turn) for launches bound by the latency of a chain, not by the stash's bandwidth
 template <bool DEEP>
-__global__ __launch_bounds__(64) void ph_sums(Tab T, TabX X, PhState P, int np, int np_pad, int ni, int it_arg, int lp, int ng_max)
+__global__ __launch_bounds__(64) void ph_sums(Tab T, TabX X, PhState P, int np, int np_pad, int ni, int it_arg, int lp, int ng_max, int share)
 {
     const int S = T.nsig, lane = threadIdx.x;
     const int slot = blockIdx.x / (S * ng_max);
@@ -614,15 +618,31 @@ __global__ __launch_bounds__(64) void ph_sums(Tab T, TabX X, PhState P, int np, 
     (void)np; (void)ni; (void)it_arg;
     const Grid gr = X.grid[sI];
     const int M = gr.nv * gr.nu * gr.nw;
-    const float *sbase = P.stash + (i64)(P.stash_base + slot) * P.trace_floats + (i64)gr.off * P.W;
     const float *wd = X.wd + gr.off;
+    const int host = (share && (X.guest_mask >> sI & 1)) ? X.share[sI] : -1; // a guest's samples: in its host's region
+    const Grid gh = X.grid[host >= 0 ? host : sI];
+    const int Mh = gh.nv * gh.nu * gh.nw; // the rows of the region read
+    const float *sbase = P.stash + (i64)(P.stash_base + slot) * P.trace_floats + (i64)gh.off * P.W;
     float cv;
     bool valid = true;
 #ifdef PNR_SMC_STAMPS
     const unsigned long long sst0 = __builtin_amdgcn_s_memtime();
-    unsigned long long sst1 = sst0;
+    unsigned long long sst1 = sst0; // (a guest's wave leaves it there)
 #endif
-    if (g < ngf) {
+    if (host >= 0) {
+        const int *rows = X.grows + X.share[8 + sI];
+        if (g < ngf) {
+            cv = zncc_from_stash_rows<64>(sbase + (i64)g * Mh * 64 + lane, rows, M, wd, T.corrc[sI]);
+        } else { // the host's narrow region of the last group (see below)
+            valid = lane < rem;
+            const float *col = sbase + (i64)ngf * Mh * 64 + (valid ? lane : rem - 1);
+            switch (last_group_stride(rem)) {
+            case 16: cv = zncc_from_stash_rows<16>(col, rows, M, wd, T.corrc[sI]); break;
+            case 32: cv = zncc_from_stash_rows<32>(col, rows, M, wd, T.corrc[sI]); break;
+            default: cv = zncc_from_stash_rows<64>(col, rows, M, wd, T.corrc[sI]); break;
+            }
+        }
+    } else if (g < ngf) {
 #ifdef PNR_SMC_STAMPS
         if constexpr (DEEP) cv = zncc_from_stash_deep<64>(sbase + (i64)g * M * 64 + lane, M, wd, T.corrc[sI], &sst1);
         else cv = zncc_from_stash<64, PH_CH>(sbase + (i64)g * M * 64 + lane, M, wd, T.corrc[sI], &sst1);
@@ -1131,6 +1151,14 @@ static bool sums_deep(const pnr_ctx *c, int active, int ngroups)
     return ngroups <= 1 || active <= c->opt.sums_deep_max;
 }
 
+// Whether a step of `active` traces samples the guest scales (tables.cpp find_scale_pairs) or reads their samples from their hosts'
+// stash (option "share_scales"; "share_min": not in steps of fewer traces, default 0 -- a guest's wave reads fewer rows than its host's,
+// so the chain a launch waits for is not longer).  Passed to ph_sample and ph_sums of the step alike.  The results are the same.
+static int share_scales(const pnr_ctx *c, int active)
+{
+    return (c->opt.share_scales && c->tab.guest_mask != 0 && active >= c->opt.share_min) ? 1 : 0;
+}
+
 // slots of ph_predict's first-occurrence table: a power of two >= 2 np (its LDS: hashes, representatives, poses, the table)
 static int ph_tbl(int np)
 {
@@ -1149,20 +1177,30 @@ static int pick_nsplit(int active, int ncu, int max_split, int x10 /* work-group
     return ns < 1 ? 1 : (ns > max_split ? max_split : ns);
 }
 
+// the ordered sums of a step: one wave per (trace, scale, chain group)
+static void launch_sums(hipStream_t st, const Tab &T, const TabX &X, const PhState &P, int np, int np_pad, int ni, int it, int lp, int active, int ng,
+                        bool deep, int share)
+{
+    const dim3 grid((unsigned)(active * T.nsig * ng));
+    if (deep) hipLaunchKernelGGL(ph_sums<true>, grid, dim3(64), 0, st, T, X, P, np, np_pad, ni, it, lp, ng, share);
+    else hipLaunchKernelGGL(ph_sums<false>, grid, dim3(64), 0, st, T, X, P, np, np_pad, ni, it, lp, ng, share);
+}
+
 // the sampling launch of a step: the traces' cubes fetched once into their compact copies (ph_cube), then the sampling work-groups
 static void launch_cube(hipStream_t st, const Vol &V, const PhState &P, int active, int lp)
 {
     hipLaunchKernelGGL(ph_cube, dim3((unsigned)(active * PH_CUBE_SPLIT)), dim3(PH_CUBE_THREADS), 0, st, V, P, lp, active);
 }
-static void launch_sample(hipStream_t st, const Vol &V, const Tab &T, const TabX &X, const PhState &P, int np, int ni, int it, int lp, int active, int nsplit, size_t cube_bytes)
+static void launch_sample(hipStream_t st, const Vol &V, const Tab &T, const TabX &X, const PhState &P, int np, int ni, int it, int lp, int active, int nsplit, size_t cube_bytes,
+                          int share)
 {
     const dim3 grid((unsigned)(active * nsplit)), blk(PH_THREADS);
     if (P.cubes) {
-        if (V.l == 1) hipLaunchKernelGGL((ph_sample<PH_CS, true, true>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active);
-        else hipLaunchKernelGGL((ph_sample<PH_CS, false, true>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active);
+        if (V.l == 1) hipLaunchKernelGGL((ph_sample<PH_CS, true, true>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active, share);
+        else hipLaunchKernelGGL((ph_sample<PH_CS, false, true>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active, share);
     } else {
-        if (V.l == 1) hipLaunchKernelGGL((ph_sample<PH_CS, true, false>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active);
-        else hipLaunchKernelGGL((ph_sample<PH_CS, false, false>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active);
+        if (V.l == 1) hipLaunchKernelGGL((ph_sample<PH_CS, true, false>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active, share);
+        else hipLaunchKernelGGL((ph_sample<PH_CS, false, false>), grid, blk, cube_bytes, st, V, T, X, P, np, ni, it, lp, active, share);
     }
 }
 
@@ -1277,6 +1315,7 @@ static int phased_env(pnr_ctx *c, int64_t want, int dbg_iters, bool xfilt, bool 
     E.X.ext_v = c->tab.ext_v; E.X.ext_uw = c->tab.ext_uw;
     for (int s2 = 0; s2 < 8; s2++) { E.X.ext_vs[s2] = s2 < S ? c->tab.ext_vs[s2] : 0.f; E.X.ext_uws[s2] = s2 < S ? c->tab.ext_uws[s2] : 0.f; }
     E.X.stash = nullptr; E.X.slot_busy = nullptr; E.X.nslots = 0; E.X.slot_floats = 0; E.X.wave_floats = 0;
+    E.X.share = c->d_share; E.X.grows = c->d_grows; E.X.guest_mask = c->tab.guest_mask;
     hipDeviceProp_t prop;
     PNR_HIP(hipGetDeviceProperties(&prop, c->device));
     E.ncu = prop.multiProcessorCount;
@@ -1307,7 +1346,7 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
     if (rc) return rc;
     const Vol &V = E.V; const Tab &T = E.T; const TabX &X = E.X; const PhState &P = E.P;
     pnr_phased *h = E.h;
-    const int np = E.np, ni = E.ni, S = E.S, np_pad = E.np_pad, ng = E.ng, ncu = E.ncu, max_split = E.max_split;
+    const int np = E.np, ni = E.ni, np_pad = E.np_pad, ng = E.ng, ncu = E.ncu, max_split = E.max_split;
     const int64_t NT = E.NT;
     const size_t cube_bytes = E.cube_bytes, upd_lds = E.upd_lds;
     dbg_iters = E.dbg_iters;
@@ -1360,14 +1399,12 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
                 launch_cube(st, V, P, active, it & 1);
                 c->toc("smc_cube", 1, st);
             }
+            const int share = share_scales(c, active);
             c->tic(st);
-            launch_sample(st, V, T, X, P, np, ni, it, it & 1, active, nsplit, cube_bytes);
+            launch_sample(st, V, T, X, P, np, ni, it, it & 1, active, nsplit, cube_bytes, share);
             c->toc("smc", 1, st);
             c->tic(st);
-            if (sums_deep(c, active, 1))
-                hipLaunchKernelGGL(ph_sums<true>, dim3((unsigned)(active * S * ng)), dim3(64), 0, st, T, X, P, np, np_pad, ni, it, it & 1, ng);
-            else
-                hipLaunchKernelGGL(ph_sums<false>, dim3((unsigned)(active * S * ng)), dim3(64), 0, st, T, X, P, np, np_pad, ni, it, it & 1, ng);
+            launch_sums(st, T, X, P, np, np_pad, ni, it, it & 1, active, ng, sums_deep(c, active, 1), share);
             c->toc("smc_sums", 1, st);
             c->tic(st);
             hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), upd_lds, st, V, T, P, np, np_pad, ni, it, it & 1, c->prm.Kc, c->prm.znccth,
@@ -1525,7 +1562,7 @@ struct PhasedEngine final : pnr::StreamEngine {
         Grp &q = grp[g];
         hipStream_t st = q.st;
         const PhState &P = q.P;
-        const int np = E.np, ni = E.ni, S = E.S, np_pad = E.np_pad, ng = E.ng;
+        const int np = E.np, ni = E.ni, np_pad = E.np_pad, ng = E.ng;
         // does this launch share the GPU with another group's steps?  (With the scheduler's `concentrate` the other groups run out.)
         q.running = active;
         int sharing = 1;
@@ -1544,14 +1581,12 @@ struct PhasedEngine final : pnr::StreamEngine {
                 launch_cube(st, E.V, P, active, lp);
                 if (prof) c->toc("smc_cube", 1, st, pw);
             }
+            const int share = share_scales(c, active);
             if (prof) c->tic(st, true);
-            launch_sample(st, E.V, E.T, E.X, P, np, ni, -1, lp, active, nsplit, E.cube_bytes);
+            launch_sample(st, E.V, E.T, E.X, P, np, ni, -1, lp, active, nsplit, E.cube_bytes, share);
             if (prof) c->toc("smc", 1, st, pw);
             if (prof) c->tic(st, true);
-            if (sums_deep(c, active, sharing))
-                hipLaunchKernelGGL(ph_sums<true>, dim3((unsigned)(active * S * ng)), dim3(64), 0, st, E.T, E.X, P, np, np_pad, ni, -1, lp, ng);
-            else
-                hipLaunchKernelGGL(ph_sums<false>, dim3((unsigned)(active * S * ng)), dim3(64), 0, st, E.T, E.X, P, np, np_pad, ni, -1, lp, ng);
+            launch_sums(st, E.T, E.X, P, np, np_pad, ni, -1, lp, active, ng, sums_deep(c, active, sharing), share);
             if (prof) c->toc("smc_sums", 1, st, pw);
             if (prof) c->tic(st, true);
             hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), E.upd_lds, st, E.V, E.T, P, np, np_pad, ni, -1, lp, c->prm.Kc, c->prm.znccth,

@@ -133,6 +133,64 @@ static void build_templates(const pnr_params &P, bool is2d, Tables &t)
     }
 }
 
+// the first run h[x0 .. x0 + ng) equal to g value for value (exact float compare)
+static bool axis_run(const float *h, int nh, const float *g, int ng, int *x0)
+{
+    for (int a = 0; a + ng <= nh; a++) {
+        int k = 0;
+        while (k < ng && h[a + k] == g[k]) k++;
+        if (k == ng) { *x0 = a; return true; }
+    }
+    return false;
+}
+
+// Guest -> host pairs of scales: the guest's grid is, axis by axis, a contiguous run of the host's.  Every sample position is
+// ((p + vv nv) + uu u) + ww w, the same float operations at every scale, and both grids are walked v-major, then u, then w, so
+// the guest's samples are the host's at the rows of the runs, in the same order: its ordered sums (tracker.cpp:1940-1955) can
+// be formed from the host's stash, bit for bit.  A guest is not sampled, so it cannot be a host; a host carries one guest.  The
+// largest guests are placed first (the most samples saved), each in the smallest free host that holds it.
+void find_scale_pairs(Tables &t)
+{
+    const int S = t.nsig;
+    t.pairs.clear();
+    std::vector<int> role(S, 0), order(S); // role: 1 guest, 2 host
+    for (int s = 0; s < S; s++) order[s] = s;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return t.M[a] > t.M[b]; });
+    const auto axis = [&](int s, int a) { return &t.axes[t.axes_off[s] + (a > 0 ? t.grid[4 * s] : 0) + (a > 1 ? t.grid[4 * s + 1] : 0)]; };
+    for (int g : order) {
+        if (role[g]) continue;
+        int best = -1;
+        Tables::ScalePair bp{};
+        for (int h = 0; h < S; h++) {
+            if (h == g || role[h] || (best >= 0 && t.M[h] >= t.M[best])) continue;
+            Tables::ScalePair p{g, h, 0, t.grid[4 * g], 0, t.grid[4 * g + 1], 0, t.grid[4 * g + 2]};
+            if (axis_run(axis(h, 0), t.grid[4 * h], axis(g, 0), p.nv, &p.v0) && axis_run(axis(h, 1), t.grid[4 * h + 1], axis(g, 1), p.nu, &p.u0) &&
+                axis_run(axis(h, 2), t.grid[4 * h + 2], axis(g, 2), p.nw, &p.w0)) {
+                best = h;
+                bp = p;
+            }
+        }
+        if (best < 0) continue;
+        role[g] = 1;
+        role[best] = 2;
+        t.pairs.push_back(bp);
+    }
+    // device tables
+    t.guest_mask = 0;
+    t.share_tab.assign(16, 0);
+    for (int s = 0; s < 8; s++) t.share_tab[s] = -1;
+    t.grows.clear();
+    for (const Tables::ScalePair &p : t.pairs) {
+        const int h = p.host, nuh = t.grid[4 * h + 1], nwh = t.grid[4 * h + 2];
+        t.guest_mask |= 1 << p.guest;
+        t.share_tab[p.guest] = h;
+        t.share_tab[8 + p.guest] = (int)t.grows.size();
+        for (int iv = 0; iv < p.nv; iv++)
+            for (int iu = 0; iu < p.nu; iu++)
+                for (int iw = 0; iw < p.nw; iw++) t.grows.push_back(((p.v0 + iv) * nuh + (p.u0 + iu)) * nwh + (p.w0 + iw));
+    }
+}
+
 static void build_prediction(const pnr_params &P, bool is2d, Tables &t)
 {
     // tracker.cpp:375-438: integer offsets inside the radius-2*step ball (2-D: disc, dz = 0), z scaled by 1/zdist
@@ -226,6 +284,7 @@ void build_tables(const pnr_params &P, bool is2d, Tables &t)
     t.ndir = is2d ? 30 : 50; // Tracker::ndirs2d / ndirs3d (tracker.cpp:27-28)
     static_assert(50 <= 64 && 30 <= 64, "ph_predict keeps the directions in an LDS array of 64");
     build_templates(P, is2d, t);
+    find_scale_pairs(t);
     build_prediction(P, is2d, t);
     build_directions(is2d, t);
     build_oriented_priors(P, t);
