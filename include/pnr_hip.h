@@ -245,6 +245,16 @@ int pnr_reconstruct(const pnr_node *nodes, int64_t n_nodes, const int32_t *links
                     float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min,
                     pnr_node *out_nodes, int32_t *out_parent, int64_t cap, int64_t *n_out);
 
+/* The same chain with its two neighbour stages -- the mean-shift refinement and the ball queries of the sphere grouping -- on
+ * ctx's GPU (on its stream, see pnr_set_stream; device buffers are allocated per call and freed before it returns).  Same
+ * arguments, defaults, tree_size_min < 0 branch, link validation and "*n_out > cap: call again" rule as pnr_reconstruct, and
+ * identical output, byte for byte.  refine_iter above PNR_RECON_MAX_ITER is rejected (PNR_E_ARG); a failed device allocation
+ * returns PNR_E_NOMEM.  Kernel times: pnr_get_kernel_ms group "recon". */
+#define PNR_RECON_MAX_ITER 1000
+int pnr_reconstruct_ctx(pnr_ctx *ctx, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
+                        float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min,
+                        pnr_node *out_nodes, int32_t *out_parent, int64_t cap, int64_t *n_out);
+
 /* The plugin's saveMidres taps inside reconstruct() (:2098-2141): the node list as it stands behind stage 1 = interpolate_nodelist
  * (_n0res_), 2 = non_blurring (_n1_), 3 = group1 (_n2_), 4 = compute_trees (_n2tree_).  out_links: pairs, every undirected link once
  * (stage 4: (child, parent)); counts are returned even when the buffers are too small. */

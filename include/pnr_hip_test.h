@@ -57,6 +57,13 @@ int pnr_sched_playback2(const pnr_params *p, int64_t w, int64_t h, int64_t l, co
                         pnr_node *nodes, int64_t cap_nodes, int64_t *n_nodes, int32_t *links, int64_t cap_links, int64_t *n_links,
                         int64_t *n_traces_used, int64_t *n_iterations_here);
 
+/* pnr_reconstruct_stage with the device stages of pnr_reconstruct_ctx: the list behind stage 2 (_n1_, after the mean-shift) and
+ * stage 3 (_n2_, after the grouping) can be compared with the host's one stage at a time.  Same arguments and rules otherwise. */
+int pnr_reconstruct_stage_ctx(pnr_ctx *ctx, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links,
+                              float trace_rsmpl, float sig2radius, int refine_iter, float epsilon2, float group_radius, int stage,
+                              pnr_node *out_nodes, int64_t cap_nodes, int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links,
+                              int64_t *n_out_links);
+
 #ifdef __cplusplus
 }
 #endif

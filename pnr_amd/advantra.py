@@ -233,7 +233,7 @@ def run_pipeline(ctx, img, verbose=False, max_seeds=None, one_shot=False, recons
     else:         # production form: seed-rank batches with early DENSITY stops (same node graph)
         T = stop = xc = None
         nodes, links, ntr, iters = ctx.trace_replay(seeds); t.append(time.time()); t.append(time.time())
-    tree, parent = lib.reconstruct(nodes, links) if reconstruct else (None, None)  # reconstruct(n0, ...) :2729
+    tree, parent = ctx.reconstruct(nodes, links) if reconstruct else (None, None)  # reconstruct(n0, ...) :2729 (its neighbour stages on the GPU)
     t.append(time.time())
     if verbose:
         names = ["frangi", "seed extraction", "seed selection & sorting", "tracing", "replay", "reconstruct"]

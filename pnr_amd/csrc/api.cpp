@@ -6,6 +6,7 @@
 #include "replay.h"
 #include "stream_sched.h"
 #include "../host/reconstruct.h"
+#include "recon.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -939,6 +940,62 @@ int pnr_reconstruct_stage(const pnr_node *nodes, int64_t n_nodes, const int32_t 
     std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
     std::vector<int32_t> lk(links, links + 2 * n_links), par, sl;
     advantra::reconstruct(in, lk, rp, out, par, stage, &sl);
+    *n_out_nodes = (int64_t)out.size();
+    *n_out_links = (int64_t)sl.size() / 2;
+    if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_out_nodes));
+    if (out_links) std::memcpy(out_links, sl.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_out_links));
+    return PNR_OK;
+}
+
+// pnr_reconstruct[_stage]_ctx: the plugin constants for values <= 0 (as pnr_reconstruct), the two neighbour stages on ctx's GPU
+static void recon_ctx_params(pnr_ctx *c, float trace_rsmpl, float sig2radius, int refine_iter, float epsilon2, float group_radius,
+                             advantra::ReconParams &rp)
+{
+    if (trace_rsmpl > 0) rp.trace_rsmpl = trace_rsmpl;
+    if (sig2radius > 0) rp.sig2radius = sig2radius;
+    if (refine_iter > 0) rp.refine_iter = refine_iter;
+    if (epsilon2 > 0) rp.epsilon2 = epsilon2;
+    if (group_radius > 0) rp.group_radius = group_radius;
+    rp.shift = [c](const std::vector<advantra::P4> &src, float s2r, int iters, float eps2, std::vector<advantra::P4> &res) {
+        return pnr_recon_shift(c, src, s2r, iters, eps2, res);
+    };
+    rp.balls = [c](const std::vector<advantra::P4> &pos, float rad, advantra::BallLists &out) { return pnr_recon_balls(c, pos, rad, out); };
+}
+
+int pnr_reconstruct_ctx(pnr_ctx *c, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
+                        float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min,
+                        pnr_node *out_nodes, int32_t *out_parent, int64_t cap, int64_t *n_out)
+{
+    PNR_REQUIRE(c && nodes && n_nodes >= 1 && n_out && (n_links == 0 || links), PNR_E_ARG, "null argument");
+    PNR_REQUIRE(refine_iter <= PNR_RECON_MAX_ITER, PNR_E_ARG, "refine_iter = %d above %d", refine_iter, PNR_RECON_MAX_ITER);
+    for (int64_t k = 0; k < 2 * n_links; k++) PNR_REQUIRE(links[k] >= 0 && links[k] < n_nodes, PNR_E_ARG, "link index out of range");
+    advantra::ReconParams rp;
+    recon_ctx_params(c, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, rp);
+    if (tree_size_min > 0) rp.tree_size_min = tree_size_min;
+    rp.single_tree = tree_size_min < 0;
+    std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
+    std::vector<int32_t> lk(links, links + 2 * n_links), par;
+    if (int rc = advantra::reconstruct(in, lk, rp, out, par)) return rc;
+    *n_out = (int64_t)out.size();
+    const size_t m = (size_t)std::min<int64_t>(cap, *n_out);
+    if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * m);
+    if (out_parent) std::memcpy(out_parent, par.data(), 4 * m);
+    return PNR_OK;
+}
+
+int pnr_reconstruct_stage_ctx(pnr_ctx *c, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
+                              float sig2radius, int refine_iter, float epsilon2, float group_radius, int stage, pnr_node *out_nodes,
+                              int64_t cap_nodes, int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links, int64_t *n_out_links)
+{
+    PNR_REQUIRE(c && nodes && n_nodes >= 1 && n_out_nodes && n_out_links && (n_links == 0 || links), PNR_E_ARG, "null argument");
+    PNR_REQUIRE(stage >= advantra::RECON_N0RES && stage <= advantra::RECON_N2TREE, PNR_E_ARG, "stage %d outside [1, 4]", stage);
+    PNR_REQUIRE(refine_iter <= PNR_RECON_MAX_ITER, PNR_E_ARG, "refine_iter = %d above %d", refine_iter, PNR_RECON_MAX_ITER);
+    for (int64_t k = 0; k < 2 * n_links; k++) PNR_REQUIRE(links[k] >= 0 && links[k] < n_nodes, PNR_E_ARG, "link index out of range");
+    advantra::ReconParams rp;
+    recon_ctx_params(c, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, rp);
+    std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
+    std::vector<int32_t> lk(links, links + 2 * n_links), par, sl;
+    if (int rc = advantra::reconstruct(in, lk, rp, out, par, stage, &sl)) return rc;
     *n_out_nodes = (int64_t)out.size();
     *n_out_links = (int64_t)sl.size() / 2;
     if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_out_nodes));

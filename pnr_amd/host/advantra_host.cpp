@@ -532,12 +532,12 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     R.t_frangi = secs(t0, t1); R.t_seeds = secs(t1, t2); R.t_select = secs(t2, t3); R.t_trace = secs(t3, t4);
     R.t_setup = secs(t_begin, t0); // context, upload of the stack, soma path
     printf("\n-----\n%g%% seeds used \n", nseeds ? 100.0 * used / nseeds : 0.0);
-    { // reconstruct(n0, ...) :2729 -> :2096-2181 (host): refinement, grouping, trees, final resampling
+    { // reconstruct(n0, ...) :2729 -> :2096-2181: refinement and grouping queries on this rank's GPU, trees and resampling on the host
         int64_t cap = std::max<int64_t>(16, 4 * nn), nt = 0;
         for (;;) {
             R.tree.resize((size_t)cap);
             R.parent.resize((size_t)cap);
-            if (pnr_reconstruct(R.nodes.data(), nn, R.links.data(), nl, 0, 0, 0, 0, 0, settings().single_tree ? -1 : 0, R.tree.data(), R.parent.data(), cap, &nt) != PNR_OK) {
+            if (pnr_reconstruct_ctx(ctx, R.nodes.data(), nn, R.links.data(), nl, 0, 0, 0, 0, 0, settings().single_tree ? -1 : 0, R.tree.data(), R.parent.data(), cap, &nt) != PNR_OK) {
                 fprintf(stderr, "%s\n", pnr_last_error());
                 pnr_destroy(ctx);
                 return false;

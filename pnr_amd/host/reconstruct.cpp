@@ -137,7 +137,6 @@ void mean_shift(List &g, float SIG2RAD, int MAXITER, float EPS2, int threads)
 {
     // in place: every trajectory reads the positions as they were on entry (kept packed, in index order), the results are
     // written back once all of them are known
-    struct P4 { float x, y, z, s; };
     const size_t n = g.size();
     std::vector<P4> src(n), res(n);
     float smax = 0;
@@ -211,8 +210,10 @@ void tidy_links(List &g)
         }
 }
 
-// :1566-1642 -- greedy sphere grouping in order of decreasing corr; a group is the running mean of its members
-void group_spheres(List &src, List &dst, float rad)
+// :1566-1642 -- greedy sphere grouping in order of decreasing corr; a group is the running mean of its members.  With `balls`
+// (the device's lists of every node's neighbours within rad, ascending) the walk reads no geometry: the still-unclaimed entries
+// of a centre's list are the members the grid query below finds, in the same order.
+void group_spheres(List &src, List &dst, float rad, const BallLists *balls = nullptr)
 {
     const size_t n = src.size();
     src[0].corr = FLT_MAX;
@@ -240,7 +241,8 @@ void group_spheres(List &src, List &dst, float rad)
             to[i] = (int)dst.size();
             dst.push_back(src[i]);
         }
-    const Grid grid(src, std::max(2.0f, rad));
+    static const List none;
+    const Grid grid(balls ? none : src, std::max(2.0f, rad)); // (no grid over the nodes when the lists are given)
     std::vector<int> cand;
     const float r2 = rad * rad;
     for (size_t oi = 1; oi < n; oi++) {
@@ -250,7 +252,11 @@ void group_spheres(List &src, List &dst, float rad)
         N grp = src[ci];
         float members = 1;
         cand.clear();
-        grid.for_cells(src[ci].x, src[ci].y, src[ci].z, rad * 1.0001f + 1e-3f, [&](int p, int e) {
+        if (balls) {
+            const int32_t *b = balls->list.data() + balls->off[(size_t)ci];
+            for (int32_t k = 0; k < balls->cnt[(size_t)ci]; k++)
+                if (to[b[k]] == -1) cand.push_back(b[k]);
+        } else grid.for_cells(src[ci].x, src[ci].y, src[ci].z, rad * 1.0001f + 1e-3f, [&](int p, int e) {
             for (; p < e; p++) {
                 const int j = grid.idx[p];
                 if (j == ci || to[j] != -1) continue;
@@ -262,7 +268,7 @@ void group_spheres(List &src, List &dst, float rad)
                 if (d2 <= r2) cand.push_back(j);
             }
         });
-        std::sort(cand.begin(), cand.end());
+        if (!balls) std::sort(cand.begin(), cand.end());
         for (int j : cand) {
             to[j] = (int)dst.size();
             grp.nbr.insert(grp.nbr.end(), src[j].nbr.begin(), src[j].nbr.end());
@@ -401,8 +407,8 @@ static void export_list(const List &g, bool tree, std::vector<pnr_node> &out_nod
     }
 }
 
-void reconstruct(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const ReconParams &rp,
-                 std::vector<pnr_node> &out_nodes, std::vector<int32_t> &out_parent, int stop_after, std::vector<int32_t> *stage_links)
+int reconstruct(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const ReconParams &rp,
+                std::vector<pnr_node> &out_nodes, std::vector<int32_t> &out_parent, int stop_after, std::vector<int32_t> *stage_links)
 {
     List n0(nodes.size());
     for (size_t i = 0; i < nodes.size(); i++) {
@@ -432,16 +438,33 @@ void reconstruct(const std::vector<pnr_node> &nodes, const std::vector<int32_t> 
     };
     resample_links(n0, rp.trace_rsmpl);
     lap("resample_links", n0.size());
-    if (tap(RECON_N0RES, n0, false)) return;
-    mean_shift(n0, rp.sig2radius, rp.refine_iter, rp.epsilon2, rp.threads);
-    lap("mean_shift", n0.size());
-    if (tap(RECON_N1, n0, false)) return;
-    group_spheres(n0, n2, rp.group_radius);
-    lap("group_spheres", n2.size());
-    if (tap(RECON_N2, n2, false)) return;
+    if (tap(RECON_N0RES, n0, false)) return 0;
+    std::vector<P4> pk(n0.size()), res;
+    if (rp.shift) {
+        for (size_t i = 0; i < n0.size(); i++) pk[i] = P4{n0[i].x, n0[i].y, n0[i].z, n0[i].sig};
+        if (int rc = rp.shift(pk, rp.sig2radius, rp.refine_iter, rp.epsilon2, res)) return rc;
+        for (size_t i = 1; i < n0.size(); i++) { n0[i].x = res[i].x; n0[i].y = res[i].y; n0[i].z = res[i].z; n0[i].sig = res[i].s; }
+        lap("mean_shift_gpu", n0.size());
+    } else {
+        mean_shift(n0, rp.sig2radius, rp.refine_iter, rp.epsilon2, rp.threads);
+        lap("mean_shift", n0.size());
+    }
+    if (tap(RECON_N1, n0, false)) return 0;
+    if (rp.balls) {
+        BallLists bl;
+        for (size_t i = 0; i < n0.size(); i++) pk[i] = P4{n0[i].x, n0[i].y, n0[i].z, n0[i].sig};
+        if (int rc = rp.balls(pk, rp.group_radius, bl)) return rc;
+        lap("ball_lists_gpu", bl.list.size());
+        group_spheres(n0, n2, rp.group_radius, &bl);
+        lap("group_walk", n2.size());
+    } else {
+        group_spheres(n0, n2, rp.group_radius);
+        lap("group_spheres", n2.size());
+    }
+    if (tap(RECON_N2, n2, false)) return 0;
     bfs_forest(n2, forest);
     lap("bfs_forest", forest.size());
-    if (tap(RECON_N2TREE, forest, true)) return;
+    if (tap(RECON_N2TREE, forest, true)) return 0;
     if (rp.single_tree) keep_largest_tree(forest, kept); // ENFORCE_SINGLE_TREE (:2142-2152)
     else drop_small_trees(forest, kept, rp.tree_size_min);
     lap(rp.single_tree ? "largest_tree" : "drop_small", kept.size());
@@ -454,6 +477,7 @@ void reconstruct(const std::vector<pnr_node> &nodes, const std::vector<int32_t> 
         out_nodes[i] = pnr_node{s.x, s.y, s.z, s.vx, s.vy, s.vz, s.corr, s.sig, s.type};
         out_parent[i] = (i > 0 && !s.nbr.empty()) ? s.nbr[0] : -1;
     }
+    return 0;
 }
 
 } // namespace advantra

@@ -8,9 +8,27 @@
 #pragma once
 #include "../../include/pnr_hip.h"
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 namespace advantra {
+
+struct P4 { float x, y, z, s; }; // a node's position and scale, packed as the device stages read them
+
+// The ball lists of the sphere grouping in CSR form: for every node ci >= 1, list[off[ci] .. off[ci] + cnt[ci]) holds every
+// j >= 1, j != ci within group_radius of ci (the grouping's distance test), in ascending order.  off / cnt have one entry per node.
+struct BallLists {
+    std::vector<int64_t> off;
+    std::vector<int32_t> cnt;
+    std::vector<int32_t> list;
+};
+
+// Device backends of the two neighbour stages (pnr_reconstruct_ctx).  Empty: the host implementations run.  Both return 0 or a
+// PNR_E_* code (with the message set), and give what the host stage gives, bit for bit.
+//   shift: non-blurring mean-shift of src (node 0 is never a member and is never moved) -> res, same size
+//   balls: the ball lists over pos (the shifted positions; .s is not read)
+typedef std::function<int(const std::vector<P4> &src, float sig2radius, int refine_iter, float epsilon2, std::vector<P4> &res)> ShiftFn;
+typedef std::function<int(const std::vector<P4> &pos, float group_radius, BallLists &out)> BallsFn;
 
 struct ReconParams {          // Advantra_plugin.cpp:72-83
     float trace_rsmpl = 1.0f;  // TRACE_RSMPL
@@ -21,6 +39,8 @@ struct ReconParams {          // Advantra_plugin.cpp:72-83
     int tree_size_min = 10;    // TREE_SIZE_MIN
     int threads = 0;           // host threads of the mean-shift (its nodes are independent); 0 = one per CPU this process may use
     bool single_tree = false;  // ENFORCE_SINGLE_TREE (:81, :2142-2152): keep the largest tree only (extract_largest_tree :546-589)
+    ShiftFn shift;             // device mean-shift (empty: host)
+    BallsFn balls;             // device ball lists of the grouping (empty: host grid queries)
 };
 
 // the node lists reconstruct() passes through, in the order of the plugin's saveMidres taps (:2098-2141)
@@ -35,8 +55,9 @@ void set_recon_timing(bool on);
 bool recon_timing();
 
 // stop_after != RECON_FINAL (with stage_links): out_nodes / *stage_links receive the list behind that stage instead (links as pairs:
-// every undirected link once; for RECON_N2TREE (child, parent)), out_parent is left empty.
-void reconstruct(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const ReconParams &rp,
+// every undirected link once; for RECON_N2TREE (child, parent)), out_parent is left empty.  Returns 0, or the code of a failed
+// device stage (rp.shift / rp.balls).
+int reconstruct(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const ReconParams &rp,
                  std::vector<pnr_node> &out_nodes, std::vector<int32_t> &out_parent, int stop_after = RECON_FINAL,
                  std::vector<int32_t> *stage_links = nullptr);
 

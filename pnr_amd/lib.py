@@ -88,6 +88,9 @@ def load():
                                     C.POINTER(i64), C.POINTER(i64)]
     L.pnr_trace_replay.argtypes = [vp, vp, i64, i64, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.pnr_reconstruct.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, vp, i64, C.POINTER(i64)]
+    L.pnr_reconstruct_ctx.argtypes = [vp, vp, i64, vp, i64, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, vp, i64, C.POINTER(i64)]
+    L.pnr_reconstruct_stage_ctx.argtypes = [vp, vp, i64, vp, i64, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, i64, C.POINTER(i64),
+                                            vp, i64, C.POINTER(i64)]
     L.pnr_get_table.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
     L.pnr_frangi_slab.argtypes = [vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pnr_quantise_j8.argtypes = [vp, C.c_float, C.c_float]
@@ -131,14 +134,14 @@ def load():
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
                    "pnr_set_volume", "pnr_set_volume_device", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
-                   "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_stage", "pnr_set_profiling",
+                   "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
                    "pnr_set_option", "pnr_get_option", "pnr_score_filter_seeds", "pnr_sort_seeds", "pnr_get_trace_log",
                    "pnr_shm_exchange_open", "pnr_shm_allgather", "pnr_shm_exchange_close",
                    "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2"]
+                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -417,6 +420,35 @@ class Context:
     # ---- profiling ----
     def set_profiling(self, on=True):
         check(self.L.pnr_set_profiling(self.h, int(on)))
+
+    # ---- reconstruct() with its neighbour stages on this GPU ----
+    def reconstruct(self, nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0, tree_size_min=0):
+        """pnr_reconstruct_ctx: the output of lib.reconstruct, byte for byte -> tree nodes (index 0 dummy), parents (-1 = root)"""
+        nodes = np.ascontiguousarray(nodes, NODE_DT)
+        links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
+        cap = max(16, 4 * len(nodes))
+        while True:
+            out = np.zeros(cap, NODE_DT)
+            par = np.zeros(cap, np.int32)
+            n = C.c_int64()
+            check(self.L.pnr_reconstruct_ctx(self.h, nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius,
+                                             refine_iter, epsilon2, group_radius, tree_size_min, out.ctypes.data, par.ctypes.data, cap,
+                                             C.byref(n)))
+            if n.value <= cap:
+                return out[:n.value].copy(), par[:n.value].copy()
+            cap = int(n.value)
+
+    def reconstruct_stage(self, nodes, links, stage, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0):
+        """test tap pnr_reconstruct_stage_ctx: lib.reconstruct_stage with the device stages -> nodes, link pairs"""
+        nodes = np.ascontiguousarray(nodes, NODE_DT)
+        links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
+        args = (nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, stage)
+        nn, nl = C.c_int64(), C.c_int64()
+        check(self.L.pnr_reconstruct_stage_ctx(self.h, *args, None, 0, C.byref(nn), None, 0, C.byref(nl)))
+        out = np.zeros(nn.value, NODE_DT)
+        lk = np.zeros((nl.value, 2), np.int32)
+        check(self.L.pnr_reconstruct_stage_ctx(self.h, *args, out.ctypes.data, len(out), C.byref(nn), lk.ctypes.data, len(lk), C.byref(nl)))
+        return out, lk
 
     def kernel_ms(self, group):
         ms, n = C.c_double(), C.c_int64()
