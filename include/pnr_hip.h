@@ -278,6 +278,8 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   trace_timing, seed_timing (0/1) statistics on stderr | recon_timing (0/1) stage times of every pnr_reconstruct on stderr (process-wide: that call takes no context) | trace_log (0/1) keep every trace's end for pnr_get_trace_log | replay_batches (0/1), batch_growth, batch_max: rank batches instead
  *   of the streaming window | no_stash (0/1) persistent driver without the sample stash | exchange_block (0 = 256 KB / world) bytes per rank
  *   and exchange of pnr_trace_replay_sharded | frangi_prune (1) skip the eigen-solver below the first J8 level (pnr_get_frangi) |
+ *   hess_chunk (0 = automatic: 2^27 voxels) at most this many planes per z-chunk of the Hessian stage, in whole marches of 32 (only
+ *   ever lowers the automatic size; the same bits -- tests reach chunk boundaries with it on small stacks) |
  *   cube_copy (1) phased driver: a trace's cube is fetched from the image once per step and copied by its sampling work-groups (0: each stages it itself) |
  *   share_scales (1) phased driver: a scale whose template grid nests in another's is not sampled, its sums read the host's stash (0: every scale samples on its
  *   own; the same bits) | share_min (0) ... in steps of at least this many traces |

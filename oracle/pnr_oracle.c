@@ -886,8 +886,8 @@ float orc_zncc(orc_tracker *t, float _x, float _y, float _z, float _vx, float _v
     }
 
     float out_corr = -FLT_MAX;
-    static float *buf = NULL;
-    static int bufcap = 0;
+    static __thread float *buf = NULL; /* (per thread: trackers may run on several threads at once, one tracker each) */
+    static __thread int bufcap = 0;
     for (int s = 0; s < t->nsig; ++s) {
         int M = t->M[s];
         if (M > bufcap) { free(buf); buf = (float *)malloc(sizeof(float) * (size_t)M); bufcap = M; }

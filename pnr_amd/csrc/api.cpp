@@ -862,6 +862,7 @@ const OptEntry OPTS[] = {
     {"lag", &pnr::Options::lag, nullptr, -1, 1023},               {"profile_every", &pnr::Options::profile_every, nullptr, 1, 1024},
     {"overfill", &pnr::Options::overfill, nullptr, 0, 1},        {"concentrate", &pnr::Options::concentrate, nullptr, 0, 100},
     {"share_scales", &pnr::Options::share_scales, nullptr, 0, 1}, {"share_min", &pnr::Options::share_min, nullptr, 0, 1 << 20},
+    {"hess_chunk", &pnr::Options::hess_chunk, nullptr, 0, 1 << 20},
 };
 } // namespace
 

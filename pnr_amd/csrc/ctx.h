@@ -90,6 +90,8 @@ struct Options {
     int batch_growth = 200, batch_max = 1024;
     int no_stash = 0;         // persistent driver: in-lane two-pass sums
     int frangi_prune = 1;       // skip the eigen-solver where the response cannot reach the first non-zero J8 level (frangi.hip)
+    int hess_chunk = 0;         // at most this many planes per z-chunk of the Hessian stage, rounded down to whole marches (0: the automatic
+                                // 2^27 voxels; frangi.hip hess_chunk_planes -- only ever lowers it: tests reach chunk boundaries on small stacks)
     int tentative = 1;          // streaming scheduler: pause traces that a tentative replay of everything recorded so far cuts (stream_sched.h)
     int gauss_march = 1;        // the fused x-y Gaussian marches down strips of a slice (gauss_xy_u8_m; 0: one 64 x 64 tile per work-group)
     int cube_copy = 1;          // phased driver: the cube of a trace is fetched from the image once per step (ph_cube) and copied by its sampling work-groups (0: each stages it itself)

@@ -1505,11 +1505,13 @@ static int ensure_scale_volume(pnr_ctx *c, int s)
     return PNR_OK;
 }
 
-// z-chunks of the Hessian stage and their survivor queue: a chunk holds at most 2^27 voxels (3.5 GB of queue at worst)
+// z-chunks of the Hessian stage and their survivor queue: a chunk holds at most 2^27 voxels (3.5 GB of queue at worst); option
+// hess_chunk caps the planes further (whole marches, at least one), so the queue sized from the first chunk never grows by it
 static int hess_chunk_planes(const pnr_ctx *c)
 {
     const i64 wh = c->w * c->h;
     i64 cz = ((i64)1 << 27) / wh / HT_Z * HT_Z;
+    if (c->opt.hess_chunk > 0) cz = std::min<i64>(cz, std::max(HT_Z, c->opt.hess_chunk / HT_Z * HT_Z));
     if (cz < HT_Z) cz = HT_Z;
     return (int)std::min<i64>(cz, (c->l + HT_Z - 1) / HT_Z * HT_Z);
 }

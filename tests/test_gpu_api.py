@@ -22,6 +22,13 @@ def test_options_roundtrip_and_errors(monkeypatch):
         c.set_option("no_such_knob", 1)
     with pytest.raises(pnr_amd.PnrError, match="outside"):
         c.set_option("groups", 9)
+    assert c.get_option("hess_chunk") == 0
+    c.set_option("hess_chunk", 1 << 20)
+    assert c.get_option("hess_chunk") == 1 << 20
+    for bad in (-1, (1 << 20) + 1):
+        with pytest.raises(pnr_amd.PnrError, match="outside"):
+            c.set_option("hess_chunk", bad)
+    assert c.get_option("hess_chunk") == 1 << 20
     with pytest.raises(pnr_amd.PnrError, match="no node graph"):
         c.get_graph()
     assert c.set_options("poll=3, groups=1") == {"poll": 3, "groups": 1} and c.get_option("poll") == 3

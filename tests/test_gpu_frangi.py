@@ -2,6 +2,7 @@
 reference's own frangi.cpp.  Gaussian / Hessian / eigenvector bytes are expected bit-exact (same
 IEEE operations in the same order, FMA contraction off); J may differ only through fp64 exp()
 (ocml vs glibc), tolerance stated below; J8 / Vx / Vy / Vz bytes must be identical."""
+import functools
 import numpy as np
 import pytest
 import orc
@@ -179,3 +180,79 @@ def test_j8_shortcut_and_foreign_extremes(oracle):
     assert c.frangi() == (jmin, jmax)
     assert np.array_equal(c.get_frangi(J=False, J8=True, V=False)["J8"], fast)
     c.close()
+
+
+HT_Z = 32  # planes one work-group of hessian_tile marches (frangi.hip PNR_HT_Z): the unit of a Hessian z-chunk
+
+
+def hessian_chunks(shape, hess_chunk, nsig, pruned):
+    """the z-chunks pnr_frangi_run_range launches hessian_tile over, per scale: at most cz planes each (hess_chunk_planes: 2^27 voxels,
+    capped by option hess_chunk in whole marches); the pruned first scale of a stack deeper than two marches runs the middle march
+    [m0, m1) first, then [0, m0) and [m1, l) in chunks of their own"""
+    l, h, w = shape
+    cz = max(HT_Z, (1 << 27) // (w * h) // HT_Z * HT_Z)
+    if hess_chunk > 0:
+        cz = min(cz, max(HT_Z, hess_chunk // HT_Z * HT_Z))
+    cz = min(cz, -(-l // HT_Z) * HT_Z)
+    split = lambda a, b: [(z, min(b, z + cz)) for z in range(a, b, cz)]
+    out = []
+    for s in range(nsig):
+        if pruned and s == 0 and l > 2 * HT_Z:
+            m0 = (l // 2) // HT_Z * HT_Z
+            out.append([(m0, m0 + HT_Z)] + split(0, m0) + split(m0 + HT_Z, l))
+        else:
+            out.append(split(0, l))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _crossed_stack_vs_oracle(l, sigs, zdist):
+    """an 83 x 61 x l stack with tubes in every plane (a second synthetic stack laid along z, so that tubes also run along it) and
+    the oracle's Frangi, J8 and seeds of it"""
+    img = np.ascontiguousarray(np.maximum(synth.synth(83, 61, l, seed=11), synth.synth(l, 61, 83, seed=12).transpose(2, 1, 0)))
+    L = orc.load_oracle()
+    J, jmin, jmax, Vx, Vy, Vz = orc.frangi3d(L, img, list(sigs), zdist)
+    J8 = orc.j8(L, J, jmin, jmax)
+    return img, (J, jmin, jmax, J8, Vx, Vy, Vz), orc.extract_seeds(L, 5, J8, Vx, Vy, Vz)
+
+
+@pytest.mark.parametrize("sigs,zdist", [((2.0, 4.0, 6.0), 2.0), ((2.0, 3.0), 1.0)])
+@pytest.mark.parametrize("hess_chunk", [32, 64])
+@pytest.mark.parametrize("l", [70, 97, 150])
+def test_chunked_and_pruned_frangi_vs_oracle(l, hess_chunk, sigs, zdist):
+    """the Hessian stage in several z-chunks (option hess_chunk: what a stack of more than 2^27 voxels gets), ragged last chunks, and
+    the pruned first scale's middle-first march (m0 = 32, 32, 64), against the oracle: the pruned run's extremes, J8 and seeds, the
+    exact re-run's J and V, bit for bit; hessian_tile launched once per chunk of the rule above; the chunking changes no byte"""
+    img, (J, jmin, jmax, J8, Vx, Vy, Vz), so = _crossed_stack_vs_oracle(l, sigs, zdist)
+    for ch in hessian_chunks(img.shape, hess_chunk, len(sigs), True):  # every chunk boundary has a response on both sides
+        for z0, _ in ch:
+            assert z0 == 0 or (J[z0 - 1] > 0).sum() > 100 and (J[z0] > 0).sum() > 100, z0
+    assert len(so) > 300 and (J8 == 0).mean() > 0.8  # (most voxels are pruned)
+    runs = []
+    for hc in (hess_chunk, 0):
+        c = ctx_for(list(sigs), zdist)
+        c.set_option("hess_chunk", hc)
+        c.set_option("frangi_prune", 1)
+        c.set_volume(img)
+        c.set_profiling(True)
+        assert c.frangi() == (jmin, jmax)
+        pruned = c.kernel_ms("hessian_tile")[1]
+        fast8 = c.get_frangi(J=False, J8=True, V=False)["J8"]
+        sg = c.extract_seeds()
+        c.reset_kernel_ms()
+        g = c.get_frangi()
+        exact = c.kernel_ms("hessian_tile")[1]
+        assert c.get_option("frangi_recomputes") == 1
+        assert np.array_equal(fast8, J8), int((fast8 != J8).sum())
+        assert len(sg) == len(so) and np.array_equal(np.stack([sg[k] for k in "xyz"] + [sg[k] for k in ("vx", "vy", "vz")], 1), so[:, :6])
+        for k, want in (("J", J), ("J8", J8), ("Vx", Vx), ("Vy", Vy), ("Vz", Vz)):
+            assert np.array_equal(g[k], want), (k, int((g[k] != want).sum()))
+        assert pruned == sum(map(len, hessian_chunks(img.shape, hc, len(sigs), True)))
+        assert exact == sum(map(len, hessian_chunks(img.shape, hc, len(sigs), False)))
+        runs.append((fast8, sg, g, exact))
+        c.close()
+    (a8, asd, ag, an), (b8, bsd, bg, bn) = runs
+    assert an >= 2 * len(sigs) and bn == len(sigs)  # (several chunks a scale; without the option one)
+    assert np.array_equal(a8, b8) and all(np.array_equal(asd[k], bsd[k], equal_nan=True) for k in asd.dtype.names)
+    for k in ag:
+        assert np.array_equal(ag[k], bg[k]), k
