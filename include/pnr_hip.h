@@ -13,7 +13,8 @@
  * Conventions
  *   - every function returns 0 on success, a negative PNR_E_* code on failure;
  *     pnr_last_error() returns a thread-local message for the last failure.
- *   - volumes are uint8, x fastest: i = z*w*h + y*w + x (frangi.cpp:307).
+ *   - volumes are uint8, x fastest: i = z*w*h + y*w + x (frangi.cpp:307); 16-bit and multi-channel stacks are windowed to
+ *     8 bits on the GPU by pnr_set_volume_u16.
  *   - one pnr_ctx = one GPU = one host thread at a time (the reference is single-threaded).
  *   - the library FAILS (PNR_E_NODEVICE) when no HIP device is present: there is no CPU path.
  */
@@ -96,6 +97,32 @@ int pnr_synchronize(pnr_ctx *ctx);
  * tables are rebuilt whenever the dimensionality changes.  2-D stacks are traced by the phased SMC driver only. */
 int pnr_set_volume(pnr_ctx *ctx, const uint8_t *img, int64_t w, int64_t h, int64_t l);
 int pnr_set_volume_device(pnr_ctx *ctx, const void *dev_img, int64_t w, int64_t h, int64_t l);
+
+/* 16-bit input (12- / 16-bit microscope stacks, one or several interleaved channels).  The reference traces 8-bit data only
+ * (channel c of what Vaa3D loaded, as unsigned char; frangi_C = 500 assumes 0-255 Hessian magnitudes), so a deeper stack is not
+ * traced as it is: the selected channel is windowed to 8 bits on the GPU, by the conversion a user would otherwise make by hand,
+ * and everything after it is the 8-bit pipeline.  Let x be the N samples of the channel (voxel i = element i * nchan + channel of
+ * img) and s = x sorted ascending.
+ *   window [lo, hi]: given (0 <= lo < hi <= 65535), or from the stack (lo = hi = -1): lo = s[k_lo], hi = s[k_hi] with
+ *     k_lo = floor(N * sat_lo_ppm / 1e6), k_hi = N - 1 - floor(N * sat_hi_ppm / 1e6) (exact integers; sat_lo_ppm + sat_hi_ppm < 1e6);
+ *     win = NULL = {-1, -1, 0, 0} = [min, max];
+ *   mapping: hi > lo: out = (510 a + d) div 2d with a = clamp(v, lo, hi) - lo, d = hi - lo (255 a / d rounded half up: 0 at lo, 255
+ *     at hi); hi == lo (a constant stack): 255 where v > lo, else 0.
+ * Afterwards the context is what pnr_set_volume of the mapped bytes leaves (l == 1 selects the 2-D mode), the window used is
+ * returned in lo_out / hi_out (nullable), and pnr_get_volume reads the bytes back.  The host variant copies img (nchan * N
+ * samples) into a device buffer of the call; the device variant reads dev_img during the call only (it does not borrow it).  The
+ * work runs on the context's stream (kernel times: group "volume").  PNR_E_ARG (nchan < 1, channel outside [0, nchan), a bad window,
+ * sat_lo_ppm + sat_hi_ppm >= 1e6): the previous volume is kept; PNR_E_NOMEM: the context has no volume. */
+typedef struct pnr_window {
+    int32_t lo, hi;                 /* 0 <= lo < hi <= 65535: this window; lo = hi = -1: from the stack, by: */
+    int32_t sat_lo_ppm, sat_hi_ppm; /* voxels clipped to 0 / to 255, parts per million of the channel's voxels */
+} pnr_window;                       /* NULL = {-1, -1, 0, 0} = [min, max] */
+int pnr_set_volume_u16(pnr_ctx *ctx, const uint16_t *img, int64_t w, int64_t h, int64_t l, int nchan, int channel,
+                       const pnr_window *win, int32_t *lo_out, int32_t *hi_out);
+int pnr_set_volume_u16_device(pnr_ctx *ctx, const void *dev_img, int64_t w, int64_t h, int64_t l, int nchan, int channel,
+                              const pnr_window *win, int32_t *lo_out, int32_t *hi_out);
+/* the 8-bit volume the context traces (owned or borrowed): N = w*h*l bytes */
+int pnr_get_volume(pnr_ctx *ctx, uint8_t *img);
 
 /* Frangi::frangi3d (frangi.cpp:152-289; called at Advantra_plugin.cpp:2496) followed by the
  * J -> J8 rule (:2499-2512).  Results stay in HBM; Jmin/Jmax are returned. */
@@ -293,7 +320,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

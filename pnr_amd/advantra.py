@@ -101,15 +101,18 @@ class Tracker:
 
 # ---------------------------------------------------------------------------------------------
 def _load_stack(path):
+    """(l, h, w) or, with several samples per pixel, (l, h, w, c): uint16 for 16-bit stacks (windowed to 8 bits on the GPU by
+    Context.set_volume), uint8 otherwise"""
     if path.endswith(".npy"):
         a = np.load(path)
     else:
-        from PIL import Image  # multi-page 8-bit TIFF (simple_loadimage_wrapper's role, Advantra_plugin.cpp:2241)
+        from PIL import Image  # multi-page 8- or 16-bit TIFF (simple_loadimage_wrapper's role, Advantra_plugin.cpp:2241)
         im = Image.open(path)
         a = np.stack([np.array(im.copy()) for _ in _frames(im)])
-    if a.ndim != 3:
+    if a.ndim not in (3, 4):
         raise PnrError("need a 3-D stack")
-    return np.ascontiguousarray(a.astype(np.uint8))
+    deep = a.dtype.kind == "u" and a.dtype.itemsize == 2
+    return np.ascontiguousarray(a.astype(np.uint16 if deep else np.uint8))
 
 
 def _frames(im):
@@ -163,7 +166,8 @@ def write_swc_tree(path, tree, parent, sig2r=1.0, name="Advantra", comment="", t
             f.write(f"{i} {t} {nd['x']:.3f} {nd['y']:.3f} {nd['z']:.3f} {sig2r * nd['sig']:.3f} {int(parent[i])}\n")
 
 
-def _comment(paras, channel=1):
+def _comment(paras, channel=1, window=None):
+    """the SWC comment of the C++ host (Advantra_plugin.cpp:2276-2306); `window` = (lo, hi) of a 16-bit stack"""
     keys = ["neuritesigmas", "somaradius", "tolerance", "znccth", "kappa", "step", "ni", "np", "zdist", "nodepervol", "vol"]
     s = "email: miro@braincadet.com\n#params:\n#channel=%d" % channel
     for k, v in zip(keys, paras):
@@ -171,14 +175,18 @@ def _comment(paras, channel=1):
     s += "\n#------------------------"
     for k, v in CONSTS.items():
         s += f"\n#{k}={v:g}" if isinstance(v, float) else f"\n#{k}={v}"
+    if window is not None:
+        s += "\n#bits=16\n#window=%d,%d" % tuple(window)
     return s
 
 
-def advantra_func(infiles, paras, device=0, rng_seed=42, image=None, verbose=True, out_suffix=""):
+def advantra_func(infiles, paras, device=0, rng_seed=42, image=None, verbose=True, out_suffix="", channel=1, window=None, saturate=None):
     """Advantra::dofunc(\"advantra_func\", ...) (Advantra_plugin.cpp:274-337): `infiles` = list of
     image paths (first is used), `paras` = the 11 positional parameters as strings.  Returns False
-    on a usage error (missing image / wrong parameter count), 0 on a range error, True on success.
-    Writes <inimg>_Advantra<suffix>.swc.  `image` may supply the stack directly (tests)."""
+    on a usage error (missing image / wrong parameter count, window / saturate on an 8-bit stack), 0 on a
+    range error, True on success.  Writes <inimg>_Advantra<suffix>.swc.  `image` may supply the stack
+    directly (tests).  `channel`: 1-based, the reference's channel.  A 16-bit stack is windowed to 8 bits:
+    `window` = (lo, hi), or `saturate` = (lo_pct, hi_pct) of the voxels clipped to 0 / 255 (default [min, max])."""
     import sys
     if not infiles and image is None:
         print("Need input image. ", file=sys.stderr)
@@ -200,25 +208,35 @@ def advantra_func(infiles, paras, device=0, rng_seed=42, image=None, verbose=Tru
             print(msg, file=sys.stderr)  # v3d_msg(...)
             return 0
     img = image if image is not None else _load_stack(infiles[0])
+    nch = img.shape[3] if img.ndim == 4 else 1
+    if not 1 <= channel <= nch:
+        print("Invalid channel number.", file=sys.stderr)  # Advantra_plugin.cpp:2245-2249
+        return 0
+    deep = img.dtype == np.uint16
+    if (window is not None or saturate is not None) and (not deep or (window is not None and saturate is not None)):
+        print("--window / --saturate: one of them, and only for a 16-bit stack", file=sys.stderr)
+        return False
+    win = window if window is not None else ({"saturate": tuple(saturate)} if saturate is not None else None)
     p = make_params(sigmas=sig, somaradius=somaradius, tolerance=tolerance, znccth=znccth, kappa=kappa, step=step, ni=ni,
                     np_=npc, zdist=zdist, nodepervol=nodepervol, vol=vol, rng_seed=rng_seed)
     ctx = Context(p, device)
-    res = run_pipeline(ctx, img, verbose=verbose)
+    res = run_pipeline(ctx, img, verbose=verbose, channel=channel - 1, window=win)
     if infiles:
         out = f"{infiles[0]}_Advantra{out_suffix}.swc"
-        write_swc_tree(out, res["tree"], res["parent"], comment=_comment(paras))
+        write_swc_tree(out, res["tree"], res["parent"], comment=_comment(paras, channel, ctx.window if deep else None))
         res["swc"] = out
     advantra_func.last = res
     ctx.close()
     return True
 
 
-def run_pipeline(ctx, img, verbose=False, max_seeds=None, one_shot=False, reconstruct=True):
+def run_pipeline(ctx, img, verbose=False, max_seeds=None, one_shot=False, reconstruct=True, channel=0, window=None):
     """reconstruction_func's hot path (Advantra_plugin.cpp:2488-2710): Frangi -> J8 -> seeds ->
-    score/filter/sort -> trace all seeds on the GPU -> host replay."""
+    score/filter/sort -> trace all seeds on the GPU -> host replay.  A uint16 `img` is windowed to 8 bits
+    first (Context.set_volume: `channel` 0-based, `window`)."""
     import time
     t = [time.time()]
-    ctx.set_volume(img) if isinstance(img, np.ndarray) else None
+    ctx.set_volume(img, channel=channel, window=window) if isinstance(img, np.ndarray) else None
     soma = ctx.soma() if ctx.p.somaradius > 0 else None  # SOMA EXTR. (Advantra_plugin.cpp:2426-2486), before Frangi
     t[0] = time.time() if soma is None else t[0]
     jmin, jmax = ctx.frangi(); t.append(time.time())

@@ -7,6 +7,7 @@
 #include "stream_sched.h"
 #include "../host/reconstruct.h"
 #include "recon.h"
+#include "volume.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -286,6 +287,74 @@ int pnr_set_volume_device(pnr_ctx *c, const void *dev_img, int64_t w, int64_t h,
     hipFree(c->d_img_owned);
     c->d_img_owned = nullptr;
     c->d_img = (const uint8_t *)dev_img;
+    return PNR_OK;
+}
+
+// pnr_set_volume_u16[_device]: arguments first (a bad one keeps the previous volume), then the dimensions, then the map (volume.hip)
+static int set_volume_u16(pnr_ctx *c, const void *img, bool host, int64_t w, int64_t h, int64_t l, int nchan, int channel,
+                          const pnr_window *win, int32_t *lo_out, int32_t *hi_out)
+{
+    PNR_REQUIRE(c && img, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(nchan >= 1 && nchan <= (1 << 16), PNR_E_ARG, "nchan = %d outside [1, 65536]", nchan);
+    PNR_REQUIRE(channel >= 0 && channel < nchan, PNR_E_ARG, "channel %d outside [0, %d)", channel, nchan);
+    PNR_REQUIRE(((uintptr_t)img & 1) == 0, PNR_E_ARG, "16-bit image not 2-byte aligned");
+    const pnr_window wd = win ? *win : pnr_window{-1, -1, 0, 0};
+    if (wd.lo == -1 && wd.hi == -1) {
+        PNR_REQUIRE(wd.sat_lo_ppm >= 0 && wd.sat_hi_ppm >= 0 && (int64_t)wd.sat_lo_ppm + wd.sat_hi_ppm < 1000000, PNR_E_ARG,
+                    "saturation %d + %d ppm: each >= 0, together below 1e6", wd.sat_lo_ppm, wd.sat_hi_ppm);
+    } else {
+        PNR_REQUIRE(wd.lo >= 0 && wd.lo < wd.hi && wd.hi <= 65535, PNR_E_ARG, "window [%d, %d]: need 0 <= lo < hi <= 65535 (or -1, -1)", wd.lo, wd.hi);
+        PNR_REQUIRE(wd.sat_lo_ppm == 0 && wd.sat_hi_ppm == 0, PNR_E_ARG, "a fixed window takes no saturation");
+    }
+    int rc = set_dims(c, w, h, l);
+    if (rc) return rc;
+    c->d_img = nullptr; // no volume until the map below has succeeded
+    const uint16_t *src = (const uint16_t *)img;
+    void *d_up = nullptr;
+    if (host) {
+        const size_t bytes = (size_t)c->N * (size_t)nchan * 2;
+        if (hipMalloc(&d_up, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("pnr_set_volume_u16: device allocation of %zu B for the 16-bit stack failed", bytes);
+            return PNR_E_NOMEM;
+        }
+        if (hipMemcpyAsync(d_up, img, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            hipFree(d_up);
+            set_error("pnr_set_volume_u16: upload of %zu B failed", bytes);
+            return PNR_E_HIP;
+        }
+        src = (const uint16_t *)d_up;
+    }
+    rc = pnr_volume_u16_run(c, src, nchan, channel, wd, lo_out, hi_out);
+    if (d_up) {
+        (void)hipStreamSynchronize(c->stream);
+        hipFree(d_up);
+    }
+    if (rc) return rc;
+    c->d_img = c->d_img_owned;
+    return PNR_OK;
+}
+
+int pnr_set_volume_u16(pnr_ctx *c, const uint16_t *img, int64_t w, int64_t h, int64_t l, int nchan, int channel, const pnr_window *win,
+                       int32_t *lo_out, int32_t *hi_out)
+{
+    return set_volume_u16(c, img, true, w, h, l, nchan, channel, win, lo_out, hi_out);
+}
+
+int pnr_set_volume_u16_device(pnr_ctx *c, const void *dev_img, int64_t w, int64_t h, int64_t l, int nchan, int channel,
+                              const pnr_window *win, int32_t *lo_out, int32_t *hi_out)
+{
+    return set_volume_u16(c, dev_img, false, w, h, l, nchan, channel, win, lo_out, hi_out);
+}
+
+int pnr_get_volume(pnr_ctx *c, uint8_t *img)
+{
+    PNR_REQUIRE(c && img, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_get_volume: no volume set");
+    PNR_HIP(hipSetDevice(c->device));
+    PNR_HIP(hipMemcpyAsync(img, c->d_img, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+    PNR_HIP(hipStreamSynchronize(c->stream));
     return PNR_OK;
 }
 

@@ -1,0 +1,9 @@
+// volume.h -- 16-bit (and multi-channel) stacks windowed to the 8-bit volume the pipeline traces (volume.hip), behind
+// pnr_set_volume_u16[_device].
+#pragma once
+#include "ctx.h"
+
+// Maps channel `channel` of the u16 device buffer d_src (voxel i at element i * nchan + channel, c->N voxels: set_dims has run)
+// into the context's owned u8 volume c->d_img_owned, on c->stream, with the window `win` (validated by the caller; lo = hi = -1:
+// from the stack).  Returns the window used.  Allocation failures return PNR_E_NOMEM; c->d_img is not touched.
+int pnr_volume_u16_run(pnr_ctx *c, const uint16_t *d_src, int nchan, int channel, const pnr_window &win, int32_t *lo_out, int32_t *hi_out);

@@ -5,8 +5,13 @@
 // (-p takes the rest of the line, as in vaa3d: put the driver's own flags before it)
 //   --ranks N [--share-gpu]: N processes of this host, one GPU each (device = -g + rank; --share-gpu: all on -g, for rehearsals),
 //   reconstruct the ONE stack together; the processes are forked before anything touches a GPU and joined through shared memory.
+//   --channel C: the channel to trace (1-based, default 1: the reference's `channel`); --raw-type u8|u16 (u16: little-endian);
+//   a 16-bit stack is windowed to 8 bits on the GPU: [min, max] by default, --window LO,HI, or --saturate LO,HI (percent of the voxels
+//   clipped to 0 / to 255, up to 4 decimals);  --info: print {"w","h","l","bits","channels","channel","min","max","sum"} of the
+//   stack's channel as one JSON line and exit (no GPU).
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +21,37 @@
 #include <time.h>
 #include <unistd.h>
 
+// "a,b" of two non-negative decimals with at most `decimals` digits after the point -> a and b times 10^decimals
+static bool parse_pair(const char *txt, int decimals, long long &a, long long &b)
+{
+    long long v[2] = {0, 0};
+    const char *q = txt;
+    for (int k = 0; k < 2; k++) {
+        if (!isdigit((unsigned char)*q)) return false;
+        long long x = 0;
+        int nd = 0;
+        for (; isdigit((unsigned char)*q); q++) {
+            if (++nd > 9) return false;
+            x = 10 * x + (*q - '0');
+        }
+        int frac = 0;
+        if (*q == '.' && decimals > 0) {
+            q++;
+            for (; isdigit((unsigned char)*q); q++) {
+                if (++frac > decimals) return false;
+                x = 10 * x + (*q - '0');
+            }
+        }
+        for (; frac < decimals; frac++) x *= 10;
+        v[k] = x;
+        if (k == 0 && *q++ != ',') return false;
+    }
+    if (*q) return false;
+    a = v[0];
+    b = v[1];
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     std::vector<char *> infiles, paras;
@@ -23,7 +59,40 @@ int main(int argc, char **argv)
     int device = 0, ranks = 1;
     bool share_gpu = false;
     std::string transport = "shm";
+    bool info = false, window = false, saturate = false;
+    advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
+        if (!strcmp(argv[i], "--info")) { info = true; continue; }
+        if (!strcmp(argv[i], "--channel") && i + 1 < argc) {
+            char *end = nullptr;
+            const long c = strtol(argv[++i], &end, 10);
+            if (!*argv[i] || *end || c < 1 || c > 65536) { fprintf(stderr, "--channel C: a channel number from 1\n"); return 1; }
+            S0.channel = (int)c;
+            continue;
+        }
+        if (!strcmp(argv[i], "--raw-type") && i + 1 < argc) {
+            const std::string t = argv[++i];
+            if (t != "u8" && t != "u16") { fprintf(stderr, "--raw-type: u8 or u16\n"); return 1; }
+            S0.raw_u16 = t == "u16";
+            continue;
+        }
+        if (!strcmp(argv[i], "--window") && i + 1 < argc) {
+            long long lo = 0, hi = 0;
+            if (!parse_pair(argv[++i], 0, lo, hi) || lo >= hi || hi > 65535) { fprintf(stderr, "--window LO,HI: integers with 0 <= LO < HI <= 65535\n"); return 1; }
+            S0.window = pnr_window{(int32_t)lo, (int32_t)hi, 0, 0};
+            S0.windowed = window = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--saturate") && i + 1 < argc) {
+            long long lo = 0, hi = 0; // parts per million
+            if (!parse_pair(argv[++i], 4, lo, hi) || lo + hi >= 1000000) {
+                fprintf(stderr, "--saturate LO,HI: percentages of the voxels clipped to 0 / to 255, up to 4 decimals, LO + HI below 100\n");
+                return 1;
+            }
+            S0.window = pnr_window{-1, -1, (int32_t)lo, (int32_t)hi};
+            S0.windowed = saturate = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--ranks") && i + 1 < argc) { ranks = atoi(argv[++i]); continue; }
         if (!strcmp(argv[i], "--share-gpu")) { share_gpu = true; continue; }
         if (!strcmp(argv[i], "--exchange") && i + 1 < argc) { transport = argv[++i]; continue; }
@@ -38,6 +107,11 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-d") && i + 1 < argc) { raw_dims = argv[++i]; continue; }
         if (!strcmp(argv[i], "-i")) { while (i + 1 < argc && argv[i + 1][0] != '-') infiles.push_back(argv[++i]); continue; }
         if (!strcmp(argv[i], "-p")) { while (i + 1 < argc) paras.push_back(argv[++i]); continue; }
+    }
+    if (window && saturate) { fprintf(stderr, "--window and --saturate: one of them\n"); return 1; }
+    if (info) {
+        if (infiles.empty()) { fprintf(stderr, "--info needs -i <inimg_file>\n"); return 1; }
+        return advantra::print_info(infiles[0], raw_dims, S0.channel - 1, S0.raw_u16) ? 0 : 1;
     }
     if (func == "help") { // funclist(): advantra_func, help (Advantra_plugin.cpp:157-162)
         advantra::print_help();

@@ -31,7 +31,7 @@ void print_help()
     printf("**** usage of Advantra tracing ****\n");
     printf("vaa3d -x Advantra -f advantra_func -i <inimg_file> -p <neuritesigmas> <somaradius> <tolerance> <znccth> <kappa> "
            "<step> <ni> <np> <zdist> <nodepervol> <vol>\n");
-    printf("inimg_file     The input image (8-bit multi-page TIFF)\n");
+    printf("inimg_file     The input image (8- or 16-bit multi-page TIFF; 16-bit stacks are windowed to 8 bits)\n");
     printf("neuritesigmas  Comma delimited list of gaussian cross-section sigmas, e.g. 2,4,6\n");
     printf("somaradius     Soma radius (0: no soma)\n");
     printf("tolerance      Seed extraction (find maxima) tolerance\n");
@@ -46,7 +46,8 @@ void print_help()
     printf("outswc_file    <inimg_file>_Advantra.swc\n");
 }
 
-// ---- minimal baseline TIFF reader: 8-bit grayscale, uncompressed strips, any number of pages ----
+// ---- baseline TIFF reader: 8- or 16-bit unsigned samples in either byte order, uncompressed strips, any number of pages; several
+// samples per pixel (chunky or planar) or ImageJ hyperstack channels, of which one is kept ----
 namespace {
 struct Reader {
     std::vector<unsigned char> buf;
@@ -71,21 +72,58 @@ struct Reader {
         return v;
     }
 };
+
+struct Page {
+    uint32_t w = 0, h = 0, bps = 1, comp = 1, spp = 1, planar = 1, fmt = 1;
+    bool mixed = false; // BitsPerSample / SampleFormat differ between the samples of a pixel
+    std::vector<uint32_t> soff, scnt;
+};
+
+// the whole file in one read
+bool read_file(const std::string &path, std::vector<unsigned char> &buf, std::string &err)
+{
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) { err = "cannot open " + path; return false; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); err = "cannot open " + path; return false; }
+    buf.resize((size_t)sb.st_size);
+    size_t got = 0;
+    while (got < buf.size()) {
+        const ssize_t n = read(fd, buf.data() + got, buf.size() - got);
+        if (n <= 0) break;
+        got += (size_t)n;
+    }
+    close(fd);
+    if (got != buf.size()) { err = "cannot read " + path; return false; }
+    return true;
+}
+
+// "key=value" of an ImageJ description (0 when absent)
+long long imagej_value(const std::string &desc, const std::string &key)
+{
+    size_t at = 0;
+    while ((at = desc.find(key + "=", at)) != std::string::npos) {
+        if (at == 0 || desc[at - 1] == '\n') return atoll(desc.c_str() + at + key.size() + 1);
+        at++;
+    }
+    return 0;
+}
 } // namespace
 
-static bool load_tiff(const std::string &path, Stack &out, std::string &err)
+static bool load_tiff(const std::string &path, int channel, Stack &out, std::string &err)
 {
     Reader r;
-    std::ifstream f(path, std::ios::binary);
-    if (!f) { err = "cannot open " + path; return false; }
-    r.buf.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    if (!read_file(path, r.buf, err)) return false;
     if (r.buf.size() < 8) { err = "not a TIFF"; return false; }
     if (r.buf[0] == 'M' && r.buf[1] == 'M') r.be = true;
     else if (!(r.buf[0] == 'I' && r.buf[1] == 'I')) { err = "not a TIFF"; return false; }
     if (r.u16(2) != 42) { err = "not a baseline TIFF (BigTIFF is not supported)"; return false; }
     size_t ifd = r.u32(4);
     out.data.clear();
+    out.data16.clear();
     out.w = out.h = out.l = 0;
+    std::vector<Page> pages;
+    std::string desc; // ImageDescription of the first page
     std::vector<size_t> seen; // IFD offsets visited: a chain that revisits one would never end
     while (ifd != 0) {
         if (ifd + 2 > r.buf.size()) { err = "truncated TIFF"; return false; }
@@ -93,79 +131,167 @@ static bool load_tiff(const std::string &path, Stack &out, std::string &err)
         seen.push_back(ifd);
         if (seen.size() > (1u << 20)) { err = "TIFF with more than 2^20 pages"; return false; }
         const uint16_t n = r.u16(ifd);
-        uint32_t w = 0, h = 0, bps = 1, comp = 1, spp = 1, rps = 0xffffffffu;
-        std::vector<uint32_t> soff, scnt;
+        Page pg;
         for (uint16_t e = 0; e < n; e++) {
             const size_t o = ifd + 2 + 12 * (size_t)e;
             if (o + 12 > r.buf.size()) { err = "truncated TIFF"; return false; }
             const uint16_t tag = r.u16(o), type = r.u16(o + 2);
             const uint32_t cnt = r.u32(o + 4);
+            if (tag == 270 && !pages.empty()) continue; // only the first page's description is read
             const std::vector<uint32_t> v = r.values(type, cnt, o + 8);
             if (v.empty()) continue;
+            const bool same = std::all_of(v.begin(), v.end(), [&](uint32_t x) { return x == v[0]; });
             switch (tag) {
-            case 256: w = v[0]; break;
-            case 257: h = v[0]; break;
-            case 258: bps = v[0]; break;
-            case 259: comp = v[0]; break;
-            case 273: soff = v; break;
-            case 277: spp = v[0]; break;
-            case 278: rps = v[0]; break;
-            case 279: scnt = v; break;
+            case 256: pg.w = v[0]; break;
+            case 257: pg.h = v[0]; break;
+            case 258: pg.bps = v[0]; pg.mixed |= !same; break;
+            case 259: pg.comp = v[0]; break;
+            case 270: if (type == 2) desc.assign(v.begin(), std::find(v.begin(), v.end(), 0u)); break;
+            case 273: pg.soff = v; break;
+            case 277: pg.spp = v[0]; break;
+            case 279: pg.scnt = v; break;
+            case 284: pg.planar = v[0]; break;
+            case 339: pg.fmt = v[0]; pg.mixed |= !same; break;
             }
         }
-        if (bps != 8 || spp != 1) { err = "only 8-bit single-channel stacks are supported (the reference assumes uint8, Advantra_plugin.cpp:2255)"; return false; }
-        if (comp != 1) { err = "compressed TIFF is not supported"; return false; }
-        if (w == 0 || h == 0 || (uint64_t)w * h > r.buf.size()) { err = "TIFF page larger than the file"; return false; } // uncompressed: w*h bytes must be in the file
-        if (out.l == 0) { out.w = w; out.h = h; }
-        else if (w != out.w || h != out.h) { err = "pages of different size"; return false; }
-        (void)rps;
-        size_t got = 0;
-        const size_t page = (size_t)w * h;
-        const size_t base = out.data.size();
-        out.data.resize(base + page);
-        for (size_t s = 0; s < soff.size() && got < page; s++) {
-            size_t c = (s < scnt.size()) ? scnt[s] : page - got;
-            c = std::min(c, page - got);
-            if ((size_t)soff[s] + c > r.buf.size()) { err = "truncated TIFF strip"; return false; }
-            std::memcpy(out.data.data() + base + got, r.buf.data() + soff[s], c);
-            got += c;
-        }
-        if (got != page) { err = "TIFF page shorter than width*height"; return false; }
-        out.l++;
+        if (pg.fmt != 1) { err = "only unsigned integer samples are supported (SampleFormat = " + std::to_string(pg.fmt) + ")"; return false; }
+        if (pg.bps != 8 && pg.bps != 16) { err = "only 8- and 16-bit samples are supported (BitsPerSample = " + std::to_string(pg.bps) + ")"; return false; }
+        if (pg.mixed) { err = "samples of different depth or format in one pixel"; return false; }
+        if (pg.comp != 1) { err = "compressed TIFF is not supported"; return false; }
+        if (pg.spp < 1) { err = "SamplesPerPixel = 0"; return false; }
+        // uncompressed: the page's samples must be in the file
+        if (pg.w == 0 || pg.h == 0 || (uint64_t)pg.w * pg.h * pg.spp * (pg.bps / 8) > r.buf.size()) { err = "TIFF page larger than the file"; return false; }
+        if (!pages.empty() && (pg.w != pages[0].w || pg.h != pages[0].h)) { err = "pages of different size"; return false; }
+        if (!pages.empty() && (pg.bps != pages[0].bps || pg.spp != pages[0].spp)) { err = "pages of different sample layout"; return false; }
+        pages.push_back(std::move(pg));
         const size_t nx = ifd + 2 + 12 * (size_t)n;
         if (nx + 4 > r.buf.size()) break;
         ifd = r.u32(nx);
     }
+    if (pages.empty()) { err = "TIFF without pages"; return false; }
+    // ImageJ hyperstack: the pages run channel-fastest (c0 z0, c1 z0, ..., c0 z1, ...)
+    long long nchan_ij = 1;
+    if (desc.rfind("ImageJ=", 0) == 0) {
+        const long long frames = imagej_value(desc, "frames");
+        if (frames > 1) { err = "time series are not supported (ImageJ frames=" + std::to_string(frames) + ")"; return false; }
+        nchan_ij = std::max(1LL, imagej_value(desc, "channels"));
+        if (nchan_ij > 1 && pages[0].spp > 1) { err = "ImageJ hyperstack with several samples per pixel is not supported"; return false; }
+        if ((long long)pages.size() % nchan_ij != 0) { err = "ImageJ hyperstack: " + std::to_string(pages.size()) + " pages are not a multiple of channels=" + std::to_string(nchan_ij); return false; }
+    }
+    const int spp = (int)pages[0].spp, B = (int)pages[0].bps / 8;
+    out.bits = 8 * B;
+    out.channels = nchan_ij > 1 ? (int)nchan_ij : spp;
+    if (channel < 0 || channel >= out.channels) { err = "Invalid channel number."; return false; } // Advantra_plugin.cpp:2245-2249
+    out.channel = channel;
+    const uint32_t w = pages[0].w, h = pages[0].h;
+    const size_t npix = (size_t)w * h;
+    const size_t nplanes = pages.size() / (size_t)nchan_ij;
+    // every sample kept is in the file: reserving for them is bounded by the file's size
+    const size_t reserve = std::min(nplanes * npix, r.buf.size() / (size_t)B);
+    if (B == 1) out.data.reserve(reserve);
+    else out.data16.reserve(reserve);
+    for (size_t z = 0; z < nplanes; z++) {
+        const Page &pg = pages[nchan_ij > 1 ? z * (size_t)nchan_ij + (size_t)channel : z];
+        // the page's stream of samples: interleaved (chunky, stride spp) or, planar, the strips of the kept channel's plane alone
+        int stride = nchan_ij > 1 ? 1 : spp, sel = nchan_ij > 1 ? 0 : channel;
+        size_t s0 = 0, s1 = pg.soff.size();
+        if (pg.planar == 2 && spp > 1) {
+            if (pg.soff.size() % (size_t)spp != 0) { err = "planar TIFF: StripOffsets is not a multiple of SamplesPerPixel"; return false; }
+            const size_t sp = pg.soff.size() / (size_t)spp;
+            s0 = sp * (size_t)channel;
+            s1 = s0 + sp;
+            stride = 1;
+            sel = 0;
+        }
+        const size_t need = npix * (size_t)stride * (size_t)B; // bytes of the stream
+        const size_t base = z * npix;
+        if (B == 1) out.data.resize(base + npix);
+        else out.data16.resize(base + npix);
+        size_t pos = 0;
+        for (size_t s = s0; s < s1 && pos < need; s++) {
+            size_t c = (s < pg.scnt.size()) ? pg.scnt[s] : need - pos; // (StripByteCounts runs parallel to StripOffsets)
+            c = std::min(c, need - pos);
+            if ((size_t)pg.soff[s] + c > r.buf.size()) { err = "truncated TIFF strip"; return false; }
+            if (c % (size_t)B) { err = "TIFF strip ends inside a sample"; return false; }
+            const unsigned char *src = r.buf.data() + pg.soff[s];
+            if (stride == 1 && B == 1) std::memcpy(out.data.data() + base + pos, src, c);
+            else if (stride == 1 && !r.be) std::memcpy(out.data16.data() + base + pos / 2, src, c); // (little-endian host)
+            else { // the kept channel's samples of this strip, de-interleaved and in the host's byte order
+                const size_t q0 = pos / (size_t)B, q1 = (pos + c) / (size_t)B;
+                for (size_t k = q0 + ((size_t)sel + (size_t)stride - q0 % (size_t)stride) % (size_t)stride; k < q1; k += (size_t)stride) {
+                    const size_t o = pg.soff[s] + (k * (size_t)B - pos);
+                    if (B == 1) out.data[base + k / (size_t)stride] = r.buf[o];
+                    else out.data16[base + k / (size_t)stride] = r.u16(o);
+                }
+            }
+            pos += c;
+        }
+        if (pos != need) { err = "TIFF page shorter than width*height"; return false; }
+    }
+    out.w = w; out.h = h; out.l = (long long)nplanes;
     return out.l > 0;
 }
 
-bool load_stack(const std::string &path, const std::string &raw_dims, Stack &out, std::string &err)
+bool load_stack(const std::string &path, const std::string &raw_dims, Stack &out, std::string &err, int channel, bool raw_u16)
 {
     const bool raw = path.size() > 4 && path.substr(path.size() - 4) == ".raw";
-    if (!raw) return load_tiff(path, out, err);
+    if (!raw) return load_tiff(path, channel, out, err);
     long long w = 0, h = 0, l = 0;
     if (sscanf(raw_dims.c_str(), "%lld,%lld,%lld", &w, &h, &l) != 3 || w <= 0 || h <= 0 || l <= 0) {
         err = "raw stacks need -d w,h,l";
         return false;
     }
+    if (channel != 0) { err = "Invalid channel number."; return false; } // a raw stack has one channel
+    const long long B = raw_u16 ? 2 : 1, bytes = w * h * l * B;
+    out.bits = (int)(8 * B);
+    out.channels = 1;
+    out.channel = 0;
     const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) { err = "cannot open " + path; return false; }
     struct stat sb;
-    if (fstat(fd, &sb) != 0 || (long long)sb.st_size < w * h * l) { close(fd); err = "raw file shorter than w*h*l"; return false; }
-    void *m = mmap(nullptr, (size_t)(w * h * l), PROT_READ, MAP_PRIVATE, fd, 0);
+    if (fstat(fd, &sb) != 0 || (long long)sb.st_size < bytes) { close(fd); err = raw_u16 ? "raw file shorter than 2*w*h*l" : "raw file shorter than w*h*l"; return false; }
+    void *m = mmap(nullptr, (size_t)bytes, PROT_READ, MAP_PRIVATE, fd, 0);
     close(fd);
     if (m == MAP_FAILED) { // (a file system that cannot map: read it)
         std::ifstream f(path, std::ios::binary);
         if (!f) { err = "cannot open " + path; return false; }
-        out.data.resize((size_t)(w * h * l));
-        f.read((char *)out.data.data(), (std::streamsize)out.data.size());
-        if ((long long)f.gcount() != w * h * l) { err = "raw file shorter than w*h*l"; return false; }
+        char *dst = nullptr;
+        if (raw_u16) { out.data16.resize((size_t)(w * h * l)); dst = (char *)out.data16.data(); } // (u16 little-endian = the host's order)
+        else { out.data.resize((size_t)(w * h * l)); dst = (char *)out.data.data(); }
+        f.read(dst, (std::streamsize)bytes);
+        if ((long long)f.gcount() != bytes) { err = "raw file shorter than w*h*l"; return false; }
     } else {
         out.view = (const unsigned char *)m;
-        out.map_len = (size_t)(w * h * l);
+        out.map_len = (size_t)bytes;
         (void)madvise(m, out.map_len, MADV_SEQUENTIAL);
     }
     out.w = w; out.h = h; out.l = l;
+    return true;
+}
+
+bool print_info(const std::string &path, const std::string &raw_dims, int channel, bool raw_u16)
+{
+    Stack st;
+    std::string err;
+    if (!load_stack(path, raw_dims, st, err, channel, raw_u16)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    const size_t n = (size_t)(st.w * st.h * st.l);
+    unsigned mn = 0xffffffffu, mx = 0;
+    unsigned long long sum = 0;
+    auto scan = [&](const auto *p) {
+        for (size_t i = 0; i < n; i++) {
+            const unsigned v = p[i];
+            mn = std::min(mn, v);
+            mx = std::max(mx, v);
+            sum += v;
+        }
+    };
+    if (st.bits == 16) scan(st.samples16());
+    else scan(st.bytes());
+    printf("{\"w\": %lld, \"h\": %lld, \"l\": %lld, \"bits\": %d, \"channels\": %d, \"channel\": %d, \"min\": %u, \"max\": %u, \"sum\": %llu}\n", st.w, st.h,
+           st.l, st.bits, st.channels, channel + 1, mn, mx, sum);
     return true;
 }
 
@@ -276,15 +402,17 @@ int parse_params(const std::vector<std::string> &paras, pnr_params &p, std::stri
     return 0;
 }
 
-static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p)
+// window: the (lo, hi) a 16-bit stack was windowed with (nullptr: 8-bit input)
+static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p, const int32_t *window)
 {
     static const char *keys[] = {"neuritesigmas", "somaradius", "tolerance", "znccth", "kappa", "step", "ni", "np", "zdist", "nodepervol", "vol"};
     std::stringstream c;
-    c << "email: miro@braincadet.com\n#params:\n#channel=1"; // Advantra_plugin.cpp:2276-2306
+    c << "email: miro@braincadet.com\n#params:\n#channel=" << settings().channel; // Advantra_plugin.cpp:2276-2306
     for (int i = 0; i < nrInputParams; i++) c << "\n#" << keys[i] << "=" << paras[i];
     c << "\n#------------------------\n#Kc=" << p.Kc << "\n#neff_ratio=" << p.neff_ratio << "\n#frangi_alfa=" << p.alpha
       << "\n#frangi_beta=" << p.beta << "\n#frangi_C=" << p.C << "\n#MAX_TRACE_COUNT=" << p.max_trace_count
       << "\n#EPSILON2=0.0001\n#REFINE_ITER=4\n#SIG2RADIUS=1.5\n#TRACE_RSMPL=1\n#GROUP_RADIUS=2\n#ENFORCE_SINGLE_TREE=0\n#TREE_SIZE_MIN=10\n#TAIL_SIZE_MIN=2";
+    if (window) c << "\n#bits=16\n#window=" << window[0] << "," << window[1];
     return c.str();
 }
 
@@ -310,16 +438,23 @@ bool advantra_func(const std::vector<char *> &infiles, const std::vector<char *>
     }
     Stack st;
     const auto tl0 = std::chrono::steady_clock::now();
-    if (!load_stack(infiles[0], raw_dims, st, err)) {
+    const Settings &S = settings();
+    if (!load_stack(infiles[0], raw_dims, st, err, S.channel - 1, S.raw_u16)) {
         fprintf(stderr, "%s\n", err.c_str());
         return true;
+    }
+    if (S.windowed && st.bits != 16) { // 8-bit input is taken as it is, as the reference does
+        fprintf(stderr, "--window / --saturate need a 16-bit stack (8-bit input is never windowed)\n");
+        return false;
     }
     Result local;
     Result *R = result ? result : &local;
     const double t_load = std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count();
     // a failure of the device library (no GPU, out of memory, a failed exchange) has no counterpart in the reference's contract:
     // it is reported on stderr by reconstruction_func and makes the function -- and the CLI's exit status -- fail
-    if (!reconstruction_func(st.bytes(), st.w, st.h, st.l, infiles[0], paras, p, device, R)) return false;
+    const uint16_t *deep = st.bits == 16 ? st.samples16() : nullptr;
+    if (!reconstruction_func(deep ? nullptr : st.bytes(), st.w, st.h, st.l, infiles[0], paras, p, device, R, deep, S.windowed ? &S.window : nullptr))
+        return false;
     if (settings().rank == 0) {
         // what a user of advantra_func waits for (Advantra_plugin.cpp:2241 load, :2183-2731 reconstruction_func, :2164 the SWC)
         R->t_load = t_load;
@@ -352,7 +487,8 @@ bool allgather_bytes(pnr_allgather_fn fn, void *user, int world, const void *sen
 } // namespace
 
 bool reconstruction_func(const unsigned char *data1d, long long w, long long h, long long l, const std::string &inimg_file,
-                         const std::vector<std::string> &paras, pnr_params p, int device, Result *result)
+                         const std::vector<std::string> &paras, pnr_params p, int device, Result *result, const uint16_t *data16,
+                         const pnr_window *win)
 {
     const int rank = settings().rank, world = settings().world;
     // the transport of the sharded path's collectives
@@ -393,8 +529,10 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     std::vector<pnr_seed> seeds;
     int64_t nfound = 0, nseeds = 0;
     auto t0 = clk::now(), t1 = t0, t2 = t0;
+    int32_t window[2] = {-1, -1}; // 16-bit input: the window it was mapped with
+    std::vector<unsigned char> mapped;
     if (!sharded) {
-        ok = pnr_set_volume(ctx, data1d, w, h, l) == PNR_OK;
+        ok = (data16 ? pnr_set_volume_u16(ctx, data16, w, h, l, 1, 0, win, &window[0], &window[1]) : pnr_set_volume(ctx, data1d, w, h, l)) == PNR_OK;
         if (settings().timing) fprintf(stderr, "[pnr host] context %.3f s, upload of %.2f GB %.3f s\n", secs(t_begin, t_created), (double)(w * h * l) / 1e9, secs(t_created, clk::now()));
         if (ok) run_soma();
         t0 = clk::now();
@@ -410,6 +548,11 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
             seeds.resize((size_t)nseeds);
         }
     } else {
+        if (data16) { // every rank maps the whole stack once and runs the 8-bit path on it: slabs and stack share one window
+            mapped.resize((size_t)(w * h * l));
+            ok = pnr_set_volume_u16(ctx, data16, w, h, l, 1, 0, win, &window[0], &window[1]) == PNR_OK && pnr_get_volume(ctx, mapped.data()) == PNR_OK;
+            data1d = mapped.data();
+        }
         // this rank's z-slab with its halo (the z pass of the widest Gaussian + the radius-2 Hessian stencil): exact Frangi / seeds
         // of the planes it owns, no halo exchange -- every rank has the whole stack
         float smax = 0;
@@ -421,7 +564,7 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
         int64_t nmine = 0;
         std::vector<pnr_seed> mine;
         if (z1 > z0) {
-            ok = pnr_set_volume(ctx, data1d + zlo * w * h, w, h, zhi - zlo) == PNR_OK;
+            ok = ok && pnr_set_volume(ctx, data1d + zlo * w * h, w, h, zhi - zlo) == PNR_OK;
             ok = ok && pnr_frangi_slab(ctx, z0 - zlo, z1 - zlo, &mm[0], &mm[1]) == PNR_OK;
         }
         // the 2-float all-reduce: one ncclAllReduce over RCCL, an all-gather + local reduction through shared memory
@@ -551,7 +694,7 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     auto t5 = clk::now();
     R.t_recon = secs(t4, t5);
     R.swc_path = inimg_file + (settings().single_tree ? "_Advantra1.swc" : "_Advantra.swc"); // :2152 / :2164
-    save_treelist(R.tree, R.parent, R.swc_path, -1, 1.f, "Advantra", swc_comment(paras, p));
+    save_treelist(R.tree, R.parent, R.swc_path, -1, 1.f, "Advantra", swc_comment(paras, p, data16 ? window : nullptr));
     if (settings().save_midres) { // the saveMidres taps of reconstruct() (:2098-2141)
         save_nodelist(R.nodes, R.links, inimg_file + "_n0_.swc");
         static const char *const names[] = {"", "_n0res_.swc", "_n1_.swc", "_n2_.swc", "_n2tree_.swc"};

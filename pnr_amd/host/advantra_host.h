@@ -14,12 +14,16 @@
 namespace advantra {
 
 struct Stack {
-    std::vector<unsigned char> data; // x fastest: i = z*w*h + y*w + x (TIFF: the pages copied out of the file)
+    std::vector<unsigned char> data; // 8-bit: x fastest: i = z*w*h + y*w + x (TIFF: the kept channel copied out of the file)
+    std::vector<uint16_t> data16;    // 16-bit: the same, in the host's byte order
     long long w = 0, h = 0, l = 0;
+    int bits = 8;                    // bits per sample: 8 or 16
+    int channels = 1, channel = 0;   // channels of the file (samples per pixel, or an ImageJ hyperstack's channels); the one kept (0-based)
     // a raw stack is mapped, not copied: 1 GiB through a zero-filled vector cost a quarter of a second that the upload pays anyway
     const unsigned char *view = nullptr;
     size_t map_len = 0;
     const unsigned char *bytes() const { return view ? view : data.data(); }
+    const uint16_t *samples16() const { return view ? (const uint16_t *)view : data16.data(); }
     Stack() = default;
     Stack(const Stack &) = delete;
     Stack &operator=(const Stack &) = delete;
@@ -56,13 +60,24 @@ struct Settings {
     // 128-byte ncclUniqueId).  force_shard: the sharded code path also for a world of one (the only RCCL world a one-GPU box can form).
     pnr_rccl_exchange *rccl = nullptr;
     bool force_shard = false;
+    // the input: --channel C (1-based; the reference's channel), --raw-type u16, and for a 16-bit stack --window LO,HI or --saturate LO,HI
+    // (windowed: either was given; window as pnr_set_volume_u16 takes it)
+    int channel = 1;
+    bool raw_u16 = false;
+    bool windowed = false;
+    pnr_window window = {-1, -1, 0, 0};
 };
 Settings &settings();
 
 void print_help();
-// simple_loadimage_wrapper's role (Advantra_plugin.cpp:2241): 8-bit multi-page uncompressed TIFF, or
-// ".raw" (u8, dims from `raw_dims` = "w,h,l").  Returns false with a message in `err`.
-bool load_stack(const std::string &path, const std::string &raw_dims, Stack &out, std::string &err);
+// simple_loadimage_wrapper's role (Advantra_plugin.cpp:2241): a multi-page uncompressed TIFF of 8- or 16-bit unsigned samples
+// (either byte order; several samples per pixel, chunky or planar, or an ImageJ hyperstack's channels), or ".raw" (u8, or u16
+// little-endian with raw_u16; dims from `raw_dims` = "w,h,l").  Keeps channel `channel` (0-based) only.  Returns false with a
+// message in `err`.
+bool load_stack(const std::string &path, const std::string &raw_dims, Stack &out, std::string &err, int channel = 0, bool raw_u16 = false);
+// advantra_cli --info: loads the stack and prints one JSON line {"w","h","l","bits","channels","channel","min","max","sum"} of the
+// kept channel (channel printed 1-based); no GPU is touched
+bool print_info(const std::string &path, const std::string &raw_dims, int channel, bool raw_u16);
 // save_nodelist (Advantra_plugin.cpp:480-523)
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,
                    int type = -1, float sig2r = 1.f, const std::string &name = "", const std::string &comment = "");
@@ -73,8 +88,11 @@ bool save_treelist(const std::vector<pnr_node> &tree, const std::vector<int32_t>
 int parse_params(const std::vector<std::string> &paras, pnr_params &p, std::string &err);
 // reconstruction_func (Advantra_plugin.cpp:2183-2731) from the point where the stack is in memory (:2255): the caller keeps
 // ownership of `data1d` (u8, x fastest).  Writes <inimg_file>_Advantra.swc; false = a library call failed (message printed).
+// data16 != nullptr: a 16-bit stack instead (data1d unused), windowed to 8 bits on the GPU with `win` (pnr_set_volume_u16; nullptr
+// = [min, max]); the SWC comment then ends in #bits=16 and #window=lo,hi.
 bool reconstruction_func(const unsigned char *data1d, long long w, long long h, long long l, const std::string &inimg_file,
-                         const std::vector<std::string> &paras, pnr_params p, int device = 0, Result *result = nullptr);
+                         const std::vector<std::string> &paras, pnr_params p, int device = 0, Result *result = nullptr,
+                         const uint16_t *data16 = nullptr, const pnr_window *win = nullptr);
 bool advantra_func(const std::vector<char *> &infiles, const std::vector<char *> &paras, int device = 0,
                    const std::string &raw_dims = "", Result *result = nullptr);
 

@@ -60,13 +60,24 @@ bool AdvantraHipPlugin::dofunc(const QString &func_name, const V3DPluginArgList 
         fprintf(stderr, "Error happens in reading the subject file [%s]. Exit. \n", infiles[0]);
         return true;
     }
-    if (datatype != 1) { // the tracer works on 8-bit stacks
-        v3d_msg("Advantra needs an 8-bit image.", 0);
+    if (datatype != 1 && datatype != 2) { // 8-bit stacks are traced as they are, 16-bit ones windowed to 8 bits on the GPU
+        v3d_msg("Advantra needs an 8- or 16-bit image.", 0);
         delete[] data1d;
         return true;
     }
-    // channel 1 = the first N*M*P bytes of data1d
-    advantra::reconstruction_func(data1d, in_sz[0], in_sz[1], in_sz[2], infiles[0], paras, prm, /*device*/ 0);
+    const int c = 1; // the reference's channel (Advantra_plugin.cpp:43, 302): hard-wired to 1
+    if (c < 1 || c > in_sz[3]) {
+        v3d_msg("Invalid channel number.", 0); // :2245-2249
+        delete[] data1d;
+        return true;
+    }
+    // channel c of Vaa3D's planar buffer starts at element (c-1)*N*M*P
+    const V3DLONG nvox = in_sz[0] * in_sz[1] * in_sz[2];
+    if (datatype == 1)
+        advantra::reconstruction_func(data1d + (c - 1) * nvox, in_sz[0], in_sz[1], in_sz[2], infiles[0], paras, prm, /*device*/ 0);
+    else // [min, max] window (pnr_set_volume_u16 with win = NULL)
+        advantra::reconstruction_func(nullptr, in_sz[0], in_sz[1], in_sz[2], infiles[0], paras, prm, /*device*/ 0, nullptr,
+                                      (const uint16_t *)data1d + (c - 1) * nvox, nullptr);
     delete[] data1d;
     return true;
 }

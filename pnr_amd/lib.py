@@ -11,6 +11,25 @@ LIB_PATH = os.environ.get("PNR_LIB_DIAG") or os.path.join(HERE, "libpnr_hip.so")
 PNR_MAX_SIGMAS = 8
 
 
+class Window(C.Structure):
+    """pnr_window (include/pnr_hip.h): a fixed [lo, hi], or lo = hi = -1 and the saturated voxels in parts per million"""
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("sat_lo_ppm", C.c_int32), ("sat_hi_ppm", C.c_int32)]
+
+
+def make_window(window):
+    """None -> NULL ([min, max]); (lo, hi) -> that window; {"saturate": (lo_pct, hi_pct)} -> the window that clips those percentages
+    of the voxels to 0 / to 255 (up to 4 decimals: parts per million)"""
+    if window is None:
+        return None
+    if isinstance(window, dict):
+        if set(window) != {"saturate"}:
+            raise PnrError(f"window: (lo, hi) or {{'saturate': (lo_pct, hi_pct)}}, got {window!r}")
+        a, b = window["saturate"]
+        return Window(-1, -1, int(round(float(a) * 1e4)), int(round(float(b) * 1e4)))
+    lo, hi = window
+    return Window(int(lo), int(hi), 0, 0)
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -72,6 +91,9 @@ def load():
     L.pnr_synchronize.argtypes = [vp]
     L.pnr_set_volume.argtypes = [vp, vp, i64, i64, i64]
     L.pnr_set_volume_device.argtypes = [vp, vp, i64, i64, i64]
+    L.pnr_set_volume_u16.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pnr_set_volume_u16_device.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pnr_get_volume.argtypes = [vp, vp]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pnr_get_frangi.argtypes = [vp] + [vp] * 5
     L.pnr_gaussian.argtypes = [vp, C.c_float, vp]
@@ -132,7 +154,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -182,6 +204,7 @@ class Context:
         check(self.L.pnr_create(C.byref(params), device, C.byref(h)))
         self.h = h
         self.shape = None
+        self.window = None  # (lo, hi) of the last 16-bit set_volume
         self._keep = None
         if DEFAULTS.get("smc_driver"):
             self.set_smc_driver(DEFAULTS["smc_driver"])
@@ -200,17 +223,53 @@ class Context:
             pass
 
     # ---- volume ----
-    def set_volume(self, img):
+    def set_volume(self, img, channel=0, window=None):
+        """u8 (l, h, w): traced as it is.  uint16 (l, h, w) or (l, h, w, c) with the channels interleaved: channel `channel` is
+        windowed to 8 bits on the GPU (pnr_set_volume_u16; `window` see make_window) and ctx.window is the (lo, hi) it used.  A u8
+        (l, h, w, c) stack only selects its channel; 8-bit input is never windowed."""
+        if isinstance(img, np.ndarray) and img.dtype.kind == "u" and img.dtype.itemsize == 2:
+            img = np.ascontiguousarray(img, np.uint16)
+            l, h, w, nc = img.shape if img.ndim == 4 else (*img.shape, 1)
+            self._set_u16(self.L.pnr_set_volume_u16, img.ctypes.data, (l, h, w), nc, channel, window)
+            return
+        if window is not None:
+            raise PnrError("8-bit input is never windowed (window / saturate need a 16-bit stack)")
+        if isinstance(img, np.ndarray) and img.ndim == 4:
+            img = img[..., channel]
         img = np.ascontiguousarray(img, np.uint8)
         l, h, w = img.shape
         check(self.L.pnr_set_volume(self.h, img.ctypes.data, w, h, l))
         self.shape = (l, h, w)
+        self.window = None
 
-    def set_volume_device(self, data_ptr, shape, keepalive=None):
+    def set_volume_device(self, data_ptr, shape, keepalive=None, dtype=np.uint8, nchan=1, channel=0, window=None):
+        """a device pointer (e.g. a torch tensor's data_ptr()): u8 is borrowed until the next set_volume; uint16 (nchan samples per
+        voxel, interleaved) is windowed into the context's own 8-bit volume during the call"""
         l, h, w = shape
+        if np.dtype(dtype) == np.uint16:
+            self._set_u16(self.L.pnr_set_volume_u16_device, data_ptr, (l, h, w), nchan, channel, window)
+            self._keep = None
+            return
+        if window is not None or nchan != 1:
+            raise PnrError("8-bit device input: one channel, never windowed")
         check(self.L.pnr_set_volume_device(self.h, data_ptr, w, h, l))
         self.shape = (l, h, w)
+        self.window = None
         self._keep = keepalive
+
+    def _set_u16(self, fn, ptr, shape, nchan, channel, window):
+        l, h, w = shape
+        win = make_window(window)
+        lo, hi = C.c_int32(), C.c_int32()
+        check(fn(self.h, ptr, w, h, l, int(nchan), int(channel), C.byref(win) if win is not None else None, C.byref(lo), C.byref(hi)))
+        self.shape = (l, h, w)
+        self.window = (lo.value, hi.value)
+
+    def get_volume(self):
+        """the 8-bit volume the context traces (pnr_get_volume)"""
+        out = np.empty(self.shape, np.uint8)
+        check(self.L.pnr_get_volume(self.h, out.ctypes.data))
+        return out
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
