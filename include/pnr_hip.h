@@ -289,6 +289,38 @@ int pnr_reconstruct_stage(const pnr_node *nodes, int64_t n_nodes, const int32_t 
                           float sig2radius, int refine_iter, float epsilon2, float group_radius, int stage, pnr_node *out_nodes,
                           int64_t cap_nodes, int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links, int64_t *n_out_links);
 
+/* Node radii measured from the image (beyond the reference, whose SWC radius is SIG2RADIUS * the winning Frangi scale: two to four
+ * values in all).  For n positions (x, y, z; f32, voxel indices as in pnr_node) the radius of the largest anisotropy-aware ball
+ * around the position that is foreground, in whole xy voxels.  THE RULE (the contract; tests restate it in numpy).  Inputs: V, the
+ * context's traced u8 volume (w x h x l, owned or borrowed; for 16-bit input the windowed bytes), zd = params.zdist, the options
+ * {thr, rel_pct, rmax, bg_permille}.  All arithmetic is exact integer arithmetic unless marked f32; f32 operations are single IEEE
+ * operations (-ffp-contract=off).
+ *   Centre: per coordinate v with its extent n: c = (int) fminf(fmaxf(v + 0.5f, 0.f), (float)(n - 1)).  A position with any
+ *     non-finite coordinate is not measured: k_out = -1.
+ *   Shells: for integer offsets (dx, dy, dz) the f32 distance d2 = (float)(dx*dx + dy*dy) + (zd*(float)dz) * (zd*(float)dz).
+ *     O_0 = {(0,0,0)}; O_k = {(dx,dy,dz) : (float)((k-1)*(k-1)) < d2 <= (float)(k*k)}, k = 1..rmax; in the 2-D mode (l == 1) only
+ *     dz = 0 occurs.  Radii are therefore in xy-voxel units.  Voxels outside the volume are not counted at all, neither as total
+ *     nor as background: a node at a face is measured on the part of the ball that exists.
+ *   Threshold t: rel_pct == 0: t = thr; thr == -1: t = max(1, floor(sum(V) / N)), the global mean from the exact u64 sum.
+ *     rel_pct in 1..100: per node t = max(1, ceil(rel_pct * m / 100)), m = the maximum of V over the in-volume voxels of
+ *     O_0 u O_1 around c (thr is ignored).  A voxel is background when V < t.
+ *   Radius: tot_k, bg_k = the in-volume voxels, and the background voxels among them, of O_0 u ... u O_k around c.  k* = the
+ *     largest k in [0, rmax] such that 1000 * bg_j <= bg_permille * tot_j (64-bit products) holds for every j in 0..k; if it fails
+ *     at j = 0 or j = 1, k* = 0.  k_out = k*.
+ * Arguments (anything else: PNR_E_ARG): rmax 1..PNR_RADIUS_MAX, thr -1..255, rel_pct 0..100, bg_permille 0..999; opts = NULL =
+ * {thr -1, rel_pct 50, rmax 32, bg_permille 1}; 0 <= n <= PNR_RADIUS_MAX_N (n = 0 is valid).  No volume in the context:
+ * PNR_E_STATE.  thr_used (nullable) receives t of the absolute mode, 0 in the relative mode.  The call needs neither Frangi nor
+ * seeds to have run and leaves the pipeline state of the context alone; it runs on the context's stream (pnr_set_stream), keeps the
+ * shell table of (rmax, zdist, 2-D) on the device for the next call and frees every other device buffer before it returns
+ * (PNR_E_NOMEM: an allocation failed).  Kernel times: pnr_get_kernel_ms group "radius". */
+#define PNR_RADIUS_MAX 64
+#define PNR_RADIUS_MAX_N (1 << 28)
+typedef struct pnr_radius_opts {
+    int32_t thr, rel_pct, rmax, bg_permille;
+} pnr_radius_opts;
+int pnr_measure_radii(pnr_ctx *ctx, const float *xyz /* n x 3 */, int64_t n, const pnr_radius_opts *opts /* NULL = defaults */,
+                      int32_t *k_out /* n */, int32_t *thr_used /* nullable */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -320,7 +352,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -64,6 +64,11 @@ int pnr_reconstruct_stage_ctx(pnr_ctx *ctx, const pnr_node *nodes, int64_t n_nod
                               pnr_node *out_nodes, int64_t cap_nodes, int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links,
                               int64_t *n_out_links);
 
+/* The shells of pnr_measure_radii's rule for (zdist, rmax, 2-D) as the device reads them, pure host code (no GPU): shell k =
+ * entries [starts[k], starts[k + 1]) of dx / dy / dz, k = 0..rmax (starts: rmax + 2 entries; raster order inside a shell).  *n = the
+ * number of offsets; up to cap of them are written; any array may be NULL. */
+int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t *dx, int32_t *dy, int32_t *dz, int64_t cap, int64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 #include "../host/reconstruct.h"
 #include "recon.h"
 #include "volume.h"
+#include "radius.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -355,6 +356,38 @@ int pnr_get_volume(pnr_ctx *c, uint8_t *img)
     PNR_HIP(hipSetDevice(c->device));
     PNR_HIP(hipMemcpyAsync(img, c->d_img, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
+    return PNR_OK;
+}
+
+// pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched
+int pnr_measure_radii(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opts *opts, int32_t *k_out, int32_t *thr_used)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    const pnr_radius_opts o = opts ? *opts : pnr_radius_opts{-1, 50, 32, 1};
+    PNR_REQUIRE(o.rmax >= 1 && o.rmax <= PNR_RADIUS_MAX, PNR_E_ARG, "pnr_measure_radii: rmax = %d outside [1, %d]", o.rmax, PNR_RADIUS_MAX);
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "pnr_measure_radii: thr = %d outside [-1, 255]", o.thr);
+    PNR_REQUIRE(o.rel_pct >= 0 && o.rel_pct <= 100, PNR_E_ARG, "pnr_measure_radii: rel_pct = %d outside [0, 100]", o.rel_pct);
+    PNR_REQUIRE(o.bg_permille >= 0 && o.bg_permille <= 999, PNR_E_ARG, "pnr_measure_radii: bg_permille = %d outside [0, 999]", o.bg_permille);
+    PNR_REQUIRE(n >= 0 && n <= PNR_RADIUS_MAX_N && (n == 0 || (xyz && k_out)), PNR_E_ARG, "pnr_measure_radii: n = %lld positions (at most 2^28) need xyz and k_out", (long long)n);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_measure_radii: no volume set");
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_radius_run(c, xyz, n, o, k_out, thr_used);
+}
+
+// test tap (pnr_hip_test.h): the shells of the rule, pure host
+int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t *dx, int32_t *dy, int32_t *dz, int64_t cap, int64_t *n)
+{
+    PNR_REQUIRE(rmax >= 1 && rmax <= PNR_RADIUS_MAX && n, PNR_E_ARG, "pnr_radius_offsets: rmax = %d outside [1, %d], or null count", rmax, PNR_RADIUS_MAX);
+    pnr::RadiusTable t;
+    pnr::build_radius_table(zdist, rmax, is2d != 0, t);
+    *n = (int64_t)t.off.size();
+    if (starts) std::copy(t.start.begin(), t.start.end(), starts);
+    for (int64_t i = 0; i < std::min(cap, *n); i++) {
+        const uint32_t o = t.off[(size_t)i];
+        if (dx) dx[i] = (int32_t)(o & 255u) - 64;
+        if (dy) dy[i] = (int32_t)((o >> 8) & 255u) - 64;
+        if (dz) dz[i] = (int32_t)((o >> 16) & 255u) - 64;
+    }
     return PNR_OK;
 }
 

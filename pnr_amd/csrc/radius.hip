@@ -1,0 +1,255 @@
+// radius.hip -- SWC node radii measured from the traced 8-bit volume (pnr_measure_radii).  The rule (include/pnr_hip.h):
+//   centre c = (int) fminf(fmaxf(v + 0.5f, 0), n - 1) per coordinate; shell O_k = offsets with (k-1)^2 < d2 <= k^2,
+//   d2 = (float)(dx^2 + dy^2) + (zd dz)(zd dz) in f32; voxels outside the volume are not counted; background = V < t with t given,
+//   the global mean, or rel_pct of the maximum over O_0 u O_1; k* = the last shell up to which 1000 bg <= bg_permille tot held for
+//   every ball O_0 u ... u O_j.
+//
+// The shells are a host table (build_radius_table: one packed word per offset, raster order inside a shell, shell start indices),
+// built once per (rmax, zdist, 2-D) and kept on the device.  One wave measures one node: its lanes stride over the offsets of the
+// current shell, gather V with bounds tests, and two ballots / popcounts per 64 offsets keep tot and bg in scalar registers, so the
+// test at every shell end is wave-uniform and the wave leaves at the first failing shell -- most nodes stop within a handful of
+// shells, nothing like a (2 rmax + 1)^3 cube is ever staged.  The nodes are handed to the waves in the order of the 8^3 cells
+// their centres lie in (a host sort; the outputs stay in input order), so that neighbouring waves gather from the same lines.
+// The global mean is one grid-stride u64 reduction with one atomic per work-group.
+#include "radius.h"
+#include <cmath>
+#include <cstring>
+
+namespace pnr {
+
+void build_radius_table(float zd, int rmax, bool is2d, RadiusTable &t)
+{
+    const int rz = is2d ? 0 : rmax;
+    const float lim = (float)(rmax * rmax);
+    // shell of an offset, -1 = none
+    auto shell = [&](int dx, int dy, int dz) -> int {
+        if (dx == 0 && dy == 0 && dz == 0) return 0;
+        const float d2 = (float)(dx * dx + dy * dy) + (zd * (float)dz) * (zd * (float)dz);
+        if (!(d2 > 0.f && d2 <= lim)) return -1; // (also a d2 that is not finite)
+        int k = std::max(1, (int)std::ceil(std::sqrt(d2)));
+        while (k > 1 && d2 <= (float)((k - 1) * (k - 1))) k--;
+        while (d2 > (float)(k * k)) k++;
+        return k <= rmax ? k : -1;
+    };
+    std::vector<int64_t> cnt((size_t)rmax + 2, 0);
+    for (int pass = 0; pass < 2; pass++) {
+        for (int dz = -rz; dz <= rz; dz++)
+            for (int dy = -rmax; dy <= rmax; dy++)
+                for (int dx = -rmax; dx <= rmax; dx++) {
+                    const int k = shell(dx, dy, dz);
+                    if (k < 0) continue;
+                    if (pass == 0) cnt[(size_t)k + 1]++;
+                    else t.off[(size_t)cnt[(size_t)k]++] = (uint32_t)(dx + 64) | (uint32_t)(dy + 64) << 8 | (uint32_t)(dz + 64) << 16;
+                }
+        if (pass == 0) {
+            for (int k = 0; k <= rmax; k++) cnt[(size_t)k + 1] += cnt[(size_t)k];
+            t.start.assign(cnt.begin(), cnt.end()); // (at most 129^3 offsets)
+            t.off.assign((size_t)cnt[(size_t)rmax + 1], 0u);
+        }
+    }
+}
+
+} // namespace pnr
+
+namespace {
+
+constexpr int RTPB = 256;          // threads of a work-group: four waves = four nodes
+constexpr int RWAVES = RTPB / 64;
+constexpr int RUNROLL = 4;         // 64-offset groups of a shell whose gathers are issued together
+constexpr int MAX_BLOCKS = 2048;   // grid-stride loop of the sum beyond this many work-groups
+
+// sum of the bytes p[0, n): scalar head up to the first 16-byte boundary, 16-byte vectors, scalar tail
+__global__ __launch_bounds__(RTPB) void rad_sum(const uint8_t *p, long long n, long long head, long long nvec, unsigned long long *out)
+{
+    __shared__ unsigned long long part[RWAVES];
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    unsigned long long s = 0;
+    const uint4 *v = (const uint4 *)(p + head);
+    auto bytes = [](unsigned x) { const unsigned y = (x & 0x00ff00ffu) + ((x >> 8) & 0x00ff00ffu); return (y & 0xffffu) + (y >> 16); };
+    for (long long g = gid; g < nvec; g += stride) {
+        const uint4 q = v[g];
+        s += bytes(q.x) + bytes(q.y) + bytes(q.z) + bytes(q.w);
+    }
+    if (gid < head) s += p[gid];
+    const long long t0 = head + 16 * nvec;
+    if (gid < n - t0) s += p[t0 + gid]; // (fewer than 16 left)
+    for (int d = 32; d >= 1; d >>= 1) s += (unsigned long long)__shfl_xor((long long)s, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < RWAVES; k++) s += part[k];
+        if (s) atomicAdd(out, s);
+    }
+}
+
+struct RadArgs {
+    const uint8_t *img;
+    int w, h, l;
+    const uint32_t *off; // the shells (radius.h)
+    const int *start;
+    const float *xyz;    // n x 3
+    const int *order;    // node measured by wave i
+    int n;
+    int rmax, t_abs, rel_pct, bg_permille;
+    int *k_out;
+};
+
+__global__ __launch_bounds__(RTPB) void rad_measure(RadArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const long long wv = (long long)blockIdx.x * RWAVES + (threadIdx.x >> 6);
+    if (wv >= a.n) return; // (the whole wave)
+    const int node = __builtin_amdgcn_readfirstlane(a.order[wv]);
+    const float px = a.xyz[3 * (long long)node], py = a.xyz[3 * (long long)node + 1], pz = a.xyz[3 * (long long)node + 2];
+    auto finite = [](float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; };
+    if (!(finite(px) && finite(py) && finite(pz))) {
+        if (lane == 0) a.k_out[node] = -1;
+        return;
+    }
+    const int cx = (int)fminf(fmaxf(px + 0.5f, 0.f), (float)(a.w - 1));
+    const int cy = (int)fminf(fmaxf(py + 0.5f, 0.f), (float)(a.h - 1));
+    const int cz = (int)fminf(fmaxf(pz + 0.5f, 0.f), (float)(a.l - 1));
+    // offset i of the table around the centre: inside the volume? v = its voxel
+    auto probe = [&](int i, bool live, unsigned &v) -> bool {
+        v = 0;
+        if (!live) return false;
+        const unsigned o = a.off[i];
+        const int x = cx + (int)(o & 255u) - 64, y = cy + (int)((o >> 8) & 255u) - 64, z = cz + (int)((o >> 16) & 255u) - 64;
+        const bool inb = (unsigned)x < (unsigned)a.w && (unsigned)y < (unsigned)a.h && (unsigned)z < (unsigned)a.l;
+        if (inb) v = a.img[((long long)z * a.h + y) * a.w + x];
+        return inb;
+    };
+    int t = a.t_abs;
+    if (a.rel_pct > 0) { // per node: rel_pct of the maximum over O_0 u O_1 (at most 7 voxels), rounded up, at least 1
+        unsigned m = 0;
+        const int s1 = a.start[2];
+        for (int base = 0; base < s1; base += 64) {
+            unsigned v;
+            probe(base + lane, base + lane < s1, v);
+            m = max(m, v);
+        }
+        for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d, 64));
+        t = max(1, (a.rel_pct * (int)m + 99) / 100);
+    }
+    unsigned tot = 0, bg = 0; // of the ball O_0 u ... u O_k: wave-uniform
+    int k = 0;
+    for (; k <= a.rmax; k++) {
+        const int s0 = a.start[k], s1 = a.start[k + 1];
+        for (int base = s0; base < s1; base += 64 * RUNROLL) {
+            unsigned v[RUNROLL];
+            bool inb[RUNROLL];
+#pragma unroll
+            for (int u = 0; u < RUNROLL; u++) {
+                const int i = base + 64 * u + lane;
+                inb[u] = probe(i, i < s1, v[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < RUNROLL; u++) {
+                tot += (unsigned)__popcll(__ballot(inb[u]));
+                bg += (unsigned)__popcll(__ballot(inb[u] && (int)v[u] < t));
+            }
+        }
+        if (1000ull * bg > (unsigned long long)a.bg_permille * tot) break;
+    }
+    // the test failed at shell k: k* = k - 1 (0 when it failed at shell 0 or 1); it never failed: rmax
+    if (lane == 0) a.k_out[node] = k > a.rmax ? a.rmax : max(0, k - 1);
+}
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+} // namespace
+
+int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opts &o, int32_t *k_out, int32_t *thr_used)
+{
+    hipStream_t st = c->stream;
+    const bool is2d = c->l == 1;
+    // the shells of (rmax, zdist, 2-D), kept in the context's named device scratch.  Which table that is, is the NAME of an empty
+    // scratch entry beside it ("radius_key/..."): the context's own structure (ctx.h) stays as it is.
+    uint32_t zbits;
+    std::memcpy(&zbits, &c->prm.zdist, 4);
+    char key[64];
+    snprintf(key, sizeof(key), "radius_key/%d/%08x/%d", o.rmax, zbits, is2d ? 1 : 0);
+    uint32_t *d_off = nullptr;
+    int *d_start = nullptr;
+    if (c->scratch.find(key) == c->scratch.end()) {
+        for (auto it = c->scratch.begin(); it != c->scratch.end();)
+            it = it->first.compare(0, 11, "radius_key/") == 0 ? c->scratch.erase(it) : std::next(it);
+        pnr::RadiusTable t;
+        pnr::build_radius_table(c->prm.zdist, o.rmax, is2d, t);
+        int rc = c->scratch_get("radius_off", t.off.size(), &d_off);
+        if (rc == PNR_OK) rc = c->scratch_get("radius_start", t.start.size(), &d_start);
+        if (rc) return rc;
+        PNR_HIP(hipMemcpyAsync(d_off, t.off.data(), t.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemcpyAsync(d_start, t.start.data(), t.start.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        PNR_HIP(hipStreamSynchronize(st)); // (the host table ends here)
+        c->scratch[key];
+    } else {
+        d_off = (uint32_t *)c->scratch["radius_off"].p;
+        d_start = (int *)c->scratch["radius_start"].p;
+    }
+    // device buffers of the call: the sum | the positions | the order of the nodes | k
+    const size_t o_xyz = 16, o_ord = o_xyz + pad16((size_t)n * 12), o_k = o_ord + pad16((size_t)n * 4), bytes = o_k + pad16((size_t)n * 4);
+    char *d_buf = nullptr;
+    if (hipMalloc(&d_buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        pnr::set_error("pnr_measure_radii: device allocation of %zu B failed", bytes);
+        return PNR_E_NOMEM;
+    }
+    auto fail = [&](hipError_t e) {
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(d_buf);
+        pnr::set_error("pnr_measure_radii: %s", hipGetErrorString(e));
+        return PNR_E_HIP;
+    };
+    hipError_t e = hipSuccess;
+    int t_abs = 0;
+    if (o.rel_pct == 0) {
+        t_abs = o.thr;
+        if (o.thr < 0) { // the global mean, from the exact sum
+            unsigned long long *d_sum = (unsigned long long *)d_buf, sum = 0;
+            const uintptr_t addr = (uintptr_t)c->d_img;
+            const long long head = std::min<long long>(c->N, (long long)((16 - (addr & 15)) & 15)), nvec = (c->N - head) >> 4;
+            const long long work = std::max<long long>(nvec, 16);
+            const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((work + RTPB - 1) / RTPB, MAX_BLOCKS));
+            if ((e = hipMemsetAsync(d_sum, 0, 8, st)) != hipSuccess) return fail(e);
+            c->tic();
+            hipLaunchKernelGGL(rad_sum, dim3(nb), dim3(RTPB), 0, st, c->d_img, (long long)c->N, head, nvec, d_sum);
+            e = hipGetLastError();
+            c->toc("radius", 1);
+            if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return fail(e);
+            t_abs = (int)std::max<unsigned long long>(1, sum / (unsigned long long)c->N);
+        }
+    }
+    if (thr_used) *thr_used = o.rel_pct ? 0 : t_abs;
+    if (n > 0) {
+        // the order of the 8^3 cells of the centres (positions that are not measured last); it changes no result
+        std::vector<std::pair<uint64_t, int>> cell((size_t)n);
+        const uint64_t nx8 = (uint64_t)(c->w + 7) >> 3, ny8 = (uint64_t)(c->h + 7) >> 3;
+        auto centre = [](float v, int64_t ext) { return (uint64_t)(int)fminf(fmaxf(v + 0.5f, 0.f), (float)(ext - 1)); };
+        for (int64_t i = 0; i < n; i++) {
+            const float *p = xyz + 3 * i;
+            uint64_t id = ~0ull;
+            if (std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))
+                id = ((centre(p[2], c->l) >> 3) * ny8 + (centre(p[1], c->h) >> 3)) * nx8 + (centre(p[0], c->w) >> 3);
+            cell[(size_t)i] = {id, (int)i};
+        }
+        std::sort(cell.begin(), cell.end());
+        std::vector<int> order((size_t)n);
+        for (int64_t i = 0; i < n; i++) order[(size_t)i] = cell[(size_t)i].second;
+        if ((e = hipMemcpyAsync(d_buf + o_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+        if ((e = hipMemcpyAsync(d_buf + o_ord, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+        RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, d_off, d_start, (const float *)(d_buf + o_xyz), (const int *)(d_buf + o_ord),
+                  (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, (int *)(d_buf + o_k)};
+        c->tic();
+        hipLaunchKernelGGL(rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), 0, st, a);
+        e = hipGetLastError();
+        c->toc("radius", 1);
+        if (e == hipSuccess) e = hipMemcpyAsync(k_out, d_buf + o_k, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st); // (the host vectors above end here)
+        if (e != hipSuccess) return fail(e);
+    }
+    (void)hipFree(d_buf);
+    return PNR_OK;
+}

@@ -9,6 +9,10 @@
 //   a 16-bit stack is windowed to 8 bits on the GPU: [min, max] by default, --window LO,HI, or --saturate LO,HI (percent of the voxels
 //   clipped to 0 / to 255, up to 4 decimals);  --info: print {"w","h","l","bits","channels","channel","min","max","sum"} of the
 //   stack's channel as one JSON line and exit (no GPU).
+//   --measure-radius: the SWC's radius column is measured from the image at the final tree's nodes (pnr_measure_radii) -- k* voxels, 0.5
+//   for a node thinner than one voxel; soma nodes keep theirs -- and the comment block ends in #radius=measured,thr=<t or rel:PCT>,rmax=K,
+//   bg=PERMILLE.  --radius-rel PCT (1..100; the default mode, 50) or --radius-threshold T (0..255, -1: the stack's mean), --radius-max K
+//   (1..64, default 32), --radius-bg PERMILLE (0..999, default 1): out-of-range values are usage errors.  --help lists all flags.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -52,6 +56,16 @@ static bool parse_pair(const char *txt, int decimals, long long &a, long long &b
     return true;
 }
 
+// the whole of txt as a decimal integer in [lo, hi]
+static bool parse_int(const char *txt, long lo, long hi, long &out)
+{
+    char *end = nullptr;
+    const long v = strtol(txt, &end, 10);
+    if (!*txt || *end || v < lo || v > hi) return false;
+    out = v;
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     std::vector<char *> infiles, paras;
@@ -59,7 +73,8 @@ int main(int argc, char **argv)
     int device = 0, ranks = 1;
     bool share_gpu = false;
     std::string transport = "shm";
-    bool info = false, window = false, saturate = false;
+    bool info = false, window = false, saturate = false, help = false;
+    bool radius_abs = false, radius_rel = false, radius_flag = false;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--info")) { info = true; continue; }
@@ -93,6 +108,34 @@ int main(int argc, char **argv)
             S0.windowed = saturate = true;
             continue;
         }
+        if (!strcmp(argv[i], "--help")) { help = true; continue; }
+        if (!strcmp(argv[i], "--measure-radius")) { S0.measure_radius = true; continue; }
+        if (!strncmp(argv[i], "--radius-", 9)) {
+            const std::string flag = argv[i];
+            long v = 0;
+            const char *txt = i + 1 < argc ? argv[++i] : "";
+            if (flag == "--radius-threshold") {
+                if (!parse_int(txt, -1, 255, v)) { fprintf(stderr, "--radius-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+                S0.radius.thr = (int32_t)v;
+                S0.radius.rel_pct = 0;
+                radius_abs = true;
+            } else if (flag == "--radius-rel") {
+                if (!parse_int(txt, 1, 100, v)) { fprintf(stderr, "--radius-rel PCT: an integer from 1 to 100\n"); return 1; }
+                S0.radius.rel_pct = (int32_t)v;
+                radius_rel = true;
+            } else if (flag == "--radius-max") {
+                if (!parse_int(txt, 1, PNR_RADIUS_MAX, v)) { fprintf(stderr, "--radius-max K: an integer from 1 to %d\n", PNR_RADIUS_MAX); return 1; }
+                S0.radius.rmax = (int32_t)v;
+            } else if (flag == "--radius-bg") {
+                if (!parse_int(txt, 0, 999, v)) { fprintf(stderr, "--radius-bg PERMILLE: an integer from 0 to 999\n"); return 1; }
+                S0.radius.bg_permille = (int32_t)v;
+            } else {
+                fprintf(stderr, "%s: unknown flag (--radius-threshold, --radius-rel, --radius-max, --radius-bg)\n", flag.c_str());
+                return 1;
+            }
+            radius_flag = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--ranks") && i + 1 < argc) { ranks = atoi(argv[++i]); continue; }
         if (!strcmp(argv[i], "--share-gpu")) { share_gpu = true; continue; }
         if (!strcmp(argv[i], "--exchange") && i + 1 < argc) { transport = argv[++i]; continue; }
@@ -109,6 +152,13 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-p")) { while (i + 1 < argc) paras.push_back(argv[++i]); continue; }
     }
     if (window && saturate) { fprintf(stderr, "--window and --saturate: one of them\n"); return 1; }
+    if (radius_abs && radius_rel) { fprintf(stderr, "--radius-threshold and --radius-rel: one of them\n"); return 1; }
+    if (radius_flag && !S0.measure_radius) { fprintf(stderr, "--radius-threshold / --radius-rel / --radius-max / --radius-bg need --measure-radius\n"); return 1; }
+    if (help) {
+        advantra::print_help();
+        advantra::print_flags();
+        return 0;
+    }
     if (info) {
         if (infiles.empty()) { fprintf(stderr, "--info needs -i <inimg_file>\n"); return 1; }
         return advantra::print_info(infiles[0], raw_dims, S0.channel - 1, S0.raw_u16) ? 0 : 1;

@@ -46,6 +46,19 @@ void print_help()
     printf("outswc_file    <inimg_file>_Advantra.swc\n");
 }
 
+void print_flags()
+{
+    printf("\nadvantra_cli [flags] -f advantra_func -i <inimg_file> -p <the 11 parameters>   (flags go before -p)\n");
+    printf("-v | --timing | --save-midres | --single-tree | --rng-seed N | -g DEVICE | -d w,h,l (.raw) | --info\n");
+    printf("--ranks N [--share-gpu] [--exchange shm|rccl]   one stack on N GPUs of this host\n");
+    printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
+    printf("--measure-radius          SWC radii measured from the image at the final nodes (default: SIG2RADIUS * the winning scale)\n");
+    printf("--radius-rel PCT          relative mode (default, 50): background below PCT %% of the node's brightest centre voxel, 1..100\n");
+    printf("--radius-threshold T      absolute mode: background below T, 0..255; -1: below the stack's mean\n");
+    printf("--radius-max K            largest radius looked for, in xy voxels, 1..%d (default 32)\n", PNR_RADIUS_MAX);
+    printf("--radius-bg PERMILLE      background voxels a ball may hold, per thousand, 0..999 (default 1)\n");
+}
+
 // ---- baseline TIFF reader: 8- or 16-bit unsigned samples in either byte order, uncompressed strips, any number of pages; several
 // samples per pixel (chunky or planar) or ImageJ hyperstack channels, of which one is kept ----
 namespace {
@@ -300,8 +313,16 @@ Stack::~Stack()
     if (view) munmap((void *)view, map_len);
 }
 
+std::vector<float> measured_radius_column(const std::vector<pnr_node> &tree, const std::vector<int32_t> &k)
+{
+    std::vector<float> r(tree.size(), -1.f);
+    for (size_t i = 1; i < tree.size() && i < k.size(); i++)
+        if (k[i] >= 0 && tree[i].type != 1) r[i] = k[i] >= 1 ? (float)k[i] : 0.5f;
+    return r;
+}
+
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname, int type,
-                   float sig2r, const std::string &name, const std::string &comment)
+                   float sig2r, const std::string &name, const std::string &comment, const std::vector<float> *radius)
 {
     // one line per (node, neighbour) pair, ids repeat; isolated nodes get parent -1; node 0 is the dummy
     std::vector<std::vector<int>> nbr(nodes.size());
@@ -326,15 +347,16 @@ bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t
     for (size_t i = 1; i < nodes.size(); i++) {
         const pnr_node &nd = nodes[i];
         const int t = (type == -1) ? nd.type : type;
-        if (nbr[i].empty()) fprintf(f, "%zu %d %.3f %.3f %.3f %.3f %d\n", i, t, nd.x, nd.y, nd.z, sig2r * nd.sig, -1);
-        for (int par : nbr[i]) fprintf(f, "%zu %d %.3f %.3f %.3f %.3f %d\n", i, t, nd.x, nd.y, nd.z, sig2r * nd.sig, par);
+        const float r = (radius && i < radius->size() && (*radius)[i] >= 0.f) ? (*radius)[i] : sig2r * nd.sig;
+        if (nbr[i].empty()) fprintf(f, "%zu %d %.3f %.3f %.3f %.3f %d\n", i, t, nd.x, nd.y, nd.z, r, -1);
+        for (int par : nbr[i]) fprintf(f, "%zu %d %.3f %.3f %.3f %.3f %d\n", i, t, nd.x, nd.y, nd.z, r, par);
     }
     fclose(f);
     return true;
 }
 
 bool save_treelist(const std::vector<pnr_node> &tree, const std::vector<int32_t> &parent, const std::string &swcname, int type,
-                   float sig2r, const std::string &name, const std::string &comment)
+                   float sig2r, const std::string &name, const std::string &comment, const std::vector<float> *radius)
 {
     FILE *f = fopen(swcname.c_str(), "w");
     if (!f) return false;
@@ -352,7 +374,8 @@ bool save_treelist(const std::vector<pnr_node> &tree, const std::vector<int32_t>
     fprintf(f, "##n,type,x,y,z,radius,parent\n");
     for (size_t i = 1; i < tree.size(); i++) {
         const pnr_node &nd = tree[i];
-        fprintf(f, "%zu %d %.3f %.3f %.3f %.3f %d\n", i, (type == -1) ? nd.type : type, nd.x, nd.y, nd.z, sig2r * nd.sig, parent[i]);
+        const float r = (radius && i < radius->size() && (*radius)[i] >= 0.f) ? (*radius)[i] : sig2r * nd.sig;
+        fprintf(f, "%zu %d %.3f %.3f %.3f %.3f %d\n", i, (type == -1) ? nd.type : type, nd.x, nd.y, nd.z, r, parent[i]);
     }
     fclose(f);
     return true;
@@ -402,8 +425,9 @@ int parse_params(const std::vector<std::string> &paras, pnr_params &p, std::stri
     return 0;
 }
 
-// window: the (lo, hi) a 16-bit stack was windowed with (nullptr: 8-bit input)
-static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p, const int32_t *window)
+// window: the (lo, hi) a 16-bit stack was windowed with (nullptr: 8-bit input); radius_thr: the threshold the radii were measured
+// with (nullptr: not measured; 0: the relative mode)
+static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p, const int32_t *window, const int32_t *radius_thr = nullptr)
 {
     static const char *keys[] = {"neuritesigmas", "somaradius", "tolerance", "znccth", "kappa", "step", "ni", "np", "zdist", "nodepervol", "vol"};
     std::stringstream c;
@@ -413,6 +437,13 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
       << "\n#frangi_beta=" << p.beta << "\n#frangi_C=" << p.C << "\n#MAX_TRACE_COUNT=" << p.max_trace_count
       << "\n#EPSILON2=0.0001\n#REFINE_ITER=4\n#SIG2RADIUS=1.5\n#TRACE_RSMPL=1\n#GROUP_RADIUS=2\n#ENFORCE_SINGLE_TREE=0\n#TREE_SIZE_MIN=10\n#TAIL_SIZE_MIN=2";
     if (window) c << "\n#bits=16\n#window=" << window[0] << "," << window[1];
+    if (radius_thr) {
+        const pnr_radius_opts &ro = settings().radius;
+        c << "\n#radius=measured,thr=";
+        if (ro.rel_pct > 0) c << "rel:" << ro.rel_pct;
+        else c << *radius_thr;
+        c << ",rmax=" << ro.rmax << ",bg=" << ro.bg_permille;
+    }
     return c.str();
 }
 
@@ -693,8 +724,33 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     }
     auto t5 = clk::now();
     R.t_recon = secs(t4, t5);
+    std::vector<float> radius; // --measure-radius: the radius column, measured on the volume this context traced
+    if (settings().measure_radius) {
+        const size_t nt = R.tree.size();
+        std::vector<float> xyz(3 * nt, 0.f);
+        for (size_t i = 0; i < nt; i++) { xyz[3 * i] = R.tree[i].x; xyz[3 * i + 1] = R.tree[i].y; xyz[3 * i + 2] = R.tree[i].z; }
+        R.radius_k.assign(nt, -1);
+        if (settings().timing) pnr_set_profiling(ctx, 1);
+        if (pnr_measure_radii(ctx, xyz.data(), (int64_t)nt, &settings().radius, R.radius_k.data(), &R.radius_thr) != PNR_OK) {
+            fprintf(stderr, "%s\n", pnr_last_error());
+            pnr_destroy(ctx);
+            return false;
+        }
+        if (nt) R.radius_k[0] = -1; // the dummy
+        radius = measured_radius_column(R.tree, R.radius_k);
+        t5 = clk::now();
+        R.t_radius = secs(t4, t5) - R.t_recon;
+        printf("radius measurement... %zu nodes, %g sec.\n", nt ? nt - 1 : 0, R.t_radius);
+        if (settings().timing) {
+            double ms = 0;
+            int64_t launches = 0;
+            pnr_get_kernel_ms(ctx, "radius", &ms, &launches);
+            fprintf(stderr, "[pnr host] radius: %.3f s, kernels %.3f ms in %lld launches\n", R.t_radius, ms, (long long)launches);
+        }
+    }
     R.swc_path = inimg_file + (settings().single_tree ? "_Advantra1.swc" : "_Advantra.swc"); // :2152 / :2164
-    save_treelist(R.tree, R.parent, R.swc_path, -1, 1.f, "Advantra", swc_comment(paras, p, data16 ? window : nullptr));
+    save_treelist(R.tree, R.parent, R.swc_path, -1, 1.f, "Advantra",
+                  swc_comment(paras, p, data16 ? window : nullptr, settings().measure_radius ? &R.radius_thr : nullptr), radius.empty() ? nullptr : &radius);
     if (settings().save_midres) { // the saveMidres taps of reconstruct() (:2098-2141)
         save_nodelist(R.nodes, R.links, inimg_file + "_n0_.swc");
         static const char *const names[] = {"", "_n0res_.swc", "_n1_.swc", "_n2_.swc", "_n2tree_.swc"};

@@ -37,8 +37,11 @@ struct Result {
     std::vector<int32_t> links;    // pairs
     std::vector<pnr_node> tree;    // reconstruct() output: tree list, tree[0] = dummy
     std::vector<int32_t> parent;   // parent index per tree node, -1 = root
+    std::vector<int32_t> radius_k; // --measure-radius: k* of pnr_measure_radii per tree node (index 0 dummy: -1), else empty
+    int32_t radius_thr = 0;        // ... the threshold it used (0: the relative mode)
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
+    double t_radius = 0;           // --measure-radius: the measurement (kernels, transfers, the first call's shell table)
     double t_load = 0, t_setup = 0, t_write = 0, t_total = 0; // stack file -> memory; context + upload (+ soma); SWC file; advantra_func as a whole
 };
 
@@ -66,10 +69,16 @@ struct Settings {
     bool raw_u16 = false;
     bool windowed = false;
     pnr_window window = {-1, -1, 0, 0};
+    // --measure-radius: the radius column of the SWC is measured from the image at the final tree's nodes (pnr_measure_radii) instead
+    // of SIG2RADIUS * the winning Frangi scale; --radius-threshold T (absolute mode, -1: the mean; sets rel_pct = 0), --radius-rel PCT
+    // (relative mode, the default), --radius-max K, --radius-bg PERMILLE.  The reference has no counterpart.
+    bool measure_radius = false;
+    pnr_radius_opts radius = {-1, 50, 32, 1};
 };
 Settings &settings();
 
 void print_help();
+void print_flags(); // advantra_cli --help: print_help() and the driver's own flags
 // simple_loadimage_wrapper's role (Advantra_plugin.cpp:2241): a multi-page uncompressed TIFF of 8- or 16-bit unsigned samples
 // (either byte order; several samples per pixel, chunky or planar, or an ImageJ hyperstack's channels), or ".raw" (u8, or u16
 // little-endian with raw_u16; dims from `raw_dims` = "w,h,l").  Keeps channel `channel` (0-based) only.  Returns false with a
@@ -78,12 +87,18 @@ bool load_stack(const std::string &path, const std::string &raw_dims, Stack &out
 // advantra_cli --info: loads the stack and prints one JSON line {"w","h","l","bits","channels","channel","min","max","sum"} of the
 // kept channel (channel printed 1-based); no GPU is touched
 bool print_info(const std::string &path, const std::string &raw_dims, int channel, bool raw_u16);
-// save_nodelist (Advantra_plugin.cpp:480-523)
+// save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
+// radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,
-                   int type = -1, float sig2r = 1.f, const std::string &name = "", const std::string &comment = "");
+                   int type = -1, float sig2r = 1.f, const std::string &name = "", const std::string &comment = "",
+                   const std::vector<float> *radius = nullptr);
 // the same writer for a tree list (each node has 0 or 1 link: its parent)
 bool save_treelist(const std::vector<pnr_node> &tree, const std::vector<int32_t> &parent, const std::string &swcname, int type = -1,
-                   float sig2r = 1.f, const std::string &name = "", const std::string &comment = "");
+                   float sig2r = 1.f, const std::string &name = "", const std::string &comment = "",
+                   const std::vector<float> *radius = nullptr);
+// the radius column of measured nodes: k* >= 1 -> k*, 0 -> 0.5; nodes that were not measured (k = -1) and soma nodes (type 1) keep
+// sig2r * sig (entry -1)
+std::vector<float> measured_radius_column(const std::vector<pnr_node> &tree, const std::vector<int32_t> &k);
 // 0 = ok, -1 = usage error (dofunc returns false), -2 = range error (dofunc "return 0"), -3 = runtime failure
 int parse_params(const std::vector<std::string> &paras, pnr_params &p, std::string &err);
 // reconstruction_func (Advantra_plugin.cpp:2183-2731) from the point where the stack is in memory (:2255): the caller keeps

@@ -30,6 +30,14 @@ def make_window(window):
     return Window(int(lo), int(hi), 0, 0)
 
 
+class RadiusOpts(C.Structure):
+    """pnr_radius_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean), rel_pct 0..100 (0: the absolute mode), rmax 1..64, bg_permille 0..999"""
+    _fields_ = [("thr", C.c_int32), ("rel_pct", C.c_int32), ("rmax", C.c_int32), ("bg_permille", C.c_int32)]
+
+
+PNR_RADIUS_MAX = 64
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -94,6 +102,8 @@ def load():
     L.pnr_set_volume_u16.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pnr_set_volume_u16_device.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pnr_get_volume.argtypes = [vp, vp]
+    L.pnr_measure_radii.argtypes = [vp, vp, i64, C.POINTER(RadiusOpts), vp, C.POINTER(C.c_int32)]
+    L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pnr_get_frangi.argtypes = [vp] + [vp] * 5
     L.pnr_gaussian.argtypes = [vp, C.c_float, vp]
@@ -154,7 +164,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -163,7 +173,7 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
                    "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx"]
+                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -270,6 +280,17 @@ class Context:
         out = np.empty(self.shape, np.uint8)
         check(self.L.pnr_get_volume(self.h, out.ctypes.data))
         return out
+
+    def measure_radii(self, xyz, thr=-1, rel_pct=50, rmax=32, bg_permille=1):
+        """pnr_measure_radii at n x 3 positions (x, y, z) on the context's volume -> (k int32[n], thr_used): k = the measured radius
+        in xy voxels (0: thinner than one voxel, -1: a position that is not finite); thr_used = the threshold of the absolute mode
+        (rel_pct = 0; thr = -1: the global mean), 0 in the relative mode"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        k = np.empty(len(xyz), np.int32)
+        o = RadiusOpts(int(thr), int(rel_pct), int(rmax), int(bg_permille))
+        t = C.c_int32()
+        check(self.L.pnr_measure_radii(self.h, xyz.ctypes.data, len(xyz), C.byref(o), k.ctypes.data, C.byref(t)))
+        return k, t.value
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
@@ -663,6 +684,19 @@ def reconstruct(nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, ep
         if n.value <= cap:
             return out[:n.value].copy(), par[:n.value].copy()
         cap = int(n.value)
+
+
+def radius_offsets(zdist, rmax, is2d=False):
+    """test tap pnr_radius_offsets (pure host; no GPU needed): the shells of measure_radii's rule -> (starts int32[rmax + 2],
+    offsets int32[n, 3] as (dx, dy, dz)); shell k = offsets[starts[k]:starts[k + 1]]"""
+    L = load()
+    n = C.c_int64()
+    starts = np.zeros(int(rmax) + 2 if 1 <= int(rmax) <= PNR_RADIUS_MAX else 2, np.int32)
+    check(L.pnr_radius_offsets(float(zdist), int(rmax), int(bool(is2d)), starts.ctypes.data, None, None, None, 0, C.byref(n)))
+    d = np.zeros((3, n.value), np.int32)
+    check(L.pnr_radius_offsets(float(zdist), int(rmax), int(bool(is2d)), starts.ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data,
+                               n.value, C.byref(n)))
+    return starts, np.ascontiguousarray(d.T)
 
 
 def reconstruct_stage(nodes, links, stage, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0):
