@@ -321,6 +321,36 @@ typedef struct pnr_radius_opts {
 int pnr_measure_radii(pnr_ctx *ctx, const float *xyz /* n x 3 */, int64_t n, const pnr_radius_opts *opts /* NULL = defaults */,
                       int32_t *k_out /* n */, int32_t *thr_used /* nullable */);
 
+/* Pre-filters of the traced volume (beyond the reference, which traces the stack as it was loaded): a 3 x 3 (x 3) median against
+ * shot noise and a flat-box top-hat against uneven background, on the GPU, between pnr_set_volume* and pnr_soma / pnr_frangi.
+ * THE RULE (the contract; tests restate it in numpy).  V is the context's traced u8 volume (w x h x l, owned or borrowed; for
+ * 16-bit input the windowed bytes).  Both stages are exact integer operations; the median runs first, then the top-hat; a stage
+ * whose option is 0 is skipped, both 0 is a valid no-op that leaves the context alone.
+ *   median = 2: the 3 x 3 window in the plane of every slice (9 samples); median = 3: the 3 x 3 x 3 window (27 samples).
+ *     Coordinates outside the volume are clamped to the edge (replicate, as Frangi::imgaussian does), so that every window has
+ *     exactly 9 / 27 samples, duplicates included.  out = the sample of rank 4 (of 9) / rank 13 (of 27) in ascending order,
+ *     0-based.  (For l == 1, median = 3 gives the bytes of median = 2.)
+ *   tophat_r = R in 1..PNR_TOPHAT_MAX_R: a flat box with the half-widths rx = ry = R, rz = (int)((float)R / zd), zd = params.zdist
+ *     (one IEEE f32 division); in the 2-D mode (l == 1) only dz = 0 exists.  B(p) = the voxels of the box around p that lie inside
+ *     the volume (voxels outside are not in the window; a box larger than the stack is legal).  e(p) = min of V over B(p),
+ *     o(p) = max of e over B(p), out(p) = V(p) - o(p); o <= V holds at every voxel, so nothing is clamped.
+ * Arguments (anything else: PNR_E_ARG): opts non-NULL, median in {0, 2, 3}, tophat_r in 0..PNR_TOPHAT_MAX_R.  No volume in the
+ * context: PNR_E_STATE.  Afterwards the context is what pnr_set_volume of the filtered bytes leaves: the same dimensions and 2-D
+ * mode, an owned volume, and no later pipeline state (soma, Frangi, J8, seeds and the graph are invalidated).  pnr_get_volume
+ * returns the filtered bytes and pnr_measure_radii measures on them (the rule of the windowed bytes of 16-bit input: the radius
+ * is measured on what is traced).  A second call filters the filtered volume.  A borrowed device volume (pnr_set_volume_device) is
+ * never written: the result is an owned buffer and the context stops borrowing.  The filter computes into buffers of the call and
+ * the context's volume changes only once everything has succeeded: on any failure (PNR_E_NOMEM: an allocation failed) the context
+ * still holds the unfiltered volume.  Device memory of the call: the filtered volume (N bytes) and, when both stages run, N bytes
+ * more that are freed before the call returns.  All voxel indices are 64-bit.  The work runs on the context's stream
+ * (pnr_set_stream); kernel times: pnr_get_kernel_ms group "filter". */
+#define PNR_TOPHAT_MAX_R 64
+typedef struct pnr_filter_opts {
+    int32_t median;   /* 0 = off, 2 = 3 x 3 in every slice, 3 = 3 x 3 x 3 */
+    int32_t tophat_r; /* 0 = off, 1..PNR_TOPHAT_MAX_R */
+} pnr_filter_opts;
+int pnr_filter_volume(pnr_ctx *ctx, const pnr_filter_opts *opts);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -352,7 +382,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

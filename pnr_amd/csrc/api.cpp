@@ -9,6 +9,7 @@
 #include "recon.h"
 #include "volume.h"
 #include "radius.h"
+#include "filter.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -356,6 +357,32 @@ int pnr_get_volume(pnr_ctx *c, uint8_t *img)
     PNR_HIP(hipSetDevice(c->device));
     PNR_HIP(hipMemcpyAsync(img, c->d_img, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
+    return PNR_OK;
+}
+
+// pnr_filter_volume: arguments first, then the state; the context changes only after the filtered volume is complete (filter.hip)
+int pnr_filter_volume(pnr_ctx *c, const pnr_filter_opts *opts)
+{
+    PNR_REQUIRE(c && opts, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(opts->median == 0 || opts->median == 2 || opts->median == 3, PNR_E_ARG, "pnr_filter_volume: median = %d, not 0, 2 or 3", opts->median);
+    PNR_REQUIRE(opts->tophat_r >= 0 && opts->tophat_r <= PNR_TOPHAT_MAX_R, PNR_E_ARG, "pnr_filter_volume: tophat_r = %d outside [0, %d]", opts->tophat_r, PNR_TOPHAT_MAX_R);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_filter_volume: no volume set");
+    if (!opts->median && !opts->tophat_r) return PNR_OK;
+    PNR_HIP(hipSetDevice(c->device));
+    uint8_t *out = nullptr;
+    const int rc = pnr_filter_run(c, *opts, &out);
+    if (rc) return rc;
+    // what pnr_set_volume of the filtered bytes leaves: an owned volume of the same dimensions, no later pipeline state
+    (void)hipFree(c->d_img_owned); // (nullptr while the volume was borrowed: a borrowed volume is never written or freed)
+    c->d_img_owned = out;
+    c->img_owned_cap = (size_t)c->N;
+    c->d_img = out;
+    c->have_j8 = false;
+    c->have_v = c->have_scale = false;
+    c->frangi_pruned = false;
+    c->seeds.clear();
+    c->have_soma = false;
+    c->have_graph = false;
     return PNR_OK;
 }
 

@@ -13,6 +13,9 @@
 //   for a node thinner than one voxel; soma nodes keep theirs -- and the comment block ends in #radius=measured,thr=<t or rel:PCT>,rmax=K,
 //   bg=PERMILLE.  --radius-rel PCT (1..100; the default mode, 50) or --radius-threshold T (0..255, -1: the stack's mean), --radius-max K
 //   (1..64, default 32), --radius-bg PERMILLE (0..999, default 1): out-of-range values are usage errors.  --help lists all flags.
+//   --median 2d|3d, --subtract-background R (1..64): the stack is pre-filtered on the GPU before it is traced (pnr_filter_volume: a 3 x 3
+//   median in every slice or a 3 x 3 x 3 one, then a top-hat with a flat box of half-width R); the comment block then has the line
+//   #filter=median:<2d|3d|off>,tophat:<R|off> behind #bits / #window and in front of #radius.  Any other value is a usage error.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -109,6 +112,18 @@ int main(int argc, char **argv)
             continue;
         }
         if (!strcmp(argv[i], "--help")) { help = true; continue; }
+        if (!strcmp(argv[i], "--median")) {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m != "2d" && m != "3d") { fprintf(stderr, "--median 2d|3d: a 3 x 3 median in every slice, or a 3 x 3 x 3 one\n"); return 1; }
+            S0.filter.median = m == "3d" ? 3 : 2;
+            continue;
+        }
+        if (!strcmp(argv[i], "--subtract-background")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 1, PNR_TOPHAT_MAX_R, v)) { fprintf(stderr, "--subtract-background R: the half-width of the top-hat's box, an integer from 1 to %d\n", PNR_TOPHAT_MAX_R); return 1; }
+            S0.filter.tophat_r = (int32_t)v;
+            continue;
+        }
         if (!strcmp(argv[i], "--measure-radius")) { S0.measure_radius = true; continue; }
         if (!strncmp(argv[i], "--radius-", 9)) {
             const std::string flag = argv[i];

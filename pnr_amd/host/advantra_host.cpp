@@ -52,6 +52,8 @@ void print_flags()
     printf("-v | --timing | --save-midres | --single-tree | --rng-seed N | -g DEVICE | -d w,h,l (.raw) | --info\n");
     printf("--ranks N [--share-gpu] [--exchange shm|rccl]   one stack on N GPUs of this host\n");
     printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
+    printf("--median 2d|3d            pre-filter: 3 x 3 median in every slice, or 3 x 3 x 3 (on the GPU, before tracing; default: off)\n");
+    printf("--subtract-background R   pre-filter: top-hat with a flat box of half-width R in xy and R / zdist in z, 1..%d (after the median)\n", PNR_TOPHAT_MAX_R);
     printf("--measure-radius          SWC radii measured from the image at the final nodes (default: SIG2RADIUS * the winning scale)\n");
     printf("--radius-rel PCT          relative mode (default, 50): background below PCT %% of the node's brightest centre voxel, 1..100\n");
     printf("--radius-threshold T      absolute mode: background below T, 0..255; -1: below the stack's mean\n");
@@ -437,6 +439,12 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
       << "\n#frangi_beta=" << p.beta << "\n#frangi_C=" << p.C << "\n#MAX_TRACE_COUNT=" << p.max_trace_count
       << "\n#EPSILON2=0.0001\n#REFINE_ITER=4\n#SIG2RADIUS=1.5\n#TRACE_RSMPL=1\n#GROUP_RADIUS=2\n#ENFORCE_SINGLE_TREE=0\n#TREE_SIZE_MIN=10\n#TAIL_SIZE_MIN=2";
     if (window) c << "\n#bits=16\n#window=" << window[0] << "," << window[1];
+    const pnr_filter_opts &fo = settings().filter;
+    if (fo.median || fo.tophat_r) {
+        c << "\n#filter=median:" << (fo.median == 3 ? "3d" : fo.median == 2 ? "2d" : "off") << ",tophat:";
+        if (fo.tophat_r) c << fo.tophat_r;
+        else c << "off";
+    }
     if (radius_thr) {
         const pnr_radius_opts &ro = settings().radius;
         c << "\n#radius=measured,thr=";
@@ -557,6 +565,25 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
         printf("imerode(%d) imgaussian(%d) maxentropy_th() %d  %lld soma regions  %.3f sec.\n", p.somaradius, p.somaradius, (int)th, (long long)nsoma,
                std::chrono::duration<double>(clk::now() - ts).count());
     };
+    const pnr_filter_opts &fo = settings().filter;
+    const bool filtered = fo.median || fo.tophat_r;
+    auto run_filter = [&]() { // --median / --subtract-background: the context's volume is replaced by its filtered bytes
+        if (!filtered || !ok) return;
+        const auto tf = clk::now();
+        const bool prof = settings().timing || settings().verbose;
+        if (prof) pnr_set_profiling(ctx, 1);
+        ok = pnr_filter_volume(ctx, &fo) == PNR_OK;
+        R.t_filter = std::chrono::duration<double>(clk::now() - tf).count();
+        double ms = 0;
+        int64_t launches = 0;
+        if (prof) {
+            pnr_get_kernel_ms(ctx, "filter", &ms, &launches);
+            pnr_set_profiling(ctx, 0);
+        }
+        printf("pre-filter... median %s, top-hat %d, %g sec.\n", fo.median == 3 ? "3d" : fo.median == 2 ? "2d" : "off", (int)fo.tophat_r, R.t_filter);
+        if (settings().verbose) printf("pre-filter kernels %.3f ms in %lld launches\n", ms, (long long)launches);
+        if (settings().timing) fprintf(stderr, "[pnr host] filter: %.3f s, kernels %.3f ms in %lld launches\n", R.t_filter, ms, (long long)launches);
+    };
     std::vector<pnr_seed> seeds;
     int64_t nfound = 0, nseeds = 0;
     auto t0 = clk::now(), t1 = t0, t2 = t0;
@@ -565,6 +592,7 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     if (!sharded) {
         ok = (data16 ? pnr_set_volume_u16(ctx, data16, w, h, l, 1, 0, win, &window[0], &window[1]) : pnr_set_volume(ctx, data1d, w, h, l)) == PNR_OK;
         if (settings().timing) fprintf(stderr, "[pnr host] context %.3f s, upload of %.2f GB %.3f s\n", secs(t_begin, t_created), (double)(w * h * l) / 1e9, secs(t_created, clk::now()));
+        run_filter();
         if (ok) run_soma();
         t0 = clk::now();
         ok = ok && pnr_frangi(ctx, &R.Jmin, &R.Jmax) == PNR_OK; // :2496-2512
@@ -582,6 +610,13 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
         if (data16) { // every rank maps the whole stack once and runs the 8-bit path on it: slabs and stack share one window
             mapped.resize((size_t)(w * h * l));
             ok = pnr_set_volume_u16(ctx, data16, w, h, l, 1, 0, win, &window[0], &window[1]) == PNR_OK && pnr_get_volume(ctx, mapped.data()) == PNR_OK;
+            data1d = mapped.data();
+        }
+        if (filtered) { // every rank filters its own copy of the whole stack (the filter is deterministic: all ranks hold the same bytes)
+            if (!data16) ok = pnr_set_volume(ctx, data1d, w, h, l) == PNR_OK;
+            run_filter();
+            mapped.resize((size_t)(w * h * l));
+            ok = ok && pnr_get_volume(ctx, mapped.data()) == PNR_OK;
             data1d = mapped.data();
         }
         // this rank's z-slab with its halo (the z pass of the widest Gaussian + the radius-2 Hessian stencil): exact Frangi / seeds

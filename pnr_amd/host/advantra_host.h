@@ -41,6 +41,7 @@ struct Result {
     int32_t radius_thr = 0;        // ... the threshold it used (0: the relative mode)
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
+    double t_filter = 0;           // --median / --subtract-background: the pre-filter (part of t_setup)
     double t_radius = 0;           // --measure-radius: the measurement (kernels, transfers, the first call's shell table)
     double t_load = 0, t_setup = 0, t_write = 0, t_total = 0; // stack file -> memory; context + upload (+ soma); SWC file; advantra_func as a whole
 };
@@ -74,6 +75,10 @@ struct Settings {
     // (relative mode, the default), --radius-max K, --radius-bg PERMILLE.  The reference has no counterpart.
     bool measure_radius = false;
     pnr_radius_opts radius = {-1, 50, 32, 1};
+    // --median 2d|3d, --subtract-background R: the traced volume is pre-filtered on the GPU (pnr_filter_volume: median first, then the
+    // top-hat with the flat box of half-width R) right after it is set -- for 16-bit input after windowing -- and before the soma
+    // path; on every rank of --ranks N.  The SWC comment then has a #filter= line.  The reference has no counterpart.
+    pnr_filter_opts filter = {0, 0};
 };
 Settings &settings();
 

@@ -38,6 +38,14 @@ class RadiusOpts(C.Structure):
 PNR_RADIUS_MAX = 64
 
 
+class FilterOpts(C.Structure):
+    """pnr_filter_opts (include/pnr_hip.h): median 0 / 2 (3 x 3 in every slice) / 3 (3 x 3 x 3), tophat_r 0..64 (0: off)"""
+    _fields_ = [("median", C.c_int32), ("tophat_r", C.c_int32)]
+
+
+PNR_TOPHAT_MAX_R = 64
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -103,6 +111,7 @@ def load():
     L.pnr_set_volume_u16_device.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pnr_get_volume.argtypes = [vp, vp]
     L.pnr_measure_radii.argtypes = [vp, vp, i64, C.POINTER(RadiusOpts), vp, C.POINTER(C.c_int32)]
+    L.pnr_filter_volume.argtypes = [vp, C.POINTER(FilterOpts)]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pnr_get_frangi.argtypes = [vp] + [vp] * 5
@@ -164,7 +173,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -280,6 +289,15 @@ class Context:
         out = np.empty(self.shape, np.uint8)
         check(self.L.pnr_get_volume(self.h, out.ctypes.data))
         return out
+
+    def filter_volume(self, median=0, tophat=0):
+        """pnr_filter_volume: the traced volume is replaced by its 3 x 3 (median = 2) or 3 x 3 x 3 (median = 3) median, then by its
+        top-hat with the flat box of half-width `tophat` (1..64; the z half-width is int(tophat / zdist)); 0 skips a stage.  The
+        result is an owned volume (a borrowed one is left as it was and released) and the later pipeline state is invalidated."""
+        o = FilterOpts(int(median), int(tophat))
+        check(self.L.pnr_filter_volume(self.h, C.byref(o)))
+        if o.median or o.tophat_r:
+            self._keep = None
 
     def measure_radii(self, xyz, thr=-1, rel_pct=50, rmax=32, bg_permille=1):
         """pnr_measure_radii at n x 3 positions (x, y, z) on the context's volume -> (k int32[n], thr_used): k = the measured radius
