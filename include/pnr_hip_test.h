@@ -69,6 +69,10 @@ int pnr_reconstruct_stage_ctx(pnr_ctx *ctx, const pnr_node *nodes, int64_t n_nod
  * number of offsets; up to cap of them are written; any array may be NULL. */
 int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t *dx, int32_t *dy, int32_t *dz, int64_t cap, int64_t *n);
 
+/* Bytes of device and of pinned host memory the library holds at this moment, over all contexts and exchanges of the process
+ * (every allocation goes through one owner type that counts them); either pointer may be NULL. */
+int pnr_live_bytes(int64_t *device, int64_t *pinned);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,10 +55,10 @@ int host_threads(const Options &o)
 using pnr::set_error;
 
 template <typename T>
-static int upload(T **dst, const std::vector<T> &src, hipStream_t s)
+static int upload(pnr::DevBuf<T> &dst, const std::vector<T> &src, hipStream_t s)
 {
-    PNR_HIP(hipMalloc(dst, std::max<size_t>(src.size(), 1) * sizeof(T)));
-    if (!src.empty()) PNR_HIP(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    PNR_HIP(dst.alloc(src.size()));
+    if (!src.empty()) PNR_HIP(hipMemcpyAsync(dst.get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
     return PNR_OK;
 }
 
@@ -74,35 +74,28 @@ static int download(pnr_ctx *c, T *dst, const T *src, size_t n)
 // resident on the device.  Rebuilt when pnr_set_volume changes the dimensionality.
 static int load_tables(pnr_ctx *c, bool is2d)
 {
-    hipFree(c->d_p); hipFree(c->d_u); hipFree(c->d_w0); hipFree(c->d_w0cws); hipFree(c->d_v); hipFree(c->d_w);
-    hipFree(c->d_wcws); hipFree(c->d_tmpl); hipFree(c->d_corrc); hipFree(c->d_sig); hipFree(c->d_M); hipFree(c->d_moff);
-    hipFree(c->d_rng); hipFree(c->d_grid); hipFree(c->d_axes); hipFree(c->d_axes_off); hipFree(c->d_wd);
-    hipFree(c->d_share); hipFree(c->d_grows);
-    c->d_p = c->d_u = c->d_w0 = c->d_w0cws = c->d_v = c->d_w = c->d_wcws = c->d_tmpl = c->d_corrc = c->d_sig = nullptr;
-    c->d_M = c->d_moff = nullptr; c->d_rng = nullptr; c->d_grid = nullptr; c->d_axes = nullptr; c->d_axes_off = nullptr; c->d_wd = nullptr;
-    c->d_share = nullptr; c->d_grows = nullptr;
     pnr::build_tables(c->prm, is2d, c->tab);
     const pnr::Tables &t = c->tab;
     std::vector<float> sig(c->prm.sig, c->prm.sig + c->prm.nsig);
-    int rc = upload(&c->d_p, t.p, c->stream);
-    if (!rc) rc = upload(&c->d_u, t.u, c->stream);
-    if (!rc) rc = upload(&c->d_w0, t.w0, c->stream);
-    if (!rc) rc = upload(&c->d_w0cws, t.w0_cws, c->stream);
-    if (!rc) rc = upload(&c->d_v, t.v, c->stream);
-    if (!rc) rc = upload(&c->d_w, t.w, c->stream);
-    if (!rc) rc = upload(&c->d_wcws, t.w_cws, c->stream);
-    if (!rc) rc = upload(&c->d_tmpl, t.tmpl, c->stream);
-    if (!rc) rc = upload(&c->d_corrc, t.corrc, c->stream);
-    if (!rc) rc = upload(&c->d_sig, sig, c->stream);
-    if (!rc) rc = upload(&c->d_M, t.M, c->stream);
-    if (!rc) rc = upload(&c->d_moff, t.moff, c->stream);
-    if (!rc) rc = upload(&c->d_rng, t.rng, c->stream);
-    if (!rc) rc = upload(&c->d_grid, t.grid, c->stream);
-    if (!rc) rc = upload(&c->d_axes, t.axes, c->stream);
-    if (!rc) rc = upload(&c->d_axes_off, t.axes_off, c->stream);
-    if (!rc) rc = upload(&c->d_wd, t.wd, c->stream);
-    if (!rc) rc = upload(&c->d_share, t.share_tab, c->stream);
-    if (!rc) rc = upload(&c->d_grows, t.grows, c->stream);
+    int rc = upload(c->d_p, t.p, c->stream);
+    if (!rc) rc = upload(c->d_u, t.u, c->stream);
+    if (!rc) rc = upload(c->d_w0, t.w0, c->stream);
+    if (!rc) rc = upload(c->d_w0cws, t.w0_cws, c->stream);
+    if (!rc) rc = upload(c->d_v, t.v, c->stream);
+    if (!rc) rc = upload(c->d_w, t.w, c->stream);
+    if (!rc) rc = upload(c->d_wcws, t.w_cws, c->stream);
+    if (!rc) rc = upload(c->d_tmpl, t.tmpl, c->stream);
+    if (!rc) rc = upload(c->d_corrc, t.corrc, c->stream);
+    if (!rc) rc = upload(c->d_sig, sig, c->stream);
+    if (!rc) rc = upload(c->d_M, t.M, c->stream);
+    if (!rc) rc = upload(c->d_moff, t.moff, c->stream);
+    if (!rc) rc = upload(c->d_rng, t.rng, c->stream);
+    if (!rc) rc = upload(c->d_grid, t.grid, c->stream);
+    if (!rc) rc = upload(c->d_axes, t.axes, c->stream);
+    if (!rc) rc = upload(c->d_axes_off, t.axes_off, c->stream);
+    if (!rc) rc = upload(c->d_wd, t.wd, c->stream);
+    if (!rc) rc = upload(c->d_share, t.share_tab, c->stream);
+    if (!rc) rc = upload(c->d_grows, t.grows, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = PNR_E_HIP;
     return rc;
 }
@@ -181,10 +174,8 @@ int pnr_create(const pnr_params *p, int device, pnr_ctx **out)
         return PNR_E_HIP;
     }
     c->stream = c->own_stream;
-    (void)hipEventCreate(&c->ev0);
-    (void)hipEventCreate(&c->ev1);
     rc = load_tables(c, /*is2d*/ false);
-    if (!rc && hipMalloc(&c->d_minmax, 8) != hipSuccess) rc = PNR_E_HIP;
+    if (!rc && c->d_minmax.alloc(2) != hipSuccess) rc = PNR_E_HIP;
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = PNR_E_HIP;
     if (rc) {
         pnr_destroy(c);
@@ -201,28 +192,14 @@ void pnr_destroy(pnr_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     pnr_job_destroy(c->job);
     pnr_phased_destroy(c->phased);
-    if (c->h_j8) (void)hipHostFree(c->h_j8);
-    if (c->h_j8v) (void)hipHostFree(c->h_j8v);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (int k = 0; k < pnr_ctx::J8_CHUNKS; k++)
         if (c->j8_ev[k]) (void)hipEventDestroy(c->j8_ev[k]);
     if (c->j8_start) (void)hipEventDestroy(c->j8_start);
-    hipFree(c->d_img_owned); hipFree(c->d_stash); hipFree(c->d_slot_busy); hipFree(c->d_den); hipFree(c->d_den_idx); hipFree(c->d_den_val);
-    hipFree(c->d_tmpA); hipFree(c->d_tmpB); hipFree(c->d_J);
-    hipFree(c->d_Vx); hipFree(c->d_Vy); hipFree(c->d_Vz); hipFree(c->d_J8); hipFree(c->d_minmax);
-    for (int s = 0; s < PNR_MAX_SIGMAS; s++) hipFree(c->d_F[s]);
-    hipFree(c->d_scale); hipFree(c->d_taps); hipFree(c->d_qh); hipFree(c->d_qidx); hipFree(c->d_qcount);
-    hipFree(c->d_p); hipFree(c->d_u); hipFree(c->d_w0); hipFree(c->d_w0cws); hipFree(c->d_v); hipFree(c->d_w);
-    hipFree(c->d_wcws); hipFree(c->d_tmpl); hipFree(c->d_corrc); hipFree(c->d_sig); hipFree(c->d_M); hipFree(c->d_moff);
-    hipFree(c->d_rng); hipFree(c->d_grid); hipFree(c->d_axes); hipFree(c->d_axes_off); hipFree(c->d_wd);
-    hipFree(c->d_share); hipFree(c->d_grows);
-    for (auto &kv : c->scratch) hipFree(kv.second.p);
     c->resolve_timers();
     for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c; // (every device and pinned buffer is a member that frees itself)
 }
 
 int pnr_set_stream(pnr_ctx *c, void *s)
@@ -240,6 +217,16 @@ int pnr_synchronize(pnr_ctx *c)
     return PNR_OK;
 }
 
+// a new or changed volume: nothing computed from the old one stays valid
+static void invalidate_pipeline(pnr_ctx *c)
+{
+    c->have_j8 = false;
+    c->have_v = c->have_scale = false;
+    c->frangi_pruned = false;
+    c->seeds.clear();
+    c->have_soma = false;
+}
+
 static int set_dims(pnr_ctx *c, int64_t w, int64_t h, int64_t l)
 {
     PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
@@ -249,11 +236,7 @@ static int set_dims(pnr_ctx *c, int64_t w, int64_t h, int64_t l)
     PNR_HIP(hipSetDevice(c->device));
     c->w = w; c->h = h; c->l = l;
     c->N = w * h * l;
-    c->have_j8 = false;
-    c->have_v = c->have_scale = false;
-    c->frangi_pruned = false;
-    c->seeds.clear();
-    c->have_soma = false;
+    invalidate_pipeline(c);
     if ((l == 1) != c->tab.is2d) { // the tracker tables depend on the dimensionality (Tracker(..., P == 1, ...))
         PNR_HIP(hipDeviceSynchronize());
         const int rc = load_tables(c, l == 1);
@@ -268,16 +251,10 @@ int pnr_set_volume(pnr_ctx *c, const uint8_t *img, int64_t w, int64_t h, int64_t
     int rc = set_dims(c, w, h, l);
     if (rc) return rc;
     c->d_img = nullptr; // never leave the context pointing at a freed image if the allocation below fails
-    if (c->img_owned_cap < (size_t)c->N) {
-        hipFree(c->d_img_owned);
-        c->d_img_owned = nullptr;
-        c->img_owned_cap = 0;
-        PNR_HIP(hipMalloc(&c->d_img_owned, (size_t)c->N));
-        c->img_owned_cap = (size_t)c->N;
-    }
-    PNR_HIP(hipMemcpyAsync(c->d_img_owned, img, (size_t)c->N, hipMemcpyHostToDevice, c->stream));
+    PNR_HIP(c->d_img_owned.reserve((size_t)c->N));
+    PNR_HIP(hipMemcpyAsync(c->d_img_owned.get(), img, (size_t)c->N, hipMemcpyHostToDevice, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
-    c->d_img = c->d_img_owned;
+    c->d_img = c->d_img_owned.get();
     return PNR_OK;
 }
 
@@ -286,8 +263,7 @@ int pnr_set_volume_device(pnr_ctx *c, const void *dev_img, int64_t w, int64_t h,
     PNR_REQUIRE(dev_img, PNR_E_ARG, "null image");
     int rc = set_dims(c, w, h, l);
     if (rc) return rc;
-    hipFree(c->d_img_owned);
-    c->d_img_owned = nullptr;
+    c->d_img_owned.reset();
     c->d_img = (const uint8_t *)dev_img;
     return PNR_OK;
 }
@@ -312,29 +288,25 @@ static int set_volume_u16(pnr_ctx *c, const void *img, bool host, int64_t w, int
     if (rc) return rc;
     c->d_img = nullptr; // no volume until the map below has succeeded
     const uint16_t *src = (const uint16_t *)img;
-    void *d_up = nullptr;
+    pnr::DevBuf<char> d_up;
     if (host) {
         const size_t bytes = (size_t)c->N * (size_t)nchan * 2;
-        if (hipMalloc(&d_up, bytes) != hipSuccess) {
+        if (d_up.alloc(bytes) != hipSuccess) {
             (void)hipGetLastError();
             set_error("pnr_set_volume_u16: device allocation of %zu B for the 16-bit stack failed", bytes);
             return PNR_E_NOMEM;
         }
-        if (hipMemcpyAsync(d_up, img, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        if (hipMemcpyAsync(d_up.get(), img, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             (void)hipStreamSynchronize(c->stream);
-            hipFree(d_up);
             set_error("pnr_set_volume_u16: upload of %zu B failed", bytes);
             return PNR_E_HIP;
         }
-        src = (const uint16_t *)d_up;
+        src = (const uint16_t *)d_up.get();
     }
     rc = pnr_volume_u16_run(c, src, nchan, channel, wd, lo_out, hi_out);
-    if (d_up) {
-        (void)hipStreamSynchronize(c->stream);
-        hipFree(d_up);
-    }
+    if (d_up) (void)hipStreamSynchronize(c->stream); // (before d_up is freed)
     if (rc) return rc;
-    c->d_img = c->d_img_owned;
+    c->d_img = c->d_img_owned.get();
     return PNR_OK;
 }
 
@@ -373,15 +345,9 @@ int pnr_filter_volume(pnr_ctx *c, const pnr_filter_opts *opts)
     const int rc = pnr_filter_run(c, *opts, &out);
     if (rc) return rc;
     // what pnr_set_volume of the filtered bytes leaves: an owned volume of the same dimensions, no later pipeline state
-    (void)hipFree(c->d_img_owned); // (nullptr while the volume was borrowed: a borrowed volume is never written or freed)
-    c->d_img_owned = out;
-    c->img_owned_cap = (size_t)c->N;
+    c->d_img_owned.adopt(out, (size_t)c->N); // (empty while the volume was borrowed: a borrowed volume is never written or freed)
     c->d_img = out;
-    c->have_j8 = false;
-    c->have_v = c->have_scale = false;
-    c->frangi_pruned = false;
-    c->seeds.clear();
-    c->have_soma = false;
+    invalidate_pipeline(c);
     c->have_graph = false;
     return PNR_OK;
 }
@@ -402,6 +368,13 @@ int pnr_measure_radii(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_
 }
 
 // test tap (pnr_hip_test.h): the shells of the rule, pure host
+int pnr_live_bytes(int64_t *device, int64_t *pinned)
+{
+    if (device) *device = pnr::live_device_bytes.load();
+    if (pinned) *pinned = pnr::live_pinned_bytes.load();
+    return PNR_OK;
+}
+
 int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t *dx, int32_t *dy, int32_t *dz, int64_t cap, int64_t *n)
 {
     PNR_REQUIRE(rmax >= 1 && rmax <= PNR_RADIUS_MAX && n, PNR_E_ARG, "pnr_radius_offsets: rmax = %d outside [1, %d], or null count", rmax, PNR_RADIUS_MAX);
@@ -453,7 +426,7 @@ int pnr_quantise_j8(pnr_ctx *c, float Jmin, float Jmax)
 
 int pnr_get_frangi(pnr_ctx *c, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, uint8_t *Vz)
 {
-    PNR_REQUIRE(c && c->have_j8 && c->d_J, PNR_E_STATE, "pnr_get_frangi: run pnr_frangi first");
+    PNR_REQUIRE(c && c->have_j8 && c->d_J.get(), PNR_E_STATE, "pnr_get_frangi: run pnr_frangi first");
     const size_t n = (size_t)c->N;
     int rc = PNR_OK;
     if ((J || Vx || Vy || Vz) && c->frangi_pruned) {
@@ -468,11 +441,11 @@ int pnr_get_frangi(pnr_ctx *c, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, 
         if (rc) return rc;
     }
     if (Vx || Vy || Vz) rc = pnr_frangi_materialise_v(c); // the pipeline itself only needs the directions at the seeds
-    if (!rc) rc = download(c, J, c->d_J, n);
-    if (!rc) rc = download(c, J8, c->d_J8, n);
-    if (!rc) rc = download(c, Vx, c->d_Vx, n);
-    if (!rc) rc = download(c, Vy, c->d_Vy, n);
-    if (!rc) rc = download(c, Vz, c->d_Vz, n);
+    if (!rc) rc = download(c, J, c->d_J.get(), n);
+    if (!rc) rc = download(c, J8, c->d_J8.get(), n);
+    if (!rc) rc = download(c, Vx, c->d_Vx.get(), n);
+    if (!rc) rc = download(c, Vy, c->d_Vy.get(), n);
+    if (!rc) rc = download(c, Vz, c->d_Vz.get(), n);
     if (rc) return rc;
     PNR_HIP(hipStreamSynchronize(c->stream));
     return PNR_OK;
@@ -485,9 +458,9 @@ int pnr_gaussian(pnr_ctx *c, float sig, float *F)
     int rc = pnr_ensure_frangi_buffers(c);
     if (!rc) rc = pnr_ensure_tmpA(c);
     if (rc) return rc;
-    rc = pnr_gaussian_run(c, sig, c->d_tmpA);
+    rc = pnr_gaussian_run(c, sig, c->d_tmpA.get());
     if (rc) return rc;
-    PNR_HIP(hipMemcpy(F, c->d_tmpA, (size_t)c->N * 4, hipMemcpyDeviceToHost));
+    PNR_HIP(hipMemcpy(F, c->d_tmpA.get(), (size_t)c->N * 4, hipMemcpyDeviceToHost));
     return PNR_OK;
 }
 
@@ -498,18 +471,19 @@ int pnr_hessian(pnr_ctx *c, float sig, float *Dzz, float *Dyy, float *Dyz, float
     PNR_REQUIRE(sig > 0, PNR_E_ARG, "sigma must be positive");
     int rc = pnr_ensure_frangi_buffers(c);
     if (rc) return rc;
-    float *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 6; k++)
-        if (hipMalloc(&d[k], (size_t)c->N * 4) != hipSuccess) {
-            for (int j = 0; j < k; j++) hipFree(d[j]);
+    pnr::DevBuf<float> own[6];
+    float *d[6];
+    for (int k = 0; k < 6; k++) {
+        if (own[k].alloc((size_t)c->N) != hipSuccess) {
             set_error("hipMalloc failed for Hessian tap");
             return PNR_E_NOMEM;
         }
+        d[k] = own[k].get();
+    }
     rc = pnr_hessian_run(c, sig, d);
     float *hst[6] = {Dzz, Dyy, Dyz, Dxx, Dxy, Dxz};
     for (int k = 0; k < 6 && !rc; k++)
         if (hst[k] && hipMemcpy(hst[k], d[k], (size_t)c->N * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = PNR_E_HIP;
-    for (int k = 0; k < 6; k++) hipFree(d[k]);
     c->have_j8 = false; // tmp buffers were reused
     return rc;
 }
@@ -522,10 +496,10 @@ int pnr_set_j8_v(pnr_ctx *c, const uint8_t *J8, const uint8_t *Vx, const uint8_t
     if (!rc) rc = pnr_ensure_v(c);
     if (rc) return rc;
     const size_t n = (size_t)c->N;
-    PNR_HIP(hipMemcpyAsync(c->d_J8, J8, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipMemcpyAsync(c->d_Vx, Vx, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipMemcpyAsync(c->d_Vy, Vy, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipMemcpyAsync(c->d_Vz, Vz, n, hipMemcpyHostToDevice, c->stream));
+    PNR_HIP(hipMemcpyAsync(c->d_J8.get(), J8, n, hipMemcpyHostToDevice, c->stream));
+    PNR_HIP(hipMemcpyAsync(c->d_Vx.get(), Vx, n, hipMemcpyHostToDevice, c->stream));
+    PNR_HIP(hipMemcpyAsync(c->d_Vy.get(), Vy, n, hipMemcpyHostToDevice, c->stream));
+    PNR_HIP(hipMemcpyAsync(c->d_Vz.get(), Vz, n, hipMemcpyHostToDevice, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
     c->have_j8 = true;
     c->have_v = true;

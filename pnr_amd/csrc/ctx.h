@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/pnr_hip.h"
 #include "../../include/pnr_hip_test.h" // the test taps (implemented beside the product entry points)
+#include "devbuf.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdarg>
@@ -119,50 +120,46 @@ struct pnr_ctx {
 
     // volume
     int64_t w = 0, h = 0, l = 0, N = 0;
-    const uint8_t *d_img = nullptr; // device
-    uint8_t *d_img_owned = nullptr;
-    size_t img_owned_cap = 0;
+    const uint8_t *d_img = nullptr; // device: a view of d_img_owned, or of borrowed memory (pnr_set_volume_device)
+    pnr::DevBuf<uint8_t> d_img_owned;
 
     // Frangi state (HBM)
-    float *d_tmpA = nullptr, *d_tmpB = nullptr, *d_J = nullptr;
-    uint8_t *d_Vx = nullptr, *d_Vy = nullptr, *d_Vz = nullptr, *d_J8 = nullptr;
-    unsigned int *d_minmax = nullptr; // [0]=min bits, [1]=max bits
-    float *d_F[PNR_MAX_SIGMAS] = {};  // smoothed volume of every scale, kept for the direction bytes (frangi.hip)
-    uint8_t *d_scale = nullptr;       // per voxel: the scale whose response is in J
+    pnr::DevBuf<float> d_tmpA, d_tmpB, d_J;
+    pnr::DevBuf<uint8_t> d_Vx, d_Vy, d_Vz, d_J8;
+    pnr::DevBuf<unsigned int> d_minmax;    // [0]=min bits, [1]=max bits
+    pnr::DevBuf<float> d_F[PNR_MAX_SIGMAS]; // smoothed volume of every scale, kept for the direction bytes (frangi.hip)
+    pnr::DevBuf<uint8_t> d_scale;          // per voxel: the scale whose response is in J
     bool frangi_pruned = false, frangi_exact_once = false; // J / the winning scale of J8 = 0 voxels are not exact (option frangi_prune); next run without it
     float Jmax_run = 0.f;                                   // the maximum the last Frangi run found itself (before pnr_quantise_j8)
     int64_t frangi_recomputes = 0;                          // exact re-runs pnr_get_frangi / pnr_quantise_j8 had to make (pnr_get_option "frangi_recomputes")
     int64_t fr_zs0 = 0, fr_zs1 = 0;                         // planes the extremes of the last Frangi run were taken over
     bool have_scale = false, have_v = false; // d_scale + d_F valid / the direction volumes Vx, Vy, Vz are filled
-    float *d_taps = nullptr;          // Gaussian taps of all scales (frangi.hip: TAPS_SLOT floats per pass, zero-padded)
+    pnr::DevBuf<float> d_taps;        // Gaussian taps of all scales (frangi.hip: TAPS_SLOT floats per pass, zero-padded)
     std::vector<float> taps_stage;    // their host staging (asynchronous uploads)
-    float *d_qh = nullptr;            // survivor queue of the Hessian stage: [region][6][entries]
-    unsigned int *d_qidx = nullptr, *d_qcount = nullptr;
-    size_t q_regions = 0;
+    pnr::DevBuf<float> d_qh;          // survivor queue of the Hessian stage: [region][6][entries]
+    pnr::DevBuf<unsigned int> d_qidx, d_qcount;
     int64_t frangi_cap = 0;           // voxels the buffers above were sized for
     bool have_j8 = false;
     float Jmin = 0, Jmax = 0;
 
     // device tables
-    float *d_p = nullptr, *d_u = nullptr, *d_w0 = nullptr, *d_w0cws = nullptr, *d_v = nullptr, *d_w = nullptr,
-          *d_wcws = nullptr, *d_tmpl = nullptr, *d_corrc = nullptr, *d_sig = nullptr;
-    int *d_M = nullptr, *d_moff = nullptr, *d_grid = nullptr, *d_axes_off = nullptr;
-    float *d_axes = nullptr, *d_wd = nullptr;
-    int *d_share = nullptr, *d_grows = nullptr; // nested scales (Tables::share_tab, grows)
-    uint32_t *d_rng = nullptr;
+    pnr::DevBuf<float> d_p, d_u, d_w0, d_w0cws, d_v, d_w, d_wcws, d_tmpl, d_corrc, d_sig;
+    pnr::DevBuf<int> d_M, d_moff, d_grid, d_axes_off;
+    pnr::DevBuf<float> d_axes, d_wd;
+    pnr::DevBuf<int> d_share, d_grows; // nested scales (Tables::share_tab, grows)
+    pnr::DevBuf<uint32_t> d_rng;
 
     // SMC pass-1 sample stash (HBM scratch, sized at the first trace batch)
-    float *d_stash = nullptr;
-    int *d_slot_busy = nullptr;
+    pnr::DevBuf<float> d_stash;
+    pnr::DevBuf<int> d_slot_busy;
     size_t stash_bytes = 0;
     int stash_slots = 0;
 
     // node-density map of earlier trace batches (u8 per voxel), read by smc_trace for early DENSITY stops
-    uint8_t *d_den = nullptr;
+    pnr::DevBuf<uint8_t> d_den;
     int64_t den_cap = 0;
-    long long *d_den_idx = nullptr; // staging for the per-batch scatter of touched voxels
-    uint8_t *d_den_val = nullptr;
-    size_t den_stage_cap = 0;
+    pnr::DevBuf<long long> d_den_idx; // staging for the per-batch scatter of touched voxels
+    pnr::DevBuf<uint8_t> d_den_val;
 
     struct pnr_trace_job *job = nullptr; // device buffers of pnr_trace_batch / the persistent driver's batches (ctx stream)
     struct pnr_phased *phased = nullptr; // state of the launch-per-phase SMC driver (smc_phased.hip)
@@ -176,8 +173,7 @@ struct pnr_ctx {
     bool have_soma = false;
 
     // seeds
-    unsigned char *h_j8 = nullptr, *h_j8v = nullptr; // pinned staging of the sparse J8 hand-over to the flood fill: bitmap | values (seeds.hip)
-    size_t h_j8_cap = 0, h_j8v_cap = 0;
+    pnr::PinBuf<unsigned char> h_j8, h_j8v; // pinned staging of the sparse J8 hand-over to the flood fill: bitmap | values (seeds.hip)
     static constexpr int J8_CHUNKS = 16;   // the download is cut into chunks of layers so that the flood fill starts on the first ones
     hipStream_t copy_stream = nullptr;
     hipEvent_t j8_ev[J8_CHUNKS] = {}, j8_start = nullptr;
@@ -193,7 +189,6 @@ struct pnr_ctx {
     // profiling: HIP event pairs recorded on the ctx stream around each kernel group, resolved
     // lazily (no host sync inside the timed region)
     bool profiling = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; // unused legacy pair (kept for create/destroy symmetry)
     struct Pending {
         std::string group;
         hipEvent_t a, b;
@@ -210,25 +205,20 @@ struct pnr_ctx {
 
     // grow-only named device scratch (per-layer tables, candidate keys, ...): nothing is allocated or freed inside a timed stage
     // once the first pass has sized it
-    struct DevScratch { void *p = nullptr; size_t cap = 0; };
-    std::map<std::string, DevScratch> scratch;
+    std::map<std::string, pnr::DevBuf<char>> scratch;
     template <typename T>
     int scratch_get(const char *name, size_t count, T **out)
     {
-        DevScratch &b = scratch[name];
+        pnr::DevBuf<char> &b = scratch[name];
         const size_t need = std::max<size_t>(count, 1) * sizeof(T);
-        if (b.cap < need) {
-            if (b.p) (void)hipFree(b.p); // (synchronises the device)
-            b.p = nullptr;
-            b.cap = 0;
+        if (b.count() < need) {
             const size_t cap = need + need / 2;
-            if (hipMalloc(&b.p, cap) != hipSuccess) {
+            if (b.alloc(cap) != hipSuccess) { // (releasing the old one synchronises the device)
                 pnr::set_error("hipMalloc of %zu B for scratch '%s' failed", cap, name);
                 return PNR_E_NOMEM;
             }
-            b.cap = cap;
         }
-        *out = (T *)b.p;
+        *out = (T *)b.get();
         return PNR_OK;
     }
 

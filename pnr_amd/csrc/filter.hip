@@ -328,12 +328,10 @@ int launch_col(hipStream_t st, const uint8_t *src, uint8_t *dst, const uint8_t *
     return 1;
 }
 
-int alloc_volume(size_t n, uint8_t **p, const char *what)
+int alloc_volume(size_t n, pnr::DevBuf<uint8_t> &p, const char *what)
 {
-    *p = nullptr;
-    if (hipMalloc(p, n) != hipSuccess) {
+    if (p.alloc(n) != hipSuccess) {
         (void)hipGetLastError();
-        *p = nullptr;
         pnr::set_error("pnr_filter_volume: device allocation of %zu B for %s failed", n, what);
         return PNR_E_NOMEM;
     }
@@ -352,13 +350,11 @@ int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, uint8_t **result)
     PNR_REQUIRE(med_blocks < (1LL << 31) && col_blocks < (1LL << 31), PNR_E_ARG, "pnr_filter_volume: volume extent too large");
     const bool both = o.median && o.tophat_r;
     hipStream_t st = c->stream;
-    uint8_t *A = nullptr, *B = nullptr; // A: the first stage's output; B: the top-hat's buffer behind a median
-    int rc = alloc_volume((size_t)N, &A, "the filtered volume");
-    if (!rc && both) rc = alloc_volume((size_t)N, &B, "the top-hat scratch");
-    if (rc) {
-        (void)hipFree(A);
-        return rc;
-    }
+    pnr::DevBuf<uint8_t> bA, bB; // A: the first stage's output; B: the top-hat's buffer behind a median
+    int rc = alloc_volume((size_t)N, bA, "the filtered volume");
+    if (!rc && both) rc = alloc_volume((size_t)N, bB, "the top-hat scratch");
+    if (rc) return rc;
+    uint8_t *const A = bA.get(), *const B = bB.get();
     const uint8_t *V = c->d_img;
     uint8_t *out = A;
     int launches = 0;
@@ -387,13 +383,10 @@ int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, uint8_t **result)
     hipError_t e = hipGetLastError();
     c->toc("filter", launches);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (out != A) (void)hipFree(A);
-    if (B && out != B) (void)hipFree(B);
     if (e != hipSuccess) {
-        (void)hipFree(out);
         pnr::set_error("pnr_filter_volume: %s", hipGetErrorString(e));
         return PNR_E_HIP;
     }
-    *result = out;
+    *result = (out == A ? bA : bB).release(); // the caller adopts it; the other buffer is freed here
     return PNR_OK;
 }

@@ -1449,21 +1449,19 @@ extern "C" int pnr_debug_ht_stamps(unsigned long long *out8, int reset)
 int pnr_ensure_frangi_buffers(pnr_ctx *c)
 {
     if (c->frangi_cap >= c->N && c->d_J) return PNR_OK;
-    hipFree(c->d_tmpA); hipFree(c->d_tmpB); hipFree(c->d_J);
-    hipFree(c->d_Vx); hipFree(c->d_Vy); hipFree(c->d_Vz); hipFree(c->d_J8); hipFree(c->d_scale);
-    c->d_tmpA = c->d_tmpB = c->d_J = nullptr;
-    c->d_Vx = c->d_Vy = c->d_Vz = c->d_J8 = c->d_scale = nullptr;
-    for (int s = 0; s < PNR_MAX_SIGMAS; s++) { hipFree(c->d_F[s]); c->d_F[s] = nullptr; }
+    for (auto *b : {&c->d_tmpA, &c->d_tmpB, &c->d_J}) b->reset();
+    for (auto *b : {&c->d_Vx, &c->d_Vy, &c->d_Vz, &c->d_J8, &c->d_scale}) b->reset();
+    for (auto &f : c->d_F) f.reset();
     c->frangi_cap = 0;
     c->have_v = c->have_scale = false;
     // tmpA and the three direction volumes (7.5 GB at 1024^3) are only allocated where they are used -- pnr_ensure_tmpA / pnr_ensure_v:
     // the default pipeline never touches them, and a first hipMalloc of tens of GB costs a one-shot process about 25 ms per GB
     // (scripts/probes/malloc_probe.py)
     const size_t n = (size_t)c->N;
-    PNR_HIP(hipMalloc(&c->d_tmpB, n * 4));
-    PNR_HIP(hipMalloc(&c->d_J, n * 4));
-    PNR_HIP(hipMalloc(&c->d_J8, n));
-    PNR_HIP(hipMalloc(&c->d_scale, n));
+    PNR_HIP(c->d_tmpB.alloc(n));
+    PNR_HIP(c->d_J.alloc(n));
+    PNR_HIP(c->d_J8.alloc(n));
+    PNR_HIP(c->d_scale.alloc(n));
     c->frangi_cap = c->N;
     return PNR_OK;
 }
@@ -1472,7 +1470,7 @@ int pnr_ensure_tmpA(pnr_ctx *c)
 {
     if (c->d_tmpA) return PNR_OK;
     PNR_REQUIRE(c->frangi_cap >= c->N, PNR_E_STATE, "the Frangi buffers are not allocated");
-    PNR_HIP(hipMalloc(&c->d_tmpA, (size_t)c->frangi_cap * 4));
+    PNR_HIP(c->d_tmpA.alloc((size_t)c->frangi_cap));
     return PNR_OK;
 }
 
@@ -1480,9 +1478,9 @@ int pnr_ensure_v(pnr_ctx *c)
 {
     if (c->d_Vx && c->d_Vy && c->d_Vz) return PNR_OK;
     PNR_REQUIRE(c->frangi_cap >= c->N, PNR_E_STATE, "the Frangi buffers are not allocated");
-    if (!c->d_Vx) PNR_HIP(hipMalloc(&c->d_Vx, (size_t)c->frangi_cap));
-    if (!c->d_Vy) PNR_HIP(hipMalloc(&c->d_Vy, (size_t)c->frangi_cap));
-    if (!c->d_Vz) PNR_HIP(hipMalloc(&c->d_Vz, (size_t)c->frangi_cap));
+    if (!c->d_Vx) PNR_HIP(c->d_Vx.alloc((size_t)c->frangi_cap));
+    if (!c->d_Vy) PNR_HIP(c->d_Vy.alloc((size_t)c->frangi_cap));
+    if (!c->d_Vz) PNR_HIP(c->d_Vz.alloc((size_t)c->frangi_cap));
     return PNR_OK;
 }
 
@@ -1490,7 +1488,7 @@ int pnr_ensure_v(pnr_ctx *c)
 static int ensure_taps(pnr_ctx *c)
 {
     if (!c->d_taps) {
-        PNR_HIP(hipMalloc(&c->d_taps, (size_t)PNR_MAX_SIGMAS * 2 * TAPS_SLOT * 4));
+        PNR_HIP(c->d_taps.alloc((size_t)PNR_MAX_SIGMAS * 2 * TAPS_SLOT));
         c->taps_stage.assign((size_t)PNR_MAX_SIGMAS * 2 * TAPS_SLOT, 0.f);
     }
     return PNR_OK;
@@ -1501,7 +1499,7 @@ static int ensure_taps(pnr_ctx *c)
 static int ensure_scale_volume(pnr_ctx *c, int s)
 {
     if (c->d_F[s]) return PNR_OK;
-    PNR_HIP(hipMalloc(&c->d_F[s], (size_t)c->frangi_cap * 4));
+    PNR_HIP(c->d_F[s].alloc((size_t)c->frangi_cap));
     return PNR_OK;
 }
 
@@ -1517,21 +1515,19 @@ static int hess_chunk_planes(const pnr_ctx *c)
 }
 static int ensure_queue(pnr_ctx *c, size_t regions)
 {
-    if (c->q_regions >= regions) return PNR_OK;
+    if (c->d_qcount.count() >= regions) return PNR_OK; // (allocated last: its count is the regions all three were sized for)
     PNR_HIP(hipDeviceSynchronize());
-    hipFree(c->d_qh); hipFree(c->d_qidx); hipFree(c->d_qcount);
-    c->d_qh = nullptr; c->d_qidx = nullptr; c->d_qcount = nullptr; c->q_regions = 0;
-    PNR_HIP(hipMalloc(&c->d_qh, regions * 6 * HT_REGION * 4));
-    PNR_HIP(hipMalloc(&c->d_qidx, regions * HT_REGION * 4));
-    PNR_HIP(hipMalloc(&c->d_qcount, regions * 4));
-    c->q_regions = regions;
+    c->d_qh.reset(), c->d_qidx.reset(), c->d_qcount.reset();
+    PNR_HIP(c->d_qh.alloc(regions * 6 * HT_REGION));
+    PNR_HIP(c->d_qidx.alloc(regions * HT_REGION));
+    PNR_HIP(c->d_qcount.alloc(regions));
     return PNR_OK;
 }
 
 // `d_slot`: a slot of c->d_taps; the kernels get d_slot + 1 (tap 0).  Staged in the context (the copy is asynchronous)
 static int upload_taps(pnr_ctx *c, const std::vector<float> &g, float *d_slot)
 {
-    float *stage = c->taps_stage.data() + (d_slot - c->d_taps);
+    float *stage = c->taps_stage.data() + (d_slot - c->d_taps.get());
     std::fill(stage, stage + TAPS_SLOT, 0.f);
     std::copy(g.begin(), g.end(), stage + 1);
     PNR_HIP(hipMemcpyAsync(d_slot, stage, (size_t)TAPS_SLOT * 4, hipMemcpyHostToDevice, c->stream));
@@ -1554,8 +1550,8 @@ static int gaussian3d(pnr_ctx *c, const std::vector<float> &gxy, const std::vect
     // z pass reads it into d_out; pass by pass, the x result may sit in d_out itself (it is consumed before d_out is written).  A
     // single-slice stack has no z pass: y writes d_out, x a scratch volume.  The scratch is tmpB (tmpA only when d_out is tmpB).
     const bool two_d = (l == 1); // the 2-D imgaussian (frangi.cpp:576-645)
-    if (d_out == c->d_tmpB) { rc = pnr_ensure_tmpA(c); if (rc) return rc; }
-    float *const scratch = d_out == c->d_tmpB ? c->d_tmpA : c->d_tmpB;
+    if (d_out == c->d_tmpB.get()) { rc = pnr_ensure_tmpA(c); if (rc) return rc; }
+    float *const scratch = d_out == c->d_tmpB.get() ? c->d_tmpA.get() : c->d_tmpB.get();
     float *bufY = two_d ? d_out : scratch;
     float *bufX = two_d ? scratch : d_out;
     float *bufZ = d_out;
@@ -1607,7 +1603,7 @@ int pnr_gaussian_run(pnr_ctx *c, float sig, float *d_out)
     std::vector<float> gxy, gz;
     pnr::gaussian_taps(sig, gxy);
     pnr::gaussian_taps(sig / c->prm.zdist, gz);
-    rc = gaussian3d(c, gxy, gz, c->d_taps, d_out);
+    rc = gaussian3d(c, gxy, gz, c->d_taps.get(), d_out);
     hipStreamSynchronize(c->stream);
     return rc;
 }
@@ -1623,14 +1619,14 @@ static void tile_grid(const pnr_ctx *c, int zc0, int zc1, int &tiles_x, int &til
 int pnr_hessian_run(pnr_ctx *c, float sig, float *const d_out[6])
 {
     int rc = pnr_ensure_tmpA(c);
-    if (!rc) rc = pnr_gaussian_run(c, sig, c->d_tmpA);
+    if (!rc) rc = pnr_gaussian_run(c, sig, c->d_tmpA.get());
     if (rc) return rc;
     const int w = (int)c->w, h = (int)c->h, l = (int)c->l;
     HessOut dump{d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5]};
     int tiles_x, tiles_y;
     unsigned blocks;
     tile_grid(c, 0, l, tiles_x, tiles_y, blocks);
-    hipLaunchKernelGGL(hessian_tile<true>, dim3(blocks), dim3(HT_THREADS), 0, c->stream, (const float *)c->d_tmpA, w, h, l, tiles_x, tiles_y, 0, l,
+    hipLaunchKernelGGL(hessian_tile<true>, dim3(blocks), dim3(HT_THREADS), 0, c->stream, (const float *)c->d_tmpA.get(), w, h, l, tiles_x, tiles_y, 0, l,
                        sig * sig, HessQueue{}, (unsigned int *)nullptr, 1, 0, l, dump, 0.f, 0);
     PNR_HIP(hipGetLastError());
     PNR_HIP(hipStreamSynchronize(c->stream));
@@ -1645,9 +1641,9 @@ int pnr_frangi_materialise_v(pnr_ctx *c)
     PNR_REQUIRE(c->have_scale, PNR_E_STATE, "no Frangi response: the direction volumes cannot be produced");
     { const int rcv = pnr_ensure_v(c); if (rcv) return rcv; }
     ScaleVols SV{};
-    for (int s = 0; s < c->prm.nsig; s++) { SV.F[s] = c->d_F[s]; SV.s2[s] = c->prm.sig[s] * c->prm.sig[s]; }
-    hipLaunchKernelGGL(vdir_points, dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, SV, (const unsigned char *)c->d_scale, (const i64 *)nullptr,
-                       (i64)c->N, (int)c->w, (int)c->h, (int)c->l, c->d_Vx, c->d_Vy, c->d_Vz, 0);
+    for (int s = 0; s < c->prm.nsig; s++) { SV.F[s] = c->d_F[s].get(); SV.s2[s] = c->prm.sig[s] * c->prm.sig[s]; }
+    hipLaunchKernelGGL(vdir_points, dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, SV, (const unsigned char *)c->d_scale.get(), (const i64 *)nullptr,
+                       (i64)c->N, (int)c->w, (int)c->h, (int)c->l, c->d_Vx.get(), c->d_Vy.get(), c->d_Vz.get(), 0);
     PNR_HIP(hipGetLastError());
     PNR_HIP(hipStreamSynchronize(c->stream));
     c->have_v = true;
@@ -1662,8 +1658,8 @@ int pnr_seed_dirs(pnr_ctx *c, const long long *d_idx, int n, unsigned char *d_di
     if (!c->have_v) {
         PNR_REQUIRE(c->have_scale, PNR_E_STATE, "no direction field: run pnr_frangi (or pnr_set_j8_v) first");
         ScaleVols SV{};
-        for (int s = 0; s < c->prm.nsig; s++) { SV.F[s] = c->d_F[s]; SV.s2[s] = c->prm.sig[s] * c->prm.sig[s]; }
-        hipLaunchKernelGGL(vdir_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, SV, (const unsigned char *)c->d_scale, (const i64 *)d_idx,
+        for (int s = 0; s < c->prm.nsig; s++) { SV.F[s] = c->d_F[s].get(); SV.s2[s] = c->prm.sig[s] * c->prm.sig[s]; }
+        hipLaunchKernelGGL(vdir_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, SV, (const unsigned char *)c->d_scale.get(), (const i64 *)d_idx,
                            (i64)n, (int)c->w, (int)c->h, (int)c->l, d_dirs, (unsigned char *)nullptr, (unsigned char *)nullptr, 1);
         PNR_HIP(hipGetLastError());
         return PNR_OK;
@@ -1676,10 +1672,11 @@ int pnr_seed_dirs(pnr_ctx *c, const long long *d_idx, int n, unsigned char *d_di
 int pnr_eigen_run(pnr_ctx *c, const double *A, int64_t n, double *V, double *d)
 {
     if (n == 0) return PNR_OK;
-    double *dA = nullptr, *dV = nullptr, *dd = nullptr;
-    PNR_HIP(hipMalloc(&dA, (size_t)n * 72));
-    hipError_t e = hipMalloc(&dd, (size_t)n * 24);
-    if (e == hipSuccess && V) e = hipMalloc(&dV, (size_t)n * 72);
+    pnr::DevBuf<double> bA, bV, bd; // (freed on every path, after the synchronise below on the good one)
+    PNR_HIP(bA.alloc((size_t)n * 9));
+    hipError_t e = bd.alloc((size_t)n * 3);
+    if (e == hipSuccess && V) e = bV.alloc((size_t)n * 9);
+    double *dA = bA.get(), *dV = bV.get(), *dd = bd.get();
     if (e == hipSuccess) e = hipMemcpyAsync(dA, A, (size_t)n * 72, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         if (V) hipLaunchKernelGGL(eigen_kat<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dA, (i64)n, dV, dd);
@@ -1689,7 +1686,6 @@ int pnr_eigen_run(pnr_ctx *c, const double *A, int64_t n, double *V, double *d)
     if (e == hipSuccess) e = hipMemcpyAsync(d, dd, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && V) e = hipMemcpyAsync(V, dV, (size_t)n * 72, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dA); (void)hipFree(dV); (void)hipFree(dd);
     PNR_HIP(e);
     return PNR_OK;
 }
@@ -1697,7 +1693,7 @@ int pnr_eigen_run(pnr_ctx *c, const double *A, int64_t n, double *V, double *d)
 // J -> J8 with the given extremes (Advantra_plugin.cpp:2499-2512)
 int pnr_j8_run(pnr_ctx *c, float jmin, float jmax)
 {
-    PNR_REQUIRE(c->d_J && c->frangi_cap >= c->N, PNR_E_STATE, "no Frangi response to quantise");
+    PNR_REQUIRE(c->d_J.get() && c->frangi_cap >= c->N, PNR_E_STATE, "no Frangi response to quantise");
     c->Jmin = jmin;
     c->Jmax = jmax;
     const int flat = std::fabs(c->Jmax - c->Jmin) <= FLT_MIN;
@@ -1705,7 +1701,7 @@ int pnr_j8_run(pnr_ctx *c, float jmin, float jmax)
     {
         i64 blocks = (c->N + 1023) / 1024;
         if (blocks > 256 * 16) blocks = 256 * 16;
-        hipLaunchKernelGGL(j8_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->d_J, c->d_J8, c->N, c->Jmin,
+        hipLaunchKernelGGL(j8_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->d_J.get(), c->d_J8.get(), c->N, c->Jmin,
                            c->Jmax, flat);
     }
     c->toc("j8");
@@ -1730,7 +1726,7 @@ int pnr_frangi_run_range(pnr_ctx *c, int64_t zs0, int64_t zs1, bool finish, floa
     const int w = (int)c->w, h = (int)c->h, l = (int)c->l;
     const pnr_params &P = c->prm;
     const unsigned int init[2] = {0xffffffffu, 0u};
-    PNR_HIP(hipMemcpyAsync(c->d_minmax, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+    PNR_HIP(hipMemcpyAsync(c->d_minmax.get(), init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     c->have_v = c->have_scale = false;
     // f32 products, as "2*alpha*alpha" etc. in frangi.cpp:214-216
     const float two_a2 = 2 * P.alpha * P.alpha, two_b2 = 2 * P.beta * P.beta, two_c2 = 2 * P.C * P.C;
@@ -1746,8 +1742,8 @@ int pnr_frangi_run_range(pnr_ctx *c, int64_t zs0, int64_t zs1, bool finish, floa
         rc = ensure_queue(c, blocks);
         if (rc) return rc;
         // the first scale writes every voxel; those whose response is proven 0 without the solver keep this 0 (and scale 0)
-        PNR_HIP(hipMemsetAsync(c->d_J, 0, (size_t)c->N * 4, c->stream));
-        PNR_HIP(hipMemsetAsync(c->d_scale, 0, (size_t)c->N, c->stream));
+        PNR_HIP(hipMemsetAsync(c->d_J.get(), 0, (size_t)c->N * 4, c->stream));
+        PNR_HIP(hipMemsetAsync(c->d_scale.get(), 0, (size_t)c->N, c->stream));
     }
     for (int s = 0; s < P.nsig; s++) {
         float *Fs = nullptr;
@@ -1755,20 +1751,20 @@ int pnr_frangi_run_range(pnr_ctx *c, int64_t zs0, int64_t zs1, bool finish, floa
             rc = pnr_ensure_tmpA(c);
             if (!rc) rc = pnr_ensure_v(c);
             if (rc) return rc;
-            Fs = c->d_tmpA;
+            Fs = c->d_tmpA.get();
         }
         if (l > 1) {
             rc = ensure_scale_volume(c, s);
             if (rc) return rc;
-            Fs = c->d_F[s];
+            Fs = c->d_F[s].get();
         }
-        rc = gaussian3d(c, c->tab.gxy[s], c->tab.gz[s], c->d_taps + (size_t)s * 2 * TAPS_SLOT, Fs);
+        rc = gaussian3d(c, c->tab.gxy[s], c->tab.gz[s], c->d_taps.get() + (size_t)s * 2 * TAPS_SLOT, Fs);
         if (rc) return rc;
         if (l == 1) { // P == 1: frangi2d (Advantra_plugin.cpp:2496-2497) with frangi_betaone = .5, frangi_betatwo = 15 (:69-70)
             c->tic();
             const float beta2d = (float)(2 * std::pow((double).5f, 2)), c2d = (float)(2 * std::pow((double)15.f, 2));
-            hipLaunchKernelGGL(frangi2d_pixel, dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, (const float *)Fs, c->d_J,
-                               c->d_Vx, c->d_Vy, c->d_Vz, w, h, P.sig[s] * P.sig[s], beta2d, c2d, s == 0 ? 1 : 0, c->d_minmax);
+            hipLaunchKernelGGL(frangi2d_pixel, dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, (const float *)Fs, c->d_J.get(),
+                               c->d_Vx.get(), c->d_Vy.get(), c->d_Vz.get(), w, h, P.sig[s] * P.sig[s], beta2d, c2d, s == 0 ? 1 : 0, c->d_minmax.get());
             c->toc("hessian_eigen");
             continue;
         }
@@ -1788,19 +1784,19 @@ int pnr_frangi_run_range(pnr_ctx *c, int64_t zs0, int64_t zs1, bool finish, floa
             int tiles_x, tiles_y;
             unsigned blocks;
             tile_grid(c, zc0, zc1, tiles_x, tiles_y, blocks);
-            const HessQueue Q{c->d_qh, c->d_qidx, c->d_qcount};
+            const HessQueue Q{c->d_qh.get(), c->d_qidx.get(), c->d_qcount.get()};
             c->tic();
             hipLaunchKernelGGL(hessian_tile<false>, dim3(blocks), dim3(HT_THREADS), 0, c->stream, (const float *)Fs, w, h, l, tiles_x, tiles_y, zc0, zc1,
-                               P.sig[s] * P.sig[s], Q, c->d_minmax, s == 0 ? 1 : 0, (int)zs0, (int)zs1, HessOut{}, two_c2, prune);
+                               P.sig[s] * P.sig[s], Q, c->d_minmax.get(), s == 0 ? 1 : 0, (int)zs0, (int)zs1, HessOut{}, two_c2, prune);
             c->toc("hessian_tile");
             c->tic();
-            hipLaunchKernelGGL(eigen_queue, dim3(blocks * EQ_SUB), dim3(EQ_BLOCK), 0, c->stream, Q, c->d_J, c->d_scale, w, h, tiles_x, tiles_y, zc0,
-                               two_a2, two_b2, two_c2, s == 0 ? 1 : 0, s, c->d_minmax, (int)zs0, (int)zs1);
+            hipLaunchKernelGGL(eigen_queue, dim3(blocks * EQ_SUB), dim3(EQ_BLOCK), 0, c->stream, Q, c->d_J.get(), c->d_scale.get(), w, h, tiles_x, tiles_y, zc0,
+                               two_a2, two_b2, two_c2, s == 0 ? 1 : 0, s, c->d_minmax.get(), (int)zs0, (int)zs1);
             c->toc("hessian_eigen");
         }
     }
     unsigned int mm[2];
-    PNR_HIP(hipMemcpyAsync(mm, c->d_minmax, sizeof(mm), hipMemcpyDeviceToHost, c->stream));
+    PNR_HIP(hipMemcpyAsync(mm, c->d_minmax.get(), sizeof(mm), hipMemcpyDeviceToHost, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
     PNR_HIP(hipGetLastError());
     c->Jmin = ord2f(mm[0]);

@@ -184,20 +184,20 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         PNR_HIP(hipStreamSynchronize(st)); // (the host table ends here)
         c->scratch[key];
     } else {
-        d_off = (uint32_t *)c->scratch["radius_off"].p;
-        d_start = (int *)c->scratch["radius_start"].p;
+        d_off = (uint32_t *)c->scratch["radius_off"].get();
+        d_start = (int *)c->scratch["radius_start"].get();
     }
     // device buffers of the call: the sum | the positions | the order of the nodes | k
     const size_t o_xyz = 16, o_ord = o_xyz + pad16((size_t)n * 12), o_k = o_ord + pad16((size_t)n * 4), bytes = o_k + pad16((size_t)n * 4);
-    char *d_buf = nullptr;
-    if (hipMalloc(&d_buf, bytes) != hipSuccess) {
+    pnr::DevBuf<char> buf; // (freed when the call returns)
+    if (buf.alloc(bytes) != hipSuccess) {
         (void)hipGetLastError();
         pnr::set_error("pnr_measure_radii: device allocation of %zu B failed", bytes);
         return PNR_E_NOMEM;
     }
+    char *const d_buf = buf.get();
     auto fail = [&](hipError_t e) {
         (void)hipStreamSynchronize(st);
-        (void)hipFree(d_buf);
         pnr::set_error("pnr_measure_radii: %s", hipGetErrorString(e));
         return PNR_E_HIP;
     };
@@ -250,6 +250,5 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         if (e == hipSuccess) e = hipStreamSynchronize(st); // (the host vectors above end here)
         if (e != hipSuccess) return fail(e);
     }
-    (void)hipFree(d_buf);
     return PNR_OK;
 }

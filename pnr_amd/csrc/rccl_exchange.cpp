@@ -71,8 +71,8 @@ struct pnr_rccl_exchange {
     hipStream_t st = nullptr;
     int rank = 0, world = 1, device = 0;
     size_t cap = 0;                // bytes per rank and call
-    unsigned char *h_send = nullptr, *h_recv = nullptr; // pinned
-    unsigned char *d_send = nullptr, *d_recv = nullptr;
+    pnr::PinBuf<unsigned char> h_send, h_recv;
+    pnr::DevBuf<unsigned char> d_send, d_recv;
 };
 
 #define RX_HIP(call, x)                                                                                                  \
@@ -108,13 +108,9 @@ void pnr_rccl_exchange_close(pnr_rccl_exchange *X)
     if (hipGetDevice(&prev) == hipSuccess) (void)hipSetDevice(X->device);
     if (X->st) (void)hipStreamSynchronize(X->st);
     if (X->comm) (void)X->A.CommDestroy(X->comm);
-    if (X->h_send) (void)hipHostFree(X->h_send);
-    if (X->h_recv) (void)hipHostFree(X->h_recv);
-    (void)hipFree(X->d_send);
-    (void)hipFree(X->d_recv);
     if (X->st) (void)hipStreamDestroy(X->st);
+    delete X; // (frees the staging buffers)
     if (prev >= 0) (void)hipSetDevice(prev);
-    delete X;
 }
 
 int pnr_rccl_exchange_open(const void *id128, int rank, int world, int device, int64_t capacity_bytes, pnr_rccl_exchange **out)
@@ -132,10 +128,10 @@ int pnr_rccl_exchange_open(const void *id128, int rank, int world, int device, i
     X->cap = (size_t)((capacity_bytes + 15) / 16 * 16);
     RX_HIP(hipSetDevice(device), pnr_rccl_exchange_close(X));
     RX_HIP(hipStreamCreateWithFlags(&X->st, hipStreamNonBlocking), pnr_rccl_exchange_close(X));
-    RX_HIP(hipHostMalloc(&X->h_send, X->cap), pnr_rccl_exchange_close(X));
-    RX_HIP(hipHostMalloc(&X->h_recv, X->cap * (size_t)world), pnr_rccl_exchange_close(X));
-    RX_HIP(hipMalloc(&X->d_send, X->cap), pnr_rccl_exchange_close(X));
-    RX_HIP(hipMalloc(&X->d_recv, X->cap * (size_t)world), pnr_rccl_exchange_close(X));
+    RX_HIP(X->h_send.alloc(X->cap), pnr_rccl_exchange_close(X));
+    RX_HIP(X->h_recv.alloc(X->cap * (size_t)world), pnr_rccl_exchange_close(X));
+    RX_HIP(X->d_send.alloc(X->cap), pnr_rccl_exchange_close(X));
+    RX_HIP(X->d_recv.alloc(X->cap * (size_t)world), pnr_rccl_exchange_close(X));
     ncclUniqueId id;
     std::memcpy(&id, id128, 128);
     RX_NCCL(X->A.CommInitRank(&X->comm, world, id, rank), pnr_rccl_exchange_close(X));
@@ -151,12 +147,12 @@ int pnr_rccl_allgather(void *user, const void *send, void *recv, int64_t bytes_p
     PNR_REQUIRE((size_t)bytes_per_rank <= X->cap, PNR_E_ARG, "RCCL exchange opened for %zu bytes per rank, asked for %lld", X->cap, (long long)bytes_per_rank);
     if (bytes_per_rank == 0) return PNR_OK;
     const size_t n = (size_t)bytes_per_rank;
-    std::memcpy(X->h_send, send, n);
-    RX_HIP(hipMemcpyAsync(X->d_send, X->h_send, n, hipMemcpyHostToDevice, X->st), );
-    RX_NCCL(X->A.AllGather(X->d_send, X->d_recv, n, ncclUint8, X->comm, X->st), );
-    RX_HIP(hipMemcpyAsync(X->h_recv, X->d_recv, n * (size_t)X->world, hipMemcpyDeviceToHost, X->st), );
+    std::memcpy(X->h_send.get(), send, n);
+    RX_HIP(hipMemcpyAsync(X->d_send.get(), X->h_send.get(), n, hipMemcpyHostToDevice, X->st), );
+    RX_NCCL(X->A.AllGather(X->d_send.get(), X->d_recv.get(), n, ncclUint8, X->comm, X->st), );
+    RX_HIP(hipMemcpyAsync(X->h_recv.get(), X->d_recv.get(), n * (size_t)X->world, hipMemcpyDeviceToHost, X->st), );
     RX_HIP(hipStreamSynchronize(X->st), );
-    std::memcpy(recv, X->h_recv, n * (size_t)X->world);
+    std::memcpy(recv, X->h_recv.get(), n * (size_t)X->world);
     return PNR_OK;
 }
 
@@ -165,12 +161,12 @@ int pnr_rccl_allreduce_minmax(pnr_rccl_exchange *X, float *mn, float *mx)
 {
     PNR_REQUIRE(X && mn && mx, PNR_E_ARG, "null argument");
     float v[2] = {-*mn, *mx};
-    std::memcpy(X->h_send, v, sizeof(v));
-    RX_HIP(hipMemcpyAsync(X->d_send, X->h_send, sizeof(v), hipMemcpyHostToDevice, X->st), );
-    RX_NCCL(X->A.AllReduce(X->d_send, X->d_recv, 2, ncclFloat32, ncclMax, X->comm, X->st), );
-    RX_HIP(hipMemcpyAsync(X->h_recv, X->d_recv, sizeof(v), hipMemcpyDeviceToHost, X->st), );
+    std::memcpy(X->h_send.get(), v, sizeof(v));
+    RX_HIP(hipMemcpyAsync(X->d_send.get(), X->h_send.get(), sizeof(v), hipMemcpyHostToDevice, X->st), );
+    RX_NCCL(X->A.AllReduce(X->d_send.get(), X->d_recv.get(), 2, ncclFloat32, ncclMax, X->comm, X->st), );
+    RX_HIP(hipMemcpyAsync(X->h_recv.get(), X->d_recv.get(), sizeof(v), hipMemcpyDeviceToHost, X->st), );
     RX_HIP(hipStreamSynchronize(X->st), );
-    std::memcpy(v, X->h_recv, sizeof(v));
+    std::memcpy(v, X->h_recv.get(), sizeof(v));
     *mn = -v[0];
     *mx = v[1];
     return PNR_OK;

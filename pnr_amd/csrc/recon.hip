@@ -404,34 +404,29 @@ static_assert(sizeof(P4) == sizeof(float4), "P4 is uploaded as float4");
 // call returns
 struct Bufs {
     hipStream_t s;
-    std::vector<void *> p;
+    std::vector<pnr::DevBuf<char>> p;
     explicit Bufs(hipStream_t s_) : s(s_) {}
-    ~Bufs()
-    {
-        (void)hipStreamSynchronize(s);
-        for (void *q : p) (void)hipFree(q);
-    }
+    ~Bufs() { (void)hipStreamSynchronize(s); } // (then p frees them)
     template <class T>
     int get(T **out, size_t count, const char *what)
     {
-        void *q = nullptr;
+        pnr::DevBuf<char> b;
         const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        if (hipMalloc(&q, bytes) != hipSuccess) {
+        if (b.alloc(bytes) != hipSuccess) {
             (void)hipGetLastError();
             pnr::set_error("reconstruct: device allocation of %zu B for %s failed", bytes, what);
             return PNR_E_NOMEM;
         }
-        p.push_back(q);
-        *out = (T *)q;
+        *out = (T *)b.get();
+        p.push_back(std::move(b));
         return PNR_OK;
     }
     void release(void *q)
     {
         for (auto &e : p)
-            if (e == q) {
+            if (e.get() == q) {
                 (void)hipStreamSynchronize(s);
-                (void)hipFree(q);
-                e = p.back();
+                e = std::move(p.back()); // (frees q)
                 p.pop_back();
                 return;
             }

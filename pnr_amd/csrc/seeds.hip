@@ -418,30 +418,27 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
         PNR_HIP(hipEventCreateWithFlags(&c->j8_start, hipEventDisableTiming));
         for (int k = 0; k < NCH; k++) PNR_HIP(hipEventCreateWithFlags(&c->j8_ev[k], hipEventDisableTiming));
     }
-    auto pinned = [&](unsigned char *&buf, size_t &cap, size_t need) -> int {
-        if (cap >= need) return PNR_OK;
-        if (buf) (void)hipHostFree(buf);
-        buf = nullptr; cap = 0;
+    auto pinned = [&](pnr::PinBuf<unsigned char> &buf, size_t need) -> int {
+        if (buf.count() >= need) return PNR_OK;
         need += need / 4 + 4096; // (the value count changes a little from stack to stack)
-        PNR_HIP(hipHostMalloc(&buf, need, hipHostMallocDefault));
-        cap = need;
+        PNR_HIP(buf.alloc(need));
         return PNR_OK;
     };
-    rc = pinned(c->h_j8, c->h_j8_cap, nwords * 8);
+    rc = pinned(c->h_j8, nwords * 8);
     if (rc) return rc;
-    const unsigned long long *h_bits = (const unsigned long long *)c->h_j8;
+    const unsigned long long *h_bits = (const unsigned long long *)c->h_j8.get();
     const int per_chunk = (nl + NCH - 1) / NCH;
 
     c->tic();
     PNR_HIP(hipMemsetAsync(d_min, 0x7f, nl * 4, c->stream));
     PNR_HIP(hipMemsetAsync(d_max, 0, nl * 4, c->stream));
-    hipLaunchKernelGGL(layer_minmax, dim3(nl * LM_PARTS), dim3(256), 0, c->stream, c->d_J8, wh, (int)z0, d_min, d_max);
+    hipLaunchKernelGGL(layer_minmax, dim3(nl * LM_PARTS), dim3(256), 0, c->stream, c->d_J8.get(), wh, (int)z0, d_min, d_max);
     PNR_HIP(hipMemsetAsync(d_cnt, 0, nl * 4, c->stream));
     PNR_HIP(hipMemsetAsync(d_rowcnt, 0, nrows * 4, c->stream));
     const int tiles_x = (w + 1023) / 1024; // a work-group of four waves covers 1024 pixels of a row
     const unsigned nblk = (unsigned)((i64)tiles_x * h * nl);
     SparseJ8 SP{d_bits, d_rowcnt, d_rowoff, d_voff, nullptr, wpr};
-    hipLaunchKernelGGL(layer_maxima<false>, dim3(nblk), dim3(256), 0, c->stream, c->d_J8, w, h, (int)z0, tiles_x, d_min,
+    hipLaunchKernelGGL(layer_maxima<false>, dim3(nblk), dim3(256), 0, c->stream, c->d_J8.get(), w, h, (int)z0, tiles_x, d_min,
                        (const float *)nullptr, d_cnt, (const i64 *)nullptr, (i64 *)nullptr, SP);
     hipLaunchKernelGGL(row_scan, dim3(nl), dim3(256), 0, c->stream, (const unsigned int *)d_rowcnt, h, d_rowoff, d_ltot);
     c->toc("seed_maxima", 3);
@@ -452,7 +449,7 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
     // the bitmap is complete: its download (1 bit per pixel) starts now, beside the second pass
     PNR_HIP(hipEventRecord(c->j8_start, c->stream));
     PNR_HIP(hipStreamWaitEvent(c->copy_stream, c->j8_start, 0));
-    PNR_HIP(hipMemcpyAsync(c->h_j8, d_bits, nwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
+    PNR_HIP(hipMemcpyAsync(c->h_j8.get(), d_bits, nwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < nl; k++) {
         off[k + 1] = off[k] + cnt[k];
@@ -461,9 +458,9 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
     }
     const i64 total = off[nl], nvals = voff[nl];
     std::vector<i64> keys((size_t)total);
-    rc = pinned(c->h_j8v, c->h_j8v_cap, (size_t)std::max<i64>(nvals, 1));
+    rc = pinned(c->h_j8v, (size_t)std::max<i64>(nvals, 1));
     if (rc) return rc;
-    const unsigned char *h_vals = c->h_j8v;
+    const unsigned char *h_vals = c->h_j8v.get();
     if (total > 0) { // (no candidate anywhere: nothing to fill, nothing to hand over)
         rc = c->scratch_get("seed_keys", (size_t)total, &d_keys);
         if (!rc) rc = c->scratch_get("seed_vals", (size_t)std::max<i64>(nvals, 1), &d_vals);
@@ -474,7 +471,7 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
         PNR_HIP(hipMemcpyAsync(d_vf, vf.data(), nl * 4, hipMemcpyHostToDevice, c->stream));
         PNR_HIP(hipMemsetAsync(d_cnt, 0, nl * 4, c->stream));
         c->tic();
-        hipLaunchKernelGGL(layer_maxima<true>, dim3(nblk), dim3(256), 0, c->stream, c->d_J8, w, h, (int)z0, tiles_x, d_min,
+        hipLaunchKernelGGL(layer_maxima<true>, dim3(nblk), dim3(256), 0, c->stream, c->d_J8.get(), w, h, (int)z0, tiles_x, d_min,
                            d_vf, d_cnt, d_off, d_keys, SP);
         c->toc("seed_maxima", 1);
         PNR_HIP(hipMemcpyAsync(keys.data(), d_keys, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
@@ -484,7 +481,7 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
         for (int k = 0; k < NCH; k++) {
             const int l0 = std::min(nl, k * per_chunk), l1 = std::min(nl, l0 + per_chunk);
             if (voff[l1] > voff[l0])
-                PNR_HIP(hipMemcpyAsync(c->h_j8v + voff[l0], d_vals + voff[l0], (size_t)(voff[l1] - voff[l0]), hipMemcpyDeviceToHost, c->copy_stream));
+                PNR_HIP(hipMemcpyAsync(c->h_j8v.get() + voff[l0], d_vals + voff[l0], (size_t)(voff[l1] - voff[l0]), hipMemcpyDeviceToHost, c->copy_stream));
             PNR_HIP(hipEventRecord(c->j8_ev[k], c->copy_stream));
         }
     }
@@ -538,7 +535,7 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
         const int how = pnr_seed_dirs(c, d_idx, ns, d_dirs); // solved at the seeds from the winning scale's smoothed volume ...
         if (how < 0) return how;
         if (how == 1) // ... or gathered from the direction volumes when those exist
-            hipLaunchKernelGGL(gather_dirs, dim3((ns + 255) / 256), dim3(256), 0, c->stream, c->d_Vx, c->d_Vy, c->d_Vz, d_idx, ns,
+            hipLaunchKernelGGL(gather_dirs, dim3((ns + 255) / 256), dim3(256), 0, c->stream, c->d_Vx.get(), c->d_Vy.get(), c->d_Vz.get(), d_idx, ns,
                                d_dirs);
         PNR_HIP(hipMemcpyAsync(dirs.data(), d_dirs, (size_t)ns * 3, hipMemcpyDeviceToHost, c->stream));
         PNR_HIP(hipStreamSynchronize(c->stream));

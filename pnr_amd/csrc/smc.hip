@@ -502,7 +502,7 @@ int pnr_zncc_run(pnr_ctx *c, const float *h_pos_dir, int64_t n, float *h_corr, f
     if (!rc) rc = c->scratch_get("zncc_corr", (size_t)n, &d_corr);
     if (!rc) rc = c->scratch_get("zncc_sig", (size_t)n, &d_sig);
     if (rc) return rc;
-    PNR_REQUIRE(c->d_wd, PNR_E_STATE, "tracker tables not loaded");
+    PNR_REQUIRE(c->d_wd.get(), PNR_E_STATE, "tracker tables not loaded");
     // poses in batches of at most 32 768: the stash of a batch is sum(M) x 4 B per pose (1.6 GB at the usual three scales)
     i64 Mtot = 0;
     for (int s = 0; s < T.nsig; s++) Mtot += c->tab.M[s];
@@ -517,7 +517,7 @@ int pnr_zncc_run(pnr_ctx *c, const float *h_pos_dir, int64_t n, float *h_corr, f
         i64 blocks = 0;
         for (int s = 0; s < T.nsig; s++) blocks += (i64)((c->tab.M[s] + 63) / 64) * ngroups;
         hipLaunchKernelGGL(zncc_sample, dim3((unsigned)blocks), dim3(256), 0, c->stream, V, T, (const float *)(d_pd + i0 * 6), nb, ngroups, d_stash);
-        hipLaunchKernelGGL(zncc_sums, dim3((unsigned)(T.nsig * ngroups)), dim3(64), 0, c->stream, T, (const float *)c->d_wd, (const float *)d_stash, ngroups,
+        hipLaunchKernelGGL(zncc_sums, dim3((unsigned)(T.nsig * ngroups)), dim3(64), 0, c->stream, T, (const float *)c->d_wd.get(), (const float *)d_stash, ngroups,
                            n_pad, (int)i0, d_cs);
         launches += 2;
     }
@@ -537,8 +537,9 @@ struct pnr_trace_job {
     bool own_stream = false;
     int64_t n = 0;      // seeds of the launch in flight (0: idle)
     int dbg_iters = 0;
-    float *d_s6 = nullptr;
-    TraceOut O{};
+    pnr::DevBuf<float> d_s6;
+    TraceOut O{}; // (views of `out`)
+    TraceOutBufs out;
     size_t cap_tr = 0, cap_dbg = 0; // capacities (traces; traces*dbg_iters) the device buffers were sized for
     std::vector<float> s6;
     // launch-per-phase driver: the host loop runs in pnr_job_finish
@@ -560,19 +561,10 @@ pnr_trace_job *pnr_job_create(pnr_ctx *c, bool own_stream)
     return j;
 }
 
-static void job_free_buffers(pnr_trace_job *j)
-{
-    hipFree(j->d_s6); hipFree(j->O.T); hipFree(j->O.stop); hipFree(j->O.xc); hipFree(j->O.xfilt); hipFree(j->O.idxres); hipFree(j->O.neff);
-    j->d_s6 = nullptr;
-    j->O = TraceOut{};
-    j->cap_tr = j->cap_dbg = 0;
-}
-
 void pnr_job_destroy(pnr_trace_job *j)
 {
     if (!j) return;
     if (j->stream) (void)hipStreamSynchronize(j->stream);
-    job_free_buffers(j);
     if (j->own_stream) (void)hipStreamDestroy(j->stream);
     delete j;
 }
@@ -617,7 +609,7 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
         PNR_REQUIRE(c->tab.grid[4 * s] <= 64 && c->tab.grid[4 * s + 1] <= 64 && c->tab.grid[4 * s + 2] <= 64, PNR_E_ARG,
                     "template grid axis longer than a wavefront");
     TabX X;
-    X.grid = (const Grid *)c->d_grid; X.axes = c->d_axes; X.axes_off = c->d_axes_off; X.wd = c->d_wd;
+    X.grid = (const Grid *)c->d_grid.get(); X.axes = c->d_axes.get(); X.axes_off = c->d_axes_off.get(); X.wd = c->d_wd.get();
     X.ext_v = c->tab.ext_v; X.ext_uw = c->tab.ext_uw;
     for (int s2 = 0; s2 < 8; s2++) { X.ext_vs[s2] = 0.f; X.ext_uws[s2] = 0.f; }
     { // pass-1 sample stash: one region per resident work-group (<= 1 per CU: each takes all 160 KB of LDS)
@@ -631,19 +623,19 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
         const bool want_stash = !c->opt.no_stash; // option "no_stash": the in-lane two-pass form
         if ((want_stash && (c->stash_bytes < need || c->stash_slots != nslots)) || (!want_stash && c->d_stash)) {
             PNR_HIP(hipDeviceSynchronize()); // no trace kernel may still hold a slot
-            hipFree(c->d_stash); hipFree(c->d_slot_busy);
-            c->d_stash = nullptr; c->d_slot_busy = nullptr; c->stash_bytes = 0;
-            if (want_stash && hipMalloc(&c->d_stash, need) == hipSuccess && hipMalloc(&c->d_slot_busy, nslots * 4) == hipSuccess) {
+            c->d_stash.reset(), c->d_slot_busy.reset();
+            c->stash_bytes = 0;
+            if (want_stash && c->d_stash.alloc(need / 4) == hipSuccess && c->d_slot_busy.alloc(nslots) == hipSuccess) {
                 c->stash_bytes = need;
                 c->stash_slots = nslots;
                 // flags are cleared once: every work-group releases its slot, also with several launches in flight
-                PNR_HIP(hipMemset(c->d_slot_busy, 0, nslots * 4));
+                PNR_HIP(hipMemset(c->d_slot_busy.get(), 0, nslots * 4));
             } else {
                 (void)hipGetLastError(); // not enough HBM for the stash: the kernel re-samples in pass 2
-                hipFree(c->d_stash); c->d_stash = nullptr;
+                c->d_stash.reset();
             }
         }
-        X.stash = c->d_stash; X.slot_busy = c->d_slot_busy; X.nslots = nslots;
+        X.stash = c->d_stash.get(); X.slot_busy = c->d_slot_busy.get(); X.nslots = nslots;
         X.slot_floats = slot_floats; X.wave_floats = wave_floats;
     }
 
@@ -658,14 +650,16 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
     if (j->cap_tr < (size_t)ntr || j->cap_dbg < need_dbg || (want_xfilt && !j->O.xfilt && dbg_iters) ||
         (want_idxres && !j->O.idxres && dbg_iters) || (want_neff && !j->O.neff && dbg_iters)) {
         PNR_HIP(hipStreamSynchronize(j->stream));
-        job_free_buffers(j);
-        PNR_HIP(hipMalloc(&j->d_s6, (size_t)ntr * 24));
-        PNR_HIP(hipMalloc(&j->O.T, (size_t)ntr * 4));
-        PNR_HIP(hipMalloc(&j->O.stop, (size_t)ntr * 4));
-        PNR_HIP(hipMalloc(&j->O.xc, (size_t)ntr * ni * 32));
-        if (dbg_iters > 0 && want_xfilt) PNR_HIP(hipMalloc(&j->O.xfilt, need_dbg * np * PSTRIDE * 4));
-        if (dbg_iters > 0 && want_idxres) PNR_HIP(hipMalloc(&j->O.idxres, need_dbg * np * 4));
-        if (dbg_iters > 0 && want_neff) PNR_HIP(hipMalloc(&j->O.neff, need_dbg * 4));
+        j->d_s6.reset(), j->out.reset();
+        j->O = TraceOut{};
+        j->cap_tr = j->cap_dbg = 0;
+        PNR_HIP(j->d_s6.alloc((size_t)ntr * 6));
+        PNR_HIP(alloc_view(j->out.T, j->O.T, (size_t)ntr));
+        PNR_HIP(alloc_view(j->out.stop, j->O.stop, (size_t)ntr));
+        PNR_HIP(alloc_view(j->out.xc, j->O.xc, (size_t)ntr * ni * 8));
+        if (dbg_iters > 0 && want_xfilt) PNR_HIP(alloc_view(j->out.xfilt, j->O.xfilt, need_dbg * np * PSTRIDE));
+        if (dbg_iters > 0 && want_idxres) PNR_HIP(alloc_view(j->out.idxres, j->O.idxres, need_dbg * np));
+        if (dbg_iters > 0 && want_neff) PNR_HIP(alloc_view(j->out.neff, j->O.neff, need_dbg));
         j->cap_tr = (size_t)ntr;
         j->cap_dbg = need_dbg;
     }
@@ -676,13 +670,13 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
     if (!want_neff || !dbg_iters) O.neff = nullptr;
     PNR_HIP(hipMemsetAsync(O.xc, 0, (size_t)ntr * ni * 32, j->stream));
     if (O.idxres) PNR_HIP(hipMemsetAsync(O.idxres, 0xff, need_dbg * np * 4, j->stream));
-    PNR_HIP(hipMemcpyAsync(j->d_s6, j->s6.data(), j->s6.size() * 4, hipMemcpyHostToDevice, j->stream));
+    PNR_HIP(hipMemcpyAsync(j->d_s6.get(), j->s6.data(), j->s6.size() * 4, hipMemcpyHostToDevice, j->stream));
     c->tic(j->stream);
 #define PNR_LAUNCH_TRACE(cs)                                                                                                   \
     case cs:                                                                                                                   \
         PNR_HIP(hipFuncSetAttribute((const void *)smc_trace<cs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-        hipLaunchKernelGGL(smc_trace<cs>, dim3((unsigned)ntr), dim3(block), lds, j->stream, V, T, X, j->d_s6, np, np_pad, ni, \
-                           c->prm.Kc, c->prm.znccth, c->prm.neff_ratio, use_density ? c->d_den : nullptr, c->prm.nodepervol, O); \
+        hipLaunchKernelGGL(smc_trace<cs>, dim3((unsigned)ntr), dim3(block), lds, j->stream, V, T, X, j->d_s6.get(), np, np_pad, ni, \
+                           c->prm.Kc, c->prm.znccth, c->prm.neff_ratio, use_density ? c->d_den.get() : nullptr, c->prm.nodepervol, O); \
         break;
     switch (CS) {
         PNR_LAUNCH_TRACE(52)
@@ -759,13 +753,11 @@ __global__ void den_scatter(unsigned char *den, const i64 *idx, const unsigned c
 int pnr_density_reset(pnr_ctx *c)
 {
     if (c->den_cap < c->N) {
-        hipFree(c->d_den);
-        c->d_den = nullptr;
         c->den_cap = 0;
-        PNR_HIP(hipMalloc(&c->d_den, ((size_t)c->N + 3) / 4 * 4)); // whole dwords: den_scatter updates a byte through its dword
+        PNR_HIP(c->d_den.alloc(((size_t)c->N + 3) / 4 * 4)); // whole dwords: den_scatter updates a byte through its dword
         c->den_cap = c->N;
     }
-    PNR_HIP(hipMemsetAsync(c->d_den, 0, ((size_t)c->N + 3) / 4 * 4, c->stream));
+    PNR_HIP(hipMemsetAsync(c->d_den.get(), 0, ((size_t)c->N + 3) / 4 * 4, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream)); // trace jobs run on their own streams
     if (!c->soma_vox.empty()) {
         // a trace that reaches a soma voxel stops there in the replay (tracker.cpp:858-869): for the kernels' early stop
@@ -778,7 +770,7 @@ int pnr_density_reset(pnr_ctx *c)
         if (rc) return rc;
         PNR_HIP(hipMemcpyAsync(d_idx, c->soma_vox.data(), n * 8, hipMemcpyHostToDevice, c->stream));
         PNR_HIP(hipMemsetAsync(d_val, 0xff, n, c->stream));
-        hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_den, (const i64 *)d_idx, (const unsigned char *)d_val, (int)n);
+        hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_den.get(), (const i64 *)d_idx, (const unsigned char *)d_val, (int)n);
         PNR_HIP(hipStreamSynchronize(c->stream));
     }
     return PNR_OK;
@@ -792,22 +784,17 @@ int pnr_density_update(pnr_ctx *c, const pnr::Replayer &r, hipStream_t on)
     std::vector<unsigned char> val(n);
     for (size_t i = 0; i < n; i++) val[i] = (unsigned char)r.den_at(r.touched[i]); // final value: duplicates agree
     // grow-only staging buffers (hipFree synchronises the whole device)
-    if (c->den_stage_cap < n) {
+    if (c->d_den_val.count() < n) { // (allocated last: its capacity is that of the pair)
         PNR_HIP(hipDeviceSynchronize());
-        hipFree(c->d_den_idx);
-        hipFree(c->d_den_val);
-        c->d_den_idx = nullptr;
-        c->d_den_val = nullptr;
-        c->den_stage_cap = 0;
+        c->d_den_idx.reset(), c->d_den_val.reset();
         const size_t cap = std::max<size_t>(2 * n, 1 << 16);
-        PNR_HIP(hipMalloc(&c->d_den_idx, cap * 8));
-        PNR_HIP(hipMalloc(&c->d_den_val, cap));
-        c->den_stage_cap = cap;
+        PNR_HIP(c->d_den_idx.alloc(cap));
+        PNR_HIP(c->d_den_val.alloc(cap));
     }
-    PNR_HIP(hipMemcpyAsync(c->d_den_idx, r.touched.data(), n * 8, hipMemcpyHostToDevice, st));
-    PNR_HIP(hipMemcpyAsync(c->d_den_val, val.data(), n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->d_den, (const i64 *)c->d_den_idx,
-                       (const unsigned char *)c->d_den_val, (int)n);
+    PNR_HIP(hipMemcpyAsync(c->d_den_idx.get(), r.touched.data(), n * 8, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(c->d_den_val.get(), val.data(), n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->d_den.get(), (const i64 *)c->d_den_idx.get(),
+                       (const unsigned char *)c->d_den_val.get(), (int)n);
     PNR_HIP(hipGetLastError());
     PNR_HIP(hipStreamSynchronize(st));
     return PNR_OK;
@@ -817,7 +804,7 @@ int pnr_density_update(pnr_ctx *c, const pnr::Replayer &r, hipStream_t on)
 int pnr_density_scatter_async(pnr_ctx *c, const long long *d_idx, const unsigned char *d_val, size_t n, hipStream_t st)
 {
     if (n == 0) return PNR_OK;
-    hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->d_den, (const i64 *)d_idx, d_val, (int)n);
+    hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->d_den.get(), (const i64 *)d_idx, d_val, (int)n);
     PNR_HIP(hipGetLastError());
     return PNR_OK;
 }
@@ -825,14 +812,14 @@ int pnr_density_scatter_async(pnr_ctx *c, const long long *d_idx, const unsigned
 int pnr_expf_run(pnr_ctx *c, const float *x, int64_t n, float *y)
 {
     if (n == 0) return PNR_OK;
-    float *dx = nullptr, *dy = nullptr;
-    PNR_HIP(hipMalloc(&dx, (size_t)n * 4));
-    PNR_HIP(hipMalloc(&dy, (size_t)n * 4));
+    pnr::DevBuf<float> bx, by;
+    PNR_HIP(bx.alloc((size_t)n));
+    PNR_HIP(by.alloc((size_t)n));
+    float *dx = bx.get(), *dy = by.get();
     PNR_HIP(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(expf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dx, (i64)n, dy);
     PNR_HIP(hipGetLastError());
     PNR_HIP(hipMemcpyAsync(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     PNR_HIP(hipStreamSynchronize(c->stream));
-    hipFree(dx); hipFree(dy);
     return PNR_OK;
 }

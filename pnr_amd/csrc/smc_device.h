@@ -182,6 +182,20 @@ struct TraceOut {
     float *neff;
 };
 
+// the owner of a TraceOut's buffers: the kernels take the plain struct, whose pointers are set as the buffers are allocated
+struct TraceOutBufs {
+    pnr::DevBuf<int> T, stop, idxres;
+    pnr::DevBuf<float> xc, xfilt, neff;
+    void reset() { T.reset(), stop.reset(), idxres.reset(), xc.reset(), xfilt.reset(), neff.reset(); }
+};
+template <typename T>
+inline hipError_t alloc_view(pnr::DevBuf<T> &b, T *&view, size_t count)
+{
+    const hipError_t e = b.alloc(count);
+    view = b.get();
+    return e;
+}
+
 // template sample grid of one sigma: nested loops vv (outer) / uu / ww (inner), tracker.cpp:219-221
 struct Grid {
     int nv, nu, nw, off; // off: first sample in tmpl / wd
@@ -911,9 +925,9 @@ int make_vol(pnr_ctx *c, Vol &V)
 
 void make_tab(pnr_ctx *c, Tab &T)
 {
-    T.p = c->d_p; T.u = c->d_u; T.w0 = c->d_w0; T.w0cws = c->d_w0cws; T.v = c->d_v; T.w = c->d_w; T.wcws = c->d_wcws;
-    T.tmpl = (const float4 *)c->d_tmpl;
-    T.M = c->d_M; T.moff = c->d_moff; T.corrc = c->d_corrc; T.sig = c->d_sig; T.rng = c->d_rng;
+    T.p = c->d_p.get(); T.u = c->d_u.get(); T.w0 = c->d_w0.get(); T.w0cws = c->d_w0cws.get(); T.v = c->d_v.get(); T.w = c->d_w.get(); T.wcws = c->d_wcws.get();
+    T.tmpl = (const float4 *)c->d_tmpl.get();
+    T.M = c->d_M.get(); T.moff = c->d_moff.get(); T.corrc = c->d_corrc.get(); T.sig = c->d_sig.get(); T.rng = c->d_rng.get();
     T.sz = c->tab.sz; T.ndir = c->tab.ndir; T.nsig = c->tab.nsig;
     T.Mtot = c->tab.moff.back() + c->tab.M.back();
 }

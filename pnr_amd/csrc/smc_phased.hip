@@ -1048,20 +1048,25 @@ struct pnr_phased {
     int64_t cap_stash = 0; // traces the sample stash holds (list positions of all trace groups together)
     int np = 0, np_pad = 0, S = 0, ni = 0;
     long long trace_floats = 0;
-    PhState P{};
-    float *d_s6 = nullptr;
-    TraceOut O{};
-    int *h_cnt = nullptr;       // pinned [RING]: active-trace counters copied back by the stream
+    PhState P{}; // the kernels' argument: views of the buffers in `state` (flags lies behind the counters in state.cnt)
+    struct {
+        pnr::DevBuf<float> part, prior, corr, xcs, stash;
+        pnr::DevBuf<int> idxres, list, cnt, ctr, uidx, cmap;
+        pnr::DevBuf<unsigned char> cubes;
+    } state;
+    pnr::DevBuf<float> d_s6;
+    TraceOut O{}; // (views of `out`)
+    TraceOutBufs out;
+    pnr::PinBuf<int> h_cnt;     // pinned [RING]: active-trace counters copied back by the stream
     hipEvent_t ev[RING] = {};   // ... and the events that say so
     // streaming trace + replay: pinned records written by the kernels / read back at every poll, admission staging
-    pnr_xest *h_xc = nullptr; int *h_flags = nullptr; int *h_new = nullptr; float *h_new_s6 = nullptr;
-    int *d_new = nullptr; float *d_new_s6 = nullptr;
-    int *h_ctl = nullptr, *d_ctl = nullptr; // pause / resume lists of the tentative replay: [group][2][stream_cap]
+    pnr::PinBuf<pnr_xest> h_xc; pnr::PinBuf<int> h_flags, h_new; pnr::PinBuf<float> h_new_s6;
+    pnr::DevBuf<int> d_new; pnr::DevBuf<float> d_new_s6;
+    pnr::PinBuf<int> h_ctl; pnr::DevBuf<int> d_ctl; // pause / resume lists of the tentative replay: [group][2][stream_cap]
     // density updates of the streaming tracer: pinned and device staging per trace group (grow-only), so that an update is queued on the
     // group's own stream and nothing waits for it
-    long long *h_den_idx[4] = {}, *d_den_idx[4] = {};
-    unsigned char *h_den_val[4] = {}, *d_den_val[4] = {};
-    size_t den_cap[4] = {};
+    pnr::PinBuf<long long> h_den_idx[4]; pnr::DevBuf<long long> d_den_idx[4];
+    pnr::PinBuf<unsigned char> h_den_val[4]; pnr::DevBuf<unsigned char> d_den_val[4];
     int64_t stream_cap = 0;
     int stream_ni = 0;
     static constexpr int MAXG = 4;
@@ -1076,12 +1081,11 @@ struct pnr_phased {
 
 static void phased_free(pnr_phased *h)
 {
-    hipFree(h->P.part); hipFree(h->P.prior); hipFree(h->P.idxres); hipFree(h->P.corr); hipFree(h->P.xcs);
-    hipFree(h->P.stash); hipFree(h->P.cubes); hipFree(h->P.list); hipFree(h->P.cnt) /* (and the flags behind the counters) */; hipFree(h->P.ctr); hipFree(h->P.uidx); hipFree(h->P.cmap); hipFree(h->d_s6);
-    hipFree(h->O.T); hipFree(h->O.stop); hipFree(h->O.xc); hipFree(h->O.xfilt); hipFree(h->O.idxres); hipFree(h->O.neff);
+    h->state = {};
+    h->d_s6.reset();
+    h->out.reset();
     h->P = PhState{};
     h->O = TraceOut{};
-    h->d_s6 = nullptr;
     h->cap_traces = h->cap_dbg = 0;
     h->cap_stash = 0;
 }
@@ -1112,21 +1116,6 @@ extern "C" int pnr_debug_ph_stamps(unsigned long long *out8, int reset)
 void pnr_phased_destroy(pnr_phased *h)
 {
     if (!h) return;
-    phased_free(h);
-    if (h->h_cnt) hipHostFree(h->h_cnt);
-    if (h->h_xc) hipHostFree(h->h_xc);
-    if (h->h_flags) hipHostFree(h->h_flags);
-    if (h->h_new) hipHostFree(h->h_new);
-    if (h->h_new_s6) hipHostFree(h->h_new_s6);
-    hipFree(h->d_new); hipFree(h->d_new_s6);
-    if (h->h_ctl) (void)hipHostFree(h->h_ctl);
-    (void)hipFree(h->d_ctl);
-    for (int g = 0; g < pnr_phased::MAXG; g++) {
-        if (h->h_den_idx[g]) (void)hipHostFree(h->h_den_idx[g]);
-        if (h->h_den_val[g]) (void)hipHostFree(h->h_den_val[g]);
-        (void)hipFree(h->d_den_idx[g]);
-        (void)hipFree(h->d_den_val[g]);
-    }
     for (int r = 0; r < pnr_phased::RING; r++)
         if (h->ev[r]) (void)hipEventDestroy(h->ev[r]);
     for (int g = 1; g < pnr_phased::MAXG; g++)
@@ -1220,12 +1209,9 @@ static int ensure_stash(pnr_ctx *c, pnr_phased *h, int64_t traces, long long tra
 {
     if (h->cap_stash >= traces && h->P.stash) return PNR_OK;
     PNR_HIP(hipDeviceSynchronize());
-    (void)hipFree(h->P.stash);
-    h->P.stash = nullptr; h->cap_stash = 0;
-    PNR_HIP(hipMalloc(&h->P.stash, (size_t)traces * trace_floats * 4));
-    (void)hipFree(h->P.cubes);
-    h->P.cubes = nullptr;
-    PNR_HIP(hipMalloc(&h->P.cubes, (size_t)traces * PH_CS * PH_PLANE)); // the compact cubes (ph_cube), one per list position as well
+    h->cap_stash = 0;
+    PNR_HIP(alloc_view(h->state.stash, h->P.stash, (size_t)traces * trace_floats));
+    PNR_HIP(alloc_view(h->state.cubes, h->P.cubes, (size_t)traces * PH_CS * PH_PLANE)); // the compact cubes (ph_cube), one per list position as well
     h->cap_stash = traces;
     // a stale stash value is only ever read for a chain whose result is discarded, but keep it finite
     PNR_HIP(hipMemsetAsync(h->P.stash, 0, (size_t)traces * trace_floats * 4, c->stream));
@@ -1250,7 +1236,7 @@ static int phased_env(pnr_ctx *c, int64_t want, int dbg_iters, bool xfilt, bool 
     if (!c->phased) c->phased = new pnr_phased();
     pnr_phased *h = c->phased;
     if (!h->h_cnt) {
-        PNR_HIP(hipHostMalloc(&h->h_cnt, sizeof(int) * pnr_phased::RING));
+        PNR_HIP(h->h_cnt.alloc(pnr_phased::RING));
         for (int r = 0; r < pnr_phased::RING; r++) PNR_HIP(hipEventCreateWithFlags(&h->ev[r], hipEventDisableTiming));
         for (int g = 1; g < pnr_phased::MAXG; g++) PNR_HIP(hipStreamCreateWithFlags(&h->stg[g], hipStreamNonBlocking));
         PNR_HIP(hipStreamCreateWithFlags(&h->st_den, hipStreamNonBlocking));
@@ -1279,26 +1265,26 @@ static int phased_env(pnr_ctx *c, int64_t want, int dbg_iters, bool xfilt, bool 
         PNR_HIP(hipDeviceSynchronize());
         phased_free(h);
         const int64_t cap = NT;
-        PNR_HIP(hipMalloc(&h->P.part, (size_t)cap * 2 * np * PSTRIDE * 4));
-        PNR_HIP(hipMalloc(&h->P.prior, (size_t)cap * np * 4));
-        PNR_HIP(hipMalloc(&h->P.idxres, (size_t)cap * np * 4));
-        PNR_HIP(hipMalloc(&h->P.corr, (size_t)cap * S * np_pad * 4));
-        PNR_HIP(hipMalloc(&h->P.xcs, (size_t)cap * 16 * 4));
+        PNR_HIP(alloc_view(h->state.part, h->P.part, (size_t)cap * 2 * np * PSTRIDE));
+        PNR_HIP(alloc_view(h->state.prior, h->P.prior, (size_t)cap * np));
+        PNR_HIP(alloc_view(h->state.idxres, h->P.idxres, (size_t)cap * np));
+        PNR_HIP(alloc_view(h->state.corr, h->P.corr, (size_t)cap * S * np_pad));
+        PNR_HIP(alloc_view(h->state.xcs, h->P.xcs, (size_t)cap * 16));
         // the counters of the step lists sit in front of the flags in ONE buffer: the streaming tracer's poll copies both with one copy
-        PNR_HIP(hipMalloc(&h->P.cnt, ((size_t)cap * FL_N + 2 * pnr_phased::MAXG) * 4));
+        PNR_HIP(alloc_view(h->state.cnt, h->P.cnt, (size_t)cap * FL_N + 2 * pnr_phased::MAXG));
         h->P.flags = h->P.cnt + 2 * pnr_phased::MAXG;
-        PNR_HIP(hipMalloc(&h->P.list, (size_t)cap * 2 * 4 * pnr_phased::MAXG)); // one pair of lists per trace group of the streaming tracer
-        PNR_HIP(hipMalloc(&h->P.ctr, (size_t)cap * 4));
-        PNR_HIP(hipMalloc(&h->P.uidx, (size_t)cap * np_pad * 4));
-        PNR_HIP(hipMalloc(&h->P.cmap, (size_t)cap * np_pad * 4));
-        PNR_HIP(hipMalloc(&h->d_s6, (size_t)cap * 24));
-        PNR_HIP(hipMalloc(&h->O.T, (size_t)cap * 4));
-        PNR_HIP(hipMalloc(&h->O.stop, (size_t)cap * 4));
-        PNR_HIP(hipMalloc(&h->O.xc, (size_t)cap * ni * 32));
+        PNR_HIP(alloc_view(h->state.list, h->P.list, (size_t)cap * 2 * pnr_phased::MAXG)); // one pair of lists per trace group of the streaming tracer
+        PNR_HIP(alloc_view(h->state.ctr, h->P.ctr, (size_t)cap));
+        PNR_HIP(alloc_view(h->state.uidx, h->P.uidx, (size_t)cap * np_pad));
+        PNR_HIP(alloc_view(h->state.cmap, h->P.cmap, (size_t)cap * np_pad));
+        PNR_HIP(h->d_s6.alloc((size_t)cap * 6));
+        PNR_HIP(alloc_view(h->out.T, h->O.T, (size_t)cap));
+        PNR_HIP(alloc_view(h->out.stop, h->O.stop, (size_t)cap));
+        PNR_HIP(alloc_view(h->out.xc, h->O.xc, (size_t)cap * ni * 8));
         const size_t dbg_cap = (size_t)cap * dbg_iters;
-        if (dbg_iters && xfilt) PNR_HIP(hipMalloc(&h->O.xfilt, dbg_cap * np * PSTRIDE * 4));
-        if (dbg_iters && idxres) PNR_HIP(hipMalloc(&h->O.idxres, dbg_cap * np * 4));
-        if (dbg_iters && neff) PNR_HIP(hipMalloc(&h->O.neff, dbg_cap * 4));
+        if (dbg_iters && xfilt) PNR_HIP(alloc_view(h->out.xfilt, h->O.xfilt, dbg_cap * np * PSTRIDE));
+        if (dbg_iters && idxres) PNR_HIP(alloc_view(h->out.idxres, h->O.idxres, dbg_cap * np));
+        if (dbg_iters && neff) PNR_HIP(alloc_view(h->out.neff, h->O.neff, dbg_cap));
         h->cap_traces = cap; h->cap_dbg = (int64_t)dbg_cap;
         h->np = np; h->np_pad = np_pad; h->S = S; h->ni = ni; h->trace_floats = trace_floats;
         PNR_HIP(hipMemsetAsync(h->P.part, 0, (size_t)cap * 2 * np * PSTRIDE * 4, c->stream));
@@ -1311,11 +1297,11 @@ static int phased_env(pnr_ctx *c, int64_t want, int dbg_iters, bool xfilt, bool 
     E.P.W = W;
     E.P.np_pad = np_pad;
     E.P.dedup = np <= 1024 ? 1 : 0; // (beyond that the poses and the table of the duplicate search no longer fit 64 KB of LDS)
-    E.X.grid = (const Grid *)c->d_grid; E.X.axes = c->d_axes; E.X.axes_off = c->d_axes_off; E.X.wd = c->d_wd;
+    E.X.grid = (const Grid *)c->d_grid.get(); E.X.axes = c->d_axes.get(); E.X.axes_off = c->d_axes_off.get(); E.X.wd = c->d_wd.get();
     E.X.ext_v = c->tab.ext_v; E.X.ext_uw = c->tab.ext_uw;
     for (int s2 = 0; s2 < 8; s2++) { E.X.ext_vs[s2] = s2 < S ? c->tab.ext_vs[s2] : 0.f; E.X.ext_uws[s2] = s2 < S ? c->tab.ext_uws[s2] : 0.f; }
     E.X.stash = nullptr; E.X.slot_busy = nullptr; E.X.nslots = 0; E.X.slot_floats = 0; E.X.wave_floats = 0;
-    E.X.share = c->d_share; E.X.grows = c->d_grows; E.X.guest_mask = c->tab.guest_mask;
+    E.X.share = c->d_share.get(); E.X.grows = c->d_grows.get(); E.X.guest_mask = c->tab.guest_mask;
     hipDeviceProp_t prop;
     PNR_HIP(hipGetDeviceProperties(&prop, c->device));
     E.ncu = prop.multiProcessorCount;
@@ -1375,7 +1361,7 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
         if (!xfilt || !dbg_iters) O.xfilt = nullptr;
         if (!idxres || !dbg_iters) O.idxres = nullptr;
         if (!neff || !dbg_iters) O.neff = nullptr;
-        PNR_HIP(hipMemcpyAsync(h->d_s6, s6.data(), s6.size() * 4, hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemcpyAsync(h->d_s6.get(), s6.data(), s6.size() * 4, hipMemcpyHostToDevice, st));
         PNR_HIP(hipMemcpyAsync(P.flags, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, st));
         PNR_HIP(hipMemcpyAsync(P.list, list0.data(), list0.size() * 4, hipMemcpyHostToDevice, st));
         PNR_HIP(hipMemcpyAsync(P.cnt, cnt0, sizeof(cnt0), hipMemcpyHostToDevice, st));
@@ -1387,12 +1373,12 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
         for (int it = 0; it <= ni; it++) {
             if (it >= LAG) { // the counter of iteration it - LAG has landed (no pipeline drain: the host stays LAG steps ahead)
                 PNR_HIP(hipEventSynchronize(h->ev[(it - LAG) % RING]));
-                active = h->h_cnt[(it - LAG) % RING];
+                active = h->h_cnt.get()[(it - LAG) % RING];
                 if (active <= 0) break;
             }
             const int nsplit = pick_nsplit(active, ncu, max_split, c->opt.split_x10);
             c->tic(st);
-            hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, T, X, P, (const float *)h->d_s6, V, np, ni, it, it & 1, CS, ph_tbl(np));
+            hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, T, X, P, (const float *)h->d_s6.get(), V, np, ni, it, it & 1, CS, ph_tbl(np));
             c->toc("smc_predict", 1, st);
             if (P.cubes) {
                 c->tic(st);
@@ -1408,9 +1394,9 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
             c->toc("smc_sums", 1, st);
             c->tic(st);
             hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), upd_lds, st, V, T, P, np, np_pad, ni, it, it & 1, c->prm.Kc, c->prm.znccth,
-                               c->prm.neff_ratio, use_density ? c->d_den : nullptr, c->prm.nodepervol, O);
+                               c->prm.neff_ratio, use_density ? c->d_den.get() : nullptr, c->prm.nodepervol, O);
             c->toc("smc_update", 1, st);
-            PNR_HIP(hipMemcpyAsync(&h->h_cnt[it % RING], P.cnt + ((it + 1) & 1), 4, hipMemcpyDeviceToHost, st));
+            PNR_HIP(hipMemcpyAsync(&h->h_cnt.get()[it % RING], P.cnt + ((it + 1) & 1), 4, hipMemcpyDeviceToHost, st));
             PNR_HIP(hipEventRecord(h->ev[it % RING], st));
         }
         PNR_HIP(hipGetLastError());
@@ -1485,30 +1471,21 @@ struct PhasedEngine final : pnr::StreamEngine {
         const int ni = E.ni;
         if (h->stream_cap < NT || h->stream_ni != ni) {
             PE_HIP(hipDeviceSynchronize());
-            if (h->h_xc) hipHostFree(h->h_xc);
-            if (h->h_flags) hipHostFree(h->h_flags);
-            if (h->h_new) hipHostFree(h->h_new);
-            if (h->h_new_s6) hipHostFree(h->h_new_s6);
-            hipFree(h->d_new); hipFree(h->d_new_s6);
-            if (h->h_ctl) (void)hipHostFree(h->h_ctl);
-            (void)hipFree(h->d_ctl);
-            h->h_ctl = nullptr; h->d_ctl = nullptr;
-            h->h_xc = nullptr; h->h_flags = nullptr; h->h_new = nullptr; h->h_new_s6 = nullptr; h->d_new = nullptr; h->d_new_s6 = nullptr;
             h->stream_cap = 0;
-            PE_HIP(hipHostMalloc(&h->h_xc, (size_t)NT * ni * sizeof(pnr_xest)));
+            PE_HIP(h->h_xc.alloc((size_t)NT * ni));
             constexpr int MG = pnr_phased::MAXG; // one set per trace group
-            PE_HIP(hipHostMalloc(&h->h_flags, ((size_t)NT * FL_N + 2 * MG) * 4 * MG)); // per group: [2 MG counters | NT x FL_N flags]
-            PE_HIP(hipHostMalloc(&h->h_new, (size_t)NT * 4 * MG));
-            PE_HIP(hipHostMalloc(&h->h_new_s6, (size_t)NT * 24 * MG));
-            PE_HIP(hipMalloc(&h->d_new, (size_t)NT * 4 * MG));
-            PE_HIP(hipMalloc(&h->d_new_s6, (size_t)NT * 24 * MG));
-            PE_HIP(hipHostMalloc(&h->h_ctl, (size_t)NT * 4 * 2 * MG));
-            PE_HIP(hipMalloc(&h->d_ctl, (size_t)NT * 4 * 2 * MG));
+            PE_HIP(h->h_flags.alloc(((size_t)NT * FL_N + 2 * MG) * MG)); // per group: [2 MG counters | NT x FL_N flags]
+            PE_HIP(h->h_new.alloc((size_t)NT * MG));
+            PE_HIP(h->h_new_s6.alloc((size_t)NT * 6 * MG));
+            PE_HIP(h->d_new.alloc((size_t)NT * MG));
+            PE_HIP(h->d_new_s6.alloc((size_t)NT * 6 * MG));
+            PE_HIP(h->h_ctl.alloc((size_t)NT * 2 * MG));
+            PE_HIP(h->d_ctl.alloc((size_t)NT * 2 * MG));
             h->stream_cap = NT;
             h->stream_ni = ni;
         }
         O = h->O;
-        O.xc = (float *)h->h_xc; // the per-iteration records go straight to pinned host memory (32 B per trace and iteration)
+        O.xc = (float *)h->h_xc.get(); // the per-iteration records go straight to pinned host memory (32 B per trace and iteration)
         O.dbg_iters = 0; O.xfilt = nullptr; O.idxres = nullptr; O.neff = nullptr;
         PE_HIP(hipMemsetAsync(E.P.cnt, 0, 2 * 4 * pnr_phased::MAXG, c->stream));
         PE_HIP(hipEventRecord(h->ev_start, c->stream)); // everything queued so far (volume, density map) precedes the other streams
@@ -1522,10 +1499,10 @@ struct PhasedEngine final : pnr::StreamEngine {
             q.P.cnt = E.P.cnt + 2 * g;
             q.st = g == 0 ? c->stream : h->stg[g];
             q.ev_state = h->ev_state[g];
-            q.h_snap = h->h_flags + (size_t)g * ((size_t)h->stream_cap * FL_N + 2 * pnr_phased::MAXG);
+            q.h_snap = h->h_flags.get() + (size_t)g * ((size_t)h->stream_cap * FL_N + 2 * pnr_phased::MAXG);
             q.h_flags = q.h_snap + 2 * pnr_phased::MAXG; q.h_cnt = q.h_snap + 2 * g;
-            q.h_new = h->h_new + (size_t)g * h->stream_cap; q.d_new = h->d_new + (size_t)g * h->stream_cap;
-            q.h_new_s6 = h->h_new_s6 + (size_t)g * h->stream_cap * 6; q.d_new_s6 = h->d_new_s6 + (size_t)g * h->stream_cap * 6;
+            q.h_new = h->h_new.get() + (size_t)g * h->stream_cap; q.d_new = h->d_new.get() + (size_t)g * h->stream_cap;
+            q.h_new_s6 = h->h_new_s6.get() + (size_t)g * h->stream_cap * 6; q.d_new_s6 = h->d_new_s6.get() + (size_t)g * h->stream_cap * 6;
         }
         return PNR_OK;
     }
@@ -1574,7 +1551,7 @@ struct PhasedEngine final : pnr::StreamEngine {
             const int lp = q.lp;
             const int nsplit = pick_nsplit(active, E.ncu, E.max_split, x10);
             if (prof) c->tic(st, k > 0); // (the first step of a poll follows the admission copies: its own opening event)
-            hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)h->d_s6, E.V, np, ni, -1, lp, PH_CS, ph_tbl(np));
+            hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)h->d_s6.get(), E.V, np, ni, -1, lp, PH_CS, ph_tbl(np));
             if (prof) c->toc("smc_predict", 1, st, pw);
             if (P.cubes) {
                 if (prof) c->tic(st, true);
@@ -1590,7 +1567,7 @@ struct PhasedEngine final : pnr::StreamEngine {
             if (prof) c->toc("smc_sums", 1, st, pw);
             if (prof) c->tic(st, true);
             hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), E.upd_lds, st, E.V, E.T, P, np, np_pad, ni, -1, lp, c->prm.Kc, c->prm.znccth,
-                               c->prm.neff_ratio, c->d_den, c->prm.nodepervol, O);
+                               c->prm.neff_ratio, c->d_den.get(), c->prm.nodepervol, O);
             if (prof) c->toc("smc_update", 1, st, pw);
             q.lp ^= 1;
             if (k == poll - 1 - lag) { // what wait() hands to the host: the state behind this step (the last `lag` steps run on meanwhile)
@@ -1623,7 +1600,7 @@ struct PhasedEngine final : pnr::StreamEngine {
         *T = fl[FL_T];
         return fl[FL_DONE] != 0;
     }
-    const pnr_xest *rows(int slot) const override { return h->h_xc + (size_t)slot * E.ni; }
+    const pnr_xest *rows(int slot) const override { return h->h_xc.get() + (size_t)slot * E.ni; }
     int progress(int g, int slot) const override
     {
         // ph_update of iteration `it` writes the estimate of iteration it - 1 (its corr is known one step late) and leaves FL_IT = it + 1
@@ -1632,7 +1609,7 @@ struct PhasedEngine final : pnr::StreamEngine {
     int control(int g, const int *pause, int np_, const int *resume, int nr) override
     {
         Grp &q = grp[g];
-        int *hc = h->h_ctl + (size_t)g * 2 * h->stream_cap, *dc = h->d_ctl + (size_t)g * 2 * h->stream_cap;
+        int *hc = h->h_ctl.get() + (size_t)g * 2 * h->stream_cap, *dc = h->d_ctl.get() + (size_t)g * 2 * h->stream_cap;
         PE_HIP(hipEventSynchronize(h->ev_ctl[g]));                  // pinned staging of this group: its previous lists have been consumed
         if (np_ > 0) std::memcpy(hc, pause, (size_t)np_ * 4);
         if (nr > 0) std::memcpy(hc + h->stream_cap, resume, (size_t)nr * 4);
@@ -1645,10 +1622,10 @@ struct PhasedEngine final : pnr::StreamEngine {
     {
         Grp &q = grp[g];
         if (!q.p_ctl && q.p_m == 0 && q.p_nt == 0) return PNR_OK;
-        int *hc = h->h_ctl + (size_t)g * 2 * h->stream_cap;
-        hipLaunchKernelGGL(ph_poll, dim3((unsigned)(1 + (q.p_nt + 255) / 256)), dim3(256), 0, q.st, q.P, h->d_s6, q.p_ctl ? 1 : 0, (const int *)hc, q.p_np,
-                           (const int *)(hc + h->stream_cap), q.p_nr, (const int *)q.h_new, (const float *)q.h_new_s6, q.p_m, q.lp, E.ni, c->d_den,
-                           (const i64 *)h->h_den_idx[g], (const unsigned char *)h->h_den_val[g], (int)q.p_nt);
+        int *hc = h->h_ctl.get() + (size_t)g * 2 * h->stream_cap;
+        hipLaunchKernelGGL(ph_poll, dim3((unsigned)(1 + (q.p_nt + 255) / 256)), dim3(256), 0, q.st, q.P, h->d_s6.get(), q.p_ctl ? 1 : 0, (const int *)hc, q.p_np,
+                           (const int *)(hc + h->stream_cap), q.p_nr, (const int *)q.h_new, (const float *)q.h_new_s6, q.p_m, q.lp, E.ni, c->d_den.get(),
+                           (const i64 *)h->h_den_idx[g].get(), (const unsigned char *)h->h_den_val[g].get(), (int)q.p_nt);
         PE_HIP(hipGetLastError());
         // The three pinned staging areas the dispatch reads (control lists, admissions, density cells) are rewritten in the group's next
         // turn at the earliest.  Where steps follow in this turn, that turn begins with wait(g) on a state snapshot queued BEHIND this
@@ -1675,24 +1652,19 @@ struct PhasedEngine final : pnr::StreamEngine {
         const size_t nt = r.touched.size();
         if (nt == 0) return PNR_OK;
         Grp &q = grp[g];
-        if (h->den_cap[g] < nt) {
+        if (h->d_den_val[g].count() < nt) { // (allocated last: its capacity is that of the four)
             PE_HIP(hipStreamSynchronize(q.st)); // (its last scatter may still read the old staging)
-            if (h->h_den_idx[g]) (void)hipHostFree(h->h_den_idx[g]);
-            if (h->h_den_val[g]) (void)hipHostFree(h->h_den_val[g]);
-            (void)hipFree(h->d_den_idx[g]);
-            (void)hipFree(h->d_den_val[g]);
-            h->h_den_idx[g] = nullptr; h->h_den_val[g] = nullptr; h->d_den_idx[g] = nullptr; h->d_den_val[g] = nullptr; h->den_cap[g] = 0;
+            h->d_den_val[g].reset();
             const size_t cap = std::max<size_t>(2 * nt, 1 << 16);
-            PE_HIP(hipHostMalloc(&h->h_den_idx[g], cap * 8));
-            PE_HIP(hipHostMalloc(&h->h_den_val[g], cap));
-            PE_HIP(hipMalloc(&h->d_den_idx[g], cap * 8));
-            PE_HIP(hipMalloc(&h->d_den_val[g], cap));
-            h->den_cap[g] = cap;
+            PE_HIP(h->h_den_idx[g].alloc(cap));
+            PE_HIP(h->h_den_val[g].alloc(cap));
+            PE_HIP(h->d_den_idx[g].alloc(cap));
+            PE_HIP(h->d_den_val[g].alloc(cap));
         }
         PE_HIP(hipEventSynchronize(h->ev_ctl[g])); // the previous update's cells have been read from the pinned staging (one event per ph_poll: flush())
         for (size_t i = 0; i < nt; i++) {
-            h->h_den_idx[g][i] = r.touched[i];
-            h->h_den_val[g][i] = (unsigned char)r.den_at(r.touched[i]); // final value: duplicates agree
+            h->h_den_idx[g].get()[i] = r.touched[i];
+            h->h_den_val[g].get()[i] = (unsigned char)r.den_at(r.touched[i]); // final value: duplicates agree
         }
         q.p_nt = nt;
         return PNR_OK;

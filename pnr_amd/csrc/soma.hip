@@ -249,34 +249,37 @@ int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold)
     std::vector<float> G;
     const int Lg = pnr::gaussian_taps(rad, G); // same kernel formula as the 3-D filter (frangi.cpp:791-803)
     hipStream_t st = c->stream;
-    float *d_G = nullptr;
-    unsigned long long *d_hist = nullptr;
-    int *d_cnt = nullptr;
-    i64 *d_off = nullptr, *d_vox = nullptr;
+    pnr::DevBuf<float> b_G; // (all freed when the call returns, on every path)
+    pnr::DevBuf<unsigned long long> b_hist;
+    pnr::DevBuf<int> b_cnt;
+    pnr::DevBuf<i64> b_off, b_vox;
     { // a +0 in front of the taps and one behind: the register-tiled x pass reads the neighbours of a tap pairwise (gauss_sums_packed)
         std::vector<float> Gp(G.size() + 2, 0.f);
         std::copy(G.begin(), G.end(), Gp.begin() + 1);
         G.swap(Gp);
     }
-    PNR_HIP(hipMalloc(&d_G, G.size() * 4));
-    PNR_HIP(hipMalloc(&d_hist, 256 * 8));
-    PNR_HIP(hipMalloc(&d_cnt, (size_t)rows * 4));
-    PNR_HIP(hipMalloc(&d_off, (size_t)rows * 8));
-    auto cleanup = [&]() { hipFree(d_G); hipFree(d_hist); hipFree(d_cnt); hipFree(d_off); hipFree(d_vox); };
+    PNR_HIP(b_G.alloc(G.size()));
+    PNR_HIP(b_hist.alloc(256));
+    PNR_HIP(b_cnt.alloc((size_t)rows));
+    PNR_HIP(b_off.alloc((size_t)rows));
+    float *const d_G = b_G.get();
+    unsigned long long *const d_hist = b_hist.get();
+    int *const d_cnt = b_cnt.get();
+    i64 *const d_off = b_off.get();
     PNR_HIP(hipMemcpyAsync(d_G, G.data(), G.size() * 4, hipMemcpyHostToDevice, st));
     PNR_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, st));
-    unsigned char *d_K = c->d_Vx, *d_E = c->d_Vy;
+    unsigned char *d_K = c->d_Vx.get(), *d_E = c->d_Vy.get();
     c->have_v = false; // the direction volumes serve as scratch here
     const unsigned nb = (unsigned)((n + SOMA_BLOCK - 1) / SOMA_BLOCK);
     c->tic();
     hipLaunchKernelGGL(erode_x, dim3(nb), dim3(SOMA_BLOCK), 0, st, c->d_img, d_K, w, n, Le);
     hipLaunchKernelGGL(erode_y, dim3(nb), dim3(SOMA_BLOCK), 0, st, (const unsigned char *)d_K, d_E, w, h, n, Le);
-    rc = pnr_gauss_x_u8_launch(c, d_E, c->d_tmpA, d_G + 1, Lg); // K[i0] += I[i1] * G[...], taps ascending, clamp-to-edge (frangi.cpp:806-836)
-    if (rc) { cleanup(); return rc; }
+    rc = pnr_gauss_x_u8_launch(c, d_E, c->d_tmpA.get(), d_G + 1, Lg); // K[i0] += I[i1] * G[...], taps ascending, clamp-to-edge (frangi.cpp:806-836)
+    if (rc) return rc;
     {
         const int tiles_x = (w + 63) / 64, tiles_y = (h + TYS - 1) / TYS;
         const size_t sm = ((size_t)(TYS + 2 * Lg) * 64 + 2 * Lg + 1) * 4 + 8 * 256 * 4;
-        hipLaunchKernelGGL(gauss_y_trunc_hist, dim3((unsigned)((i64)tiles_x * tiles_y * l)), dim3(256), sm, st, (const float *)c->d_tmpA, d_E,
+        hipLaunchKernelGGL(gauss_y_trunc_hist, dim3((unsigned)((i64)tiles_x * tiles_y * l)), dim3(256), sm, st, (const float *)c->d_tmpA.get(), d_E,
                            (const float *)(d_G + 1), w, h, tiles_x, tiles_y, Lg, d_hist);
     }
     c->toc("soma", 4);
@@ -295,14 +298,14 @@ int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold)
     for (i64 r = 0; r < rows; r++) { off[(size_t)r] = K; K += cnt[(size_t)r]; }
     c->soma_vox.resize((size_t)K);
     if (K > 0) {
-        if (hipMalloc(&d_vox, (size_t)K * 8) != hipSuccess) { cleanup(); PNR_REQUIRE(false, PNR_E_HIP, "out of device memory for %lld soma voxels", (long long)K); }
+        PNR_REQUIRE(b_vox.alloc((size_t)K) == hipSuccess, PNR_E_HIP, "out of device memory for %lld soma voxels", (long long)K);
+        i64 *d_vox = b_vox.get();
         PNR_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)rows * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(row_compact, dim3((unsigned)rows), dim3(64), 0, st, (const unsigned char *)d_E, w, th, (const i64 *)d_off, d_vox);
         PNR_HIP(hipMemcpyAsync(c->soma_vox.data(), d_vox, (size_t)K * 8, hipMemcpyDeviceToHost, st));
         PNR_HIP(hipStreamSynchronize(st));
     }
     PNR_HIP(hipGetLastError());
-    cleanup();
     std::vector<i64> vox(c->soma_vox.begin(), c->soma_vox.end());
     grow_regions(vox, w, h, l, c->soma_lab, c->soma_nodes);
     c->soma_map.reserve((size_t)K * 2 + 16);

@@ -227,30 +227,21 @@ int pnr_volume_u16_run(pnr_ctx *c, const uint16_t *d_src, int nchan, int channel
 {
     const long long N = c->N;
     hipStream_t st = c->stream;
-    if (!c->d_img_owned || c->img_owned_cap < (size_t)N) {
-        (void)hipFree(c->d_img_owned);
-        c->d_img_owned = nullptr;
-        c->img_owned_cap = 0;
-        if (hipMalloc(&c->d_img_owned, (size_t)N) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_img_owned = nullptr;
-            pnr::set_error("pnr_set_volume_u16: device allocation of %lld B for the 8-bit volume failed", N);
-            return PNR_E_NOMEM;
-        }
-        c->img_owned_cap = (size_t)N;
+    if (c->d_img_owned.reserve((size_t)N) != hipSuccess) {
+        (void)hipGetLastError();
+        pnr::set_error("pnr_set_volume_u16: device allocation of %lld B for the 8-bit volume failed", N);
+        return PNR_E_NOMEM;
     }
     const bool fixed = win.lo >= 0, minmax = !fixed && win.sat_lo_ppm == 0 && win.sat_hi_ppm == 0;
-    VolState *d_st = nullptr;
-    if (!fixed) {
-        if (hipMalloc(&d_st, sizeof(VolState)) != hipSuccess) {
-            (void)hipGetLastError();
-            pnr::set_error("pnr_set_volume_u16: device allocation of %zu B of window state failed", sizeof(VolState));
-            return PNR_E_NOMEM;
-        }
+    pnr::DevBuf<VolState> b_st; // (freed when the call returns: every path below has drained the stream or failed to)
+    if (!fixed && b_st.alloc(1) != hipSuccess) {
+        (void)hipGetLastError();
+        pnr::set_error("pnr_set_volume_u16: device allocation of %zu B of window state failed", sizeof(VolState));
+        return PNR_E_NOMEM;
     }
+    VolState *d_st = b_st.get();
     hipError_t e = d_st ? hipMemsetAsync(d_st, 0, sizeof(VolState), st) : hipSuccess;
     if (e != hipSuccess) {
-        (void)hipFree(d_st);
         pnr::set_error("pnr_set_volume_u16: %s", hipGetErrorString(e));
         return PNR_E_HIP;
     }
@@ -278,16 +269,15 @@ int pnr_volume_u16_run(pnr_ctx *c, const uint16_t *d_src, int nchan, int channel
     }
     const unsigned mb = blocks_for(N >> 3, TPB, MAX_BLOCKS);
     if (nchan == 1 && (addr & 15) == 0)
-        hipLaunchKernelGGL(vol_map<true>, dim3(mb), dim3(TPB), 0, st, s, (const VolState *)d_st, (unsigned)win.lo, (unsigned)win.hi, c->d_img_owned);
+        hipLaunchKernelGGL(vol_map<true>, dim3(mb), dim3(TPB), 0, st, s, (const VolState *)d_st, (unsigned)win.lo, (unsigned)win.hi, c->d_img_owned.get());
     else
-        hipLaunchKernelGGL(vol_map<false>, dim3(mb), dim3(TPB), 0, st, s, (const VolState *)d_st, (unsigned)win.lo, (unsigned)win.hi, c->d_img_owned);
+        hipLaunchKernelGGL(vol_map<false>, dim3(mb), dim3(TPB), 0, st, s, (const VolState *)d_st, (unsigned)win.lo, (unsigned)win.hi, c->d_img_owned.get());
     launches++;
     if (e == hipSuccess) e = hipGetLastError();
     c->toc("volume", launches);
     unsigned w2[2] = {65535u - (unsigned)win.lo, (unsigned)win.hi};
     if (e == hipSuccess && d_st) e = hipMemcpyAsync(w2, d_st->win, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_st) (void)hipFree(d_st);
     if (e != hipSuccess) {
         pnr::set_error("pnr_set_volume_u16: %s", hipGetErrorString(e));
         return PNR_E_HIP;

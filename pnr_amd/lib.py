@@ -113,6 +113,7 @@ def load():
     L.pnr_measure_radii.argtypes = [vp, vp, i64, C.POINTER(RadiusOpts), vp, C.POINTER(C.c_int32)]
     L.pnr_filter_volume.argtypes = [vp, C.POINTER(FilterOpts)]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.pnr_live_bytes.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pnr_get_frangi.argtypes = [vp] + [vp] * 5
     L.pnr_gaussian.argtypes = [vp, C.c_float, vp]
@@ -182,7 +183,7 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
                    "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets"]
+                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_live_bytes"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -702,6 +703,13 @@ def reconstruct(nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, ep
         if n.value <= cap:
             return out[:n.value].copy(), par[:n.value].copy()
         cap = int(n.value)
+
+
+def live_bytes():
+    """test tap pnr_live_bytes: (device bytes, pinned host bytes) the library holds now, over every context and exchange of the process"""
+    dev, pin = C.c_int64(), C.c_int64()
+    check(load().pnr_live_bytes(C.byref(dev), C.byref(pin)))
+    return dev.value, pin.value
 
 
 def radius_offsets(zdist, rmax, is2d=False):
