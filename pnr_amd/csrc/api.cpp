@@ -190,7 +190,7 @@ void pnr_destroy(pnr_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    pnr_job_destroy(c->job);
+    pnr_persistent_destroy(c->job);
     pnr_phased_destroy(c->phased);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (int k = 0; k < pnr_ctx::J8_CHUNKS; k++)

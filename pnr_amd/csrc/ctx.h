@@ -161,7 +161,7 @@ struct pnr_ctx {
     pnr::DevBuf<long long> d_den_idx; // staging for the per-batch scatter of touched voxels
     pnr::DevBuf<uint8_t> d_den_val;
 
-    struct pnr_trace_job *job = nullptr; // device buffers of pnr_trace_batch / the persistent driver's batches (ctx stream)
+    struct pnr_persistent_bufs *job = nullptr; // device buffers of the persistent driver's batches (smc.hip; run on the ctx stream)
     struct pnr_phased *phased = nullptr; // state of the launch-per-phase SMC driver (smc_phased.hip)
     int smc_driver = 0;                  // 0: launch per phase (default), 1: one persistent work-group per trace
 
@@ -291,12 +291,8 @@ int pnr_zncc_run(pnr_ctx *c, const float *h_pos_dir, int64_t n, float *h_corr, f
 int pnr_trace_run(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *T, int32_t *stop, pnr_xest *xc,
                   int dbg_iters, float *xfilt, int32_t *idxres, float *neff, int use_density);
 namespace pnr { struct Replayer; struct ShardSpec; }
-struct pnr_trace_job;
-pnr_trace_job *pnr_job_create(pnr_ctx *c, bool own_stream);
-void pnr_job_destroy(pnr_trace_job *j);
-int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t n, int dbg_iters, bool want_xfilt, bool want_idxres,
-                   bool want_neff, int use_density);
-int pnr_job_finish(pnr_ctx *c, pnr_trace_job *j, int32_t *T, int32_t *stop, pnr_xest *xc, float *xfilt, int32_t *idxres, float *neff);
+struct pnr_persistent_bufs;
+void pnr_persistent_destroy(pnr_persistent_bufs *j);
 struct pnr_phased;
 int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *T, int32_t *stop, pnr_xest *xc, int dbg_iters,
                          float *xfilt, int32_t *idxres, float *neff, int use_density);
@@ -304,7 +300,6 @@ void pnr_phased_destroy(pnr_phased *h);
 int pnr_trace_replay_stream(pnr_ctx *c, const pnr_seed *seeds, int64_t n, pnr::Replayer &r, const pnr::ShardSpec &sh, int64_t *iters);
 int pnr_density_reset(pnr_ctx *c);                       // zero the device density map (allocating it on first use)
 int pnr_density_update(pnr_ctx *c, const pnr::Replayer &r, hipStream_t on = nullptr); // push the voxels touched since Replayer::touched was cleared
-int pnr_density_scatter_async(pnr_ctx *c, const long long *d_idx, const unsigned char *d_val, size_t n, hipStream_t st); // (staging owned by the caller, no wait)
 int pnr_expf_run(pnr_ctx *c, const float *x, int64_t n, float *y);
 int pnr_eigen_run(pnr_ctx *c, const double *A, int64_t n, double *V, double *d); // test tap (pnr_hip_test.h)
 int pnr_ensure_frangi_buffers(pnr_ctx *c);

@@ -531,58 +531,24 @@ int pnr_zncc_run(pnr_ctx *c, const float *h_pos_dir, int64_t n, float *h_corr, f
     return PNR_OK;
 }
 
-// ---- asynchronous trace jobs: launch on the job's stream, collect later -------------------------------
-struct pnr_trace_job {
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int64_t n = 0;      // seeds of the launch in flight (0: idle)
-    int dbg_iters = 0;
+// ---- the persistent driver's batch: one work-group per trace, launched and read back on the context's stream ----
+struct pnr_persistent_bufs { // (hangs on pnr_ctx::job; grow-only)
     pnr::DevBuf<float> d_s6;
     TraceOut O{}; // (views of `out`)
     TraceOutBufs out;
     size_t cap_tr = 0, cap_dbg = 0; // capacities (traces; traces*dbg_iters) the device buffers were sized for
     std::vector<float> s6;
-    // launch-per-phase driver: the host loop runs in pnr_job_finish
-    bool phased = false;
-    std::vector<pnr_seed> seeds;
-    bool want_xfilt = false, want_idxres = false, want_neff = false;
-    int use_density = 0;
 };
 
-pnr_trace_job *pnr_job_create(pnr_ctx *c, bool own_stream)
-{
-    pnr_trace_job *j = new pnr_trace_job();
-    if (own_stream) {
-        if (hipStreamCreateWithFlags(&j->stream, hipStreamNonBlocking) != hipSuccess) { delete j; return nullptr; }
-        j->own_stream = true;
-    } else {
-        j->stream = c->stream;
-    }
-    return j;
-}
+void pnr_persistent_destroy(pnr_persistent_bufs *j) { delete j; }
 
-void pnr_job_destroy(pnr_trace_job *j)
+static int trace_run_persistent(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *T_out, int32_t *stop_out, pnr_xest *xc, int dbg_iters,
+                                float *xfilt, int32_t *idxres, float *neff, int use_density)
 {
-    if (!j) return;
-    if (j->stream) (void)hipStreamSynchronize(j->stream);
-    if (j->own_stream) (void)hipStreamDestroy(j->stream);
-    delete j;
-}
-
-int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t n, int dbg_iters, bool want_xfilt,
-                   bool want_idxres, bool want_neff, int use_density)
-{
-    j->n = 0;
-    if (n == 0) return PNR_OK;
-    if (!j->own_stream) j->stream = c->stream;
-    j->phased = (c->smc_driver == 0);
-    PNR_REQUIRE(j->phased || c->l > 1, PNR_E_ARG, "single-slice (2-D) stacks are traced by the phased SMC driver only");
-    if (j->phased) {
-        j->seeds.assign(seeds, seeds + n);
-        j->n = n; j->dbg_iters = dbg_iters; j->use_density = use_density;
-        j->want_xfilt = want_xfilt; j->want_idxres = want_idxres; j->want_neff = want_neff;
-        return PNR_OK;
-    }
+    PNR_REQUIRE(c->l > 1, PNR_E_ARG, "single-slice (2-D) stacks are traced by the phased SMC driver only");
+    if (!c->job) c->job = new pnr_persistent_bufs();
+    pnr_persistent_bufs *j = c->job;
+    hipStream_t st = c->stream;
     Vol V;
     int rc = make_vol(c, V);
     if (rc) return rc;
@@ -647,9 +613,9 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
         b[3] = -seeds[i].vx; b[4] = -seeds[i].vy; b[5] = -seeds[i].vz; // trackNeg (tracker.cpp:819-823)
     }
     const size_t need_dbg = (size_t)ntr * dbg_iters;
-    if (j->cap_tr < (size_t)ntr || j->cap_dbg < need_dbg || (want_xfilt && !j->O.xfilt && dbg_iters) ||
-        (want_idxres && !j->O.idxres && dbg_iters) || (want_neff && !j->O.neff && dbg_iters)) {
-        PNR_HIP(hipStreamSynchronize(j->stream));
+    if (j->cap_tr < (size_t)ntr || j->cap_dbg < need_dbg || (xfilt && !j->O.xfilt && dbg_iters) ||
+        (idxres && !j->O.idxres && dbg_iters) || (neff && !j->O.neff && dbg_iters)) {
+        PNR_HIP(hipStreamSynchronize(st));
         j->d_s6.reset(), j->out.reset();
         j->O = TraceOut{};
         j->cap_tr = j->cap_dbg = 0;
@@ -657,25 +623,25 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
         PNR_HIP(alloc_view(j->out.T, j->O.T, (size_t)ntr));
         PNR_HIP(alloc_view(j->out.stop, j->O.stop, (size_t)ntr));
         PNR_HIP(alloc_view(j->out.xc, j->O.xc, (size_t)ntr * ni * 8));
-        if (dbg_iters > 0 && want_xfilt) PNR_HIP(alloc_view(j->out.xfilt, j->O.xfilt, need_dbg * np * PSTRIDE));
-        if (dbg_iters > 0 && want_idxres) PNR_HIP(alloc_view(j->out.idxres, j->O.idxres, need_dbg * np));
-        if (dbg_iters > 0 && want_neff) PNR_HIP(alloc_view(j->out.neff, j->O.neff, need_dbg));
+        if (dbg_iters > 0 && xfilt) PNR_HIP(alloc_view(j->out.xfilt, j->O.xfilt, need_dbg * np * PSTRIDE));
+        if (dbg_iters > 0 && idxres) PNR_HIP(alloc_view(j->out.idxres, j->O.idxres, need_dbg * np));
+        if (dbg_iters > 0 && neff) PNR_HIP(alloc_view(j->out.neff, j->O.neff, need_dbg));
         j->cap_tr = (size_t)ntr;
         j->cap_dbg = need_dbg;
     }
     TraceOut O = j->O;
     O.dbg_iters = dbg_iters;
-    if (!want_xfilt || !dbg_iters) O.xfilt = nullptr;
-    if (!want_idxres || !dbg_iters) O.idxres = nullptr;
-    if (!want_neff || !dbg_iters) O.neff = nullptr;
-    PNR_HIP(hipMemsetAsync(O.xc, 0, (size_t)ntr * ni * 32, j->stream));
-    if (O.idxres) PNR_HIP(hipMemsetAsync(O.idxres, 0xff, need_dbg * np * 4, j->stream));
-    PNR_HIP(hipMemcpyAsync(j->d_s6.get(), j->s6.data(), j->s6.size() * 4, hipMemcpyHostToDevice, j->stream));
-    c->tic(j->stream);
+    if (!xfilt || !dbg_iters) O.xfilt = nullptr;
+    if (!idxres || !dbg_iters) O.idxres = nullptr;
+    if (!neff || !dbg_iters) O.neff = nullptr;
+    PNR_HIP(hipMemsetAsync(O.xc, 0, (size_t)ntr * ni * 32, st));
+    if (O.idxres) PNR_HIP(hipMemsetAsync(O.idxres, 0xff, need_dbg * np * 4, st));
+    PNR_HIP(hipMemcpyAsync(j->d_s6.get(), j->s6.data(), j->s6.size() * 4, hipMemcpyHostToDevice, st));
+    c->tic(st);
 #define PNR_LAUNCH_TRACE(cs)                                                                                                   \
     case cs:                                                                                                                   \
         PNR_HIP(hipFuncSetAttribute((const void *)smc_trace<cs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-        hipLaunchKernelGGL(smc_trace<cs>, dim3((unsigned)ntr), dim3(block), lds, j->stream, V, T, X, j->d_s6.get(), np, np_pad, ni, \
+        hipLaunchKernelGGL(smc_trace<cs>, dim3((unsigned)ntr), dim3(block), lds, st, V, T, X, j->d_s6.get(), np, np_pad, ni, \
                            c->prm.Kc, c->prm.znccth, c->prm.neff_ratio, use_density ? c->d_den.get() : nullptr, c->prm.nodepervol, O); \
         break;
     switch (CS) {
@@ -687,33 +653,15 @@ int pnr_job_launch(pnr_ctx *c, pnr_trace_job *j, const pnr_seed *seeds, int64_t 
         PNR_LAUNCH_TRACE(32)
     }
 #undef PNR_LAUNCH_TRACE
-    c->toc("smc", 1, j->stream);
+    c->toc("smc", 1, st);
     PNR_HIP(hipGetLastError());
-    j->n = n;
-    j->dbg_iters = dbg_iters;
-    return PNR_OK;
-}
-
-int pnr_job_finish(pnr_ctx *c, pnr_trace_job *j, int32_t *T_out, int32_t *stop_out, pnr_xest *xc, float *xfilt, int32_t *idxres,
-                   float *neff)
-{
-    if (j->n == 0) return PNR_OK;
-    if (j->phased) {
-        const int64_t n = j->n;
-        j->n = 0;
-        return pnr_trace_run_phased(c, j->seeds.data(), n, T_out, stop_out, xc, j->dbg_iters, j->want_xfilt ? xfilt : nullptr,
-                                    j->want_idxres ? idxres : nullptr, j->want_neff ? neff : nullptr, j->use_density);
-    }
-    const i64 ntr = 2 * j->n;
-    const int np = c->prm.np, ni = c->prm.ni, dbg = j->dbg_iters;
-    PNR_HIP(hipMemcpyAsync(T_out, j->O.T, (size_t)ntr * 4, hipMemcpyDeviceToHost, j->stream));
-    PNR_HIP(hipMemcpyAsync(stop_out, j->O.stop, (size_t)ntr * 4, hipMemcpyDeviceToHost, j->stream));
-    PNR_HIP(hipMemcpyAsync(xc, j->O.xc, (size_t)ntr * ni * 32, hipMemcpyDeviceToHost, j->stream));
-    if (dbg && xfilt && j->O.xfilt) PNR_HIP(hipMemcpyAsync(xfilt, j->O.xfilt, (size_t)ntr * dbg * np * PSTRIDE * 4, hipMemcpyDeviceToHost, j->stream));
-    if (dbg && idxres && j->O.idxres) PNR_HIP(hipMemcpyAsync(idxres, j->O.idxres, (size_t)ntr * dbg * np * 4, hipMemcpyDeviceToHost, j->stream));
-    if (dbg && neff && j->O.neff) PNR_HIP(hipMemcpyAsync(neff, j->O.neff, (size_t)ntr * dbg * 4, hipMemcpyDeviceToHost, j->stream));
-    PNR_HIP(hipStreamSynchronize(j->stream));
-    j->n = 0;
+    PNR_HIP(hipMemcpyAsync(T_out, O.T, (size_t)ntr * 4, hipMemcpyDeviceToHost, st));
+    PNR_HIP(hipMemcpyAsync(stop_out, O.stop, (size_t)ntr * 4, hipMemcpyDeviceToHost, st));
+    PNR_HIP(hipMemcpyAsync(xc, O.xc, (size_t)ntr * ni * 32, hipMemcpyDeviceToHost, st));
+    if (O.xfilt) PNR_HIP(hipMemcpyAsync(xfilt, O.xfilt, need_dbg * np * PSTRIDE * 4, hipMemcpyDeviceToHost, st));
+    if (O.idxres) PNR_HIP(hipMemcpyAsync(idxres, O.idxres, need_dbg * np * 4, hipMemcpyDeviceToHost, st));
+    if (O.neff) PNR_HIP(hipMemcpyAsync(neff, O.neff, need_dbg * 4, hipMemcpyDeviceToHost, st));
+    PNR_HIP(hipStreamSynchronize(st));
     return PNR_OK;
 }
 
@@ -721,32 +669,15 @@ int pnr_trace_run(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *T_out, 
                   float *xfilt, int32_t *idxres, float *neff, int use_density)
 {
     if (n == 0) return PNR_OK;
-    pnr_trace_job *&sj = c->job;
-    if (!sj) sj = pnr_job_create(c, false);
-    PNR_REQUIRE(sj, PNR_E_HIP, "could not create a trace job");
-    int rc = pnr_job_launch(c, sj, seeds, n, dbg_iters, xfilt != nullptr, idxres != nullptr, neff != nullptr, use_density);
-    if (rc) return rc;
-    return pnr_job_finish(c, sj, T_out, stop_out, xc, xfilt, idxres, neff);
+    if (c->smc_driver == 0) return pnr_trace_run_phased(c, seeds, n, T_out, stop_out, xc, dbg_iters, xfilt, idxres, neff, use_density);
+    return trace_run_persistent(c, seeds, n, T_out, stop_out, xc, dbg_iters, xfilt, idxres, neff, use_density);
 }
 
 namespace {
-// Monotone: a voxel's density only ever grows (the replay adds nodes; a soma voxel is saturated from the start), and updates of
-// different trace groups arrive on different streams in no particular order -- so a value is only written over a smaller one (a
-// compare-and-swap on the byte's dword), and a late older update can never lower what a newer one wrote.
 __global__ void den_scatter(unsigned char *den, const i64 *idx, const unsigned char *val, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const i64 at = idx[i];
-    unsigned *w = (unsigned *)(den + (at & ~(i64)3)); // (the map is allocated in whole dwords)
-    const int sh = (int)(at & 3) * 8;
-    const unsigned v = val[i];
-    unsigned old = __atomic_load_n(w, __ATOMIC_RELAXED);
-    while (((old >> sh) & 0xffu) < v) {
-        const unsigned got = atomicCAS(w, old, (old & ~(0xffu << sh)) | (v << sh));
-        if (got == old) break;
-        old = got;
-    }
+    if (i < n) den_raise(den, idx[i], val[i]);
 }
 } // namespace
 
@@ -758,7 +689,7 @@ int pnr_density_reset(pnr_ctx *c)
         c->den_cap = c->N;
     }
     PNR_HIP(hipMemsetAsync(c->d_den.get(), 0, ((size_t)c->N + 3) / 4 * 4, c->stream));
-    PNR_HIP(hipStreamSynchronize(c->stream)); // trace jobs run on their own streams
+    PNR_HIP(hipStreamSynchronize(c->stream)); // (the streaming tracer's trace groups run on streams of their own)
     if (!c->soma_vox.empty()) {
         // a trace that reaches a soma voxel stops there in the replay (tracker.cpp:858-869): for the kernels' early stop
         // the soma is simply saturated density
@@ -797,15 +728,6 @@ int pnr_density_update(pnr_ctx *c, const pnr::Replayer &r, hipStream_t on)
                        (const unsigned char *)c->d_den_val.get(), (int)n);
     PNR_HIP(hipGetLastError());
     PNR_HIP(hipStreamSynchronize(st));
-    return PNR_OK;
-}
-
-// the scatter alone, on a stream of the caller's, from device staging the caller owns: nothing here waits for anything
-int pnr_density_scatter_async(pnr_ctx *c, const long long *d_idx, const unsigned char *d_val, size_t n, hipStream_t st)
-{
-    if (n == 0) return PNR_OK;
-    hipLaunchKernelGGL(den_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->d_den.get(), (const i64 *)d_idx, d_val, (int)n);
-    PNR_HIP(hipGetLastError());
     return PNR_OK;
 }
 

@@ -68,6 +68,20 @@ __device__ __forceinline__ float clampf(float x, float lo, float hi)
     return (c > hi) ? hi : c;
 }
 
+// Raise voxel `at` of the density map to `v`.  Monotone: a voxel's density only ever grows (the replay adds nodes; a soma voxel is
+// saturated from the start), and updates of different trace groups arrive on different streams in no particular order -- so a value is
+// only written over a smaller one (a compare-and-swap on the byte's dword), and a late older update can never lower what a newer one wrote.
+__device__ __forceinline__ void den_raise(unsigned char *den, i64 at, unsigned v)
+{
+    unsigned *w = (unsigned *)(den + (at & ~(i64)3)); // (the map is allocated in whole dwords)
+    const int sh = (int)(at & 3) * 8;
+    unsigned old = __atomic_load_n(w, __ATOMIC_RELAXED);
+    while (((old >> sh) & 0xffu) < v) {
+        const unsigned got = atomicCAS(w, old, (old & ~(0xffu << sh)) | (v << sh));
+        if (got == old) break;
+        old = got;
+    }
+}
 
 // Tracker::interp, 3-D branch (tracker.cpp:2178-2213)
 __device__ __forceinline__ float interp(const Vol &V, float x, float y, float z)

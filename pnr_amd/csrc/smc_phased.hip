@@ -706,7 +706,7 @@ __global__ __launch_bounds__(256) void ph_update(Vol V, Tab T, PhState P, int np
     if ((int)blockIdx.x >= P.cnt[lp]) return;
     const int tr = P.list[lp * P.cap + blockIdx.x];
     int *fl = P.flags + (i64)tr * FL_N;
-    if (fl[FL_PAUSE]) return; // (not appended to the next step's list: it comes back through ph_control)
+    if (fl[FL_PAUSE]) return; // (not appended to the next step's list: it comes back through a resume list of ph_poll)
     const int it = it_arg >= 0 ? it_arg : fl[FL_IT];
     float *cur = lds;                 // [np][9]
     float *prvw = cur + np * PSTRIDE; // [np] weights of the previous iteration
@@ -914,62 +914,13 @@ __global__ __launch_bounds__(256) void ph_snapshot(const int4 *__restrict__ src,
     if (i < n4) dst[i] = src[i];
 }
 
-// streaming mode: hand `m` free slots to new traces and append them to the list of this step (one work-group, runs
-// alone in stream order between two steps)
-__global__ __launch_bounds__(256) void ph_admit(PhState P, float *__restrict__ s6, const int *__restrict__ new_slots,
-                                                 const float *__restrict__ new_s6, int m, int lp, int ni)
-{
-    __shared__ int base;
-    if (threadIdx.x == 0) base = P.cnt[lp];
-    __syncthreads();
-    for (int j = threadIdx.x; j < m; j += blockDim.x) {
-        const int slot = new_slots[j];
-        for (int a = 0; a < 6; a++) s6[(i64)slot * 6 + a] = new_s6[(i64)j * 6 + a];
-        int *fl = P.flags + (i64)slot * FL_N;
-        for (int a = 0; a < FL_N; a++) fl[a] = 0;
-        fl[FL_T] = ni;
-        for (int a = 0; a < 16; a++) P.xcs[(i64)slot * 16 + a] = 0.f;
-        P.list[lp * P.cap + base + j] = slot;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) P.cnt[lp] = base + m;
-}
-
-// streaming mode, tentative replay: take some traces off the list of this step (they keep slot and state; FL_PAUSE marks them) and
-// put paused ones back on it (one work-group, runs alone in stream order between two steps).  The list is compacted here, so a
-// pause takes effect at once and the slot of a trace the host has ended can be handed to a new trace in the same turn.
-__global__ __launch_bounds__(256) void ph_control(PhState P, const int *__restrict__ pause, int np_, const int *__restrict__ resume, int nr, int lp)
-{
-    __shared__ int kept;
-    const int n = P.cnt[lp];
-    int *list = P.list + (size_t)lp * P.cap, *tmp = P.list + (size_t)(lp ^ 1) * P.cap; // (the other list is only filled by the next ph_update)
-    if (threadIdx.x == 0) kept = 0;
-    for (int j = threadIdx.x; j < np_; j += blockDim.x) P.flags[(i64)pause[j] * FL_N + FL_PAUSE] = 1;
-    __syncthreads();
-    if (np_ > 0) {
-        for (int j = threadIdx.x; j < n; j += blockDim.x) {
-            const int tr = list[j];
-            if (!P.flags[(i64)tr * FL_N + FL_PAUSE]) tmp[atomicAdd(&kept, 1)] = tr;
-        }
-        __syncthreads();
-        for (int j = threadIdx.x; j < kept; j += blockDim.x) list[j] = tmp[j];
-        __syncthreads();
-    } else if (threadIdx.x == 0) {
-        kept = n;
-    }
-    __syncthreads();
-    const int base = kept;
-    for (int j = threadIdx.x; j < nr; j += blockDim.x) {
-        P.flags[(i64)resume[j] * FL_N + FL_PAUSE] = 0;
-        list[base + j] = resume[j];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) P.cnt[lp] = base + nr;
-}
-
 // What a poll asks of a trace group, in ONE dispatch (each dispatch in front of the group's next step costs ~14 us of its chain, and
-// there were three): work-group 0 runs ph_control's and then ph_admit's work (same order, same code); the work-groups behind it
-// raise the density map (den_scatter's monotone byte-wise maximum).  The lists are read from pinned host staging by the kernel.
+// there were three).  Work-group 0 runs alone in stream order between two steps and does two things, control first:
+//  - control (tentative replay): takes the `pause` traces off the list of this step (they keep slot and state; FL_PAUSE marks them)
+//    and puts the `resume` ones back on it.  The list is compacted here, so a pause takes effect at once and the slot of a trace the
+//    host has ended can be handed to a new trace in the same turn;
+//  - admission: hands `m` free slots to new traces and appends them to the list of this step.
+// The work-groups behind it raise the density map (den_raise).  The lists are read from pinned host staging by the kernel.
 __global__ __launch_bounds__(256) void ph_poll(PhState P, float *__restrict__ s6, int do_ctl, const int *__restrict__ pause, int np_,
                                                 const int *__restrict__ resume, int nr, const int *__restrict__ new_slots,
                                                 const float *__restrict__ new_s6, int m, int lp, int ni, unsigned char *__restrict__ den,
@@ -977,24 +928,14 @@ __global__ __launch_bounds__(256) void ph_poll(PhState P, float *__restrict__ s6
 {
     if (blockIdx.x > 0) {
         const int i = ((int)blockIdx.x - 1) * (int)blockDim.x + (int)threadIdx.x;
-        if (i >= nt) return;
-        const i64 at = didx[i];
-        unsigned *w = (unsigned *)(den + (at & ~(i64)3)); // (the map is allocated in whole dwords)
-        const int sh = (int)(at & 3) * 8;
-        const unsigned v = dval[i];
-        unsigned old = __atomic_load_n(w, __ATOMIC_RELAXED);
-        while (((old >> sh) & 0xffu) < v) {
-            const unsigned got = atomicCAS(w, old, (old & ~(0xffu << sh)) | (v << sh));
-            if (got == old) break;
-            old = got;
-        }
+        if (i < nt) den_raise(den, didx[i], dval[i]);
         return;
     }
     __shared__ int kept, cntv;
     if (threadIdx.x == 0) { cntv = P.cnt[lp]; kept = 0; }
     __syncthreads();
     int *list = P.list + (size_t)lp * P.cap, *tmp = P.list + (size_t)(lp ^ 1) * P.cap; // (the other list is only filled by the next ph_update)
-    if (do_ctl) { // ---- ph_control
+    if (do_ctl) { // ---- control
         const int n = cntv;
         for (int j = threadIdx.x; j < np_; j += blockDim.x) P.flags[(i64)pause[j] * FL_N + FL_PAUSE] = 1;
         __syncthreads();
@@ -1019,7 +960,7 @@ __global__ __launch_bounds__(256) void ph_poll(PhState P, float *__restrict__ s6
         if (threadIdx.x == 0) cntv = base + nr;
         __syncthreads();
     }
-    if (m > 0) { // ---- ph_admit
+    if (m > 0) { // ---- admission
         const int base = cntv;
         for (int j = threadIdx.x; j < m; j += blockDim.x) {
             const int slot = new_slots[j];
@@ -1043,7 +984,7 @@ __global__ __launch_bounds__(256) void ph_poll(PhState P, float *__restrict__ s6
 // host driver
 // ---------------------------------------------------------------------------------------------------------
 struct pnr_phased {
-    static constexpr int RING = 8;
+    static constexpr int RING = 8, MAXG = 4; // MAXG: the trace groups of the streaming tracer
     int64_t cap_traces = 0, cap_dbg = 0;
     int64_t cap_stash = 0; // traces the sample stash holds (list positions of all trace groups together)
     int np = 0, np_pad = 0, S = 0, ni = 0;
@@ -1061,22 +1002,19 @@ struct pnr_phased {
     hipEvent_t ev[RING] = {};   // ... and the events that say so
     // streaming trace + replay: pinned records written by the kernels / read back at every poll, admission staging
     pnr::PinBuf<pnr_xest> h_xc; pnr::PinBuf<int> h_flags, h_new; pnr::PinBuf<float> h_new_s6;
-    pnr::DevBuf<int> d_new; pnr::DevBuf<float> d_new_s6;
-    pnr::PinBuf<int> h_ctl; pnr::DevBuf<int> d_ctl; // pause / resume lists of the tentative replay: [group][2][stream_cap]
-    // density updates of the streaming tracer: pinned and device staging per trace group (grow-only), so that an update is queued on the
-    // group's own stream and nothing waits for it
-    pnr::PinBuf<long long> h_den_idx[4]; pnr::DevBuf<long long> d_den_idx[4];
-    pnr::PinBuf<unsigned char> h_den_val[4]; pnr::DevBuf<unsigned char> d_den_val[4];
+    pnr::PinBuf<int> h_ctl; // pause / resume lists of the tentative replay: [group][2][stream_cap]
+    // density updates of the streaming tracer: pinned staging per trace group (grow-only, read by ph_poll itself), so that an update
+    // is queued on the group's own stream and nothing waits for it
+    pnr::PinBuf<long long> h_den_idx[MAXG];
+    pnr::PinBuf<unsigned char> h_den_val[MAXG];
     int64_t stream_cap = 0;
     int stream_ni = 0;
-    static constexpr int MAXG = 4;
-    static_assert(MAXG == 4, "the density staging above is declared with four entries");
-    hipStream_t stg[MAXG] = {}, st_den = nullptr; // [1..]: the further trace groups of the streaming tracer; density uploads
+    hipStream_t stg[MAXG] = {}; // [1..]: the further trace groups of the streaming tracer
     hipEvent_t ev_start = nullptr;
-    hipEvent_t ev_state[4] = {}; // per trace group: the state copies of its last launch have landed (PhasedEngine::wait)
-    // per trace group: the last upload from its pinned admission / control / density staging has been consumed.  A group whose traces are
-    // all paused is not launched, so no wait() lies between two of its turns: the staging is only rewritten behind these events.
-    hipEvent_t ev_adm[4] = {}, ev_ctl[4] = {}, ev_den[4] = {};
+    hipEvent_t ev_state[MAXG] = {}; // per trace group: the state copies of its last launch have landed (PhasedEngine::wait)
+    // per trace group: the last ph_poll has consumed its pinned admission / control / density staging.  A group whose traces are all
+    // paused is not launched, so no wait() lies between two of its turns: the staging is only rewritten behind this event.
+    hipEvent_t ev_ctl[MAXG] = {};
 };
 
 static void phased_free(pnr_phased *h)
@@ -1120,18 +1058,12 @@ void pnr_phased_destroy(pnr_phased *h)
         if (h->ev[r]) (void)hipEventDestroy(h->ev[r]);
     for (int g = 1; g < pnr_phased::MAXG; g++)
         if (h->stg[g]) (void)hipStreamDestroy(h->stg[g]);
-    if (h->st_den) (void)hipStreamDestroy(h->st_den);
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     for (hipEvent_t &e : h->ev_state) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->ev_adm) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t &e : h->ev_ctl) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->ev_den) if (e) (void)hipEventDestroy(e);
     delete h;
 }
 
-// Work-groups per trace for the sampling launch.  One work-group per CU is resident (the cube fills the LDS); all
-// work-groups of a trace pull items from its counter, so what matters is that there are a few times more work-groups
-// than CUs (the dispatcher keeps every CU busy until the items run out) without paying the cube staging too often.
 // Which form of the ordered sums a launch of `active` traces takes (option "sums_deep": -1 automatic, 0 / 1 forced; the results
 // are the same): the four-buffer form when the launch has the GPU to itself, or is so small that a chain's latency is all it costs
 static bool sums_deep(const pnr_ctx *c, int active, int ngroups)
@@ -1159,6 +1091,9 @@ static int ph_tbl(int np)
 // dynamic LDS of ph_predict: representatives (+ hashes, poses and the table when it searches for duplicates)
 static size_t ph_predict_lds(int np, int dedup) { return dedup ? (size_t)(np * 8 + 2 * ph_tbl(np)) * 4 : (size_t)np * 8; }
 
+// Work-groups per trace for the sampling launch.  One work-group per CU is resident (the cube fills the LDS); all
+// work-groups of a trace pull items from its counter, so what matters is that there are a few times more work-groups
+// than CUs (the dispatcher keeps every CU busy until the items run out) without paying the cube staging too often.
 static int pick_nsplit(int active, int ncu, int max_split, int x10 /* work-groups per CU x 10 */)
 {
     if (x10 <= 0) x10 = 40;
@@ -1175,11 +1110,7 @@ static void launch_sums(hipStream_t st, const Tab &T, const TabX &X, const PhSta
     else hipLaunchKernelGGL(ph_sums<false>, grid, dim3(64), 0, st, T, X, P, np, np_pad, ni, it, lp, ng, share);
 }
 
-// the sampling launch of a step: the traces' cubes fetched once into their compact copies (ph_cube), then the sampling work-groups
-static void launch_cube(hipStream_t st, const Vol &V, const PhState &P, int active, int lp)
-{
-    hipLaunchKernelGGL(ph_cube, dim3((unsigned)(active * PH_CUBE_SPLIT)), dim3(PH_CUBE_THREADS), 0, st, V, P, lp, active);
-}
+// the sampling launch of a step (behind ph_cube, which has fetched the traces' cubes once into their compact copies)
 static void launch_sample(hipStream_t st, const Vol &V, const Tab &T, const TabX &X, const PhState &P, int np, int ni, int it, int lp, int active, int nsplit, size_t cube_bytes,
                           int share)
 {
@@ -1202,8 +1133,42 @@ struct PhEnv {
     pnr_phased *h;
 };
 
-// device state for up to `want` concurrent traces (fewer if their sample stash exceeds the budget: PNR_STASH_GB,
-// default 64 GB, or half of the free HBM) and everything the four kernels take as arguments
+// the kernel timers of a step (pnr_set_profiling): whether it is timed at all, whether the tic in front of its first kernel / of its
+// further kernels chains onto the toc before it (pnr_ctx::tic), and how many steps like it the measurement stands for
+struct StepTimers { bool on, chain_first, chain_rest; int weight; };
+
+// One SMC step over the `active` traces of list `lp`, queued on `st`: ph_predict, ph_cube (option "cube_copy"), ph_sample, ph_sums,
+// ph_update.  The one place that launches them: the batch driver and the streaming engine both step through here.
+//   it: the iteration, or -1 for "every trace at its own";  x10: sampling work-groups per CU x 10 (pick_nsplit);
+//   sharing: trace groups that share the GPU with this step (sums_deep);  den: the density map, or nullptr for no DENSITY stops
+static void smc_step(pnr_ctx *c, const PhEnv &E, hipStream_t st, const PhState &P, int active, int it, int lp, int x10, int sharing,
+                     const unsigned char *den, const TraceOut &O, const StepTimers &tm)
+{
+    const int np = E.np, ni = E.ni;
+    const int nsplit = pick_nsplit(active, E.ncu, E.max_split, x10), share = share_scales(c, active);
+    bool chain = tm.chain_first;
+    auto tic = [&] { if (tm.on) c->tic(st, chain); chain = tm.chain_rest; };
+    auto toc = [&](const char *group) { if (tm.on) c->toc(group, 1, st, tm.weight); };
+    tic();
+    hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)E.h->d_s6.get(), E.V, np, ni, it, lp, PH_CS, ph_tbl(np));
+    toc("smc_predict");
+    if (P.cubes) {
+        tic();
+        hipLaunchKernelGGL(ph_cube, dim3((unsigned)(active * PH_CUBE_SPLIT)), dim3(PH_CUBE_THREADS), 0, st, E.V, P, lp, active);
+        toc("smc_cube");
+    }
+    tic();
+    launch_sample(st, E.V, E.T, E.X, P, np, ni, it, lp, active, nsplit, E.cube_bytes, share);
+    toc("smc");
+    tic();
+    launch_sums(st, E.T, E.X, P, np, E.np_pad, ni, it, lp, active, E.ng, sums_deep(c, active, sharing), share);
+    toc("smc_sums");
+    tic();
+    hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), E.upd_lds, st, E.V, E.T, P, np, E.np_pad, ni, it, lp, c->prm.Kc, c->prm.znccth,
+                       c->prm.neff_ratio, den, c->prm.nodepervol, O);
+    toc("smc_update");
+}
+
 // the sample stash for `traces` list positions (all trace groups together); grows only
 static int ensure_stash(pnr_ctx *c, pnr_phased *h, int64_t traces, long long trace_floats)
 {
@@ -1219,6 +1184,8 @@ static int ensure_stash(pnr_ctx *c, pnr_phased *h, int64_t traces, long long tra
     return PNR_OK;
 }
 
+// device state for up to `want` concurrent traces (fewer if their sample stash exceeds the budget: PNR_STASH_GB,
+// default 64 GB, or half of the free HBM) and everything the four kernels take as arguments
 // stash_want: list positions the stash must hold at once (<= 0: one per trace slot -- a one-shot batch starts all its traces together)
 static int phased_env(pnr_ctx *c, int64_t want, int dbg_iters, bool xfilt, bool idxres, bool neff, PhEnv &E, int64_t stash_want = 0)
 {
@@ -1239,12 +1206,9 @@ static int phased_env(pnr_ctx *c, int64_t want, int dbg_iters, bool xfilt, bool 
         PNR_HIP(h->h_cnt.alloc(pnr_phased::RING));
         for (int r = 0; r < pnr_phased::RING; r++) PNR_HIP(hipEventCreateWithFlags(&h->ev[r], hipEventDisableTiming));
         for (int g = 1; g < pnr_phased::MAXG; g++) PNR_HIP(hipStreamCreateWithFlags(&h->stg[g], hipStreamNonBlocking));
-        PNR_HIP(hipStreamCreateWithFlags(&h->st_den, hipStreamNonBlocking));
         PNR_HIP(hipEventCreateWithFlags(&h->ev_start, hipEventDisableTiming));
         for (hipEvent_t &e : h->ev_state) PNR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : h->ev_adm) PNR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         for (hipEvent_t &e : h->ev_ctl) PNR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : h->ev_den) PNR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     // stash rows of a trace hold at most np + 1 chains: full groups of 64 + the last group's stride (16 / 32 / 64)
     const int ngf = (np + 1) / 64, rem = (np + 1) - 64 * ngf, R = rem == 0 ? 0 : (rem > 32 ? 64 : (rem > 16 ? 32 : 16)), W = 64 * ngf + R;
@@ -1330,13 +1294,11 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
     const int64_t ntr_all = 2 * n;
     int rc = phased_env(c, ntr_all, dbg_iters, xfilt != nullptr, idxres != nullptr, neff != nullptr, E);
     if (rc) return rc;
-    const Vol &V = E.V; const Tab &T = E.T; const TabX &X = E.X; const PhState &P = E.P;
+    const PhState &P = E.P;
     pnr_phased *h = E.h;
-    const int np = E.np, ni = E.ni, np_pad = E.np_pad, ng = E.ng, ncu = E.ncu, max_split = E.max_split;
+    const int np = E.np, ni = E.ni;
     const int64_t NT = E.NT;
-    const size_t cube_bytes = E.cube_bytes, upd_lds = E.upd_lds;
     dbg_iters = E.dbg_iters;
-    constexpr int CS = PH_CS;
     hipStream_t st = c->stream;
 
     constexpr int LAG = 3, RING = pnr_phased::RING; // the host runs at most LAG iterations ahead of the active-trace counter
@@ -1376,26 +1338,7 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
                 active = h->h_cnt.get()[(it - LAG) % RING];
                 if (active <= 0) break;
             }
-            const int nsplit = pick_nsplit(active, ncu, max_split, c->opt.split_x10);
-            c->tic(st);
-            hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, T, X, P, (const float *)h->d_s6.get(), V, np, ni, it, it & 1, CS, ph_tbl(np));
-            c->toc("smc_predict", 1, st);
-            if (P.cubes) {
-                c->tic(st);
-                launch_cube(st, V, P, active, it & 1);
-                c->toc("smc_cube", 1, st);
-            }
-            const int share = share_scales(c, active);
-            c->tic(st);
-            launch_sample(st, V, T, X, P, np, ni, it, it & 1, active, nsplit, cube_bytes, share);
-            c->toc("smc", 1, st);
-            c->tic(st);
-            launch_sums(st, T, X, P, np, np_pad, ni, it, it & 1, active, ng, sums_deep(c, active, 1), share);
-            c->toc("smc_sums", 1, st);
-            c->tic(st);
-            hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), upd_lds, st, V, T, P, np, np_pad, ni, it, it & 1, c->prm.Kc, c->prm.znccth,
-                               c->prm.neff_ratio, use_density ? c->d_den.get() : nullptr, c->prm.nodepervol, O);
-            c->toc("smc_update", 1, st);
+            smc_step(c, E, st, P, active, it, it & 1, c->opt.split_x10, 1, use_density ? c->d_den.get() : nullptr, O, StepTimers{true, false, false, 1});
             PNR_HIP(hipMemcpyAsync(&h->h_cnt.get()[it % RING], P.cnt + ((it + 1) & 1), 4, hipMemcpyDeviceToHost, st));
             PNR_HIP(hipEventRecord(h->ev[it % RING], st));
         }
@@ -1435,7 +1378,7 @@ struct PhasedEngine final : pnr::StreamEngine {
     TraceOut O{};
     struct Grp {
         PhState P; hipStream_t st; int lp = 0;
-        int *h_snap, *h_flags, *h_cnt, *h_new, *d_new; float *h_new_s6, *d_new_s6;
+        int *h_snap, *h_flags, *h_cnt, *h_new; float *h_new_s6;
         // what this turn's control() / density_update() / admit() asked for: sent as one dispatch by flush()
         bool p_ctl = false; int p_np = 0, p_nr = 0, p_m = 0; size_t p_nt = 0;
         long long poll_no = 0;
@@ -1477,10 +1420,7 @@ struct PhasedEngine final : pnr::StreamEngine {
             PE_HIP(h->h_flags.alloc(((size_t)NT * FL_N + 2 * MG) * MG)); // per group: [2 MG counters | NT x FL_N flags]
             PE_HIP(h->h_new.alloc((size_t)NT * MG));
             PE_HIP(h->h_new_s6.alloc((size_t)NT * 6 * MG));
-            PE_HIP(h->d_new.alloc((size_t)NT * MG));
-            PE_HIP(h->d_new_s6.alloc((size_t)NT * 6 * MG));
             PE_HIP(h->h_ctl.alloc((size_t)NT * 2 * MG));
-            PE_HIP(h->d_ctl.alloc((size_t)NT * 2 * MG));
             h->stream_cap = NT;
             h->stream_ni = ni;
         }
@@ -1490,7 +1430,6 @@ struct PhasedEngine final : pnr::StreamEngine {
         PE_HIP(hipMemsetAsync(E.P.cnt, 0, 2 * 4 * pnr_phased::MAXG, c->stream));
         PE_HIP(hipEventRecord(h->ev_start, c->stream)); // everything queued so far (volume, density map) precedes the other streams
         for (int g = 1; g < pnr_phased::MAXG; g++) PE_HIP(hipStreamWaitEvent(h->stg[g], h->ev_start, 0));
-        PE_HIP(hipStreamWaitEvent(h->st_den, h->ev_start, 0));
         for (int g = 0; g < pnr_phased::MAXG; g++) {
             Grp &q = grp[g];
             q.P = E.P;
@@ -1501,8 +1440,8 @@ struct PhasedEngine final : pnr::StreamEngine {
             q.ev_state = h->ev_state[g];
             q.h_snap = h->h_flags.get() + (size_t)g * ((size_t)h->stream_cap * FL_N + 2 * pnr_phased::MAXG);
             q.h_flags = q.h_snap + 2 * pnr_phased::MAXG; q.h_cnt = q.h_snap + 2 * g;
-            q.h_new = h->h_new.get() + (size_t)g * h->stream_cap; q.d_new = h->d_new.get() + (size_t)g * h->stream_cap;
-            q.h_new_s6 = h->h_new_s6.get() + (size_t)g * h->stream_cap * 6; q.d_new_s6 = h->d_new_s6.get() + (size_t)g * h->stream_cap * 6;
+            q.h_new = h->h_new.get() + (size_t)g * h->stream_cap;
+            q.h_new_s6 = h->h_new_s6.get() + (size_t)g * h->stream_cap * 6;
         }
         return PNR_OK;
     }
@@ -1538,8 +1477,6 @@ struct PhasedEngine final : pnr::StreamEngine {
         { const int rc = flush(g, /*followed_by_steps*/ true); if (rc) return rc; }
         Grp &q = grp[g];
         hipStream_t st = q.st;
-        const PhState &P = q.P;
-        const int np = E.np, ni = E.ni, np_pad = E.np_pad, ng = E.ng;
         // does this launch share the GPU with another group's steps?  (With the scheduler's `concentrate` the other groups run out.)
         q.running = active;
         int sharing = 1;
@@ -1548,27 +1485,8 @@ struct PhasedEngine final : pnr::StreamEngine {
         const int pw = std::max(1, c->opt.profile_every);
         const bool prof = (q.poll_no++ % pw) == 0; // the kernel timers (pnr_set_profiling) look at every pw-th poll of the group
         for (int k = 0; k < poll; k++) { // `poll` SMC steps over the group's active list (every trace at its own iteration)
-            const int lp = q.lp;
-            const int nsplit = pick_nsplit(active, E.ncu, E.max_split, x10);
-            if (prof) c->tic(st, k > 0); // (the first step of a poll follows the admission copies: its own opening event)
-            hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)h->d_s6.get(), E.V, np, ni, -1, lp, PH_CS, ph_tbl(np));
-            if (prof) c->toc("smc_predict", 1, st, pw);
-            if (P.cubes) {
-                if (prof) c->tic(st, true);
-                launch_cube(st, E.V, P, active, lp);
-                if (prof) c->toc("smc_cube", 1, st, pw);
-            }
-            const int share = share_scales(c, active);
-            if (prof) c->tic(st, true);
-            launch_sample(st, E.V, E.T, E.X, P, np, ni, -1, lp, active, nsplit, E.cube_bytes, share);
-            if (prof) c->toc("smc", 1, st, pw);
-            if (prof) c->tic(st, true);
-            launch_sums(st, E.T, E.X, P, np, np_pad, ni, -1, lp, active, ng, sums_deep(c, active, sharing), share);
-            if (prof) c->toc("smc_sums", 1, st, pw);
-            if (prof) c->tic(st, true);
-            hipLaunchKernelGGL(ph_update, dim3(active), dim3(256), E.upd_lds, st, E.V, E.T, P, np, np_pad, ni, -1, lp, c->prm.Kc, c->prm.znccth,
-                               c->prm.neff_ratio, c->d_den.get(), c->prm.nodepervol, O);
-            if (prof) c->toc("smc_update", 1, st, pw);
+            // (the first step of a poll follows the admission dispatch: its own opening event; every later tic chains)
+            smc_step(c, E, st, q.P, active, -1, q.lp, x10, sharing, c->d_den.get(), O, StepTimers{prof, k > 0, true, pw});
             q.lp ^= 1;
             if (k == poll - 1 - lag) { // what wait() hands to the host: the state behind this step (the last `lag` steps run on meanwhile)
                 // one copy: the counters of all step lists and the flags of all slots (every copy is a dispatch of its own in the stream,
@@ -1609,11 +1527,10 @@ struct PhasedEngine final : pnr::StreamEngine {
     int control(int g, const int *pause, int np_, const int *resume, int nr) override
     {
         Grp &q = grp[g];
-        int *hc = h->h_ctl.get() + (size_t)g * 2 * h->stream_cap, *dc = h->d_ctl.get() + (size_t)g * 2 * h->stream_cap;
+        int *hc = h->h_ctl.get() + (size_t)g * 2 * h->stream_cap;
         PE_HIP(hipEventSynchronize(h->ev_ctl[g]));                  // pinned staging of this group: its previous lists have been consumed
         if (np_ > 0) std::memcpy(hc, pause, (size_t)np_ * 4);
         if (nr > 0) std::memcpy(hc + h->stream_cap, resume, (size_t)nr * 4);
-        (void)dc;
         q.p_ctl = true; q.p_np = np_; q.p_nr = nr;
         return PNR_OK;
     }
@@ -1652,14 +1569,11 @@ struct PhasedEngine final : pnr::StreamEngine {
         const size_t nt = r.touched.size();
         if (nt == 0) return PNR_OK;
         Grp &q = grp[g];
-        if (h->d_den_val[g].count() < nt) { // (allocated last: its capacity is that of the four)
+        if (h->h_den_val[g].count() < nt) { // (allocated last: its capacity is that of the pair)
             PE_HIP(hipStreamSynchronize(q.st)); // (its last scatter may still read the old staging)
-            h->d_den_val[g].reset();
             const size_t cap = std::max<size_t>(2 * nt, 1 << 16);
             PE_HIP(h->h_den_idx[g].alloc(cap));
             PE_HIP(h->h_den_val[g].alloc(cap));
-            PE_HIP(h->d_den_idx[g].alloc(cap));
-            PE_HIP(h->d_den_val[g].alloc(cap));
         }
         PE_HIP(hipEventSynchronize(h->ev_ctl[g])); // the previous update's cells have been read from the pinned staging (one event per ph_poll: flush())
         for (size_t i = 0; i < nt; i++) {
@@ -1673,7 +1587,6 @@ struct PhasedEngine final : pnr::StreamEngine {
     {
         if (!h) return;
         for (int g = 0; g < pnr_phased::MAXG; g++) (void)hipStreamSynchronize(g == 0 ? c->stream : h->stg[g]);
-        (void)hipStreamSynchronize(h->st_den);
     }
 #undef PE_HIP
 };
