@@ -351,6 +351,59 @@ typedef struct pnr_filter_opts {
 } pnr_filter_opts;
 int pnr_filter_volume(pnr_ctx *ctx, const pnr_filter_opts *opts);
 
+/* Tree distance: one SWC tree scored against another (beyond the reference, which has no evaluation code).  This follows the
+ * published definition of Vaa3D's "neuron distance" (SD, SSD, %SSD): resample both trees, take the distance of every point of one
+ * tree to the nearest line segment of the other, average in both directions, and report the share and the mean of the points
+ * further away than 2 voxels.  Vaa3D's own digits are not pinned (none of its code was at hand); the contract is THE RULE below,
+ * which the tests restate in numpy.  Every f32 operation is a single IEEE operation (-ffp-contract=off, correctly rounded division
+ * and square root); parentheses give the order.
+ *   Point to segment.  Point p, segment j = (a, b), all f32.  Per segment, computed once: ab = b - a;
+ *     den = (ab.x*ab.x + ab.y*ab.y) + ab.z*ab.z;  r = den > 0 ? 1.0f / den : 0.0f.  Per pair: ap = p - a;
+ *     num = (ap.x*ab.x + ap.y*ab.y) + ap.z*ab.z;  t = fminf(fmaxf(num * r, 0.f), 1.f);  e = p - (a + t*ab) componentwise (one
+ *     multiply, one add, one subtract);  d2 = (e.x*e.x + e.y*e.y) + e.z*e.z.  Per point: d = sqrtf(min over j of d2), j* = the
+ *     smallest j that attains the minimum.  A minimum does not depend on order: every tiling gives the same bits.  All inputs must
+ *     be finite (PNR_E_ARG otherwise); the rule is meant for voxel coordinates (|v| < 2^60: no intermediate overflows).
+ *   Tree.  n nodes xyz (f32) and parent[i] in [-1, n), any negative value = none: the layout of pnr_reconstruct's output, the caller
+ *     drops the dummy node.  First z *= zscale (one f32 multiply; zscale > 0, default 1; pass zdist for distances in xy voxels).
+ *     Segments: one per node, (x_i, x_parent[i]); a node without a parent gives (x_i, x_i): m = n, an isolated node still counts.
+ *     Sample points, in node order: the node itself, then, if it has a parent and step > 0, the interior points of its segment:
+ *     L = the f64 length sqrt((dx*dx + dy*dy) + dz*dz) of the segment, q = ceil(L / step), the points a + (b - a) * (k / q) for
+ *     k = 1..q-1 with a = x_i, b = x_parent[i], computed in f64 and rounded to f32.  step = 0: the nodes only.  Host code.
+ *   Metrics.  A direction X -> Y with the distances d_k of X's N points to Y's segments: mean = sum(d) / N; big = {k : d_k >= thr}
+ *     (an f32 compare; thr default 2); ssd = sum over big of d / |big|, 0 when big is empty; pct = |big| / N; max = max d.  The sums
+ *     are sequential f64 additions in point order, on the host.  Combined: sd, ssd, pct = the means (x + y) / 2 of the two
+ *     directions, hausdorff = the larger max.
+ * pnr_point_segment_distance: the GPU call of the first paragraph for n points against m segments (seg_a, seg_b: m x 3 each);
+ *   d_out[n], j_out[n] (nullable).  1 <= m, 0 <= n (n = 0 is a valid no-op), both at most PNR_DISTANCE_MAX_N.  It needs no volume
+ *   and leaves the pipeline state of the context alone; it runs on the context's stream (pnr_set_stream) in launches of a bounded
+ *   number of pairs and frees every device buffer before it returns (PNR_E_NOMEM: an allocation failed).  Kernel times:
+ *   pnr_get_kernel_ms group "distance".
+ * pnr_tree_sample: the sample points of a tree, host only, no context.  *n_out = their number; the first min(cap, *n_out) are written
+ *   to pts_out (x, y, z) and owner_out (the node of the point), either may be NULL: *n_out > cap: call again, as pnr_reconstruct.
+ * pnr_tree_distance: both directions (A's points to B's segments, then B's to A's) on ctx's GPU and the metrics.  opts = NULL =
+ *   {zscale 1, step 1, thr 2}.  dA_out / ownerA_out (nullable, capA entries) receive the distance and the node of A's first
+ *   min(capA, result->ab.n) sample points, likewise for B.  PNR_E_ARG: an empty tree (n < 1) on either side, zscale <= 0, step < 0,
+ *   a value that is not finite, a parent outside [-1, n), more than PNR_DISTANCE_MAX_N nodes or sample points on a side. */
+#define PNR_DISTANCE_MAX_N (1 << 22)
+typedef struct pnr_distance_opts {
+    float zscale, step, thr;
+} pnr_distance_opts; /* NULL = {1, 1, 2} */
+typedef struct pnr_distance_dir {
+    int64_t n, n_big; /* sample points of the source tree; those with d >= thr */
+    double mean, ssd, pct, max;
+} pnr_distance_dir;
+typedef struct pnr_distance_result {
+    pnr_distance_dir ab, ba; /* A's points against B's segments; B's points against A's */
+    double sd, ssd, pct, hausdorff;
+} pnr_distance_result;
+int pnr_point_segment_distance(pnr_ctx *ctx, const float *pts /* n x 3 */, int64_t n, const float *seg_a /* m x 3 */, const float *seg_b /* m x 3 */,
+                               int64_t m, float *d_out /* n */, int32_t *j_out /* n, nullable */);
+int pnr_tree_sample(const float *xyz /* n x 3 */, const int32_t *parent /* n */, int64_t n, float zscale, float step, float *pts_out, int32_t *owner_out,
+                    int64_t cap, int64_t *n_out);
+int pnr_tree_distance(pnr_ctx *ctx, const float *xyzA, const int32_t *parentA, int64_t nA, const float *xyzB, const int32_t *parentB, int64_t nB,
+                      const pnr_distance_opts *opts /* NULL = defaults */, pnr_distance_result *result, float *dA_out, int32_t *ownerA_out, int64_t capA,
+                      float *dB_out, int32_t *ownerB_out, int64_t capB);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -373,6 +426,8 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   share_scales (1) phased driver: a scale whose template grid nests in another's is not sampled, its sums read the host's stash (0: every scale samples on its
  *   own; the same bits) | share_min (0) ... in steps of at least this many traces |
  *   gauss_march (1) the fused x-y Gaussian marches down strips of a slice (0: one 64 x 64 tile per work-group; the same bits) |
+ *   dist_split (0 = automatic: enough slices to fill the chip) segments per blockIdx.y slice of a launch of pnr_point_segment_distance |
+ *   dist_pairs_per_launch (0 = automatic: 2^34) at most this many (point, segment) pairs per launch (the same bits -- tests reach slice and launch boundaries with them on small inputs) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
  *   pnr_get_option also knows "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
@@ -382,7 +437,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

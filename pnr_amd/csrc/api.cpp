@@ -10,6 +10,7 @@
 #include "volume.h"
 #include "radius.h"
 #include "filter.h"
+#include "distance.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -365,6 +366,112 @@ int pnr_measure_radii(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_
     PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_measure_radii: no volume set");
     PNR_HIP(hipSetDevice(c->device));
     return pnr_radius_run(c, xyz, n, o, k_out, thr_used);
+}
+
+// ---- tree distance (distance.hip): arguments first; neither a volume nor any pipeline state is needed or touched ----
+static bool all_finite(const float *v, int64_t count)
+{
+    for (int64_t i = 0; i < count; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int pnr_point_segment_distance(pnr_ctx *c, const float *pts, int64_t n, const float *seg_a, const float *seg_b, int64_t m, float *d_out, int32_t *j_out)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    PNR_REQUIRE(m >= 1 && m <= PNR_DISTANCE_MAX_N && seg_a && seg_b, PNR_E_ARG, "pnr_point_segment_distance: m = %lld segments (1 to 2^22) need seg_a and seg_b", (long long)m);
+    PNR_REQUIRE(n >= 0 && n <= PNR_DISTANCE_MAX_N && (n == 0 || (pts && d_out)), PNR_E_ARG, "pnr_point_segment_distance: n = %lld points (at most 2^22) need pts and d_out", (long long)n);
+    PNR_REQUIRE(all_finite(seg_a, 3 * m) && all_finite(seg_b, 3 * m) && all_finite(pts, 3 * n), PNR_E_ARG, "pnr_point_segment_distance: a coordinate is not finite");
+    if (n == 0) return PNR_OK;
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_distance_run(c, pts, n, seg_a, seg_b, m, d_out, j_out);
+}
+
+int pnr_tree_sample(const float *xyz, const int32_t *parent, int64_t n, float zscale, float step, float *pts_out, int32_t *owner_out, int64_t cap, int64_t *n_out)
+{
+    PNR_REQUIRE(n >= 0 && n <= PNR_DISTANCE_MAX_N && (n == 0 || (xyz && parent)) && n_out && cap >= 0, PNR_E_ARG, "pnr_tree_sample: n = %lld nodes (at most 2^22) need xyz, parent and n_out", (long long)n);
+    PNR_REQUIRE(std::isfinite(zscale) && zscale > 0.f, PNR_E_ARG, "pnr_tree_sample: zscale = %g must be positive", (double)zscale);
+    PNR_REQUIRE(std::isfinite(step) && step >= 0.f, PNR_E_ARG, "pnr_tree_sample: step = %g must not be negative", (double)step);
+    return pnr::tree_sample(xyz, parent, n, zscale, step, pts_out, owner_out, cap, n_out);
+}
+
+namespace {
+// one side of pnr_tree_distance: the sample points with their nodes, and the segments (a = the node, b = its parent or itself)
+struct TreeSide {
+    std::vector<float> pts, a, b, d;
+    std::vector<int32_t> owner;
+    int64_t np = 0, n = 0;
+};
+int tree_side(const char *which, const float *xyz, const int32_t *parent, int64_t n, const pnr_distance_opts &o, TreeSide &s)
+{
+    PNR_REQUIRE(n >= 1 && n <= PNR_DISTANCE_MAX_N && xyz && parent, PNR_E_ARG, "pnr_tree_distance: tree %s has %lld nodes (1 to 2^22)", which, (long long)n);
+    int rc = pnr::tree_sample(xyz, parent, n, o.zscale, o.step, nullptr, nullptr, 0, &s.np);
+    if (rc) return rc;
+    PNR_REQUIRE(s.np <= PNR_DISTANCE_MAX_N, PNR_E_ARG, "pnr_tree_distance: tree %s has %lld sample points (at most 2^22): raise the step", which, (long long)s.np);
+    s.n = n;
+    s.pts.resize((size_t)s.np * 3);
+    s.owner.resize((size_t)s.np);
+    s.d.resize((size_t)s.np);
+    if ((rc = pnr::tree_sample(xyz, parent, n, o.zscale, o.step, s.pts.data(), s.owner.data(), s.np, &s.np))) return rc;
+    s.a.resize((size_t)n * 3);
+    s.b.resize((size_t)n * 3);
+    for (int64_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) s.a[(size_t)(3 * i + k)] = k == 2 ? xyz[3 * i + 2] * o.zscale : xyz[3 * i + k];
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t q = parent[i] < 0 ? i : parent[i];
+        for (int k = 0; k < 3; k++) s.b[(size_t)(3 * i + k)] = s.a[(size_t)(3 * q + k)];
+    }
+    return PNR_OK;
+}
+// the metrics of one direction: sequential f64 sums in point order
+void direction_metrics(const std::vector<float> &d, float thr, pnr_distance_dir &r)
+{
+    double sum = 0, sum_big = 0;
+    float mx = 0.f;
+    int64_t big = 0;
+    for (float v : d) {
+        sum += (double)v;
+        if (v >= thr) sum_big += (double)v, big++;
+        mx = std::max(mx, v);
+    }
+    r.n = (int64_t)d.size();
+    r.n_big = big;
+    r.mean = sum / (double)r.n;
+    r.ssd = big ? sum_big / (double)big : 0.0;
+    r.pct = (double)big / (double)r.n;
+    r.max = (double)mx;
+}
+} // namespace
+
+int pnr_tree_distance(pnr_ctx *c, const float *xyzA, const int32_t *parentA, int64_t nA, const float *xyzB, const int32_t *parentB, int64_t nB,
+                      const pnr_distance_opts *opts, pnr_distance_result *result, float *dA_out, int32_t *ownerA_out, int64_t capA, float *dB_out,
+                      int32_t *ownerB_out, int64_t capB)
+{
+    PNR_REQUIRE(c && result, PNR_E_ARG, "null argument");
+    const pnr_distance_opts o = opts ? *opts : pnr_distance_opts{1.f, 1.f, 2.f};
+    PNR_REQUIRE(std::isfinite(o.zscale) && o.zscale > 0.f, PNR_E_ARG, "pnr_tree_distance: zscale = %g must be positive", (double)o.zscale);
+    PNR_REQUIRE(std::isfinite(o.step) && o.step >= 0.f, PNR_E_ARG, "pnr_tree_distance: step = %g must not be negative", (double)o.step);
+    PNR_REQUIRE(std::isfinite(o.thr), PNR_E_ARG, "pnr_tree_distance: thr is not finite");
+    PNR_REQUIRE(capA >= 0 && capB >= 0, PNR_E_ARG, "pnr_tree_distance: negative capacity");
+    TreeSide A, B;
+    int rc = tree_side("A", xyzA, parentA, nA, o, A);
+    if (!rc) rc = tree_side("B", xyzB, parentB, nB, o, B);
+    if (rc) return rc;
+    PNR_HIP(hipSetDevice(c->device));
+    if ((rc = pnr_distance_run(c, A.pts.data(), A.np, B.a.data(), B.b.data(), B.n, A.d.data(), nullptr))) return rc;
+    if ((rc = pnr_distance_run(c, B.pts.data(), B.np, A.a.data(), A.b.data(), A.n, B.d.data(), nullptr))) return rc;
+    direction_metrics(A.d, o.thr, result->ab);
+    direction_metrics(B.d, o.thr, result->ba);
+    result->sd = (result->ab.mean + result->ba.mean) / 2;
+    result->ssd = (result->ab.ssd + result->ba.ssd) / 2;
+    result->pct = (result->ab.pct + result->ba.pct) / 2;
+    result->hausdorff = std::max(result->ab.max, result->ba.max);
+    const size_t ka = (size_t)std::min(capA, A.np), kb = (size_t)std::min(capB, B.np);
+    if (dA_out) std::memcpy(dA_out, A.d.data(), 4 * ka);
+    if (ownerA_out) std::memcpy(ownerA_out, A.owner.data(), 4 * ka);
+    if (dB_out) std::memcpy(dB_out, B.d.data(), 4 * kb);
+    if (ownerB_out) std::memcpy(ownerB_out, B.owner.data(), 4 * kb);
+    return PNR_OK;
 }
 
 // test tap (pnr_hip_test.h): the shells of the rule, pure host
@@ -966,6 +1073,7 @@ const OptEntry OPTS[] = {
     {"overfill", &pnr::Options::overfill, nullptr, 0, 1},        {"concentrate", &pnr::Options::concentrate, nullptr, 0, 100},
     {"share_scales", &pnr::Options::share_scales, nullptr, 0, 1}, {"share_min", &pnr::Options::share_min, nullptr, 0, 1 << 20},
     {"hess_chunk", &pnr::Options::hess_chunk, nullptr, 0, 1 << 20},
+    {"dist_split", &pnr::Options::dist_split, nullptr, 0, 1 << 22}, {"dist_pairs_per_launch", nullptr, &pnr::Options::dist_pairs_per_launch, 0, 1ll << 44},
 };
 } // namespace
 

@@ -100,6 +100,9 @@ struct Options {
                                 // stash (tables.cpp find_scale_pairs; 0: every scale samples on its own -- the same results)
     int share_min = 0;          // ... in steps of at least this many traces (a guest's wave is not the longest of its trace, so small
                                 // steps lose nothing by it: 0, not tuned on a workload of its own)
+    int dist_split = 0;         // pnr_point_segment_distance: segments per blockIdx.y slice of a launch (0: automatic, distance.hip -- enough slices to fill the chip)
+    int64_t dist_pairs_per_launch = 0; // ... and at most this many (point, segment) pairs per launch (0: automatic, 2^34); neither changes a result:
+                                       // tests reach slice and launch boundaries with them on small inputs
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host

@@ -1,0 +1,18 @@
+// distance.h -- the bidirectional tree distance (distance.hip), behind pnr_point_segment_distance / pnr_tree_sample / pnr_tree_distance.
+#pragma once
+#include "ctx.h"
+
+namespace pnr {
+// The sample points of a tree by the rule of include/pnr_hip.h: z *= zscale (f32), then in node order the node itself and, for a
+// node with a parent and step > 0, the q - 1 interior points of its segment (f64, rounded to f32).  *n_out = the number of points;
+// the first min(cap, *n_out) of them are written to pts_out (x, y, z) and owner_out (the node), either may be NULL.  Pure host
+// code.  PNR_E_ARG: a parent outside [-1, n) (any negative value = none), a coordinate that is not finite, a segment of more than
+// 2^31 steps.
+int tree_sample(const float *xyz, const int32_t *parent, int64_t n, float zscale, float step, float *pts_out, int32_t *owner_out, int64_t cap,
+                int64_t *n_out);
+} // namespace pnr
+
+// d_out[i] = the distance of point i (pts: host, n x 3) to the nearest of the m segments (seg_a, seg_b: host, m x 3), j_out[i]
+// (nullable) = the smallest index of a segment at that distance; validated arguments, n >= 1.  Runs on c's stream; every device
+// buffer is freed before the call returns.
+int pnr_distance_run(pnr_ctx *c, const float *pts, int64_t n, const float *seg_a, const float *seg_b, int64_t m, float *d_out, int32_t *j_out);

@@ -16,6 +16,10 @@
 //   --median 2d|3d, --subtract-background R (1..64): the stack is pre-filtered on the GPU before it is traced (pnr_filter_volume: a 3 x 3
 //   median in every slice or a 3 x 3 x 3 one, then a top-hat with a flat box of half-width R); the comment block then has the line
 //   #filter=median:<2d|3d|off>,tophat:<R|off> behind #bits / #window and in front of #radius.  Any other value is a usage error.
+//   --swc-info FILE.swc: {"nodes","roots","segments","length","bbox"} of an SWC file as one JSON line (no GPU; the sibling of --info).
+//   --distance A.swc B.swc [--distance-step S] [--distance-threshold T] [--zscale Z] [--per-node PREFIX]: the tree distance of the two
+//   files (pnr_tree_distance on device -g, a context of pnr_default_params) as one JSON line; --per-node also writes PREFIX_ab.csv and
+//   PREFIX_ba.csv, one row `id,d` per sample point.  Any failure (an unreadable or malformed file, a bad value) exits non-zero.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -59,6 +63,16 @@ static bool parse_pair(const char *txt, int decimals, long long &a, long long &b
     return true;
 }
 
+// the whole of txt as a finite decimal number
+static bool parse_float(const char *txt, float &out)
+{
+    char *end = nullptr;
+    const double v = strtod(txt, &end);
+    if (!*txt || *end || !(v == v) || v > 3e38 || v < -3e38) return false;
+    out = (float)v;
+    return true;
+}
+
 // the whole of txt as a decimal integer in [lo, hi]
 static bool parse_int(const char *txt, long lo, long hi, long &out)
 {
@@ -78,6 +92,9 @@ int main(int argc, char **argv)
     std::string transport = "shm";
     bool info = false, window = false, saturate = false, help = false;
     bool radius_abs = false, radius_rel = false, radius_flag = false;
+    bool distance = false, dist_flag = false;
+    std::string swc_info, dist_a, dist_b, per_node;
+    pnr_distance_opts dist_opts = {1.f, 1.f, 2.f};
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--info")) { info = true; continue; }
@@ -112,6 +129,35 @@ int main(int argc, char **argv)
             continue;
         }
         if (!strcmp(argv[i], "--help")) { help = true; continue; }
+        if (!strcmp(argv[i], "--swc-info")) {
+            if (i + 1 >= argc) { fprintf(stderr, "--swc-info FILE.swc\n"); return 1; }
+            swc_info = argv[++i];
+            continue;
+        }
+        if (!strcmp(argv[i], "--distance")) {
+            if (i + 2 >= argc) { fprintf(stderr, "--distance A.swc B.swc\n"); return 1; }
+            dist_a = argv[++i];
+            dist_b = argv[++i];
+            distance = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--distance-step") || !strcmp(argv[i], "--distance-threshold") || !strcmp(argv[i], "--zscale")) {
+            const std::string flag = argv[i];
+            float v = 0;
+            if (!parse_float(i + 1 < argc ? argv[++i] : "", v) || v < 0 || (flag == "--zscale" && !(v > 0))) {
+                fprintf(stderr, "%s: a number, %s\n", flag.c_str(), flag == "--zscale" ? "above 0" : "0 or more");
+                return 1;
+            }
+            (flag == "--zscale" ? dist_opts.zscale : flag == "--distance-step" ? dist_opts.step : dist_opts.thr) = v;
+            dist_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--per-node")) {
+            if (i + 1 >= argc) { fprintf(stderr, "--per-node PREFIX\n"); return 1; }
+            per_node = argv[++i];
+            dist_flag = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--median")) {
             const std::string m = i + 1 < argc ? argv[++i] : "";
             if (m != "2d" && m != "3d") { fprintf(stderr, "--median 2d|3d: a 3 x 3 median in every slice, or a 3 x 3 x 3 one\n"); return 1; }
@@ -174,6 +220,9 @@ int main(int argc, char **argv)
         advantra::print_flags();
         return 0;
     }
+    if (dist_flag && !distance) { fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc\n"); return 1; }
+    if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (distance) return advantra::print_tree_distance(dist_a, dist_b, dist_opts, device, per_node) ? 0 : 1;
     if (info) {
         if (infiles.empty()) { fprintf(stderr, "--info needs -i <inimg_file>\n"); return 1; }
         return advantra::print_info(infiles[0], raw_dims, S0.channel - 1, S0.raw_u16) ? 0 : 1;

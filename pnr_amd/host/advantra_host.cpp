@@ -14,6 +14,7 @@
 #include <cstring>
 #include <fstream>
 #include <sstream>
+#include <unordered_map>
 
 namespace advantra {
 
@@ -51,6 +52,12 @@ void print_flags()
     printf("\nadvantra_cli [flags] -f advantra_func -i <inimg_file> -p <the 11 parameters>   (flags go before -p)\n");
     printf("-v | --timing | --save-midres | --single-tree | --rng-seed N | -g DEVICE | -d w,h,l (.raw) | --info\n");
     printf("--ranks N [--share-gpu] [--exchange shm|rccl]   one stack on N GPUs of this host\n");
+    printf("--swc-info FILE.swc       one JSON line about an SWC file: nodes, roots, segments, total length, bounding box (no GPU)\n");
+    printf("--distance A.swc B.swc    the tree distance of two SWC files on the GPU (SD, SSD, %%SSD per direction and combined) as one JSON line\n");
+    printf("  --distance-step S         resampling step of both trees (default 1; 0: the nodes only)\n");
+    printf("  --distance-threshold T    a point counts as far away from T on (default 2)\n");
+    printf("  --zscale Z                z is multiplied by Z first (default 1; the stack's zdist gives distances in xy voxels)\n");
+    printf("  --per-node PREFIX         also write PREFIX_ab.csv / PREFIX_ba.csv: `id,d` of every sample point of A / of B\n");
     printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
     printf("--median 2d|3d            pre-filter: 3 x 3 median in every slice, or 3 x 3 x 3 (on the GPU, before tracing; default: off)\n");
     printf("--subtract-background R   pre-filter: top-hat with a flat box of half-width R in xy and R / zdist in z, 1..%d (after the median)\n", PNR_TOPHAT_MAX_R);
@@ -307,6 +314,138 @@ bool print_info(const std::string &path, const std::string &raw_dims, int channe
     else scan(st.bytes());
     printf("{\"w\": %lld, \"h\": %lld, \"l\": %lld, \"bits\": %d, \"channels\": %d, \"channel\": %d, \"min\": %u, \"max\": %u, \"sum\": %llu}\n", st.w, st.h,
            st.l, st.bits, st.channels, channel + 1, mn, mx, sum);
+    return true;
+}
+
+bool load_swc(const std::string &path, SwcTree &out, std::string &err)
+{
+    std::ifstream f(path);
+    if (!f) {
+        err = path + ": cannot open the file";
+        return false;
+    }
+    out = SwcTree();
+    std::vector<long long> pid;
+    std::unordered_map<long long, int32_t> index;
+    std::string line;
+    for (long long ln = 1; std::getline(f, line); ln++) {
+        std::istringstream is(line);
+        std::vector<std::string> t;
+        for (std::string w; is >> w;) t.push_back(w);
+        if (t.empty() || t[0][0] == '#') continue;
+        auto bad = [&](const std::string &what) {
+            err = path + ":" + std::to_string(ln) + ": " + what;
+            return false;
+        };
+        if (t.size() < 7) return bad("not an SWC line `n type x y z r parent` (" + std::to_string(t.size()) + " fields)");
+        double v[7];
+        for (int k = 0; k < 7; k++) {
+            char *end = nullptr;
+            v[k] = strtod(t[(size_t)k].c_str(), &end);
+            if (*end || !std::isfinite(v[k])) return bad("field " + std::to_string(k + 1) + " `" + t[(size_t)k] + "` is not a number");
+        }
+        if (v[0] != std::floor(v[0]) || v[6] != std::floor(v[6]) || std::fabs(v[0]) > 9e15 || std::fabs(v[6]) > 9e15) return bad("the node id and the parent id must be whole numbers");
+        const long long id = (long long)v[0];
+        if (!index.emplace(id, (int32_t)out.id.size()).second) return bad("duplicate node id " + std::to_string(id));
+        out.id.push_back(id);
+        out.type.push_back((int32_t)v[1]);
+        for (int k = 2; k < 5; k++) out.xyz.push_back((float)v[k]);
+        out.radius.push_back((float)v[5]);
+        pid.push_back((long long)v[6]);
+    }
+    out.parent.resize(pid.size());
+    for (size_t i = 0; i < pid.size(); i++) {
+        const auto it = pid[i] < 0 ? index.end() : index.find(pid[i]);
+        out.parent[i] = it == index.end() ? -1 : it->second;
+    }
+    return true;
+}
+
+bool print_swc_info(const std::string &path)
+{
+    SwcTree t;
+    std::string err;
+    if (!load_swc(path, t, err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    long long roots = 0;
+    double length = 0;
+    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    for (long long i = 0; i < t.n(); i++) {
+        const float *p = &t.xyz[(size_t)(3 * i)];
+        for (int k = 0; k < 3; k++) lo[k] = std::min(lo[k], p[k]), hi[k] = std::max(hi[k], p[k]);
+        if (t.parent[(size_t)i] < 0) {
+            roots++;
+            continue;
+        }
+        const float *q = &t.xyz[(size_t)(3 * (long long)t.parent[(size_t)i])];
+        const double dx = (double)q[0] - p[0], dy = (double)q[1] - p[1], dz = (double)q[2] - p[2];
+        length += std::sqrt((dx * dx + dy * dy) + dz * dz);
+    }
+    printf("{\"nodes\": %lld, \"roots\": %lld, \"segments\": %lld, \"length\": %.17g, \"bbox\": ", t.n(), roots, t.n() - roots, length);
+    if (t.n()) printf("[%.9g, %.9g, %.9g, %.9g, %.9g, %.9g]}\n", lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
+    else printf("null}\n");
+    return true;
+}
+
+bool print_tree_distance(const std::string &a, const std::string &b, const pnr_distance_opts &opts, int device, const std::string &per_node)
+{
+    SwcTree A, B;
+    std::string err;
+    if (!load_swc(a, A, err) || !load_swc(b, B, err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    for (const auto &side : {std::make_pair(&a, &A), std::make_pair(&b, &B)})
+        if (side.second->n() == 0) {
+            fprintf(stderr, "%s: no nodes\n", side.first->c_str());
+            return false;
+        }
+    auto lib_fail = [](const char *what) {
+        fprintf(stderr, "%s: %s\n", what, pnr_last_error());
+        return false;
+    };
+    // the sample points of either side first: the sizes of the per-point arrays (and an empty or malformed tree before any GPU work)
+    int64_t na = 0, nb = 0;
+    if (pnr_tree_sample(A.xyz.data(), A.parent.data(), A.n(), opts.zscale, opts.step, nullptr, nullptr, 0, &na) != PNR_OK) return lib_fail(a.c_str());
+    if (pnr_tree_sample(B.xyz.data(), B.parent.data(), B.n(), opts.zscale, opts.step, nullptr, nullptr, 0, &nb) != PNR_OK) return lib_fail(b.c_str());
+    pnr_params p;
+    pnr_default_params(&p);
+    pnr_ctx *ctx = nullptr;
+    if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+    std::vector<float> da((size_t)na), db((size_t)nb);
+    std::vector<int32_t> oa((size_t)na), ob((size_t)nb);
+    pnr_distance_result r;
+    const int rc = pnr_tree_distance(ctx, A.xyz.data(), A.parent.data(), A.n(), B.xyz.data(), B.parent.data(), B.n(), &opts, &r, da.data(), oa.data(), na,
+                                     db.data(), ob.data(), nb);
+    pnr_destroy(ctx);
+    if (rc != PNR_OK) return lib_fail("pnr_tree_distance");
+    if (!per_node.empty()) {
+        const struct { const char *tag; const SwcTree &t; const std::vector<float> &d; const std::vector<int32_t> &o; } side[2] = {{"_ab.csv", A, da, oa}, {"_ba.csv", B, db, ob}};
+        for (const auto &s : side) {
+            const std::string name = per_node + s.tag;
+            FILE *f = fopen(name.c_str(), "w");
+            if (!f) {
+                fprintf(stderr, "%s: cannot write the file\n", name.c_str());
+                return false;
+            }
+            fprintf(f, "id,d\n");
+            for (size_t k = 0; k < s.d.size(); k++) fprintf(f, "%lld,%.9g\n", s.t.id[(size_t)s.o[k]], (double)s.d[k]);
+            if (fclose(f) != 0) {
+                fprintf(stderr, "%s: write failed\n", name.c_str());
+                return false;
+            }
+        }
+    }
+    auto dir = [](const char *k, const pnr_distance_dir &d) {
+        printf("\"%s\": {\"n\": %lld, \"n_big\": %lld, \"mean\": %.17g, \"ssd\": %.17g, \"pct\": %.17g, \"max\": %.17g}, ", k, (long long)d.n, (long long)d.n_big, d.mean,
+               d.ssd, d.pct, d.max);
+    };
+    printf("{\"zscale\": %.9g, \"step\": %.9g, \"thr\": %.9g, \"nodes_a\": %lld, \"nodes_b\": %lld, ", (double)opts.zscale, (double)opts.step, (double)opts.thr, A.n(), B.n());
+    dir("ab", r.ab);
+    dir("ba", r.ba);
+    printf("\"sd\": %.17g, \"ssd\": %.17g, \"pct\": %.17g, \"hausdorff\": %.17g}\n", r.sd, r.ssd, r.pct, r.hausdorff);
     return true;
 }
 

@@ -92,6 +92,24 @@ bool load_stack(const std::string &path, const std::string &raw_dims, Stack &out
 // advantra_cli --info: loads the stack and prints one JSON line {"w","h","l","bits","channels","channel","min","max","sum"} of the
 // kept channel (channel printed 1-based); no GPU is touched
 bool print_info(const std::string &path, const std::string &raw_dims, int channel, bool raw_u16);
+// An SWC file as the tree distance takes it: lines `n type x y z r parent`; `#` comments and blank lines are skipped; ids may be
+// written as 3.0 and come in any order; a parent id that is not in the file means "none" (as -1 does).  Numbers are read as
+// doubles and rounded to f32.  A duplicate id, a line of fewer than 7 fields or a field that is no number fails with
+// "<file>:<line>: ..." in err.  parent[i] = the index of the parent's node in file order, -1 = none.
+struct SwcTree {
+    std::vector<float> xyz, radius; // n x 3; n
+    std::vector<int32_t> parent, type;
+    std::vector<long long> id;
+    long long n() const { return (long long)id.size(); }
+};
+bool load_swc(const std::string &path, SwcTree &out, std::string &err);
+// advantra_cli --swc-info: one JSON line {"nodes", "roots", "segments", "length", "bbox": [x0, y0, z0, x1, y1, z1]} (segments = nodes
+// with a parent; length = the f64 sum of their lengths in file order; bbox null for an empty file); no GPU is touched
+bool print_swc_info(const std::string &path);
+// advantra_cli --distance A.swc B.swc: pnr_tree_distance of the two files on `device` (a context of pnr_default_params) as one JSON
+// line; per_node (not empty): <per_node>_ab.csv / _ba.csv with one row `id,d` per sample point of A / of B (id = the SWC id of the
+// point's node) under a header line
+bool print_tree_distance(const std::string &a, const std::string &b, const pnr_distance_opts &opts, int device, const std::string &per_node);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

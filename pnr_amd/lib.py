@@ -46,6 +46,29 @@ class FilterOpts(C.Structure):
 PNR_TOPHAT_MAX_R = 64
 
 
+class DistanceOpts(C.Structure):
+    """pnr_distance_opts (include/pnr_hip.h): zscale > 0 (z *= zscale first), step >= 0 (0: the nodes only), thr (the "big" distances)"""
+    _fields_ = [("zscale", C.c_float), ("step", C.c_float), ("thr", C.c_float)]
+
+
+class DistanceDir(C.Structure):
+    """pnr_distance_dir: one direction of the tree distance"""
+    _fields_ = [("n", C.c_int64), ("n_big", C.c_int64), ("mean", C.c_double), ("ssd", C.c_double), ("pct", C.c_double), ("max", C.c_double)]
+
+
+class DistanceResult(C.Structure):
+    """pnr_distance_result: ab = A's points against B's segments, ba = the reverse, and the combined metrics"""
+    _fields_ = [("ab", DistanceDir), ("ba", DistanceDir), ("sd", C.c_double), ("ssd", C.c_double), ("pct", C.c_double), ("hausdorff", C.c_double)]
+
+    def as_dict(self):
+        d = {k: {f: getattr(getattr(self, k), f) for f, _ in DistanceDir._fields_} for k in ("ab", "ba")}
+        d.update(sd=self.sd, ssd=self.ssd, pct=self.pct, hausdorff=self.hausdorff)
+        return d
+
+
+PNR_DISTANCE_MAX_N = 1 << 22
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -112,6 +135,9 @@ def load():
     L.pnr_get_volume.argtypes = [vp, vp]
     L.pnr_measure_radii.argtypes = [vp, vp, i64, C.POINTER(RadiusOpts), vp, C.POINTER(C.c_int32)]
     L.pnr_filter_volume.argtypes = [vp, C.POINTER(FilterOpts)]
+    L.pnr_point_segment_distance.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
+    L.pnr_tree_sample.argtypes = [vp, vp, i64, C.c_float, C.c_float, vp, vp, i64, C.POINTER(i64)]
+    L.pnr_tree_distance.argtypes = [vp, vp, vp, i64, vp, vp, i64, C.POINTER(DistanceOpts), C.POINTER(DistanceResult), vp, vp, i64, vp, vp, i64]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.pnr_live_bytes.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -174,7 +200,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -310,6 +336,40 @@ class Context:
         t = C.c_int32()
         check(self.L.pnr_measure_radii(self.h, xyz.ctypes.data, len(xyz), C.byref(o), k.ctypes.data, C.byref(t)))
         return k, t.value
+
+    def point_segment_distance(self, pts, a, b):
+        """pnr_point_segment_distance: n x 3 points against the m segments (a[j], b[j]) -> (d float32[n], j int32[n]): the distance to
+        the nearest segment and the smallest index of a segment at that distance"""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+        if len(a) != len(b):
+            raise PnrError("point_segment_distance: a and b differ in length")
+        d = np.empty(len(pts), np.float32)
+        j = np.empty(len(pts), np.int32)
+        check(self.L.pnr_point_segment_distance(self.h, pts.ctypes.data, len(pts), a.ctypes.data, b.ctypes.data, len(a), d.ctypes.data, j.ctypes.data))
+        return d, j
+
+    def tree_distance(self, xyzA, parentA, xyzB, parentB, zscale=1, step=1, thr=2, per_point=False):
+        """pnr_tree_distance of two trees (n x 3 positions, parent indices with a negative value for none; drop the dummy node of a
+        reconstruct() result first) -> the result as a dict {"ab", "ba": {n, n_big, mean, ssd, pct, max}, sd, ssd, pct, hausdorff};
+        per_point: -> (dict, (dA, ownerA), (dB, ownerB)) with the distance and the node of every sample point of A and of B"""
+        xa = np.ascontiguousarray(xyzA, np.float32).reshape(-1, 3)
+        xb = np.ascontiguousarray(xyzB, np.float32).reshape(-1, 3)
+        pa = np.ascontiguousarray(parentA, np.int32).reshape(-1)
+        pb = np.ascontiguousarray(parentB, np.int32).reshape(-1)
+        if len(pa) != len(xa) or len(pb) != len(xb):
+            raise PnrError("tree_distance: one parent per node")
+        o = DistanceOpts(float(zscale), float(step), float(thr))
+        r = DistanceResult()
+        out = [None] * 4
+        if per_point:
+            na, nb = (tree_sample(x, p, zscale, step, count_only=True) for x, p in ((xa, pa), (xb, pb)))
+            out = [np.empty(na, np.float32), np.empty(na, np.int32), np.empty(nb, np.float32), np.empty(nb, np.int32)]
+        ptr = [v.ctypes.data if v is not None else None for v in out]
+        check(self.L.pnr_tree_distance(self.h, xa.ctypes.data, pa.ctypes.data, len(xa), xb.ctypes.data, pb.ctypes.data, len(xb), C.byref(o), C.byref(r),
+                                       ptr[0], ptr[1], len(out[0]) if per_point else 0, ptr[2], ptr[3], len(out[2]) if per_point else 0))
+        return (r.as_dict(), (out[0], out[1]), (out[2], out[3])) if per_point else r.as_dict()
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
@@ -703,6 +763,52 @@ def reconstruct(nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, ep
         if n.value <= cap:
             return out[:n.value].copy(), par[:n.value].copy()
         cap = int(n.value)
+
+
+def tree_sample(xyz, parent, zscale=1, step=1, count_only=False):
+    """pnr_tree_sample (pure host; no GPU needed): the sample points of a tree by the rule of the tree distance -> (pts float32[k, 3],
+    owner int32[k]), or only k"""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    if len(parent) != len(xyz):
+        raise PnrError("tree_sample: one parent per node")
+    n = C.c_int64()
+    check(L.pnr_tree_sample(xyz.ctypes.data, parent.ctypes.data, len(xyz), float(zscale), float(step), None, None, 0, C.byref(n)))
+    if count_only:
+        return n.value
+    pts = np.empty((n.value, 3), np.float32)
+    owner = np.empty(n.value, np.int32)
+    check(L.pnr_tree_sample(xyz.ctypes.data, parent.ctypes.data, len(xyz), float(zscale), float(step), pts.ctypes.data, owner.ctypes.data, n.value, C.byref(n)))
+    return pts, owner
+
+
+def read_swc(path):
+    """an SWC file as advantra_cli --distance reads it -> (xyz float32[n, 3], parent int32[n] (index of the parent's line among the
+    nodes, -1: none or not in the file), ids int64[n]).  Lines `n type x y z r parent`; `#` comments and blank lines are skipped; ids
+    may be written as 3.0 and come in any order; a duplicate id or a short line is an error that names the file and the line."""
+    ids, xyz, par, index = [], [], [], {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            try:
+                if len(t) < 7:
+                    raise ValueError
+                v = [float(x) for x in t[:7]]
+                if not all(np.isfinite(v)) or v[0] != int(v[0]) or v[6] != int(v[6]):
+                    raise ValueError
+            except (ValueError, OverflowError):
+                raise PnrError(f"{path}:{ln}: not an SWC line `n type x y z r parent`") from None
+            if int(v[0]) in index:
+                raise PnrError(f"{path}:{ln}: duplicate node id {int(v[0])}")
+            index[int(v[0])] = len(ids)
+            ids.append(int(v[0]))
+            xyz.append(v[2:5])
+            par.append(int(v[6]))
+    parent = np.array([index.get(p, -1) if p >= 0 else -1 for p in par], np.int32).reshape(-1)
+    return np.array(xyz, np.float64).reshape(-1, 3).astype(np.float32), parent, np.array(ids, np.int64).reshape(-1)
 
 
 def live_bytes():
