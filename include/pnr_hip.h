@@ -404,6 +404,60 @@ int pnr_tree_distance(pnr_ctx *ctx, const float *xyzA, const int32_t *parentA, i
                       const pnr_distance_opts *opts /* NULL = defaults */, pnr_distance_result *result, float *dA_out, int32_t *ownerA_out, int64_t capA,
                       float *dB_out, int32_t *ownerB_out, int64_t capB);
 
+/* Joining the traced forest into one tree (beyond the reference, whose only tool against a forest is ENFORCE_SINGLE_TREE: every tree
+ * but the largest is thrown away).  This is the step between a tracer and morphometry, a simulator or a tree comparison that Vaa3D
+ * calls sort_neuron_swc: fragments whose closest nodes lie within a gap are bridged, the result is re-rooted and put in tree order.
+ * Vaa3D's own digits are not pinned; the contract is THE RULE below, which the tests restate in numpy.  Every f32 operation is a
+ * single IEEE operation (-ffp-contract=off); parentheses give the order.
+ *   Input.  n nodes xyz (f32) and parent[i] in [-1, n), any negative value = none: the layout of pnr_reconstruct's output with the
+ *     dummy node dropped, and of pnr_tree_distance.  Options {zscale, gap, root}.  First z *= zscale (one f32 multiply; zscale > 0,
+ *     default 1).  The input trees are the connected components of the parent links.  PNR_E_ARG: a parent chain that does not end
+ *     within n steps (a cycle), a coordinate that is not finite, a parent >= n.  Meant for voxel coordinates (|v| < 2^60).
+ *   Pair weight.  For nodes i != j of DIFFERENT input trees: dx = x_i - x_j, likewise dy, dz; d2 = (dx*dx + dy*dy) + dz*dz, which is
+ *     bit-symmetric in (i, j) because negation is exact.  The key of the pair is the triple (bits(d2), min(i, j), max(i, j)), compared
+ *     lexicographically: d2 >= +0, so its bit pattern orders like its value, and no two pairs share a key.
+ *   Bridges.  g2 = gap * gap (one f32 multiply); gap == 0: no limit.  The bridges are the edges of the UNIQUE minimum spanning forest
+ *     of the graph whose vertices are the input trees and whose edges are all pairs with d2 <= g2, under that key order: what Kruskal's
+ *     algorithm over the ascending pairs gives, and what Boruvka's rounds give in any order -- the result does not depend on tiling,
+ *     slices, launches or round structure.  They are reported in ascending key order as (lo, hi, d = sqrtf(d2)).
+ *   Re-rooting.  The output components are the components of {parent links} + {bridges}; each is a tree.  Its root is `root` if
+ *     root >= 0 and the component holds that node, else the input root of the input tree with the most nodes in the component (ties:
+ *     the smallest root index).  parent_out is the unique orientation of the component's edges away from that root; node order and
+ *     xyz are not changed.
+ *   Numbering and order.  comp_out[i]: the component of `root` first (if given), then the others by descending node count, ties by
+ *     ascending root index.  order_out is a permutation of 0..n-1: the components in that numbering, each in depth-first pre-order
+ *     from its root with the children visited in ascending node index -- a file written in order_out has every parent before its
+ *     children.
+ * pnr_nearest_other: the GPU call of the rule's inner search on coordinates as they are (no zscale).  For every point i with
+ *   label[i] >= 0: d_out[i] = sqrtf of the minimum of d2 over the points j with label[j] >= 0 and label[j] != label[i], j_out[i] = the
+ *   smallest j at the minimum; without such a point, and for a point with a negative label (neither source nor target), +inf and -1.
+ *   1 <= n <= PNR_JOIN_MAX_N; all coordinates finite.  It needs no volume and leaves the pipeline state alone; it runs on the
+ *   context's stream in launches of a bounded pair count and frees every device buffer before it returns (PNR_E_NOMEM: an allocation
+ *   failed).  Kernel times: pnr_get_kernel_ms group "join".
+ * pnr_join_trees: Boruvka's rounds on ctx's GPU -- labels = the current components, one nearest-other pass per round, the per-component
+ *   minimum under the full key and the union-find on the host; a component whose best edge exceeds g2 can never be joined and leaves
+ *   the search -- then the re-rooting.  opts = NULL = {1, 0, -1}; gap < 0 (or not finite), zscale <= 0 and root >= n are PNR_E_ARG.
+ *   parent_out, order_out, comp_out (n entries each) and bridges_out (cap_bridges entries) are nullable; *n_bridges > cap_bridges: call
+ *   again, as pnr_reconstruct.  n_trees_in / n_trees_out (nullable): input trees, output components.  pnr_get_option "join_rounds":
+ *   the passes the last call took.
+ * pnr_join_reroot: the re-rooting and ordering half alone, pure host, no context: the same code pnr_join_trees ends in.  PNR_E_ARG
+ *   also for a bridge outside [0, n) or between two nodes of one (already joined) tree. */
+#define PNR_JOIN_MAX_N (1 << 22)
+typedef struct pnr_join_opts {
+    float zscale, gap;
+    int32_t root; /* a node index, or negative: none */
+} pnr_join_opts; /* NULL = {1, 0, -1} */
+typedef struct pnr_bridge {
+    int32_t lo, hi;
+    float d;
+} pnr_bridge;
+int pnr_nearest_other(pnr_ctx *ctx, const float *xyz /* n x 3 */, const int32_t *label /* n */, int64_t n, float *d_out /* n */, int32_t *j_out /* n */);
+int pnr_join_trees(pnr_ctx *ctx, const float *xyz /* n x 3 */, const int32_t *parent /* n */, int64_t n, const pnr_join_opts *opts /* NULL = defaults */,
+                   int32_t *parent_out, int32_t *order_out, int32_t *comp_out, pnr_bridge *bridges_out, int64_t cap_bridges, int64_t *n_bridges,
+                   int64_t *n_trees_in, int64_t *n_trees_out);
+int pnr_join_reroot(const int32_t *parent /* n */, int64_t n, const pnr_bridge *bridges, int64_t nb, int64_t root, int32_t *parent_out, int32_t *order_out,
+                    int32_t *comp_out);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -428,16 +482,17 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   gauss_march (1) the fused x-y Gaussian marches down strips of a slice (0: one 64 x 64 tile per work-group; the same bits) |
  *   dist_split (0 = automatic: enough slices to fill the chip) segments per blockIdx.y slice of a launch of pnr_point_segment_distance |
  *   dist_pairs_per_launch (0 = automatic: 2^34) at most this many (point, segment) pairs per launch (the same bits -- tests reach slice and launch boundaries with them on small inputs) |
+ *   join_split (0 = automatic), join_pairs_per_launch (0 = automatic: 2^34): the same for the targets and the (point, target) pairs of pnr_nearest_other / pnr_join_trees (the same bits) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
- *   pnr_get_option also knows "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
+ *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
  *   re-run Frangi without the frangi_prune shortcut -- one pnr_frangi worth of GPU time each; also printed with trace_timing /
  *   seed_timing).  The kernel timers (pnr_get_kernel_ms) include those re-runs. */
 int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

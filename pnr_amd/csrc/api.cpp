@@ -11,6 +11,7 @@
 #include "radius.h"
 #include "filter.h"
 #include "distance.h"
+#include "join.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -471,6 +472,55 @@ int pnr_tree_distance(pnr_ctx *c, const float *xyzA, const int32_t *parentA, int
     if (ownerA_out) std::memcpy(ownerA_out, A.owner.data(), 4 * ka);
     if (dB_out) std::memcpy(dB_out, B.d.data(), 4 * kb);
     if (ownerB_out) std::memcpy(ownerB_out, B.owner.data(), 4 * kb);
+    return PNR_OK;
+}
+
+// ---- joining the forest (join.hip): arguments first; neither a volume nor any pipeline state is needed or touched ----
+int pnr_nearest_other(pnr_ctx *c, const float *xyz, const int32_t *label, int64_t n, float *d_out, int32_t *j_out)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    PNR_REQUIRE(n >= 1 && n <= PNR_JOIN_MAX_N && xyz && label && d_out && j_out, PNR_E_ARG, "pnr_nearest_other: n = %lld points (1 to 2^22) need xyz, label, d_out and j_out", (long long)n);
+    PNR_REQUIRE(all_finite(xyz, 3 * n), PNR_E_ARG, "pnr_nearest_other: a coordinate is not finite");
+    PNR_HIP(hipSetDevice(c->device));
+    pnr::JoinSearch search;
+    const int rc = search.begin(c, xyz, n, "pnr_nearest_other");
+    return rc ? rc : search.run(label, true, d_out, j_out, "pnr_nearest_other");
+}
+
+int pnr_join_reroot(const int32_t *parent, int64_t n, const pnr_bridge *bridges, int64_t nb, int64_t root, int32_t *parent_out, int32_t *order_out, int32_t *comp_out)
+{
+    PNR_REQUIRE(n >= 1 && n <= PNR_JOIN_MAX_N && parent, PNR_E_ARG, "pnr_join_reroot: n = %lld nodes (1 to 2^22) need parent", (long long)n);
+    PNR_REQUIRE(nb >= 0 && nb < n && (nb == 0 || bridges), PNR_E_ARG, "pnr_join_reroot: %lld bridges (0 to n - 1) need bridges", (long long)nb);
+    return pnr::join_reroot(parent, n, bridges, nb, root, parent_out, order_out, comp_out, nullptr);
+}
+
+int pnr_join_trees(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t n, const pnr_join_opts *opts, int32_t *parent_out, int32_t *order_out,
+                   int32_t *comp_out, pnr_bridge *bridges_out, int64_t cap_bridges, int64_t *n_bridges, int64_t *n_trees_in, int64_t *n_trees_out)
+{
+    PNR_REQUIRE(c && n_bridges, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(n >= 1 && n <= PNR_JOIN_MAX_N && xyz && parent, PNR_E_ARG, "pnr_join_trees: n = %lld nodes (1 to 2^22) need xyz and parent", (long long)n);
+    const pnr_join_opts o = opts ? *opts : pnr_join_opts{1.f, 0.f, -1};
+    PNR_REQUIRE(std::isfinite(o.zscale) && o.zscale > 0.f, PNR_E_ARG, "pnr_join_trees: zscale = %g must be positive", (double)o.zscale);
+    PNR_REQUIRE(std::isfinite(o.gap) && o.gap >= 0.f, PNR_E_ARG, "pnr_join_trees: gap = %g must not be negative", (double)o.gap);
+    PNR_REQUIRE(o.root < n, PNR_E_ARG, "pnr_join_trees: root = %d outside [-1, %lld)", o.root, (long long)n);
+    PNR_REQUIRE(cap_bridges >= 0 && (cap_bridges == 0 || bridges_out), PNR_E_ARG, "pnr_join_trees: cap_bridges = %lld needs bridges_out", (long long)cap_bridges);
+    std::vector<float> scaled(xyz, xyz + 3 * n);
+    for (int64_t i = 0; i < n; i++) {
+        float *p = &scaled[(size_t)(3 * i)];
+        p[2] = p[2] * o.zscale;
+        PNR_REQUIRE(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(xyz[3 * i + 2]) && std::isfinite(p[2]), PNR_E_ARG,
+                    "pnr_join_trees: node %lld has a coordinate that is not finite", (long long)i);
+    }
+    PNR_HIP(hipSetDevice(c->device));
+    std::vector<pnr_bridge> bridges;
+    int64_t trees_in = 0, trees_out = 0;
+    int rc = pnr::join_bridges(c, scaled.data(), parent, n, o.gap, bridges, &trees_in, &c->join_rounds);
+    if (rc) return rc;
+    if ((rc = pnr::join_reroot(parent, n, bridges.data(), (int64_t)bridges.size(), o.root, parent_out, order_out, comp_out, &trees_out))) return rc;
+    *n_bridges = (int64_t)bridges.size();
+    if (bridges_out) std::memcpy(bridges_out, bridges.data(), sizeof(pnr_bridge) * (size_t)std::min<int64_t>(cap_bridges, *n_bridges));
+    if (n_trees_in) *n_trees_in = trees_in;
+    if (n_trees_out) *n_trees_out = trees_out;
     return PNR_OK;
 }
 
@@ -1074,6 +1124,7 @@ const OptEntry OPTS[] = {
     {"share_scales", &pnr::Options::share_scales, nullptr, 0, 1}, {"share_min", &pnr::Options::share_min, nullptr, 0, 1 << 20},
     {"hess_chunk", &pnr::Options::hess_chunk, nullptr, 0, 1 << 20},
     {"dist_split", &pnr::Options::dist_split, nullptr, 0, 1 << 22}, {"dist_pairs_per_launch", nullptr, &pnr::Options::dist_pairs_per_launch, 0, 1ll << 44},
+    {"join_split", &pnr::Options::join_split, nullptr, 0, 1 << 22}, {"join_pairs_per_launch", nullptr, &pnr::Options::join_pairs_per_launch, 0, 1ll << 44},
 };
 } // namespace
 
@@ -1100,6 +1151,7 @@ int pnr_get_option(pnr_ctx *c, const char *key, int64_t *value)
     PNR_REQUIRE(c && key && value, PNR_E_ARG, "null argument");
     if (std::strcmp(key, "recon_timing") == 0) { *value = advantra::recon_timing() ? 1 : 0; return PNR_OK; }
     if (std::strcmp(key, "host_threads_effective") == 0) { *value = pnr::host_threads(c->opt); return PNR_OK; }
+    if (std::strcmp(key, "join_rounds") == 0) { *value = c->join_rounds; return PNR_OK; }
     if (std::strcmp(key, "frangi_recomputes") == 0) { *value = c->frangi_recomputes; return PNR_OK; } // exact Frangi re-runs so far (one pnr_frangi of GPU time each)
     for (const OptEntry &e : OPTS)
         if (std::strcmp(e.key, key) == 0) {

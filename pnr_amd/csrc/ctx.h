@@ -103,6 +103,8 @@ struct Options {
     int dist_split = 0;         // pnr_point_segment_distance: segments per blockIdx.y slice of a launch (0: automatic, distance.hip -- enough slices to fill the chip)
     int64_t dist_pairs_per_launch = 0; // ... and at most this many (point, segment) pairs per launch (0: automatic, 2^34); neither changes a result:
                                        // tests reach slice and launch boundaries with them on small inputs
+    int join_split = 0;         // pnr_nearest_other / pnr_join_trees: targets per blockIdx.y slice of a launch (0: automatic, join.hip), and
+    int64_t join_pairs_per_launch = 0; // at most this many (point, target) pairs per launch (0: automatic, 2^34): the counterparts of dist_*; the same bits
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host
@@ -187,6 +189,7 @@ struct pnr_ctx {
     std::vector<int32_t> graph_links;
     int graph_traces = 0;
     bool have_graph = false;
+    int64_t join_rounds = 0; // nearest-other passes of the last pnr_join_trees (pnr_get_option "join_rounds")
     std::vector<int32_t> graph_log; // 5 ints per replayed trace (option "trace_log")
 
     // profiling: HIP event pairs recorded on the ctx stream around each kernel group, resolved

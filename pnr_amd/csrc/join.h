@@ -1,0 +1,30 @@
+// join.h -- the traced forest joined into one tree (join.hip), behind pnr_nearest_other / pnr_join_trees / pnr_join_reroot.
+#pragma once
+#include "ctx.h"
+
+namespace pnr {
+// The nearest-other search of one call: the device buffers (one DevBuf, freed with the object) and the packed points.  begin() once,
+// then run() per set of labels: every point i with label[i] >= 0 gets the minimum of d2 over the points j with label[j] >= 0 and
+// label[j] != label[i], and the smallest j at that minimum (j = -1 and +inf without one, and for a negative label).  xyz is taken
+// as it is (the caller has applied zscale).  root: d_out = sqrtf(d2), else d2 itself.  Runs on c's stream and returns synchronised.
+class JoinSearch {
+    pnr_ctx *c_ = nullptr;
+    int64_t n_ = 0;
+    DevBuf<char> buf_;
+    size_t o_key_ = 0, o_xyz_ = 0, o_lab_ = 0, o_d_ = 0, o_j_ = 0;
+
+public:
+    int begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who);
+    int run(const int32_t *label, bool root, float *d_out, int32_t *j_out, const char *who);
+};
+
+// parent[i] in [-1, n) (any negative value = none) without a cycle, or PNR_E_ARG; comp_out[i] (nullable) = the smallest node index of
+// i's input tree -- a label >= 0 per tree
+int join_input_trees(const int32_t *parent, int64_t n, int32_t *comp_out, const char *who);
+// the re-rooting and ordering half of the rule (include/pnr_hip.h); pure host.  n_trees_out is nullable.
+int join_reroot(const int32_t *parent, int64_t n, const pnr_bridge *bridges, int64_t nb, int64_t root, int32_t *parent_out, int32_t *order_out,
+                int32_t *comp_out, int64_t *n_trees_out);
+// Boruvka rounds on c's GPU: the bridges in ascending key order; rounds = the nearest-other passes it took
+int join_bridges(pnr_ctx *c, const float *xyz_scaled, const int32_t *parent, int64_t n, float gap, std::vector<pnr_bridge> &bridges, int64_t *n_trees_in,
+                 int64_t *rounds);
+} // namespace pnr

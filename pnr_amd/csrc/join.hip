@@ -1,0 +1,327 @@
+// join.hip -- all-pairs nearest point of ANOTHER tree behind pnr_nearest_other / pnr_join_trees, and the host half of the join.  The rule
+// (include/pnr_hip.h): per pair dx = x_i - x_j (likewise y, z), d2 = (dx*dx + dy*dy) + dz*dz -- bit-symmetric in (i, j), negation is
+// exact --; per point the minimum of d2 over the points of a different, non-negative label and the smallest j at that minimum.  Every
+// operation is one IEEE f32 operation (the build has -ffp-contract=off).
+//
+// join_prep packs a point as one float4 (x, y, z, the bits of its label).  join_min is dist_min's form (distance.hip): one thread
+// holds its point and label in registers; the target index of its loop is the same in every lane, so a target arrives through ONE
+// scalar 16-byte load per wave and the vector unit only does the dozen operations of the pair -- no vector load, no LDS, nothing per
+// lane inside the loop.  blockIdx.y cuts the targets into slices, so that a few thousand points still fill the chip; every thread ends
+// with ONE 64-bit atomicMin on (bits(d2) << 32) | j -- d2 >= +0 orders like its bits, the low word makes the smallest j win a tie.  The
+// result therefore does not depend on the slices or on how the (points x targets) square is cut into launches of a bounded pair count.
+// join_finish unpacks.  Below the kernels: the host side -- input trees, Boruvka's rounds over the passes, re-rooting and ordering.
+#include "join.h"
+#include <cmath>
+#include <cstring>
+#include <numeric>
+
+namespace {
+
+constexpr int JTPB = 256;                   // threads of a work-group = points of a block row
+constexpr int MIN_SPLIT = 64;               // automatic slices hold at least this many targets: one atomic per 64 pairs at the most
+constexpr int TARGET_BLOCKS = 2048;         // automatic slices: work-groups of a launch that fill 256 CUs eight deep
+constexpr long long AUTO_PAIRS = 1ll << 34; // pairs per launch
+
+__global__ __launch_bounds__(JTPB) void join_prep(const float *__restrict__ xyz, const int *__restrict__ label, int n, float4 *__restrict__ tgt)
+{
+    const int i = blockIdx.x * JTPB + threadIdx.x;
+    if (i >= n) return;
+    tgt[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float(label[i]));
+}
+
+// points [p0, p1) x targets [s0, s1); blockIdx.y = the slice of `split` targets
+__global__ __launch_bounds__(JTPB) void join_min(const float4 *__restrict__ tgt, int p0, int p1, int s0, int s1, int split, unsigned long long *__restrict__ key)
+{
+    const int i = p0 + blockIdx.x * JTPB + threadIdx.x;
+    const int j0 = s0 + blockIdx.y * split, j1 = min(j0 + split, s1);
+    const float4 P = tgt[min(i, p1 - 1)]; // (the lanes past the last point run along on it and write nothing)
+    const int li = __float_as_int(P.w);
+    float best = INFINITY;
+    int bj = -1;
+#pragma unroll 4
+    for (int j = j0; j < j1; j++) { // j is wave-uniform: a scalar load
+        const float4 T = tgt[j];
+        const int lj = __float_as_int(T.w);
+        const float dx = P.x - T.x, dy = P.y - T.y, dz = P.z - T.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (lj >= 0 && lj != li && d2 < best) best = d2, bj = j; // (ascending j: the first of equals stays)
+    }
+    if (i < p1 && li >= 0) atomicMin(&key[i], (unsigned long long)__float_as_uint(best) << 32 | (unsigned)bj);
+}
+
+// root: d = sqrtf(d2), else d2; a point without a partner (its key untouched, or its minimum still +inf): +inf and j = -1
+__global__ __launch_bounds__(JTPB) void join_finish(const unsigned long long *__restrict__ key, int n, int root, float *__restrict__ d, int *__restrict__ j)
+{
+    const int i = blockIdx.x * JTPB + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = key[i];
+    const int bj = (int)(unsigned)k;
+    const float d2 = __uint_as_float((unsigned)(k >> 32));
+    d[i] = bj < 0 ? INFINITY : root ? sqrtf(d2) : d2;
+    j[i] = bj;
+}
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+} // namespace
+
+namespace pnr {
+
+int JoinSearch::begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who)
+{
+    c_ = c;
+    n_ = n;
+    // device buffers of the call: the packed points | the packed minima | xyz | the labels | d | j
+    o_key_ = pad16((size_t)n * 16);
+    o_xyz_ = o_key_ + pad16((size_t)n * 8);
+    o_lab_ = o_xyz_ + pad16((size_t)n * 12);
+    o_d_ = o_lab_ + pad16((size_t)n * 4);
+    o_j_ = o_d_ + pad16((size_t)n * 4);
+    const size_t bytes = o_j_ + pad16((size_t)n * 4);
+    if (buf_.alloc(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: device allocation of %zu B failed", who, bytes);
+        return PNR_E_NOMEM;
+    }
+    const hipError_t e = hipMemcpyAsync(buf_.get() + o_xyz_, xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        set_error("%s: %s", who, hipGetErrorString(e));
+        return PNR_E_HIP;
+    }
+    return PNR_OK;
+}
+
+int JoinSearch::run(const int32_t *label, bool root, float *d_out, int32_t *j_out, const char *who)
+{
+    pnr_ctx *const c = c_;
+    hipStream_t st = c->stream;
+    const long long n = n_;
+    char *const d_buf = buf_.get();
+    float4 *const d_tgt = (float4 *)d_buf;
+    unsigned long long *const d_key = (unsigned long long *)(d_buf + o_key_);
+    auto fail = [&](hipError_t e) {
+        (void)hipStreamSynchronize(st);
+        set_error("%s: %s", who, hipGetErrorString(e));
+        return PNR_E_HIP;
+    };
+    hipError_t e;
+    if ((e = hipMemcpyAsync(d_buf + o_lab_, label, (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return fail(e);
+    // the (points x targets) square in launches of at most `budget` pairs (whole block rows; at least one row by one target)
+    const long long budget = c->opt.join_pairs_per_launch > 0 ? c->opt.join_pairs_per_launch : AUTO_PAIRS;
+    const long long rows_fit = budget / n / JTPB * JTPB;
+    const long long rows = std::min<long long>(std::max<long long>(rows_fit, JTPB), (n + JTPB - 1) / JTPB * JTPB);
+    const long long tgts = rows_fit >= JTPB ? n : std::max<long long>(1, budget / JTPB);
+    int launches = 2;
+    c->tic();
+    hipLaunchKernelGGL(join_prep, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const float *)(d_buf + o_xyz_), (const int *)(d_buf + o_lab_), (int)n, d_tgt);
+    e = hipGetLastError();
+    for (long long p0 = 0; p0 < n && e == hipSuccess; p0 += rows)
+        for (long long s0 = 0; s0 < n && e == hipSuccess; s0 += tgts) {
+            const long long p1 = std::min<long long>(p0 + rows, n), s1 = std::min<long long>(s0 + tgts, n), ms = s1 - s0;
+            const long long bx = (p1 - p0 + JTPB - 1) / JTPB;
+            long long split = c->opt.join_split;
+            if (split <= 0) { // enough slices to fill the chip, of at least MIN_SPLIT targets
+                const long long slices = std::max<long long>(1, std::min<long long>((TARGET_BLOCKS + bx - 1) / bx, ms / MIN_SPLIT));
+                split = (ms + slices - 1) / slices;
+            }
+            split = std::max<long long>(split, (ms + 65534) / 65535); // (gridDim.y)
+            const long long by = (ms + split - 1) / split;
+            hipLaunchKernelGGL(join_min, dim3((unsigned)bx, (unsigned)by), dim3(JTPB), 0, st, (const float4 *)d_tgt, (int)p0, (int)p1, (int)s0, (int)s1, (int)split, d_key);
+            e = hipGetLastError();
+            launches++;
+        }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(join_finish, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const unsigned long long *)d_key, (int)n, root ? 1 : 0,
+                           (float *)(d_buf + o_d_), (int *)(d_buf + o_j_));
+        e = hipGetLastError();
+    }
+    c->toc("join", launches);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_buf + o_d_, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(j_out, d_buf + o_j_, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(e);
+    return PNR_OK;
+}
+
+// ---- the host side ----
+namespace {
+struct UnionFind {
+    std::vector<int32_t> up;
+    explicit UnionFind(int64_t n) : up((size_t)n) { std::iota(up.begin(), up.end(), 0); }
+    int32_t find(int32_t a)
+    {
+        while (up[(size_t)a] != a) a = up[(size_t)a] = up[(size_t)up[(size_t)a]];
+        return a;
+    }
+    bool unite(int32_t a, int32_t b) // the smaller index stays the representative
+    {
+        a = find(a), b = find(b);
+        if (a == b) return false;
+        if (a > b) std::swap(a, b);
+        up[(size_t)b] = a;
+        return true;
+    }
+};
+// the parent links as a union-find; a link inside one set closes a cycle (every node has at most one link of its own)
+int link_trees(const int32_t *parent, int64_t n, UnionFind &uf, const char *who)
+{
+    for (int64_t i = 0; i < n; i++) {
+        PNR_REQUIRE(parent[i] < n, PNR_E_ARG, "%s: parent[%lld] = %d outside [-1, %lld)", who, (long long)i, parent[i], (long long)n);
+        if (parent[i] < 0) continue;
+        PNR_REQUIRE(uf.unite((int32_t)i, parent[i]), PNR_E_ARG, "%s: the parent chain of node %lld does not end (a cycle)", who, (long long)i);
+    }
+    return PNR_OK;
+}
+struct Key { // (bits(d2), lo, hi), compared lexicographically
+    uint32_t bits;
+    int32_t lo, hi;
+    bool operator<(const Key &o) const { return bits != o.bits ? bits < o.bits : lo != o.lo ? lo < o.lo : hi < o.hi; }
+    bool operator==(const Key &o) const { return bits == o.bits && lo == o.lo && hi == o.hi; }
+};
+} // namespace
+
+int join_input_trees(const int32_t *parent, int64_t n, int32_t *comp_out, const char *who)
+{
+    UnionFind uf(n);
+    const int rc = link_trees(parent, n, uf, who);
+    if (rc) return rc;
+    if (comp_out)
+        for (int64_t i = 0; i < n; i++) comp_out[i] = uf.find((int32_t)i);
+    return PNR_OK;
+}
+
+int join_bridges(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t n, float gap, std::vector<pnr_bridge> &bridges, int64_t *n_trees_in, int64_t *rounds)
+{
+    static const char *who = "pnr_join_trees";
+    UnionFind uf(n);
+    int rc = link_trees(parent, n, uf, who);
+    if (rc) return rc;
+    int64_t live = 0;
+    for (int64_t i = 0; i < n; i++) live += parent[i] < 0;
+    *n_trees_in = live;
+    *rounds = 0;
+    bridges.clear();
+    if (live < 2) return PNR_OK;
+    const float g2 = gap * gap;
+    JoinSearch search;
+    if ((rc = search.begin(c, xyz, n, who))) return rc;
+    std::vector<int32_t> label((size_t)n), jj((size_t)n);
+    std::vector<float> d2((size_t)n);
+    std::vector<char> dead((size_t)n, 0); // per representative: its best edge exceeds the gap -- it can never be joined
+    std::vector<Key> best((size_t)n), edges, all;
+    while (live >= 2) {
+        for (int64_t i = 0; i < n; i++) {
+            const int32_t r = uf.find((int32_t)i);
+            label[(size_t)i] = dead[(size_t)r] ? -1 : r;
+        }
+        if ((rc = search.run(label.data(), false, d2.data(), jj.data(), who))) return rc;
+        ++*rounds;
+        // per component the smallest key: for a fixed i the smallest j is the smallest key, so the per-node result suffices
+        for (int64_t i = 0; i < n; i++)
+            if (label[(size_t)i] == (int32_t)i) best[(size_t)i].lo = -1;
+        for (int64_t i = 0; i < n; i++) {
+            const int32_t j = jj[(size_t)i], r = label[(size_t)i];
+            if (j < 0 || r < 0) continue;
+            uint32_t bits;
+            std::memcpy(&bits, &d2[(size_t)i], 4);
+            const Key k{bits, std::min((int32_t)i, j), std::max((int32_t)i, j)};
+            Key &b = best[(size_t)r];
+            if (b.lo < 0 || k < b) b = k;
+        }
+        edges.clear();
+        for (int64_t r = 0; r < n; r++) {
+            if (label[(size_t)r] != (int32_t)r || best[(size_t)r].lo < 0) continue;
+            float v;
+            std::memcpy(&v, &best[(size_t)r].bits, 4);
+            if (gap > 0.f && !(v <= g2)) dead[(size_t)r] = 1, live--;
+            else edges.push_back(best[(size_t)r]);
+        }
+        if (edges.empty()) break;
+        std::sort(edges.begin(), edges.end());
+        edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+        for (const Key &k : edges)
+            if (uf.unite(k.lo, k.hi)) all.push_back(k), live--;
+    }
+    std::sort(all.begin(), all.end());
+    for (const Key &k : all) {
+        float v;
+        std::memcpy(&v, &k.bits, 4);
+        bridges.push_back(pnr_bridge{k.lo, k.hi, std::sqrt(v)});
+    }
+    return PNR_OK;
+}
+
+int join_reroot(const int32_t *parent, int64_t n, const pnr_bridge *bridges, int64_t nb, int64_t root, int32_t *parent_out, int32_t *order_out, int32_t *comp_out,
+                int64_t *n_trees_out)
+{
+    static const char *who = "pnr_join_reroot";
+    UnionFind uf(n);
+    const int rc = link_trees(parent, n, uf, who);
+    if (rc) return rc;
+    PNR_REQUIRE(root < n, PNR_E_ARG, "%s: root = %lld outside [-1, %lld)", who, (long long)root, (long long)n);
+    // the input trees: node count and root per representative
+    std::vector<int32_t> in_rep((size_t)n), in_size((size_t)n, 0);
+    for (int64_t i = 0; i < n; i++) in_size[(size_t)(in_rep[(size_t)i] = uf.find((int32_t)i))]++;
+    for (int64_t k = 0; k < nb; k++) {
+        const pnr_bridge &b = bridges[k];
+        PNR_REQUIRE(b.lo >= 0 && b.lo < n && b.hi >= 0 && b.hi < n, PNR_E_ARG, "%s: bridge %lld = (%d, %d) outside [0, %lld)", who, (long long)k, b.lo, b.hi, (long long)n);
+        PNR_REQUIRE(uf.unite(b.lo, b.hi), PNR_E_ARG, "%s: bridge %lld = (%d, %d) joins two nodes of one tree", who, (long long)k, b.lo, b.hi);
+    }
+    // neighbours of every node in ascending order (CSR)
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    auto each_edge = [&](auto &&f) {
+        for (int64_t i = 0; i < n; i++)
+            if (parent[i] >= 0) f((int32_t)i, parent[i]);
+        for (int64_t k = 0; k < nb; k++) f(bridges[k].lo, bridges[k].hi);
+    };
+    each_edge([&](int32_t a, int32_t b) { off[(size_t)a + 1]++, off[(size_t)b + 1]++; });
+    for (int64_t i = 0; i < n; i++) off[(size_t)i + 1] += off[(size_t)i];
+    std::vector<int32_t> nbr((size_t)off[(size_t)n]);
+    std::vector<int64_t> fill(off.begin(), off.end() - 1);
+    each_edge([&](int32_t a, int32_t b) { nbr[(size_t)fill[(size_t)a]++] = b, nbr[(size_t)fill[(size_t)b]++] = a; });
+    for (int64_t i = 0; i < n; i++) std::sort(nbr.begin() + off[(size_t)i], nbr.begin() + off[(size_t)i + 1]);
+    // per output component: its size and its root -- `root` where given, else the input root of its largest input tree (ties: the smallest root)
+    std::vector<int32_t> size((size_t)n, 0), top((size_t)n, -1);
+    for (int64_t i = 0; i < n; i++) size[(size_t)uf.find((int32_t)i)]++;
+    for (int64_t i = 0; i < n; i++) { // input roots in ascending order: only a strictly larger tree replaces an earlier one
+        if (parent[i] >= 0) continue;
+        int32_t &t = top[(size_t)uf.find((int32_t)i)];
+        if (t < 0 || in_size[(size_t)in_rep[(size_t)i]] > in_size[(size_t)in_rep[(size_t)t]]) t = (int32_t)i;
+    }
+    const int32_t root_comp = root >= 0 ? uf.find((int32_t)root) : -1;
+    if (root >= 0) top[(size_t)root_comp] = (int32_t)root;
+    std::vector<int32_t> comps;
+    for (int64_t i = 0; i < n; i++)
+        if (uf.find((int32_t)i) == (int32_t)i) comps.push_back((int32_t)i);
+    std::sort(comps.begin(), comps.end(), [&](int32_t a, int32_t b) {
+        if ((a == root_comp) != (b == root_comp)) return a == root_comp;
+        if (size[(size_t)a] != size[(size_t)b]) return size[(size_t)a] > size[(size_t)b];
+        return top[(size_t)a] < top[(size_t)b];
+    });
+    if (n_trees_out) *n_trees_out = (int64_t)comps.size();
+    // depth-first pre-order from every root, children in ascending index
+    std::vector<int32_t> par((size_t)n, -1), stack;
+    int64_t pos = 0;
+    for (size_t ci = 0; ci < comps.size(); ci++) {
+        stack.assign(1, top[(size_t)comps[ci]]);
+        while (!stack.empty()) {
+            const int32_t v = stack.back();
+            stack.pop_back();
+            if (order_out) order_out[pos] = v;
+            if (comp_out) comp_out[v] = (int32_t)ci;
+            pos++;
+            for (int64_t k = off[(size_t)v + 1]; k-- > off[(size_t)v];) {
+                const int32_t u = nbr[(size_t)k];
+                if (u == par[(size_t)v]) continue;
+                par[(size_t)u] = v;
+                stack.push_back(u);
+            }
+        }
+    }
+    if (parent_out) std::memcpy(parent_out, par.data(), (size_t)n * 4);
+    return PNR_OK;
+}
+
+} // namespace pnr

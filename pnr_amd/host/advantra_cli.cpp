@@ -20,6 +20,11 @@
 //   --distance A.swc B.swc [--distance-step S] [--distance-threshold T] [--zscale Z] [--per-node PREFIX]: the tree distance of the two
 //   files (pnr_tree_distance on device -g, a context of pnr_default_params) as one JSON line; --per-node also writes PREFIX_ab.csv and
 //   PREFIX_ba.csv, one row `id,d` per sample point.  Any failure (an unreadable or malformed file, a bad value) exits non-zero.
+//   --join GAP [--join-root soma|ID] [--join-keep-largest]: while tracing, the reconstructed forest is joined into one tree on the GPU
+//   (pnr_join_trees with zscale = zdist; GAP in xy voxels, 0 = any distance), re-rooted (default: at the first soma node, if any; ID = a
+//   node id of the file without --join) and written in tree order; the comment block gains #join=gap:G,bridges:K,trees:T0->T1.
+//   --join-swc IN.swc OUT.swc [--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]: the same on a file (device -g); one JSON
+//   line {"nodes","trees_in","trees_out","bridges","longest_bridge","rounds"}.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -95,6 +100,11 @@ int main(int argc, char **argv)
     bool distance = false, dist_flag = false;
     std::string swc_info, dist_a, dist_b, per_node;
     pnr_distance_opts dist_opts = {1.f, 1.f, 2.f};
+    // --join and its companions are parsed into locals: they reach the tracing Settings only where the run traces (not under --join-swc)
+    bool zscale_flag = false, join_flag = false, join_root_soma = false, join_given = false, join_keep_largest = false;
+    float join_gap = 0.f;
+    long join_root_id = 0;
+    std::string join_in, join_out;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--info")) { info = true; continue; }
@@ -149,7 +159,30 @@ int main(int argc, char **argv)
                 return 1;
             }
             (flag == "--zscale" ? dist_opts.zscale : flag == "--distance-step" ? dist_opts.step : dist_opts.thr) = v;
-            dist_flag = true;
+            (flag == "--zscale" ? zscale_flag : dist_flag) = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--join")) {
+            float v = 0;
+            if (!parse_float(i + 1 < argc ? argv[++i] : "", v) || v < 0) { fprintf(stderr, "--join GAP: the largest bridge in xy voxels, a number, 0 (any distance) or more\n"); return 1; }
+            join_given = true;
+            join_gap = v;
+            continue;
+        }
+        if (!strcmp(argv[i], "--join-root")) {
+            const char *txt = i + 1 < argc ? argv[++i] : "";
+            long v = 0;
+            join_root_soma = !strcmp(txt, "soma");
+            if (!join_root_soma && !parse_int(txt, 1, PNR_JOIN_MAX_N, v)) { fprintf(stderr, "--join-root soma|ID: `soma` or a node id from 1\n"); return 1; }
+            join_root_id = v;
+            join_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--join-keep-largest")) { join_keep_largest = join_flag = true; continue; }
+        if (!strcmp(argv[i], "--join-swc")) {
+            if (i + 2 >= argc || argv[i + 1][0] == '-' || argv[i + 2][0] == '-') { fprintf(stderr, "--join-swc IN.swc OUT.swc\n"); return 1; }
+            join_in = argv[++i];
+            join_out = argv[++i];
             continue;
         }
         if (!strcmp(argv[i], "--per-node")) {
@@ -220,8 +253,12 @@ int main(int argc, char **argv)
         advantra::print_flags();
         return 0;
     }
-    if (dist_flag && !distance) { fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc\n"); return 1; }
+    if ((dist_flag && !distance) || (zscale_flag && !distance && join_in.empty())) { fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc)\n"); return 1; }
+    if (join_flag && !join_given && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP or --join-swc IN.swc OUT.swc\n"); return 1; }
+    if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (!join_in.empty()) return advantra::join_swc_file(join_in, join_out, join_gap, dist_opts.zscale, join_root_id, join_keep_largest, device) ? 0 : 1;
+    if (join_given) S0.join = true, S0.join_gap = join_gap, S0.join_root_id = join_root_id, S0.join_keep_largest = join_keep_largest;
     if (distance) return advantra::print_tree_distance(dist_a, dist_b, dist_opts, device, per_node) ? 0 : 1;
     if (info) {
         if (infiles.empty()) { fprintf(stderr, "--info needs -i <inimg_file>\n"); return 1; }

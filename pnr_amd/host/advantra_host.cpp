@@ -58,6 +58,11 @@ void print_flags()
     printf("  --distance-threshold T    a point counts as far away from T on (default 2)\n");
     printf("  --zscale Z                z is multiplied by Z first (default 1; the stack's zdist gives distances in xy voxels)\n");
     printf("  --per-node PREFIX         also write PREFIX_ab.csv / PREFIX_ba.csv: `id,d` of every sample point of A / of B\n");
+    printf("--join GAP                join the traced forest into one tree on the GPU: fragments whose closest nodes lie within GAP xy voxels\n");
+    printf("                          (0: any distance) are bridged, the tree is re-rooted and written with every parent before its children\n");
+    printf("  --join-root soma|ID       the root: the first soma node if there is one (default), or the node with this id in the file without --join\n");
+    printf("  --join-keep-largest       write only the largest component (the root's, if a root is given)\n");
+    printf("--join-swc IN.swc OUT.swc the same on an SWC file ([--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]); one JSON line\n");
     printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
     printf("--median 2d|3d            pre-filter: 3 x 3 median in every slice, or 3 x 3 x 3 (on the GPU, before tracing; default: off)\n");
     printf("--subtract-background R   pre-filter: top-hat with a flat box of half-width R in xy and R / zdist in z, 1..%d (after the median)\n", PNR_TOPHAT_MAX_R);
@@ -449,6 +454,79 @@ bool print_tree_distance(const std::string &a, const std::string &b, const pnr_d
     return true;
 }
 
+// the shortest decimal text without an exponent (nine digits at the most) that reads back as the same f32
+static std::string f32_text(float v)
+{
+    char buf[40];
+    for (int prec = 1; prec <= 9; prec++) {
+        snprintf(buf, sizeof buf, "%.*g", prec, (double)v);
+        if ((float)strtod(buf, nullptr) == v && !strchr(buf, 'e')) break;
+    }
+    return buf;
+}
+
+bool join_swc_file(const std::string &in, const std::string &out, float gap, float zscale, long long root_id, bool keep_largest, int device)
+{
+    SwcTree T;
+    std::string err;
+    if (!load_swc(in, T, err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    const int64_t n = T.n();
+    if (n == 0) {
+        fprintf(stderr, "%s: no nodes\n", in.c_str());
+        return false;
+    }
+    int64_t root = -1;
+    if (root_id > 0) {
+        const auto it = std::find(T.id.begin(), T.id.end(), root_id);
+        if (it == T.id.end()) {
+            fprintf(stderr, "--join-root %lld: %s has no node with this id\n", root_id, in.c_str());
+            return false;
+        }
+        root = it - T.id.begin();
+    }
+    auto lib_fail = [](const char *what) {
+        fprintf(stderr, "%s: %s\n", what, pnr_last_error());
+        return false;
+    };
+    pnr_params p;
+    pnr_default_params(&p);
+    pnr_ctx *ctx = nullptr;
+    if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+    const pnr_join_opts jo = {zscale, gap, (int32_t)root};
+    std::vector<int32_t> par_out((size_t)n), order((size_t)n), comp((size_t)n);
+    std::vector<pnr_bridge> bridges((size_t)n);
+    int64_t nb = 0, t_in = 0, t_out = 0, rounds = 0;
+    const int rc = pnr_join_trees(ctx, T.xyz.data(), T.parent.data(), n, &jo, par_out.data(), order.data(), comp.data(), bridges.data(), n, &nb, &t_in, &t_out);
+    pnr_get_option(ctx, "join_rounds", &rounds);
+    pnr_destroy(ctx);
+    if (rc != PNR_OK) return lib_fail("pnr_join_trees");
+    FILE *f = fopen(out.c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "%s: cannot write the file\n", out.c_str());
+        return false;
+    }
+    fprintf(f, "#join=gap:%s,bridges:%lld,trees:%lld->%lld\n##n,type,x,y,z,radius,parent\n", f32_text(gap).c_str(), (long long)nb, (long long)t_in, (long long)t_out);
+    std::vector<int64_t> pos((size_t)n, -1);
+    int64_t written = 0;
+    for (int64_t k = 0; k < n; k++) {
+        const size_t v = (size_t)order[(size_t)k];
+        if (keep_largest && comp[v] != 0) break;
+        pos[v] = ++written;
+        fprintf(f, "%lld %d %s %s %s %s %lld\n", (long long)written, T.type[v], f32_text(T.xyz[3 * v]).c_str(), f32_text(T.xyz[3 * v + 1]).c_str(),
+                f32_text(T.xyz[3 * v + 2]).c_str(), f32_text(T.radius[v]).c_str(), par_out[v] < 0 ? -1LL : (long long)pos[(size_t)par_out[v]]);
+    }
+    if (fclose(f) != 0) {
+        fprintf(stderr, "%s: write failed\n", out.c_str());
+        return false;
+    }
+    printf("{\"nodes\": %lld, \"trees_in\": %lld, \"trees_out\": %lld, \"bridges\": %lld, \"longest_bridge\": %.9g, \"rounds\": %lld}\n", (long long)written,
+           (long long)t_in, (long long)t_out, (long long)nb, nb ? (double)bridges[(size_t)nb - 1].d : 0.0, (long long)rounds);
+    return true;
+}
+
 Stack::~Stack()
 {
     if (view) munmap((void *)view, map_len);
@@ -568,7 +646,9 @@ int parse_params(const std::vector<std::string> &paras, pnr_params &p, std::stri
 
 // window: the (lo, hi) a 16-bit stack was windowed with (nullptr: 8-bit input); radius_thr: the threshold the radii were measured
 // with (nullptr: not measured; 0: the relative mode)
-static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p, const int32_t *window, const int32_t *radius_thr = nullptr)
+// join: the result of a --join run (nullptr: not joined)
+static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p, const int32_t *window, const int32_t *radius_thr = nullptr,
+                               const Result *join = nullptr)
 {
     static const char *keys[] = {"neuritesigmas", "somaradius", "tolerance", "znccth", "kappa", "step", "ni", "np", "zdist", "nodepervol", "vol"};
     std::stringstream c;
@@ -584,6 +664,7 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         if (fo.tophat_r) c << fo.tophat_r;
         else c << "off";
     }
+    if (join) c << "\n#join=gap:" << f32_text(settings().join_gap) <<",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->" << join->join_trees_out;
     if (radius_thr) {
         const pnr_radius_opts &ro = settings().radius;
         c << "\n#radius=measured,thr=";
@@ -896,6 +977,58 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
         R.tree.resize((size_t)nt);
         R.parent.resize((size_t)nt);
     }
+    if (settings().join && R.tree.size() > 1) { // --join: the forest becomes one tree (pnr_join_trees), the tree list is rewritten in tree order
+        const auto tj = clk::now();
+        const Settings &S = settings();
+        const int64_t n = (int64_t)R.tree.size() - 1; // without the dummy
+        std::vector<float> xyz((size_t)(3 * n));
+        std::vector<int32_t> par((size_t)n), par_out((size_t)n), order((size_t)n), comp((size_t)n);
+        int64_t root = -1;
+        for (int64_t i = 0; i < n; i++) {
+            const pnr_node &nd = R.tree[(size_t)i + 1];
+            xyz[(size_t)(3 * i)] = nd.x, xyz[(size_t)(3 * i + 1)] = nd.y, xyz[(size_t)(3 * i + 2)] = nd.z;
+            par[(size_t)i] = R.parent[(size_t)i + 1] > 0 ? R.parent[(size_t)i + 1] - 1 : -1;
+            if (S.join_root_id == 0 && root < 0 && nd.type == 1) root = i; // the first soma node
+        }
+        if (S.join_root_id > 0) root = S.join_root_id - 1;
+        if (root >= n) {
+            fprintf(stderr, "--join-root %lld: the tree has %lld nodes\n", S.join_root_id, (long long)n);
+            pnr_destroy(ctx);
+            return false;
+        }
+        const pnr_join_opts jo = {p.zdist, S.join_gap, (int32_t)root};
+        int64_t nb = 0, t_in = 0, t_out = 0;
+        if (S.timing) pnr_set_profiling(ctx, 1);
+        if (pnr_join_trees(ctx, xyz.data(), par.data(), n, &jo, par_out.data(), order.data(), comp.data(), nullptr, 0, &nb, &t_in, &t_out) != PNR_OK) {
+            fprintf(stderr, "%s\n", pnr_last_error());
+            pnr_destroy(ctx);
+            return false;
+        }
+        R.join_bridges = nb, R.join_trees_in = t_in, R.join_trees_out = t_out;
+        std::vector<int32_t> pos((size_t)n, -1); // node -> its line; component 0 comes first in the order
+        std::vector<pnr_node> tree(1, R.tree[0]);
+        std::vector<int32_t> parent(1, R.parent[0]);
+        for (int64_t k = 0; k < n; k++) {
+            const int32_t v = order[(size_t)k];
+            if (S.join_keep_largest && comp[(size_t)v] != 0) break;
+            pos[(size_t)v] = (int32_t)tree.size();
+            tree.push_back(R.tree[(size_t)v + 1]);
+            parent.push_back(par_out[(size_t)v] < 0 ? -1 : pos[(size_t)par_out[(size_t)v]]); // (the parent was written before)
+        }
+        R.tree.swap(tree);
+        R.parent.swap(parent);
+        R.t_join = secs(tj, clk::now());
+        printf("join... gap %g, %lld bridges, %lld -> %lld trees, %zu nodes written, %g sec.\n", (double)S.join_gap, (long long)nb, (long long)t_in, (long long)t_out,
+               R.tree.size() - 1, R.t_join);
+        if (S.timing) {
+            double ms = 0;
+            int64_t launches = 0, rounds = 0;
+            pnr_get_kernel_ms(ctx, "join", &ms, &launches);
+            pnr_get_option(ctx, "join_rounds", &rounds);
+            pnr_set_profiling(ctx, 0);
+            fprintf(stderr, "[pnr host] join: %.3f s, %lld rounds, kernels %.3f ms in %lld launches\n", R.t_join, (long long)rounds, ms, (long long)launches);
+        }
+    }
     auto t5 = clk::now();
     R.t_recon = secs(t4, t5);
     std::vector<float> radius; // --measure-radius: the radius column, measured on the volume this context traced
@@ -924,7 +1057,8 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     }
     R.swc_path = inimg_file + (settings().single_tree ? "_Advantra1.swc" : "_Advantra.swc"); // :2152 / :2164
     save_treelist(R.tree, R.parent, R.swc_path, -1, 1.f, "Advantra",
-                  swc_comment(paras, p, data16 ? window : nullptr, settings().measure_radius ? &R.radius_thr : nullptr), radius.empty() ? nullptr : &radius);
+                  swc_comment(paras, p, data16 ? window : nullptr, settings().measure_radius ? &R.radius_thr : nullptr, settings().join ? &R : nullptr),
+                  radius.empty() ? nullptr : &radius);
     if (settings().save_midres) { // the saveMidres taps of reconstruct() (:2098-2141)
         save_nodelist(R.nodes, R.links, inimg_file + "_n0_.swc");
         static const char *const names[] = {"", "_n0res_.swc", "_n1_.swc", "_n2_.swc", "_n2tree_.swc"};

@@ -39,6 +39,8 @@ struct Result {
     std::vector<int32_t> parent;   // parent index per tree node, -1 = root
     std::vector<int32_t> radius_k; // --measure-radius: k* of pnr_measure_radii per tree node (index 0 dummy: -1), else empty
     int32_t radius_thr = 0;        // ... the threshold it used (0: the relative mode)
+    long long join_bridges = 0, join_trees_in = 0, join_trees_out = 0; // --join: what pnr_join_trees reported
+    double t_join = 0;
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
     double t_filter = 0;           // --median / --subtract-background: the pre-filter (part of t_setup)
@@ -79,6 +81,14 @@ struct Settings {
     // top-hat with the flat box of half-width R) right after it is set -- for 16-bit input after windowing -- and before the soma
     // path; on every rank of --ranks N.  The SWC comment then has a #filter= line.  The reference has no counterpart.
     pnr_filter_opts filter = {0, 0};
+    // --join GAP: the reconstructed forest is joined on the GPU (pnr_join_trees, zscale = zdist) right after reconstruct() and before
+    // --measure-radius: fragments whose closest nodes lie within GAP xy voxels (0: any distance) are bridged, the result is re-rooted
+    // and the SWC written in tree order (every parent before its children) with a #join= comment line.  --join-root soma (the default:
+    // the first soma node, type 1, if there is one) or ID (a node id of the file without --join); --join-keep-largest: only component
+    // 0 is written.  The reference has no counterpart (ENFORCE_SINGLE_TREE throws the other trees away).
+    bool join = false, join_keep_largest = false;
+    float join_gap = 0.f;
+    long long join_root_id = 0; // 0: the first soma node, if any
 };
 Settings &settings();
 
@@ -110,6 +120,10 @@ bool print_swc_info(const std::string &path);
 // line; per_node (not empty): <per_node>_ab.csv / _ba.csv with one row `id,d` per sample point of A / of B (id = the SWC id of the
 // point's node) under a header line
 bool print_tree_distance(const std::string &a, const std::string &b, const pnr_distance_opts &opts, int device, const std::string &per_node);
+// advantra_cli --join-swc IN.swc OUT.swc: pnr_join_trees of the file on `device`; OUT.swc has the nodes in tree order with ids 1..n, the
+// type and radius columns carried over and a #join= comment line; root_id: an SWC id of IN (0: none); keep_largest: component 0 only.
+// Prints one JSON line {"nodes", "trees_in", "trees_out", "bridges", "longest_bridge", "rounds"}.
+bool join_swc_file(const std::string &in, const std::string &out, float gap, float zscale, long long root_id, bool keep_largest, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

@@ -69,6 +69,15 @@ class DistanceResult(C.Structure):
 PNR_DISTANCE_MAX_N = 1 << 22
 
 
+class JoinOpts(C.Structure):
+    """pnr_join_opts (include/pnr_hip.h): zscale > 0 (z *= zscale first), gap >= 0 (0: no limit), root (a node index, negative: none)"""
+    _fields_ = [("zscale", C.c_float), ("gap", C.c_float), ("root", C.c_int32)]
+
+
+BRIDGE = np.dtype([("lo", np.int32), ("hi", np.int32), ("d", np.float32)])  # pnr_bridge
+PNR_JOIN_MAX_N = 1 << 22
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -138,6 +147,9 @@ def load():
     L.pnr_point_segment_distance.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
     L.pnr_tree_sample.argtypes = [vp, vp, i64, C.c_float, C.c_float, vp, vp, i64, C.POINTER(i64)]
     L.pnr_tree_distance.argtypes = [vp, vp, vp, i64, vp, vp, i64, C.POINTER(DistanceOpts), C.POINTER(DistanceResult), vp, vp, i64, vp, vp, i64]
+    L.pnr_nearest_other.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.pnr_join_trees.argtypes = [vp, vp, vp, i64, C.POINTER(JoinOpts), vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.pnr_join_reroot.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.pnr_live_bytes.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -200,7 +212,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -370,6 +382,42 @@ class Context:
         check(self.L.pnr_tree_distance(self.h, xa.ctypes.data, pa.ctypes.data, len(xa), xb.ctypes.data, pb.ctypes.data, len(xb), C.byref(o), C.byref(r),
                                        ptr[0], ptr[1], len(out[0]) if per_point else 0, ptr[2], ptr[3], len(out[2]) if per_point else 0))
         return (r.as_dict(), (out[0], out[1]), (out[2], out[3])) if per_point else r.as_dict()
+
+    def nearest_other(self, xyz, label):
+        """pnr_nearest_other: for every point with label >= 0 the nearest point of another non-negative label -> (d float32[n], j int32[n]):
+        its distance and the smallest index at that distance; (+inf, -1) without one and for a negative label"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        label = np.ascontiguousarray(label, np.int32).reshape(-1)
+        if len(label) != len(xyz):
+            raise PnrError("nearest_other: one label per point")
+        d = np.empty(len(xyz), np.float32)
+        j = np.empty(len(xyz), np.int32)
+        check(self.L.pnr_nearest_other(self.h, xyz.ctypes.data, label.ctypes.data, len(xyz), d.ctypes.data, j.ctypes.data))
+        return d, j
+
+    def join_trees(self, xyz, parent, zscale=1, gap=0, root=-1, counts=False):
+        """pnr_join_trees of a forest (n x 3 positions, parent indices with a negative value for none; drop the dummy node of a
+        reconstruct() result first): fragments whose closest nodes lie within `gap` (0: any distance) are bridged, every component is
+        re-rooted (at `root` where given) -> (parent int32[n], order int32[n], comp int32[n], bridges BRIDGE[k]); a file written in
+        `order` has every parent before its children.  counts: a fifth item {"trees_in", "trees_out", "rounds"}"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        if len(parent) != len(xyz):
+            raise PnrError("join_trees: one parent per node")
+        n = len(xyz)
+        o = JoinOpts(float(zscale), float(gap), int(root))
+        out = [np.empty(n, np.int32) for _ in range(3)]
+        nb, t0, t1 = C.c_int64(), C.c_int64(), C.c_int64()
+        cap = 64
+        while True:  # "*n_bridges > cap: call again"
+            bridges = np.empty(cap, BRIDGE)
+            check(self.L.pnr_join_trees(self.h, xyz.ctypes.data, parent.ctypes.data, n, C.byref(o), out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data,
+                                        bridges.ctypes.data, cap, C.byref(nb), C.byref(t0), C.byref(t1)))
+            if nb.value <= cap:
+                break
+            cap = nb.value
+        res = (out[0], out[1], out[2], bridges[:nb.value].copy())
+        return res + ({"trees_in": t0.value, "trees_out": t1.value, "rounds": self.get_option("join_rounds")},) if counts else res
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
@@ -781,6 +829,22 @@ def tree_sample(xyz, parent, zscale=1, step=1, count_only=False):
     owner = np.empty(n.value, np.int32)
     check(L.pnr_tree_sample(xyz.ctypes.data, parent.ctypes.data, len(xyz), float(zscale), float(step), pts.ctypes.data, owner.ctypes.data, n.value, C.byref(n)))
     return pts, owner
+
+
+def join_reroot(parent, bridges=(), root=-1):
+    """pnr_join_reroot (pure host; no GPU needed): the re-rooting and ordering half of the join -> (parent int32[n], order int32[n],
+    comp int32[n]); bridges: a BRIDGE array, or (lo, hi) pairs"""
+    L = load()
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    if not (isinstance(bridges, np.ndarray) and bridges.dtype == BRIDGE):
+        pairs = np.asarray(bridges, np.int64).reshape(-1, 2)
+        bridges = np.zeros(len(pairs), BRIDGE)
+        bridges["lo"], bridges["hi"] = pairs[:, 0], pairs[:, 1]
+    bridges = np.ascontiguousarray(bridges)
+    out = [np.empty(len(parent), np.int32) for _ in range(3)]
+    check(L.pnr_join_reroot(parent.ctypes.data, len(parent), bridges.ctypes.data if len(bridges) else None, len(bridges), int(root),
+                            out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+    return tuple(out)
 
 
 def read_swc(path):
