@@ -69,6 +69,12 @@ int pnr_reconstruct_stage_ctx(pnr_ctx *ctx, const pnr_node *nodes, int64_t n_nod
  * number of offsets; up to cap of them are written; any array may be NULL. */
 int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t *dx, int32_t *dy, int32_t *dz, int64_t cap, int64_t *n);
 
+/* The launch plan of the all-pairs minimum behind pnr_point_segment_distance (n points x m segments) and pnr_nearest_other /
+ * pnr_join_trees (n x n), pure host code (no GPU): the launches in their order, rows outer, 7 values each -- points [p0, p1), segments
+ * or targets [s0, s1), the slice length `split`, the grid (x, y).  split / budget: the options *_split / *_pairs_per_launch (0 =
+ * automatic).  *count = the number of launches; up to cap of them are written to tiles (cap x 7; NULL with cap = 0). */
+int pnr_pair_tiles(int64_t n, int64_t m, int64_t split, int64_t budget, int64_t *tiles, int64_t cap, int64_t *count);
+
 /* Bytes of device and of pinned host memory the library holds at this moment, over all contexts and exchanges of the process
  * (every allocation goes through one owner type that counts them); either pointer may be NULL. */
 int pnr_live_bytes(int64_t *device, int64_t *pinned);

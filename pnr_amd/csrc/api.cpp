@@ -12,6 +12,7 @@
 #include "filter.h"
 #include "distance.h"
 #include "join.h"
+#include "pairmin.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -524,7 +525,6 @@ int pnr_join_trees(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t 
     return PNR_OK;
 }
 
-// test tap (pnr_hip_test.h): the shells of the rule, pure host
 int pnr_live_bytes(int64_t *device, int64_t *pinned)
 {
     if (device) *device = pnr::live_device_bytes.load();
@@ -532,6 +532,7 @@ int pnr_live_bytes(int64_t *device, int64_t *pinned)
     return PNR_OK;
 }
 
+// test tap (pnr_hip_test.h): the shells of the rule, pure host
 int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t *dx, int32_t *dy, int32_t *dz, int64_t cap, int64_t *n)
 {
     PNR_REQUIRE(rmax >= 1 && rmax <= PNR_RADIUS_MAX && n, PNR_E_ARG, "pnr_radius_offsets: rmax = %d outside [1, %d], or null count", rmax, PNR_RADIUS_MAX);
@@ -545,6 +546,25 @@ int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t
         if (dy) dy[i] = (int32_t)((o >> 8) & 255u) - 64;
         if (dz) dz[i] = (int32_t)((o >> 16) & 255u) - 64;
     }
+    return PNR_OK;
+}
+
+// test tap (pnr_hip_test.h): the launch plan of the pair minimum, pure host
+int pnr_pair_tiles(int64_t n, int64_t m, int64_t split, int64_t budget, int64_t *tiles, int64_t cap, int64_t *count)
+{
+    PNR_REQUIRE(n >= 1 && m >= 1 && split >= 0 && budget >= 0 && count && (cap <= 0 || tiles), PNR_E_ARG,
+                "pnr_pair_tiles: %lld x %lld (at least 1 x 1), split = %lld and budget = %lld (not negative) need a count, and tiles for cap = %lld", (long long)n,
+                (long long)m, (long long)split, (long long)budget, (long long)cap);
+    int64_t k = 0;
+    pnr::pair_tiles(n, m, split, budget, [&](const pnr::PairTile &t) {
+        if (k < cap) {
+            const int64_t row[7] = {t.p0, t.p1, t.s0, t.s1, t.split, t.gx, t.gy};
+            std::copy(row, row + 7, tiles + 7 * k);
+        }
+        k++;
+        return true;
+    });
+    *count = k;
     return PNR_OK;
 }
 

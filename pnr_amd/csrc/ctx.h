@@ -34,6 +34,38 @@ void set_error(const char *fmt, ...);
         }                                 \
     } while (0)
 
+// All device buffers of one call as ONE DevBuf (pnr_live_bytes sees one allocation, which ends with its owner): add() the parts --
+// each starts on a 16-byte boundary --, alloc() once, then at<T>(offset).
+class CallBuf {
+    DevBuf<char> buf_;
+    size_t bytes_ = 0;
+
+public:
+    size_t add(size_t bytes) // -> the offset of the part
+    {
+        const size_t o = bytes_;
+        bytes_ += (bytes + 15) & ~(size_t)15;
+        return o;
+    }
+    int alloc(const char *who)
+    {
+        if (buf_.alloc(bytes_) == hipSuccess) return PNR_OK;
+        (void)hipGetLastError();
+        set_error("%s: device allocation of %zu B failed", who, bytes_);
+        return PNR_E_NOMEM;
+    }
+    template <typename T>
+    T *at(size_t offset) const { return (T *)(buf_.get() + offset); }
+};
+
+// the way out of a call that has work queued on st when a HIP call fails
+inline int hip_fail(hipStream_t st, const char *who, hipError_t e)
+{
+    (void)hipStreamSynchronize(st);
+    set_error("%s: %s", who, hipGetErrorString(e));
+    return PNR_E_HIP;
+}
+
 // ---- host tables (tables.cpp): Tracker::Tracker (tracker.cpp:79-527) + Gaussian taps ----
 struct Tables {
     int sz = 0, ndir = 50, nsig = 0;
@@ -100,11 +132,12 @@ struct Options {
                                 // stash (tables.cpp find_scale_pairs; 0: every scale samples on its own -- the same results)
     int share_min = 0;          // ... in steps of at least this many traces (a guest's wave is not the longest of its trace, so small
                                 // steps lose nothing by it: 0, not tuned on a workload of its own)
-    int dist_split = 0;         // pnr_point_segment_distance: segments per blockIdx.y slice of a launch (0: automatic, distance.hip -- enough slices to fill the chip)
-    int64_t dist_pairs_per_launch = 0; // ... and at most this many (point, segment) pairs per launch (0: automatic, 2^34); neither changes a result:
-                                       // tests reach slice and launch boundaries with them on small inputs
-    int join_split = 0;         // pnr_nearest_other / pnr_join_trees: targets per blockIdx.y slice of a launch (0: automatic, join.hip), and
-    int64_t join_pairs_per_launch = 0; // at most this many (point, target) pairs per launch (0: automatic, 2^34): the counterparts of dist_*; the same bits
+    int dist_split = 0;         // the pair minimum (pairmin.h pair_tiles) of pnr_point_segment_distance: segments per blockIdx.y slice of a launch (0:
+                                // automatic -- enough slices to fill the chip), and
+    int64_t dist_pairs_per_launch = 0; // at most this many (point, segment) pairs per launch (0: automatic, 2^34); neither changes a result: tests
+                                       // reach slice and launch boundaries with them on small inputs
+    int join_split = 0;         // the same two for the targets and (point, target) pairs of pnr_nearest_other / pnr_join_trees
+    int64_t join_pairs_per_launch = 0;
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host

@@ -13,6 +13,6 @@ int tree_sample(const float *xyz, const int32_t *parent, int64_t n, float zscale
 } // namespace pnr
 
 // d_out[i] = the distance of point i (pts: host, n x 3) to the nearest of the m segments (seg_a, seg_b: host, m x 3), j_out[i]
-// (nullable) = the smallest index of a segment at that distance; validated arguments, n >= 1.  Runs on c's stream; every device
-// buffer is freed before the call returns.
+// (nullable) = the smallest index of a segment at that distance; validated arguments, n >= 1.  DistRule under the pair minimum of
+// pairmin.h.  Runs on c's stream; every device buffer is freed before the call returns.
 int pnr_distance_run(pnr_ctx *c, const float *pts, int64_t n, const float *seg_a, const float *seg_b, int64_t m, float *d_out, int32_t *j_out);

@@ -1,16 +1,13 @@
-// distance.hip -- all-pairs point-to-segment minimum behind pnr_point_segment_distance / pnr_tree_distance.  The rule
+// distance.hip -- the point-to-segment rule behind pnr_point_segment_distance / pnr_tree_distance, under the pair minimum of pairmin.h.  The rule
 // (include/pnr_hip.h): per segment ab = b - a, den = (ab.x^2 + ab.y^2) + ab.z^2, r = den > 0 ? 1 / den : 0; per pair
 // t = min(max(((p - a) . ab) * r, 0), 1), e = p - (a + t ab), d2 = e . e; per point d = sqrt(min_j d2), j* = the smallest j at the minimum.
 // Every operation is one IEEE f32 operation in the order of the header (the build has -ffp-contract=off).
 //
-// dist_prep turns the segments into two float4 each: (a, r) and (ab, 0).  dist_min has one thread per point with the point in
-// registers; the segment index of its loop is the same in every lane, so a segment arrives through scalar loads (two dwordx4 per
-// segment and wave, none per lane) and the vector unit only does the ~25 operations of the pair.  blockIdx.y cuts the segments into
-// slices, so that a few thousand points still fill the chip; every thread ends with ONE 64-bit atomicMin on
-// (bits(d2) << 32) | j -- d2 >= +0, so its bit pattern orders like its value, and the low word makes the smallest j win a tie.
-// The result therefore does not depend on the slices or on how the (points x segments) rectangle is cut into launches: a launch
-// is bounded by a pair budget, so that no single kernel occupies the GPU for seconds.  dist_finish unpacks and takes the root.
+// dist_prep turns the segments into two float4 each: (a, r) and (ab, 0), so a segment is two scalar dwordx4 loads per wave and the
+// vector unit only does the ~25 operations of the pair.  Every pair counts, so a point whose minimum stays +inf reports the first
+// segment of the smallest slice.  Above it: tree_sample, the host's sampling of a tree.
 #include "distance.h"
+#include "pairmin.h"
 #include <cmath>
 
 namespace pnr {
@@ -54,10 +51,7 @@ int tree_sample(const float *xyz, const int32_t *parent, int64_t n, float zscale
 
 namespace {
 
-constexpr int DTPB = 256;              // threads of a work-group = points of a block row
-constexpr int MIN_SPLIT = 64;          // automatic slices hold at least this many segments: one atomic per 64 pairs at the most
-constexpr int TARGET_BLOCKS = 2048;    // automatic slices: work-groups of a launch that fill 256 CUs eight deep
-constexpr long long AUTO_PAIRS = 1ll << 34; // pairs per launch: some 10 ms
+constexpr int DTPB = pnr::PAIR_TPB;
 
 __global__ __launch_bounds__(DTPB) void dist_prep(const float *__restrict__ a, const float *__restrict__ b, int m, float4 *__restrict__ seg)
 {
@@ -71,102 +65,59 @@ __global__ __launch_bounds__(DTPB) void dist_prep(const float *__restrict__ a, c
     seg[2 * j + 1] = make_float4(abx, aby, abz, 0.f);
 }
 
-// points [p0, p1) x segments [s0, s1); blockIdx.y = the slice of `split` segments
-__global__ __launch_bounds__(DTPB) void dist_min(const float *__restrict__ pts, int p0, int p1, const float4 *__restrict__ seg, int s0, int s1, int split,
-                                                 unsigned long long *__restrict__ key)
-{
-    const int i = p0 + blockIdx.x * DTPB + threadIdx.x;
-    const int j0 = s0 + blockIdx.y * split, j1 = min(j0 + split, s1);
-    const int ip = min(i, p1 - 1); // (the lanes past the last point run along on it and write nothing)
-    const float px = pts[3 * ip], py = pts[3 * ip + 1], pz = pts[3 * ip + 2];
-    float best = INFINITY;
-    int bj = j0;
-#pragma unroll 4
-    for (int j = j0; j < j1; j++) { // j is wave-uniform: scalar loads
+struct DistRule {
+    const float *__restrict__ pts;
+    const float4 *__restrict__ seg; // (dist_prep)
+    struct Point {
+        float x, y, z;
+    };
+    __device__ Point point(int i) const { return {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}; }
+    __device__ bool live(const Point &) const { return true; }
+    __device__ int first(int j0) const { return j0; }
+    __device__ bool pair(const Point &p, int j, float &d2) const
+    {
         const float4 A = seg[2 * j], B = seg[2 * j + 1];
-        const float apx = px - A.x, apy = py - A.y, apz = pz - A.z;
+        const float apx = p.x - A.x, apy = p.y - A.y, apz = p.z - A.z;
         const float num = (apx * B.x + apy * B.y) + apz * B.z;
         const float t = fminf(fmaxf(num * A.w, 0.f), 1.f);
-        const float ex = px - (A.x + t * B.x), ey = py - (A.y + t * B.y), ez = pz - (A.z + t * B.z);
-        const float d2 = (ex * ex + ey * ey) + ez * ez;
-        if (d2 < best) best = d2, bj = j; // (ascending j: the first of equals stays)
+        const float ex = p.x - (A.x + t * B.x), ey = p.y - (A.y + t * B.y), ez = p.z - (A.z + t * B.z);
+        d2 = (ex * ex + ey * ey) + ez * ez;
+        return true;
     }
-    if (i < p1) atomicMin(&key[i], (unsigned long long)__float_as_uint(best) << 32 | (unsigned)bj);
-}
-
-__global__ __launch_bounds__(DTPB) void dist_finish(const unsigned long long *__restrict__ key, int n, float *__restrict__ d, int *__restrict__ j)
-{
-    const int i = blockIdx.x * DTPB + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long k = key[i];
-    d[i] = sqrtf(__uint_as_float((unsigned)(k >> 32)));
-    j[i] = (int)(unsigned)k;
-}
-
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+};
 
 } // namespace
 
 int pnr_distance_run(pnr_ctx *c, const float *pts, int64_t n, const float *seg_a, const float *seg_b, int64_t m, float *d_out, int32_t *j_out)
 {
+    static const char *who = "pnr_point_segment_distance";
     hipStream_t st = c->stream;
-    // device buffers of the call: the prepared segments | the packed minima | the points | a | b | d | j
-    const size_t o_key = pad16((size_t)m * 32), o_pts = o_key + pad16((size_t)n * 8), o_a = o_pts + pad16((size_t)n * 12), o_b = o_a + pad16((size_t)m * 12),
-                 o_d = o_b + pad16((size_t)m * 12), o_j = o_d + pad16((size_t)n * 4), bytes = o_j + pad16((size_t)n * 4);
-    pnr::DevBuf<char> buf; // (freed when the call returns)
-    if (buf.alloc(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("pnr_point_segment_distance: device allocation of %zu B failed", bytes);
-        return PNR_E_NOMEM;
-    }
-    char *const d_buf = buf.get();
-    auto fail = [&](hipError_t e) {
-        (void)hipStreamSynchronize(st);
-        pnr::set_error("pnr_point_segment_distance: %s", hipGetErrorString(e));
-        return PNR_E_HIP;
-    };
-    float4 *const d_seg = (float4 *)d_buf;
-    unsigned long long *const d_key = (unsigned long long *)(d_buf + o_key);
-    float *const d_pts = (float *)(d_buf + o_pts);
+    pnr::CallBuf buf; // (freed when the call returns)
+    const size_t o_seg = buf.add((size_t)m * 32), o_key = buf.add((size_t)n * 8), o_pts = buf.add((size_t)n * 12), o_a = buf.add((size_t)m * 12),
+                 o_b = buf.add((size_t)m * 12), o_d = buf.add((size_t)n * 4), o_j = buf.add((size_t)n * 4);
+    const int rc = buf.alloc(who);
+    if (rc) return rc;
+    float4 *const d_seg = buf.at<float4>(o_seg);
+    unsigned long long *const d_key = buf.at<unsigned long long>(o_key);
+    float *const d_pts = buf.at<float>(o_pts);
     hipError_t e;
-    if ((e = hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(d_buf + o_a, seg_a, (size_t)m * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(d_buf + o_b, seg_b, (size_t)m * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return fail(e);
-    // the (points x segments) rectangle in launches of at most `budget` pairs (whole block rows; at least one row by one segment)
-    const long long budget = c->opt.dist_pairs_per_launch > 0 ? c->opt.dist_pairs_per_launch : AUTO_PAIRS;
-    const long long rows_fit = budget / m / DTPB * DTPB;
-    const long long rows = std::min<long long>(std::max<long long>(rows_fit, DTPB), (n + DTPB - 1) / DTPB * DTPB);
-    const long long segs = rows_fit >= DTPB ? m : std::max<long long>(1, budget / DTPB);
-    int launches = 2;
+    if ((e = hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+    if ((e = hipMemcpyAsync(buf.at<float>(o_a), seg_a, (size_t)m * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+    if ((e = hipMemcpyAsync(buf.at<float>(o_b), seg_b, (size_t)m * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+    int launches = 0;
     c->tic();
-    hipLaunchKernelGGL(dist_prep, dim3((unsigned)((m + DTPB - 1) / DTPB)), dim3(DTPB), 0, st, (const float *)(d_buf + o_a), (const float *)(d_buf + o_b), (int)m, d_seg);
+    hipLaunchKernelGGL(dist_prep, dim3((unsigned)((m + DTPB - 1) / DTPB)), dim3(DTPB), 0, st, (const float *)buf.at<float>(o_a), (const float *)buf.at<float>(o_b), (int)m, d_seg);
     e = hipGetLastError();
-    for (long long p0 = 0; p0 < n && e == hipSuccess; p0 += rows)
-        for (long long s0 = 0; s0 < m && e == hipSuccess; s0 += segs) {
-            const long long p1 = std::min<long long>(p0 + rows, n), s1 = std::min<long long>(s0 + segs, m), ms = s1 - s0;
-            const long long bx = (p1 - p0 + DTPB - 1) / DTPB;
-            long long split = c->opt.dist_split;
-            if (split <= 0) { // enough slices to fill the chip, of at least MIN_SPLIT segments
-                const long long slices = std::max<long long>(1, std::min<long long>((TARGET_BLOCKS + bx - 1) / bx, ms / MIN_SPLIT));
-                split = (ms + slices - 1) / slices;
-            }
-            split = std::max<long long>(split, (ms + 65534) / 65535); // (gridDim.y)
-            const long long by = (ms + split - 1) / split;
-            hipLaunchKernelGGL(dist_min, dim3((unsigned)bx, (unsigned)by), dim3(DTPB), 0, st, (const float *)d_pts, (int)p0, (int)p1, (const float4 *)d_seg, (int)s0,
-                               (int)s1, (int)split, d_key);
-            e = hipGetLastError();
-            launches++;
-        }
+    if (e == hipSuccess) e = pnr::pair_sweep(st, DistRule{d_pts, d_seg}, n, m, c->opt.dist_split, c->opt.dist_pairs_per_launch, d_key, &launches);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(dist_finish, dim3((unsigned)((n + DTPB - 1) / DTPB)), dim3(DTPB), 0, st, (const unsigned long long *)d_key, (int)n, (float *)(d_buf + o_d),
-                           (int *)(d_buf + o_j));
+        hipLaunchKernelGGL(pnr::pair_finish, dim3((unsigned)((n + DTPB - 1) / DTPB)), dim3(DTPB), 0, st, (const unsigned long long *)d_key, (int)n, 1, buf.at<float>(o_d), buf.at<int>(o_j));
         e = hipGetLastError();
     }
-    c->toc("distance", launches);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_buf + o_d, (size_t)n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && j_out) e = hipMemcpyAsync(j_out, d_buf + o_j, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    c->toc("distance", 2 + launches);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, buf.at<float>(o_d), (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && j_out) e = hipMemcpyAsync(j_out, buf.at<int>(o_j), (size_t)n * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(e);
+    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
     return PNR_OK;
 }

@@ -3,15 +3,16 @@
 #include "ctx.h"
 
 namespace pnr {
-// The nearest-other search of one call: the device buffers (one DevBuf, freed with the object) and the packed points.  begin() once,
-// then run() per set of labels: every point i with label[i] >= 0 gets the minimum of d2 over the points j with label[j] >= 0 and
-// label[j] != label[i], and the smallest j at that minimum (j = -1 and +inf without one, and for a negative label).  xyz is taken
-// as it is (the caller has applied zscale).  root: d_out = sqrtf(d2), else d2 itself.  Runs on c's stream and returns synchronised.
+// The nearest-other search of one call (JoinRule under the pair minimum of pairmin.h): the device buffers (one CallBuf, freed with the
+// object) and the packed points.  begin() once, then run() per set of labels: every point i with label[i] >= 0 gets the minimum of d2
+// over the points j with label[j] >= 0 and label[j] != label[i], and the smallest j at that minimum (j = -1 and +inf without one, and
+// for a negative label).  xyz is taken as it is (the caller has applied zscale).  root: d_out = sqrtf(d2), else d2 itself.  Runs on
+// c's stream and returns synchronised.
 class JoinSearch {
     pnr_ctx *c_ = nullptr;
     int64_t n_ = 0;
-    DevBuf<char> buf_;
-    size_t o_key_ = 0, o_xyz_ = 0, o_lab_ = 0, o_d_ = 0, o_j_ = 0;
+    CallBuf buf_;
+    size_t o_tgt_ = 0, o_key_ = 0, o_xyz_ = 0, o_lab_ = 0, o_d_ = 0, o_j_ = 0;
 
 public:
     int begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who);

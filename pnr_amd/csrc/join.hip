@@ -1,26 +1,20 @@
-// join.hip -- all-pairs nearest point of ANOTHER tree behind pnr_nearest_other / pnr_join_trees, and the host half of the join.  The rule
-// (include/pnr_hip.h): per pair dx = x_i - x_j (likewise y, z), d2 = (dx*dx + dy*dy) + dz*dz -- bit-symmetric in (i, j), negation is
-// exact --; per point the minimum of d2 over the points of a different, non-negative label and the smallest j at that minimum.  Every
-// operation is one IEEE f32 operation (the build has -ffp-contract=off).
+// join.hip -- the nearest point of ANOTHER tree behind pnr_nearest_other / pnr_join_trees, under the pair minimum of pairmin.h, and the host
+// half of the join.  The rule (include/pnr_hip.h): per pair dx = x_i - x_j (likewise y, z), d2 = (dx*dx + dy*dy) + dz*dz -- bit-symmetric
+// in (i, j), negation is exact --; per point the minimum of d2 over the points of a different, non-negative label and the smallest j at
+// that minimum.  Every operation is one IEEE f32 operation (the build has -ffp-contract=off).
 //
-// join_prep packs a point as one float4 (x, y, z, the bits of its label).  join_min is dist_min's form (distance.hip): one thread
-// holds its point and label in registers; the target index of its loop is the same in every lane, so a target arrives through ONE
-// scalar 16-byte load per wave and the vector unit only does the dozen operations of the pair -- no vector load, no LDS, nothing per
-// lane inside the loop.  blockIdx.y cuts the targets into slices, so that a few thousand points still fill the chip; every thread ends
-// with ONE 64-bit atomicMin on (bits(d2) << 32) | j -- d2 >= +0 orders like its bits, the low word makes the smallest j win a tie.  The
-// result therefore does not depend on the slices or on how the (points x targets) square is cut into launches of a bounded pair count.
-// join_finish unpacks.  Below the kernels: the host side -- input trees, Boruvka's rounds over the passes, re-rooting and ordering.
+// join_prep packs a point as one float4 (x, y, z, the bits of its label), so a target is ONE scalar 16-byte load per wave and the vector
+// unit only does the dozen operations of the pair.  A point of negative label takes no part, and one without a partner reports -1.
+// Below the search: the host side -- input trees, Boruvka's rounds over the passes, re-rooting and ordering.
 #include "join.h"
+#include "pairmin.h"
 #include <cmath>
 #include <cstring>
 #include <numeric>
 
 namespace {
 
-constexpr int JTPB = 256;                   // threads of a work-group = points of a block row
-constexpr int MIN_SPLIT = 64;               // automatic slices hold at least this many targets: one atomic per 64 pairs at the most
-constexpr int TARGET_BLOCKS = 2048;         // automatic slices: work-groups of a launch that fill 256 CUs eight deep
-constexpr long long AUTO_PAIRS = 1ll << 34; // pairs per launch
+constexpr int JTPB = pnr::PAIR_TPB;
 
 __global__ __launch_bounds__(JTPB) void join_prep(const float *__restrict__ xyz, const int *__restrict__ label, int n, float4 *__restrict__ tgt)
 {
@@ -29,39 +23,21 @@ __global__ __launch_bounds__(JTPB) void join_prep(const float *__restrict__ xyz,
     tgt[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float(label[i]));
 }
 
-// points [p0, p1) x targets [s0, s1); blockIdx.y = the slice of `split` targets
-__global__ __launch_bounds__(JTPB) void join_min(const float4 *__restrict__ tgt, int p0, int p1, int s0, int s1, int split, unsigned long long *__restrict__ key)
-{
-    const int i = p0 + blockIdx.x * JTPB + threadIdx.x;
-    const int j0 = s0 + blockIdx.y * split, j1 = min(j0 + split, s1);
-    const float4 P = tgt[min(i, p1 - 1)]; // (the lanes past the last point run along on it and write nothing)
-    const int li = __float_as_int(P.w);
-    float best = INFINITY;
-    int bj = -1;
-#pragma unroll 4
-    for (int j = j0; j < j1; j++) { // j is wave-uniform: a scalar load
+struct JoinRule {
+    const float4 *__restrict__ tgt; // (join_prep)
+    using Point = float4;
+    __device__ Point point(int i) const { return tgt[i]; }
+    __device__ bool live(const Point &p) const { return __float_as_int(p.w) >= 0; }
+    __device__ int first(int) const { return -1; }
+    __device__ bool pair(const Point &p, int j, float &d2) const
+    {
         const float4 T = tgt[j];
         const int lj = __float_as_int(T.w);
-        const float dx = P.x - T.x, dy = P.y - T.y, dz = P.z - T.z;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        if (lj >= 0 && lj != li && d2 < best) best = d2, bj = j; // (ascending j: the first of equals stays)
+        const float dx = p.x - T.x, dy = p.y - T.y, dz = p.z - T.z;
+        d2 = (dx * dx + dy * dy) + dz * dz;
+        return lj >= 0 && lj != __float_as_int(p.w);
     }
-    if (i < p1 && li >= 0) atomicMin(&key[i], (unsigned long long)__float_as_uint(best) << 32 | (unsigned)bj);
-}
-
-// root: d = sqrtf(d2), else d2; a point without a partner (its key untouched, or its minimum still +inf): +inf and j = -1
-__global__ __launch_bounds__(JTPB) void join_finish(const unsigned long long *__restrict__ key, int n, int root, float *__restrict__ d, int *__restrict__ j)
-{
-    const int i = blockIdx.x * JTPB + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long k = key[i];
-    const int bj = (int)(unsigned)k;
-    const float d2 = __uint_as_float((unsigned)(k >> 32));
-    d[i] = bj < 0 ? INFINITY : root ? sqrtf(d2) : d2;
-    j[i] = bj;
-}
-
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+};
 
 } // namespace
 
@@ -72,24 +48,12 @@ int JoinSearch::begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who)
     c_ = c;
     n_ = n;
     // device buffers of the call: the packed points | the packed minima | xyz | the labels | d | j
-    o_key_ = pad16((size_t)n * 16);
-    o_xyz_ = o_key_ + pad16((size_t)n * 8);
-    o_lab_ = o_xyz_ + pad16((size_t)n * 12);
-    o_d_ = o_lab_ + pad16((size_t)n * 4);
-    o_j_ = o_d_ + pad16((size_t)n * 4);
-    const size_t bytes = o_j_ + pad16((size_t)n * 4);
-    if (buf_.alloc(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("%s: device allocation of %zu B failed", who, bytes);
-        return PNR_E_NOMEM;
-    }
-    const hipError_t e = hipMemcpyAsync(buf_.get() + o_xyz_, xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return PNR_E_HIP;
-    }
-    return PNR_OK;
+    o_tgt_ = buf_.add((size_t)n * 16), o_key_ = buf_.add((size_t)n * 8), o_xyz_ = buf_.add((size_t)n * 12);
+    o_lab_ = buf_.add((size_t)n * 4), o_d_ = buf_.add((size_t)n * 4), o_j_ = buf_.add((size_t)n * 4);
+    const int rc = buf_.alloc(who);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(buf_.at<float>(o_xyz_), xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+    return e == hipSuccess ? PNR_OK : hip_fail(c->stream, who, e);
 }
 
 int JoinSearch::run(const int32_t *label, bool root, float *d_out, int32_t *j_out, const char *who)
@@ -97,51 +61,25 @@ int JoinSearch::run(const int32_t *label, bool root, float *d_out, int32_t *j_ou
     pnr_ctx *const c = c_;
     hipStream_t st = c->stream;
     const long long n = n_;
-    char *const d_buf = buf_.get();
-    float4 *const d_tgt = (float4 *)d_buf;
-    unsigned long long *const d_key = (unsigned long long *)(d_buf + o_key_);
-    auto fail = [&](hipError_t e) {
-        (void)hipStreamSynchronize(st);
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return PNR_E_HIP;
-    };
+    float4 *const d_tgt = buf_.at<float4>(o_tgt_);
+    unsigned long long *const d_key = buf_.at<unsigned long long>(o_key_);
     hipError_t e;
-    if ((e = hipMemcpyAsync(d_buf + o_lab_, label, (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return fail(e);
-    // the (points x targets) square in launches of at most `budget` pairs (whole block rows; at least one row by one target)
-    const long long budget = c->opt.join_pairs_per_launch > 0 ? c->opt.join_pairs_per_launch : AUTO_PAIRS;
-    const long long rows_fit = budget / n / JTPB * JTPB;
-    const long long rows = std::min<long long>(std::max<long long>(rows_fit, JTPB), (n + JTPB - 1) / JTPB * JTPB);
-    const long long tgts = rows_fit >= JTPB ? n : std::max<long long>(1, budget / JTPB);
-    int launches = 2;
+    if ((e = hipMemcpyAsync(buf_.at<int>(o_lab_), label, (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(st, who, e);
+    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return hip_fail(st, who, e);
+    int launches = 0;
     c->tic();
-    hipLaunchKernelGGL(join_prep, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const float *)(d_buf + o_xyz_), (const int *)(d_buf + o_lab_), (int)n, d_tgt);
+    hipLaunchKernelGGL(join_prep, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const float *)buf_.at<float>(o_xyz_), (const int *)buf_.at<int>(o_lab_), (int)n, d_tgt);
     e = hipGetLastError();
-    for (long long p0 = 0; p0 < n && e == hipSuccess; p0 += rows)
-        for (long long s0 = 0; s0 < n && e == hipSuccess; s0 += tgts) {
-            const long long p1 = std::min<long long>(p0 + rows, n), s1 = std::min<long long>(s0 + tgts, n), ms = s1 - s0;
-            const long long bx = (p1 - p0 + JTPB - 1) / JTPB;
-            long long split = c->opt.join_split;
-            if (split <= 0) { // enough slices to fill the chip, of at least MIN_SPLIT targets
-                const long long slices = std::max<long long>(1, std::min<long long>((TARGET_BLOCKS + bx - 1) / bx, ms / MIN_SPLIT));
-                split = (ms + slices - 1) / slices;
-            }
-            split = std::max<long long>(split, (ms + 65534) / 65535); // (gridDim.y)
-            const long long by = (ms + split - 1) / split;
-            hipLaunchKernelGGL(join_min, dim3((unsigned)bx, (unsigned)by), dim3(JTPB), 0, st, (const float4 *)d_tgt, (int)p0, (int)p1, (int)s0, (int)s1, (int)split, d_key);
-            e = hipGetLastError();
-            launches++;
-        }
+    if (e == hipSuccess) e = pair_sweep(st, JoinRule{d_tgt}, n, n, c->opt.join_split, c->opt.join_pairs_per_launch, d_key, &launches);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(join_finish, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const unsigned long long *)d_key, (int)n, root ? 1 : 0,
-                           (float *)(d_buf + o_d_), (int *)(d_buf + o_j_));
+        hipLaunchKernelGGL(pair_finish, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const unsigned long long *)d_key, (int)n, root ? 1 : 0, buf_.at<float>(o_d_), buf_.at<int>(o_j_));
         e = hipGetLastError();
     }
-    c->toc("join", launches);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_buf + o_d_, (size_t)n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(j_out, d_buf + o_j_, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    c->toc("join", 2 + launches);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, buf_.at<float>(o_d_), (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(j_out, buf_.at<int>(o_j_), (size_t)n * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(e);
+    if (e != hipSuccess) return hip_fail(st, who, e);
     return PNR_OK;
 }
 

@@ -155,12 +155,11 @@ __global__ __launch_bounds__(RTPB) void rad_measure(RadArgs a)
     if (lane == 0) a.k_out[node] = k > a.rmax ? a.rmax : max(0, k - 1);
 }
 
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 } // namespace
 
 int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opts &o, int32_t *k_out, int32_t *thr_used)
 {
+    static const char *who = "pnr_measure_radii";
     hipStream_t st = c->stream;
     const bool is2d = c->l == 1;
     // the shells of (rmax, zdist, 2-D), kept in the context's named device scratch.  Which table that is, is the NAME of an empty
@@ -188,37 +187,28 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         d_start = (int *)c->scratch["radius_start"].get();
     }
     // device buffers of the call: the sum | the positions | the order of the nodes | k
-    const size_t o_xyz = 16, o_ord = o_xyz + pad16((size_t)n * 12), o_k = o_ord + pad16((size_t)n * 4), bytes = o_k + pad16((size_t)n * 4);
-    pnr::DevBuf<char> buf; // (freed when the call returns)
-    if (buf.alloc(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("pnr_measure_radii: device allocation of %zu B failed", bytes);
-        return PNR_E_NOMEM;
-    }
-    char *const d_buf = buf.get();
-    auto fail = [&](hipError_t e) {
-        (void)hipStreamSynchronize(st);
-        pnr::set_error("pnr_measure_radii: %s", hipGetErrorString(e));
-        return PNR_E_HIP;
-    };
+    pnr::CallBuf buf; // (freed when the call returns)
+    const size_t o_sum = buf.add(8), o_xyz = buf.add((size_t)n * 12), o_ord = buf.add((size_t)n * 4), o_k = buf.add((size_t)n * 4);
+    const int rc = buf.alloc(who);
+    if (rc) return rc;
     hipError_t e = hipSuccess;
     int t_abs = 0;
     if (o.rel_pct == 0) {
         t_abs = o.thr;
         if (o.thr < 0) { // the global mean, from the exact sum
-            unsigned long long *d_sum = (unsigned long long *)d_buf, sum = 0;
+            unsigned long long *d_sum = buf.at<unsigned long long>(o_sum), sum = 0;
             const uintptr_t addr = (uintptr_t)c->d_img;
             const long long head = std::min<long long>(c->N, (long long)((16 - (addr & 15)) & 15)), nvec = (c->N - head) >> 4;
             const long long work = std::max<long long>(nvec, 16);
             const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((work + RTPB - 1) / RTPB, MAX_BLOCKS));
-            if ((e = hipMemsetAsync(d_sum, 0, 8, st)) != hipSuccess) return fail(e);
+            if ((e = hipMemsetAsync(d_sum, 0, 8, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
             c->tic();
             hipLaunchKernelGGL(rad_sum, dim3(nb), dim3(RTPB), 0, st, c->d_img, (long long)c->N, head, nvec, d_sum);
             e = hipGetLastError();
             c->toc("radius", 1);
             if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return fail(e);
+            if (e != hipSuccess) return pnr::hip_fail(st, who, e);
             t_abs = (int)std::max<unsigned long long>(1, sum / (unsigned long long)c->N);
         }
     }
@@ -238,17 +228,17 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         std::sort(cell.begin(), cell.end());
         std::vector<int> order((size_t)n);
         for (int64_t i = 0; i < n; i++) order[(size_t)i] = cell[(size_t)i].second;
-        if ((e = hipMemcpyAsync(d_buf + o_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-        if ((e = hipMemcpyAsync(d_buf + o_ord, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-        RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, d_off, d_start, (const float *)(d_buf + o_xyz), (const int *)(d_buf + o_ord),
-                  (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, (int *)(d_buf + o_k)};
+        if ((e = hipMemcpyAsync(buf.at<float>(o_xyz), xyz, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+        if ((e = hipMemcpyAsync(buf.at<int>(o_ord), order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+        RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, d_off, d_start, buf.at<float>(o_xyz), buf.at<int>(o_ord),
+                  (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, buf.at<int>(o_k)};
         c->tic();
         hipLaunchKernelGGL(rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), 0, st, a);
         e = hipGetLastError();
         c->toc("radius", 1);
-        if (e == hipSuccess) e = hipMemcpyAsync(k_out, d_buf + o_k, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(k_out, buf.at<int>(o_k), (size_t)n * 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st); // (the host vectors above end here)
-        if (e != hipSuccess) return fail(e);
+        if (e != hipSuccess) return pnr::hip_fail(st, who, e);
     }
     return PNR_OK;
 }

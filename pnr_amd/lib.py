@@ -151,6 +151,7 @@ def load():
     L.pnr_join_trees.argtypes = [vp, vp, vp, i64, C.POINTER(JoinOpts), vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.pnr_join_reroot.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.pnr_pair_tiles.argtypes = [i64, i64, i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_live_bytes.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pnr_get_frangi.argtypes = [vp] + [vp] * 5
@@ -221,7 +222,7 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
                    "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_live_bytes"]
+                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -893,6 +894,17 @@ def radius_offsets(zdist, rmax, is2d=False):
     check(L.pnr_radius_offsets(float(zdist), int(rmax), int(bool(is2d)), starts.ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data,
                                n.value, C.byref(n)))
     return starts, np.ascontiguousarray(d.T)
+
+
+def pair_tiles(n, m, split=0, budget=0):
+    """test tap pnr_pair_tiles (pure host; no GPU needed): the launches of the pair minimum over n points x m segments or targets with the
+    options *_split = split and *_pairs_per_launch = budget -> int64[launches, 7] of (p0, p1, s0, s1, split, grid x, grid y)"""
+    L = load()
+    k = C.c_int64()
+    check(L.pnr_pair_tiles(int(n), int(m), int(split), int(budget), None, 0, C.byref(k)))
+    tiles = np.zeros((k.value, 7), np.int64)
+    check(L.pnr_pair_tiles(int(n), int(m), int(split), int(budget), tiles.ctypes.data, k.value, C.byref(k)))
+    return tiles
 
 
 def reconstruct_stage(nodes, links, stage, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0):

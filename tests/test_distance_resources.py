@@ -1,5 +1,5 @@
 """CPU (hipcc cross-compiles gfx950 without a GPU): what the tree distance's inner loop rests on, read from the compiler's own report
-(-Rpass-analysis=kernel-resource-usage) and the ISA (-S): dist_min runs eight waves per SIMD without scratch, fetches its segments
+(-Rpass-analysis=kernel-resource-usage) and the ISA (-S): pair_min<DistRule> (pairmin.h) runs eight waves per SIMD without scratch, fetches its segments
 with scalar loads only (the segment index is wave-uniform: no vector load and no LDS access inside the loop), spends at most 24 vector
 instructions per (point, segment) pair, and ends in one 64-bit atomic minimum without a compare-and-swap loop."""
 import pytest
@@ -13,14 +13,12 @@ def compiled(tmp_path_factory):
 
 def test_budgets(compiled):
     usage, _ = compiled
-    for frag in ("dist_prep", "dist_min", "dist_finish"):
+    for frag in ("dist_prep", "pair_min", "pair_finish"):
         u, _ = find(usage, frag)
         assert u["ScratchSize"] == 0 and u["VGPRs"] <= 64 and u["Occupancy"] == 8 and u["LDS"] == 0, (frag, u)
 
 
-def test_inner_loop_reads_segments_through_scalar_loads(compiled):
-    usage, asm = compiled
-    body = kernel_body(usage, asm, "dist_min")
+def inner_loops(body):
     loops, cur = [], None
     for ln in body:  # the instructions of every innermost loop: from its header to its backward branch
         if ln.startswith(".LBB"):
@@ -32,6 +30,14 @@ def test_inner_loop_reads_segments_through_scalar_loads(compiled):
             cur.append(ln.split()[0])
             if cur[-1].startswith("s_cbranch"):
                 cur = None
+    return loops
+
+
+def test_inner_loop_reads_segments_through_scalar_loads(compiled):
+    usage, asm = compiled
+    assert "DistRule" in find(usage, "pair_min")[1]
+    body = kernel_body(usage, asm, "pair_min")
+    loops = inner_loops(body)
     assert len(loops) == 2, len(loops)  # the loop unrolled by four and its remainder
     for ins in loops:
         pairs = sum(i == "s_load_dwordx8" for i in ins)  # one scalar load of 32 bytes per segment

@@ -81,7 +81,8 @@ def fuzz_case(n, m):
 FUZZ_REF = {}
 
 
-@pytest.mark.parametrize("n,m", [(1, 1), (63, 1), (65, 257), (1000, 777), (4099, 2053)])
+@pytest.mark.parametrize("n,m", [(1, 1), (63, 1), (65, 257), (1000, 777), (4099, 2053),
+                                 (1000, 100)])  # forced: two row launches of 768 and 232 points, each over all segments (tests/test_pair_tiles.py)
 def test_fuzz_against_the_restatement(ctx, n, m):
     pts, a, b = fuzz_case(n, m)
     if (n, m) not in FUZZ_REF:
