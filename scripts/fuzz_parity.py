@@ -1,12 +1,20 @@
 """Randomised parity campaign (tests/fuzzcase.py) on the GPU box: random small stacks and parameters, HIP path against the oracle
 stage by stage; every comparison is for equality of bytes.
-usage: fuzz_parity.py [seconds] [first_case]     FUZZ_DRIVER=persistent  FUZZ_BIG=1 (stacks up to 192 x 160 x 80)"""
+usage: fuzz_parity.py [--images CLASS[,CLASS]] [seconds] [first_case]     FUZZ_DRIVER=persistent  FUZZ_BIG=1 (stacks up to 192 x 160 x 80)
+--images: the stacks come from tests/imgclass.py (the named classes in turn; "all": every class) instead of the synthetic tubes"""
 import os, sys, time, traceback
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
-import orc, fuzzcase
+import orc, fuzzcase, imgclass
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
-case = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+argv = sys.argv[1:]
+images = None
+if "--images" in argv:
+    i = argv.index("--images")
+    images = list(imgclass.CLASSES) if argv[i + 1] == "all" else argv[i + 1].split(",")
+    assert all(k in imgclass.CLASSES for k in images), f"--images: classes are {imgclass.CLASSES}"
+    del argv[i:i + 2]
+budget = float(argv[0]) if len(argv) > 0 else 300.0
+case = int(argv[1]) if len(argv) > 1 else 0
 L = orc.load_oracle()
 t_end = time.time() + budget
 nbad = ncases = 0
@@ -14,7 +22,7 @@ stats = {}
 while time.time() < t_end:
     desc = {}
     try:
-        fuzzcase.run_case(L, case, stats, desc, driver=os.environ.get("FUZZ_DRIVER"), big=bool(os.environ.get("FUZZ_BIG")))
+        fuzzcase.run_case(L, case, stats, desc, driver=os.environ.get("FUZZ_DRIVER"), big=bool(os.environ.get("FUZZ_BIG")), images=images)
     except Exception as e:  # noqa
         nbad += 1
         print("MISMATCH", desc, "->", repr(e)[:300], flush=True)

@@ -1,18 +1,21 @@
 """One case of the randomised parity campaign: a random small stack and random parameters, the HIP path against the oracle stage
-by stage (Frangi J / J8 / V, seeds, seed scores, every trace iteration, streamed vs one-shot graph, replay, reconstruct, soma).
-Every comparison is for equality of bytes.  Used by scripts/fuzz_parity.py (open-ended campaign on the GPU box) and by
-tests/test_gpu_fuzz.py (a fixed set of cases inside `-m gpu`).  The oracle is the checker."""
+by stage (Frangi J / J8 / V, seeds, seed scores and the order of ties, every trace iteration, streamed vs one-shot graph, replay,
+reconstruct, soma).  Every comparison is for equality of bytes.  run_case() draws a case; check_stack() is the comparison itself on
+a given stack.  Used by scripts/fuzz_parity.py (open-ended campaign on the GPU box), tests/test_gpu_fuzz.py (a fixed set of cases
+inside `-m gpu`) and tests/test_gpu_image_classes.py (the stacks of tests/imgclass.py).  The oracle is the checker."""
 import numpy as np
 import orc
 import synth
+import imgclass
 import pnr_amd
 from pnr_amd import lib
 
 mat = lambda a: np.stack([a[k] for k in a.dtype.names], -1)
 
 
-def run_case(L, case, stats, desc, driver=None, big=False):
-    """raises AssertionError on the first difference; fills `desc` with the case's parameters, adds its work to `stats`"""
+def run_case(L, case, stats, desc, driver=None, big=False, images=None):
+    """raises AssertionError on the first difference; fills `desc` with the case's parameters, adds its work to `stats`.  `images`: names
+    of imgclass classes -- the stack is drawn from them in turn instead of from synth (same shape, parameters and knobs)"""
     rs = np.random.RandomState(1000 + case)
     two_d = rs.rand() < 0.12 and driver != "persistent"  # (the persistent driver is 3-D only)
     big = 2 if big else 1  # stacks up to 192 x 160 x 80
@@ -30,7 +33,11 @@ def run_case(L, case, stats, desc, driver=None, big=False):
     rad = int(rs.choice([2, 3, 4])) if (not two_d and rs.rand() < 0.3) else 0
     groups = int(rs.choice([1, 1, 2, 3]))
     desc.update(case=case, shape=(w, h, l), sigs=sigs, zdist=zdist, np=np_, ni=ni, step=step, kappa=kappa, tol=tol, znccth=znccth, npv=npv, vol=vol, img=seed_img, somaradius=rad, groups=groups)
-    img = synth.synth(w, h, l, seed=seed_img) if not two_d else synth.synth(w, h, 3, seed=seed_img)[1:2].copy()
+    if images:
+        desc.update(image=images[case % len(images)])
+        img = imgclass.make(images[case % len(images)], w, h, l)
+    else:
+        img = synth.synth(w, h, l, seed=seed_img) if not two_d else synth.synth(w, h, 3, seed=seed_img)[1:2].copy()
     if rad:
         img = synth.add_somas(img, [(int(rs.randint(8, w - 8)), int(rs.randint(8, h - 8)), int(rs.randint(4, max(5, l - 4))), int(rs.randint(rad + 1, rad + 5)))
                                     for _ in range(int(rs.randint(1, 3)))])
@@ -38,7 +45,21 @@ def run_case(L, case, stats, desc, driver=None, big=False):
     rk = np.random.RandomState(900000 + case)  # (a stream of its own: the cases keep the stacks and parameters they had before these knobs existed)
     knobs.update(target=int(rk.choice([-1, 0, 4, 16, 64])), overfill=int(rk.randint(2)), concentrate=int(rk.randint(2)), sums_deep=int(rk.choice([-1, 0, 1])), lag=int(rk.choice([-1, 0, 1, 2])))
     desc.update(knobs=knobs)
-    p = pnr_amd.make_params(sigmas=sigs, somaradius=rad, step=step, kappa=kappa, zdist=zdist, np_=np_, ni=ni, tolerance=tol, znccth=znccth, nodepervol=npv, vol=vol)
+    params = dict(sigmas=sigs, somaradius=rad, step=step, kappa=kappa, zdist=zdist, np_=np_, ni=ni, tolerance=tol, znccth=znccth, nodepervol=npv, vol=vol)
+    check_stack(L, img, params, knobs, rs, stats, driver=driver, shard=(case if case % 3 == 0 else None))
+
+
+def check_stack(L, img, params, knobs, rs, stats, driver=None, shard=None, nsel=None, ref=None):
+    """one stack [l][h][w] (l == 1: the 2-D path) with the make_params() arguments `params` and the options `knobs`, stage by stage
+    against the oracle; raises AssertionError on the first difference.  The first `nsel` sorted seeds are traced (None: 2..8 of them,
+    drawn from `rs`); `shard`: a number that picks the logical ranks and block size of the sharded run (None: none); `ref`: a dict
+    that keeps the oracle's Frangi, seeds and scores between calls on the same stack and parameters"""
+    sigs, rad, step, kappa, zdist, np_, ni = (params[k] for k in ("sigmas", "somaradius", "step", "kappa", "zdist", "np_", "ni"))
+    tol, znccth, npv, vol = (params[k] for k in ("tolerance", "znccth", "nodepervol", "vol"))
+    l, h, w = img.shape
+    two_d = l == 1
+    ref = {} if ref is None else ref
+    p = pnr_amd.make_params(**params)
     c = pnr_amd.Context(p, 0)
     if driver:
         c.set_smc_driver(driver)
@@ -56,15 +77,15 @@ def run_case(L, case, stats, desc, driver=None, big=False):
     fast8 = c.get_frangi(J=False, J8=True, V=False)["J8"]  # what the pipeline uses: the run that skips the solver below the first J8 level
     fast_seeds = c.extract_seeds()
     g = c.get_frangi(J=True, J8=True, V=True)              # asking for J / V recomputes without that shortcut
-    if two_d:
-        J, jmin, jmax, Vx, Vy, Vz = orc.frangi2d(L, img, sigs)
-    else:
-        J, jmin, jmax, Vx, Vy, Vz = orc.frangi3d(L, img, sigs, zdist)
-    J8 = orc.j8(L, J, jmin, jmax)
+    if "frangi" not in ref:
+        ref["frangi"] = orc.frangi2d(L, img, sigs) if two_d else orc.frangi3d(L, img, sigs, zdist)
+        ref["J8"] = orc.j8(L, ref["frangi"][0], *ref["frangi"][1:3])
+        ref["seeds"] = orc.extract_seeds(L, tol, ref["J8"], *ref["frangi"][3:])
+    (J, jmin, jmax, Vx, Vy, Vz), J8 = ref["frangi"], ref["J8"]
     for k, want in (("J", J), ("J8", J8), ("Vx", Vx), ("Vy", Vy), ("Vz", Vz)):
         assert np.array_equal(g[k].reshape(want.shape), want), f"frangi {k}: {(g[k].reshape(want.shape) != want).sum()} voxels differ"
     assert np.array_equal(fast8.reshape(J8.shape), J8) and gext == (jmin, jmax), "J8 / extremes of the pruned run"
-    so = orc.extract_seeds(L, tol, J8, Vx, Vy, Vz)
+    so = ref["seeds"]
     sg = c.extract_seeds()
     assert len(fast_seeds) == len(sg) and all(np.array_equal(fast_seeds[k], sg[k], equal_nan=True) for k in sg.dtype.names), "seeds of the pruned run"
     assert len(sg) == len(so) and np.array_equal(mat(sg)[:, :6], so[:, :6]), "seeds"
@@ -74,11 +95,17 @@ def run_case(L, case, stats, desc, driver=None, big=False):
     T = orc.Tracker(L, sigs, step, np_, ni, kappa, znccth, zdist=zdist, nodespervol=npv, is2d=two_d)
     ss = c.score_filter_sort(sg)
     if len(so):
-        corr, sig = T.zncc(img, so[:, :6])
+        if "corr" not in ref:
+            ref["corr"] = T.zncc(img, so[:, :6])[0]
+        corr = ref["corr"]
         keep = corr >= np.float32(znccth)
         order = np.argsort(-corr[keep], kind="stable")
         assert len(ss) == keep.sum() and np.array_equal(ss["corr"], corr[keep][order]), "seed scores"
-    sel = ss[: int(rs.randint(2, 9))]
+        assert np.array_equal(mat(ss)[:, :6], so[keep][order][:, :6]), "order of the sorted seeds (ties keep the z-major order)"
+        stats["kept"] = stats.get("kept", 0) + int(keep.sum())
+    else:
+        assert len(ss) == 0, "seed scores"
+    sel = ss[: int(rs.randint(2, 9)) if nsel is None else nsel]
     Tg, stop, xc, _ = c.trace_batch(sel)
     for i in range(len(sel)):
         for d_, sgn in enumerate((1, -1)):
@@ -89,16 +116,17 @@ def run_case(L, case, stats, desc, driver=None, big=False):
             rows = min(Tn + 1, ni)
             assert np.array_equal(mat(xc[j])[:rows], xco[:rows], equal_nan=True), f"trace {j}: xc differs"
             stats["iters"] = stats.get("iters", 0) + rows
+            stats.setdefault("stops", set()).add(int(st))
         stats["traces"] = stats.get("traces", 0) + 2
     n1, l1, nt1 = c.replay(sel, Tg, xc)
     n2, l2, nt2, _ = c.trace_replay(sel)
     assert nt1 == nt2 and np.array_equal(l1, l2) and all(np.array_equal(n1[k], n2[k], equal_nan=True) for k in n1.dtype.names), "streamed vs one-shot graph"
-    if case % 3 == 0 and driver != "persistent" and len(ss) >= 2:
+    if shard is not None and driver != "persistent" and len(ss) >= 2:
         # BASELINE configs[3]: more of the sorted seeds dealt to 2 / 3 logical ranks (a context and a host thread per rank, joined by an
         # in-process all-gather) -- every rank must end with the one-GPU graph of the same seeds
         import threading
         from pnr_amd import multigpu
-        world = 2 + (case // 3) % 2
+        world = 2 + (shard // 3) % 2
         many = ss[:24]
         nr, lr, ntr, _ = c.trace_replay(many)
         X = multigpu.ThreadExchange(world)
@@ -107,7 +135,7 @@ def run_case(L, case, stats, desc, driver=None, big=False):
             cr = pnr_amd.Context(p, 0)
             for k, v in knobs.items():
                 cr.set_option(k, v)
-            cr.set_option("exchange_block", [0, 2048, 700][case // 3 % 3])  # small blocks: records queue up and are carried over
+            cr.set_option("exchange_block", [0, 2048, 700][shard // 3 % 3])  # small blocks: records queue up and are carried over
             cr.set_volume(img)
             if rad:
                 cr.soma()
