@@ -458,6 +458,61 @@ int pnr_join_trees(pnr_ctx *ctx, const float *xyz /* n x 3 */, const int32_t *pa
 int pnr_join_reroot(const int32_t *parent /* n */, int64_t n, const pnr_bridge *bridges, int64_t nb, int64_t root, int32_t *parent_out, int32_t *order_out,
                     int32_t *comp_out);
 
+/* Rendering the tree into the stack (beyond the reference, which has no way back from the tree to the voxels).  This is the step Vaa3D
+ * calls swc2mask: which voxels the tree occupies, and with the traced volume how much of the image's signal the trace explains, where it
+ * does not (the residual) and which nodes run through background (the per-segment counts).  Vaa3D's own digits are not pinned; the
+ * contract is THE RULE below, which the tests restate in numpy.  Every f32 operation is a single IEEE operation (-ffp-contract=off,
+ * correctly rounded division); parentheses give the order.
+ *   Input.  n nodes xyz (f32, voxel indices as in pnr_node), radius[i] (f32, xy voxels) and parent[i] in [-1, n), any negative value =
+ *     none: the layout of pnr_tree_distance and pnr_join_trees.  A grid w x h x l.  Options {zscale, rscale, radd, thr}; opts = NULL =
+ *     {1, 1, 0, -1}.
+ *   Scaling.  Node z *= zscale (one multiply; zscale > 0).  rr_i = fmaxf(radius_i * rscale + radd, 0) (one multiply, one add).  Voxel
+ *     (x, y, z) is the point p = ((float)x, (float)y, (float)z * zscale); with l == 1 only z = 0 exists.
+ *   Segment i.  a = x_i, b = x_parent[i], ra = rr_i, rb = rr_parent[i]; without a parent b = a and rb = ra: a ball, so an isolated node
+ *     still renders.  Computed once per segment, exactly as in the distance rule: ab = b - a, den = (ab.x*ab.x + ab.y*ab.y) + ab.z*ab.z,
+ *     r = den > 0 ? 1.0f / den : 0.0f, and dr = rb - ra.
+ *   Pair (p, i).  ap, num, t = fminf(fmaxf(num * r, 0.f), 1.f), e and d2 are those of the point-to-segment paragraph of
+ *     pnr_point_segment_distance, operation for operation.  rt = ra + t * dr (one multiply, one add).  The voxel is inside segment i iff
+ *     d2 <= rt * rt (one multiply, an f32 compare).
+ *   Label.  L(p) = 1 + the smallest i whose test passes; 0 if none.  A minimum does not depend on order: every cut into pieces, boxes
+ *     and launches gives the same bits.  mask(p) = L > 0 ? 255 : 0.
+ *   Coverage, on the context's traced u8 volume V (w x h x l, owned or borrowed; windowed and pre-filtered as traced), whose dimensions
+ *     are the grid.  t = thr, or for thr == -1: max(1, floor(sum(V) / N)) from the exact u64 sum -- the absolute mode of the radius
+ *     rule.  Foreground means V >= t.  Exact u64 counts: n_vox, n_tree (L > 0), n_fg, n_both, sum_fg (the sum of V over the
+ *     foreground), sum_both (the sum of V over the foreground under the tree).  Per segment i: seg_vox[i], seg_fg[i], seg_sum[i] =
+ *     the voxels labelled i + 1, those of them that are foreground, and the sum of V over all of them.  Derived on the host as f64, 0
+ *     when the denominator is 0: covered = n_both / n_fg, on_signal = n_both / n_tree, covered_intensity = sum_both / sum_fg.
+ *     residual(p) = L > 0 ? 0 : V(p).
+ *   Arguments (anything else: PNR_E_ARG): 0 <= n <= PNR_RENDER_MAX_N (n = 0 gives an all-zero label volume); w, h, l >= 1 (each below
+ *     2^31, at most 2^40 voxels); every coordinate (also z * zscale) and radius finite, radius >= 0; zscale > 0, rscale >= 0, radd finite;
+ *     every rr_i <= PNR_RENDER_MAX_R; parent < n; thr in -1..255.  Meant for voxel coordinates, as the distance rule.
+ * pnr_render_tree: label_out / mask_out (N = w*h*l each, nullable) on any grid.  It needs no volume and leaves the pipeline state of the
+ *   context alone.
+ * pnr_tree_coverage: renders on the grid of the context's volume (PNR_E_STATE without one) and never writes V.  cov, the per-segment
+ *   arrays (n each), mask_out and residual_out (N each) are all nullable.
+ * Both run on the context's stream (pnr_set_stream), use 64-bit voxel indices throughout and free every device buffer before they
+ *   return (PNR_E_NOMEM: an allocation failed; device memory of a call: 4 N bytes of labels, N more for each of mask and residual).
+ *   The host cuts every segment along its axis into pieces of at most render_piece xy voxels, gives each piece the integer box of its
+ *   sub-interval grown by max(ra, rb) + 1 and cuts boxes of more than render_box voxels; the pair test always uses the whole segment, so
+ *   the options change no bit.  Kernel times: pnr_get_kernel_ms group "render" (= "render_scatter" + "render_finish"); pnr_get_option
+ *   "render_items" / "render_pairs": the work items and (voxel, segment) tests of the last call. */
+#define PNR_RENDER_MAX_N (1 << 22)
+#define PNR_RENDER_MAX_R 1024
+typedef struct pnr_render_opts {
+    float zscale, rscale, radd;
+    int32_t thr;
+} pnr_render_opts; /* NULL = {1, 1, 0, -1} */
+typedef struct pnr_coverage {
+    int64_t n_vox, n_tree, n_fg, n_both, sum_fg, sum_both;
+    int32_t thr_used, pad;
+    double covered, on_signal, covered_intensity;
+} pnr_coverage;
+int pnr_render_tree(pnr_ctx *ctx, const float *xyz /* n x 3 */, const float *radius /* n */, const int32_t *parent /* n */, int64_t n, int64_t w, int64_t h,
+                    int64_t l, const pnr_render_opts *opts /* NULL = defaults */, int32_t *label_out /* N, nullable */, uint8_t *mask_out /* N, nullable */);
+int pnr_tree_coverage(pnr_ctx *ctx, const float *xyz /* n x 3 */, const float *radius /* n */, const int32_t *parent /* n */, int64_t n,
+                      const pnr_render_opts *opts /* NULL = defaults */, pnr_coverage *cov, int64_t *seg_vox, int64_t *seg_fg, int64_t *seg_sum /* n each, nullable */,
+                      uint8_t *mask_out, uint8_t *residual_out /* N each, nullable */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -483,16 +538,18 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   dist_split (0 = automatic: enough slices to fill the chip) segments per blockIdx.y slice of a launch of pnr_point_segment_distance |
  *   dist_pairs_per_launch (0 = automatic: 2^34) at most this many (point, segment) pairs per launch (the same bits -- tests reach slice and launch boundaries with them on small inputs) |
  *   join_split (0 = automatic), join_pairs_per_launch (0 = automatic: 2^34): the same for the targets and the (point, target) pairs of pnr_nearest_other / pnr_join_trees (the same bits) |
+ *   render_piece (0 = automatic: 16) xy voxels of a segment's axis per work item of pnr_render_tree / pnr_tree_coverage | render_box (0 = automatic: 2^15) voxels per item, larger boxes are cut |
+ *   render_items_per_launch (0 = automatic: 2^18) items per launch (the same bits -- tests reach piece, box and launch boundaries with them on small inputs) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
- *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
+ *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
  *   re-run Frangi without the frangi_prune shortcut -- one pnr_frangi worth of GPU time each; also printed with trace_timing /
  *   seed_timing).  The kernel timers (pnr_get_kernel_ms) include those re-runs. */
 int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish").  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -75,6 +75,18 @@ int pnr_radius_offsets(float zdist, int rmax, int is2d, int32_t *starts, int32_t
  * automatic).  *count = the number of launches; up to cap of them are written to tiles (cap x 7; NULL with cap = 0). */
 int pnr_pair_tiles(int64_t n, int64_t m, int64_t split, int64_t budget, int64_t *tiles, int64_t cap, int64_t *count);
 
+/* The work items of pnr_render_tree / pnr_tree_coverage for a tree on the grid w x h x l, pure host code (no GPU, no context): 7 values
+ * each -- the segment, then the inclusive box x0, y0, z0, x1, y1, z1 (inside the grid) -- in segment order.  piece / box: the options
+ * render_piece / render_box (0 = automatic).  Same argument rules as pnr_render_tree.  *count = the number of items; up to cap of them
+ * are written to items_out (cap x 7; NULL with cap = 0): *count > cap: call again. */
+int pnr_render_items(const float *xyz, const float *radius, const int32_t *parent, int64_t n, int64_t w, int64_t h, int64_t l, const pnr_render_opts *opts,
+                     int64_t piece, int64_t box, int64_t *items_out, int64_t cap, int64_t *count);
+
+/* The host's volume writer (pnr_amd/host/stack_io.h save_stack_u8), pure host code: img (w*h*l bytes, x fastest) as a multi-page
+ * uncompressed 8-bit TIFF, or the bare bytes for a name ending in .raw; written to a temporary file, then renamed.  A file that would
+ * pass classic TIFF's 4 GiB is refused from the dimensions alone (PNR_E_ARG, nothing is written; img may then be NULL). */
+int pnr_test_write_tiff(const char *path, const uint8_t *img, int64_t w, int64_t h, int64_t l);
+
 /* Bytes of device and of pinned host memory the library holds at this moment, over all contexts and exchanges of the process
  * (every allocation goes through one owner type that counts them); either pointer may be NULL. */
 int pnr_live_bytes(int64_t *device, int64_t *pinned);

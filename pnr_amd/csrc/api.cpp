@@ -13,6 +13,8 @@
 #include "distance.h"
 #include "join.h"
 #include "pairmin.h"
+#include "render.h"
+#include "../host/stack_io.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -522,6 +524,96 @@ int pnr_join_trees(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t 
     if (bridges_out) std::memcpy(bridges_out, bridges.data(), sizeof(pnr_bridge) * (size_t)std::min<int64_t>(cap_bridges, *n_bridges));
     if (n_trees_in) *n_trees_in = trees_in;
     if (n_trees_out) *n_trees_out = trees_out;
+    return PNR_OK;
+}
+
+// ---- rendering the tree (render.hip): arguments first; pnr_render_tree needs no volume, neither call touches the pipeline state ----
+static int render_grid_ok(const char *who, int64_t w, int64_t h, int64_t l)
+{
+    const int64_t lim = 0x7fffffffll;
+    PNR_REQUIRE(w >= 1 && h >= 1 && l >= 1 && w <= lim && h <= lim && l <= lim && w <= (1ll << 40) / h && w * h <= (1ll << 40) / l, PNR_E_ARG,
+                "%s: the grid %lld x %lld x %lld needs sides from 1 and at most 2^40 voxels", who, (long long)w, (long long)h, (long long)l);
+    return PNR_OK;
+}
+static int render_tree_ok(const char *who, const float *xyz, const float *radius, const int32_t *parent, int64_t n, const pnr_render_opts &o)
+{
+    PNR_REQUIRE(n >= 0 && n <= PNR_RENDER_MAX_N && (n == 0 || (xyz && radius && parent)), PNR_E_ARG, "%s: n = %lld nodes (at most 2^22) need xyz, radius and parent", who, (long long)n);
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "%s: thr = %d outside [-1, 255]", who, o.thr);
+    return PNR_OK;
+}
+
+int pnr_render_tree(pnr_ctx *c, const float *xyz, const float *radius, const int32_t *parent, int64_t n, int64_t w, int64_t h, int64_t l,
+                    const pnr_render_opts *opts, int32_t *label_out, uint8_t *mask_out)
+{
+    static const char *who = "pnr_render_tree";
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    const pnr_render_opts o = opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1};
+    int rc = render_tree_ok(who, xyz, radius, parent, n, o);
+    if (!rc) rc = render_grid_ok(who, w, h, l);
+    pnr::RenderTree t;
+    if (!rc) rc = pnr::render_prepare(who, xyz, radius, parent, n, o, t);
+    if (rc) return rc;
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_render_run(c, who, t, w, h, l, nullptr, 0, label_out, mask_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int pnr_tree_coverage(pnr_ctx *c, const float *xyz, const float *radius, const int32_t *parent, int64_t n, const pnr_render_opts *opts, pnr_coverage *cov,
+                      int64_t *seg_vox, int64_t *seg_fg, int64_t *seg_sum, uint8_t *mask_out, uint8_t *residual_out)
+{
+    static const char *who = "pnr_tree_coverage";
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    const pnr_render_opts o = opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1};
+    int rc = render_tree_ok(who, xyz, radius, parent, n, o);
+    pnr::RenderTree t;
+    if (!rc) rc = pnr::render_prepare(who, xyz, radius, parent, n, o, t);
+    if (rc) return rc;
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_tree_coverage: no volume set");
+    PNR_HIP(hipSetDevice(c->device));
+    pnr_coverage r;
+    std::memset(&r, 0, sizeof(r));
+    if ((rc = pnr_render_run(c, who, t, c->w, c->h, c->l, c->d_img, o.thr, nullptr, mask_out, residual_out, &r, seg_vox, seg_fg, seg_sum))) return rc;
+    r.covered = r.n_fg ? (double)r.n_both / (double)r.n_fg : 0.0;
+    r.on_signal = r.n_tree ? (double)r.n_both / (double)r.n_tree : 0.0;
+    r.covered_intensity = r.sum_fg ? (double)r.sum_both / (double)r.sum_fg : 0.0;
+    if (cov) *cov = r;
+    return PNR_OK;
+}
+
+// test tap (pnr_hip_test.h): the work items of a render, pure host
+int pnr_render_items(const float *xyz, const float *radius, const int32_t *parent, int64_t n, int64_t w, int64_t h, int64_t l, const pnr_render_opts *opts,
+                     int64_t piece, int64_t box, int64_t *items_out, int64_t cap, int64_t *count)
+{
+    static const char *who = "pnr_render_items";
+    PNR_REQUIRE(count && piece >= 0 && box >= 0 && (cap <= 0 || items_out), PNR_E_ARG, "%s: piece and box (not negative) need a count, and items_out for cap = %lld", who, (long long)cap);
+    const pnr_render_opts o = opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1};
+    int rc = render_tree_ok(who, xyz, radius, parent, n, o);
+    if (!rc) rc = render_grid_ok(who, w, h, l);
+    pnr::RenderTree t;
+    if (!rc) rc = pnr::render_prepare(who, xyz, radius, parent, n, o, t);
+    if (rc) return rc;
+    int64_t k = 0;
+    pnr::render_items(t, w, h, l, piece, box, [&](const pnr::RenderItem &it) {
+        if (k < cap) {
+            const int64_t row[7] = {it.seg, it.x0, it.y0, it.z0, it.x1, it.y1, it.z1};
+            std::copy(row, row + 7, items_out + 7 * k);
+        }
+        k++;
+        return true;
+    });
+    *count = k;
+    return PNR_OK;
+}
+
+// test tap (pnr_hip_test.h): the host's volume writer
+int pnr_test_write_tiff(const char *path, const uint8_t *img, int64_t w, int64_t h, int64_t l)
+{
+    PNR_REQUIRE(path && w >= 1 && h >= 1 && l >= 1, PNR_E_ARG, "pnr_test_write_tiff: a path and sides from 1");
+    const std::string name = path;
+    const bool raw = name.size() > 4 && name.substr(name.size() - 4) == ".raw";
+    std::string err;
+    if (!raw && advantra::tiff_u8_bytes(w, h, l) < 0) img = (const uint8_t *)""; // (refused from the dimensions: never read)
+    PNR_REQUIRE(img, PNR_E_ARG, "pnr_test_write_tiff: null image");
+    PNR_REQUIRE(advantra::save_stack_u8(name, img, w, h, l, err), PNR_E_ARG, "%s", err.c_str());
     return PNR_OK;
 }
 
@@ -1145,6 +1237,8 @@ const OptEntry OPTS[] = {
     {"hess_chunk", &pnr::Options::hess_chunk, nullptr, 0, 1 << 20},
     {"dist_split", &pnr::Options::dist_split, nullptr, 0, 1 << 22}, {"dist_pairs_per_launch", nullptr, &pnr::Options::dist_pairs_per_launch, 0, 1ll << 44},
     {"join_split", &pnr::Options::join_split, nullptr, 0, 1 << 22}, {"join_pairs_per_launch", nullptr, &pnr::Options::join_pairs_per_launch, 0, 1ll << 44},
+    {"render_piece", &pnr::Options::render_piece, nullptr, 0, 1 << 20}, {"render_box", nullptr, &pnr::Options::render_box, 0, 1 << 24},
+    {"render_items_per_launch", nullptr, &pnr::Options::render_items_per_launch, 0, 1 << 24},
 };
 } // namespace
 
@@ -1172,6 +1266,8 @@ int pnr_get_option(pnr_ctx *c, const char *key, int64_t *value)
     if (std::strcmp(key, "recon_timing") == 0) { *value = advantra::recon_timing() ? 1 : 0; return PNR_OK; }
     if (std::strcmp(key, "host_threads_effective") == 0) { *value = pnr::host_threads(c->opt); return PNR_OK; }
     if (std::strcmp(key, "join_rounds") == 0) { *value = c->join_rounds; return PNR_OK; }
+    if (std::strcmp(key, "render_items") == 0) { *value = c->render_items; return PNR_OK; }
+    if (std::strcmp(key, "render_pairs") == 0) { *value = c->render_pairs; return PNR_OK; }
     if (std::strcmp(key, "frangi_recomputes") == 0) { *value = c->frangi_recomputes; return PNR_OK; } // exact Frangi re-runs so far (one pnr_frangi of GPU time each)
     for (const OptEntry &e : OPTS)
         if (std::strcmp(e.key, key) == 0) {
@@ -1346,6 +1442,15 @@ int pnr_get_kernel_ms(pnr_ctx *c, const char *group, double *ms, int64_t *launch
 {
     PNR_REQUIRE(c && group && ms, PNR_E_ARG, "null argument");
     c->resolve_timers();
+    if (std::strcmp(group, "render") == 0) { // the two halves of a render are timed apart
+        double a = 0, b = 0;
+        int64_t la = 0, lb = 0;
+        pnr_get_kernel_ms(c, "render_scatter", &a, &la);
+        pnr_get_kernel_ms(c, "render_finish", &b, &lb);
+        *ms = a + b;
+        if (launches) *launches = la + lb;
+        return PNR_OK;
+    }
     auto it = c->timers.find(group);
     *ms = (it == c->timers.end()) ? 0.0 : it->second.ms;
     if (launches) *launches = (it == c->timers.end()) ? 0 : it->second.launches;

@@ -138,6 +138,9 @@ struct Options {
                                        // reach slice and launch boundaries with them on small inputs
     int join_split = 0;         // the same two for the targets and (point, target) pairs of pnr_nearest_other / pnr_join_trees
     int64_t join_pairs_per_launch = 0;
+    int render_piece = 0;       // pnr_render_tree / pnr_tree_coverage (render.h render_items): xy voxels of a segment's axis per piece (0: automatic, 16),
+    int64_t render_box = 0;     // voxels per item: larger boxes are cut into sub-boxes (0: automatic, 2^15), and
+    int64_t render_items_per_launch = 0; // items per rn_scatter launch (0: automatic, 2^18); none changes a result: tests reach piece, box and launch boundaries with them
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host
@@ -223,6 +226,7 @@ struct pnr_ctx {
     int graph_traces = 0;
     bool have_graph = false;
     int64_t join_rounds = 0; // nearest-other passes of the last pnr_join_trees (pnr_get_option "join_rounds")
+    int64_t render_items = 0, render_pairs = 0; // work items and (voxel, segment) tests of the last render (pnr_get_option "render_items" / "render_pairs")
     std::vector<int32_t> graph_log; // 5 ints per replayed trace (option "trace_log")
 
     // profiling: HIP event pairs recorded on the ctx stream around each kernel group, resolved

@@ -25,6 +25,12 @@
 //   node id of the file without --join) and written in tree order; the comment block gains #join=gap:G,bridges:K,trees:T0->T1.
 //   --join-swc IN.swc OUT.swc [--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]: the same on a file (device -g); one JSON
 //   line {"nodes","trees_in","trees_out","bridges","longest_bridge","rounds"}.
+//   --render-swc IN.swc -i stack [--mask OUT] [--residual OUT] [--per-node FILE.csv] [--zscale Z] [--radius-scale S] [--radius-add A]
+//   [--coverage-threshold T]: the file rendered into the stack on the GPU (pnr_tree_coverage on device -g; the stack goes through the
+//   same volume setup as tracing: --channel, --window / --saturate, --median, --subtract-background); one JSON line with the fields of
+//   pnr_coverage, then "nodes" and "items"; the CSV is `id,vox,fg,sum` per node.  Without -i, -d w,h,l gives the grid and only --mask is
+//   allowed.  While tracing, --mask OUT, --residual OUT and --coverage render the final tree (after --join and --measure-radius, zscale =
+//   zdist) and add #coverage=thr:T,covered:..,on_signal:..,intensity:..,tree_voxels:N to the comment block.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -105,6 +111,9 @@ int main(int argc, char **argv)
     float join_gap = 0.f;
     long join_root_id = 0;
     std::string join_in, join_out;
+    advantra::RenderJob render;
+    std::string mask_out, residual_out;
+    bool coverage = false, render_flag = false, per_node_flag = false;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--info")) { info = true; continue; }
@@ -186,9 +195,36 @@ int main(int argc, char **argv)
             continue;
         }
         if (!strcmp(argv[i], "--per-node")) {
-            if (i + 1 >= argc) { fprintf(stderr, "--per-node PREFIX\n"); return 1; }
+            if (i + 1 >= argc) { fprintf(stderr, "--per-node PREFIX (--distance) or FILE.csv (--render-swc)\n"); return 1; }
             per_node = argv[++i];
-            dist_flag = true;
+            per_node_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--render-swc")) {
+            if (i + 1 >= argc || argv[i + 1][0] == '-') { fprintf(stderr, "--render-swc IN.swc\n"); return 1; }
+            render.swc = argv[++i];
+            continue;
+        }
+        if (!strcmp(argv[i], "--mask") || !strcmp(argv[i], "--residual")) {
+            const bool m = !strcmp(argv[i], "--mask");
+            if (i + 1 >= argc || argv[i + 1][0] == '-') { fprintf(stderr, "%s OUT: a .tif or .raw file name\n", argv[i]); return 1; }
+            (m ? mask_out : residual_out) = argv[++i];
+            continue;
+        }
+        if (!strcmp(argv[i], "--coverage")) { coverage = true; continue; }
+        if (!strcmp(argv[i], "--radius-scale") || !strcmp(argv[i], "--radius-add")) {
+            const bool sc = !strcmp(argv[i], "--radius-scale");
+            float v = 0;
+            if (!parse_float(i + 1 < argc ? argv[++i] : "", v) || (sc && v < 0)) { fprintf(stderr, "%s\n", sc ? "--radius-scale S: a number, 0 or more" : "--radius-add A: a number"); return 1; }
+            (sc ? render.opts.rscale : render.opts.radd) = v;
+            render_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--coverage-threshold")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--coverage-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+            render.opts.thr = (int32_t)v;
+            render_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--median")) {
@@ -253,10 +289,26 @@ int main(int argc, char **argv)
         advantra::print_flags();
         return 0;
     }
-    if ((dist_flag && !distance) || (zscale_flag && !distance && join_in.empty())) { fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc)\n"); return 1; }
+    const bool rendering = !render.swc.empty();
+    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering) || (zscale_flag && !distance && join_in.empty() && !rendering)) {
+        fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc; --zscale, --per-node: or --render-swc)\n");
+        return 1;
+    }
+    if (render_flag && !rendering) { fprintf(stderr, "--radius-scale / --radius-add / --coverage-threshold need --render-swc IN.swc\n"); return 1; }
     if (join_flag && !join_given && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (rendering) {
+        if (distance || !join_in.empty() || coverage) { fprintf(stderr, "--render-swc: not with --distance, --join-swc or --coverage (the JSON line has the coverage)\n"); return 1; }
+        if (infiles.empty() && (mask_out.empty() || !residual_out.empty() || !per_node.empty() || render.opts.thr != -1)) {
+            fprintf(stderr, "--render-swc without -i: -d w,h,l gives the grid and only --mask OUT is allowed (and needed)\n");
+            return 1;
+        }
+        render.mask = mask_out, render.residual = residual_out, render.per_node = per_node, render.opts.zscale = dist_opts.zscale;
+        return advantra::render_swc_file(render, infiles, raw_dims, device) ? 0 : 1;
+    }
+    if ((!mask_out.empty() || !residual_out.empty() || coverage) && (distance || !join_in.empty() || info)) { fprintf(stderr, "--mask / --residual / --coverage need a tracing run or --render-swc IN.swc\n"); return 1; }
+    S0.mask_out = mask_out, S0.residual_out = residual_out, S0.coverage = coverage;
     if (!join_in.empty()) return advantra::join_swc_file(join_in, join_out, join_gap, dist_opts.zscale, join_root_id, join_keep_largest, device) ? 0 : 1;
     if (join_given) S0.join = true, S0.join_gap = join_gap, S0.join_root_id = join_root_id, S0.join_keep_largest = join_keep_largest;
     if (distance) return advantra::print_tree_distance(dist_a, dist_b, dist_opts, device, per_node) ? 0 : 1;

@@ -1,6 +1,7 @@
 // advantra_host.cpp -- see advantra_host.h.  Host orchestration only: every compute stage is a call
 // through the C ABI into libpnr_hip.so.
 #include "advantra_host.h"
+#include "stack_io.h"
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -63,6 +64,16 @@ void print_flags()
     printf("  --join-root soma|ID       the root: the first soma node if there is one (default), or the node with this id in the file without --join\n");
     printf("  --join-keep-largest       write only the largest component (the root's, if a root is given)\n");
     printf("--join-swc IN.swc OUT.swc the same on an SWC file ([--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]); one JSON line\n");
+    printf("--render-swc IN.swc       render an SWC file into the stack given with -i (the same volume setup as tracing) on the GPU; one JSON line with\n");
+    printf("                          the coverage counts: how much of the foreground the tree covers, how much of the tree lies on signal\n");
+    printf("  --mask OUT                write the mask (255 under the tree) as a multi-page 8-bit TIFF, or bare bytes for a .raw name\n");
+    printf("  --residual OUT            write the stack with the tree's voxels set to 0: the signal the trace does not explain\n");
+    printf("  --per-node FILE.csv       `id,vox,fg,sum` per node: its voxels, the foreground among them, their summed intensity\n");
+    printf("  --zscale Z | --radius-scale S | --radius-add A   z and the radii as rendered: z * Z, max(radius * S + A, 0)\n");
+    printf("  --coverage-threshold T    foreground from T on, 0..255 (default -1: the stack's mean)\n");
+    printf("                          without -i: -d w,h,l gives the grid and only --mask is allowed\n");
+    printf("--mask OUT | --residual OUT | --coverage   while tracing: the final tree rendered on the traced stack (zscale = zdist); the comment block\n");
+    printf("                          gains #coverage=thr:T,covered:..,on_signal:..,intensity:..,tree_voxels:N\n");
     printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
     printf("--median 2d|3d            pre-filter: 3 x 3 median in every slice, or 3 x 3 x 3 (on the GPU, before tracing; default: off)\n");
     printf("--subtract-background R   pre-filter: top-hat with a flat box of half-width R in xy and R / zdist in z, 1..%d (after the median)\n", PNR_TOPHAT_MAX_R);
@@ -527,6 +538,107 @@ bool join_swc_file(const std::string &in, const std::string &out, float gap, flo
     return true;
 }
 
+bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device)
+{
+    SwcTree T;
+    std::string err;
+    if (!load_swc(job.swc, T, err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    auto lib_fail = [](const char *what) {
+        fprintf(stderr, "%s: %s\n", what, pnr_last_error());
+        return false;
+    };
+    auto write_stack = [&](const std::string &name, const std::vector<unsigned char> &vol, long long w, long long h, long long l) {
+        std::string e;
+        if (save_stack_u8(name, vol.data(), w, h, l, e)) return true;
+        fprintf(stderr, "%s\n", e.c_str());
+        return false;
+    };
+    const Settings &S = settings();
+    const int64_t n = T.n();
+    pnr_params p;
+    pnr_default_params(&p);
+    if (job.opts.zscale >= 1.f) p.zdist = job.opts.zscale; // (the z half-width of --subtract-background)
+    int64_t items = 0;
+    if (infiles.empty()) { // the mask alone, on the grid of -d
+        long long w = 0, h = 0, l = 0;
+        if (sscanf(raw_dims.c_str(), "%lld,%lld,%lld", &w, &h, &l) != 3 || w <= 0 || h <= 0 || l <= 0) {
+            fprintf(stderr, "--render-swc without -i needs the grid: -d w,h,l\n");
+            return false;
+        }
+        std::string e;
+        if (job.mask.size() > 4 && job.mask.substr(job.mask.size() - 4) != ".raw" && tiff_u8_bytes(w, h, l) < 0 && !save_stack_u8(job.mask, nullptr, w, h, l, e)) {
+            fprintf(stderr, "%s\n", e.c_str()); // (refused from the dimensions, before any GPU work)
+            return false;
+        }
+        pnr_ctx *ctx = nullptr;
+        if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+        std::vector<unsigned char> mask((size_t)(w * h * l));
+        const int rc = pnr_render_tree(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), n, w, h, l, &job.opts, nullptr, mask.data());
+        pnr_get_option(ctx, "render_items", &items);
+        pnr_destroy(ctx);
+        if (rc != PNR_OK) return lib_fail("pnr_render_tree");
+        if (!write_stack(job.mask, mask, w, h, l)) return false;
+        long long n_tree = 0;
+        for (unsigned char v : mask) n_tree += v != 0;
+        printf("{\"n_vox\": %lld, \"n_tree\": %lld, \"nodes\": %lld, \"items\": %lld}\n", w * h * l, n_tree, (long long)n, (long long)items);
+        return true;
+    }
+    Stack st;
+    if (!load_stack(infiles[0], raw_dims, st, err, S.channel - 1, S.raw_u16)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    if (S.windowed && st.bits != 16) {
+        fprintf(stderr, "--window / --saturate need a 16-bit stack (8-bit input is never windowed)\n");
+        return false;
+    }
+    pnr_ctx *ctx = nullptr;
+    if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+    // the volume as it would be traced: windowed to 8 bits, then pre-filtered
+    bool ok = (st.bits == 16 ? pnr_set_volume_u16(ctx, st.samples16(), st.w, st.h, st.l, 1, 0, S.windowed ? &S.window : nullptr, nullptr, nullptr)
+                             : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
+    if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
+    if (!ok) {
+        lib_fail("volume");
+        pnr_destroy(ctx);
+        return false;
+    }
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<unsigned char> mask(job.mask.empty() ? 0 : N), residual(job.residual.empty() ? 0 : N);
+    std::vector<int64_t> vox, fg, sum;
+    if (!job.per_node.empty()) vox.assign((size_t)n, 0), fg.assign((size_t)n, 0), sum.assign((size_t)n, 0);
+    pnr_coverage c;
+    const int rc = pnr_tree_coverage(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), n, &job.opts, &c, job.per_node.empty() ? nullptr : vox.data(),
+                                     job.per_node.empty() ? nullptr : fg.data(), job.per_node.empty() ? nullptr : sum.data(),
+                                     job.mask.empty() ? nullptr : mask.data(), job.residual.empty() ? nullptr : residual.data());
+    pnr_get_option(ctx, "render_items", &items);
+    pnr_destroy(ctx);
+    if (rc != PNR_OK) return lib_fail("pnr_tree_coverage");
+    if (!job.mask.empty() && !write_stack(job.mask, mask, st.w, st.h, st.l)) return false;
+    if (!job.residual.empty() && !write_stack(job.residual, residual, st.w, st.h, st.l)) return false;
+    if (!job.per_node.empty()) {
+        FILE *f = fopen(job.per_node.c_str(), "w");
+        if (!f) {
+            fprintf(stderr, "%s: cannot write the file\n", job.per_node.c_str());
+            return false;
+        }
+        fprintf(f, "id,vox,fg,sum\n");
+        for (size_t k = 0; k < (size_t)n; k++) fprintf(f, "%lld,%lld,%lld,%lld\n", T.id[k], (long long)vox[k], (long long)fg[k], (long long)sum[k]);
+        if (fclose(f) != 0) {
+            fprintf(stderr, "%s: write failed\n", job.per_node.c_str());
+            return false;
+        }
+    }
+    printf("{\"n_vox\": %lld, \"n_tree\": %lld, \"n_fg\": %lld, \"n_both\": %lld, \"sum_fg\": %lld, \"sum_both\": %lld, \"thr_used\": %d, \"covered\": %.17g, "
+           "\"on_signal\": %.17g, \"covered_intensity\": %.17g, \"nodes\": %lld, \"items\": %lld}\n",
+           (long long)c.n_vox, (long long)c.n_tree, (long long)c.n_fg, (long long)c.n_both, (long long)c.sum_fg, (long long)c.sum_both, (int)c.thr_used, c.covered,
+           c.on_signal, c.covered_intensity, (long long)n, (long long)items);
+    return true;
+}
+
 Stack::~Stack()
 {
     if (view) munmap((void *)view, map_len);
@@ -646,9 +758,9 @@ int parse_params(const std::vector<std::string> &paras, pnr_params &p, std::stri
 
 // window: the (lo, hi) a 16-bit stack was windowed with (nullptr: 8-bit input); radius_thr: the threshold the radii were measured
 // with (nullptr: not measured; 0: the relative mode)
-// join: the result of a --join run (nullptr: not joined)
+// join: the result of a --join run (nullptr: not joined); cover: the result of a --mask / --residual / --coverage run (nullptr: none)
 static std::string swc_comment(const std::vector<std::string> &paras, const pnr_params &p, const int32_t *window, const int32_t *radius_thr = nullptr,
-                               const Result *join = nullptr)
+                               const Result *join = nullptr, const Result *cover = nullptr)
 {
     static const char *keys[] = {"neuritesigmas", "somaradius", "tolerance", "znccth", "kappa", "step", "ni", "np", "zdist", "nodepervol", "vol"};
     std::stringstream c;
@@ -671,6 +783,12 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         if (ro.rel_pct > 0) c << "rel:" << ro.rel_pct;
         else c << *radius_thr;
         c << ",rmax=" << ro.rmax << ",bg=" << ro.bg_permille;
+    }
+    if (cover && cover->have_coverage) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "\n#coverage=thr:%d,covered:%.6f,on_signal:%.6f,intensity:%.6f,tree_voxels:%lld", (int)cover->coverage.thr_used, cover->coverage.covered,
+                 cover->coverage.on_signal, cover->coverage.covered_intensity, (long long)cover->coverage.n_tree);
+        c << buf;
     }
     return c.str();
 }
@@ -1055,9 +1173,49 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
             fprintf(stderr, "[pnr host] radius: %.3f s, kernels %.3f ms in %lld launches\n", R.t_radius, ms, (long long)launches);
         }
     }
+    if (!settings().mask_out.empty() || !settings().residual_out.empty() || settings().coverage) { // the final tree rendered on the traced volume
+        const auto tr = clk::now();
+        const Settings &S = settings();
+        const int64_t n = (int64_t)R.tree.size() - 1; // without the dummy
+        std::vector<float> xyz((size_t)(3 * std::max<int64_t>(n, 0))), rad((size_t)std::max<int64_t>(n, 0));
+        std::vector<int32_t> par((size_t)std::max<int64_t>(n, 0));
+        for (int64_t i = 0; i < n; i++) {
+            const pnr_node &nd = R.tree[(size_t)i + 1];
+            xyz[(size_t)(3 * i)] = nd.x, xyz[(size_t)(3 * i + 1)] = nd.y, xyz[(size_t)(3 * i + 2)] = nd.z;
+            par[(size_t)i] = R.parent[(size_t)i + 1] > 0 ? R.parent[(size_t)i + 1] - 1 : -1;
+            rad[(size_t)i] = (!radius.empty() && radius[(size_t)i + 1] >= 0.f) ? radius[(size_t)i + 1] : 1.f * nd.sig; // what save_treelist writes
+        }
+        const size_t N = (size_t)(w * h * l);
+        std::vector<unsigned char> mask(S.mask_out.empty() ? 0 : N), residual(S.residual_out.empty() ? 0 : N);
+        const pnr_render_opts ro = {p.zdist, 1.f, 0.f, -1};
+        if (S.timing) pnr_set_profiling(ctx, 1);
+        std::string werr;
+        bool rok = pnr_tree_coverage(ctx, xyz.data(), rad.data(), par.data(), std::max<int64_t>(n, 0), &ro, &R.coverage, nullptr, nullptr, nullptr,
+                                     S.mask_out.empty() ? nullptr : mask.data(), S.residual_out.empty() ? nullptr : residual.data()) == PNR_OK;
+        if (!rok) werr = pnr_last_error();
+        rok = rok && (S.mask_out.empty() || save_stack_u8(S.mask_out, mask.data(), w, h, l, werr));
+        rok = rok && (S.residual_out.empty() || save_stack_u8(S.residual_out, residual.data(), w, h, l, werr));
+        if (!rok) {
+            fprintf(stderr, "%s\n", werr.c_str());
+            pnr_destroy(ctx);
+            return false;
+        }
+        R.have_coverage = true;
+        R.t_render = secs(tr, clk::now());
+        printf("render... %lld tree voxels, covered %.4f, on signal %.4f, intensity %.4f (threshold %d), %g sec.\n", (long long)R.coverage.n_tree, R.coverage.covered,
+               R.coverage.on_signal, R.coverage.covered_intensity, (int)R.coverage.thr_used, R.t_render);
+        if (S.timing) {
+            double ms = 0;
+            int64_t launches = 0;
+            pnr_get_kernel_ms(ctx, "render", &ms, &launches);
+            pnr_set_profiling(ctx, 0);
+            fprintf(stderr, "[pnr host] render: %.3f s, kernels %.3f ms in %lld launches\n", R.t_render, ms, (long long)launches);
+        }
+        t5 = clk::now();
+    }
     R.swc_path = inimg_file + (settings().single_tree ? "_Advantra1.swc" : "_Advantra.swc"); // :2152 / :2164
     save_treelist(R.tree, R.parent, R.swc_path, -1, 1.f, "Advantra",
-                  swc_comment(paras, p, data16 ? window : nullptr, settings().measure_radius ? &R.radius_thr : nullptr, settings().join ? &R : nullptr),
+                  swc_comment(paras, p, data16 ? window : nullptr, settings().measure_radius ? &R.radius_thr : nullptr, settings().join ? &R : nullptr, &R),
                   radius.empty() ? nullptr : &radius);
     if (settings().save_midres) { // the saveMidres taps of reconstruct() (:2098-2141)
         save_nodelist(R.nodes, R.links, inimg_file + "_n0_.swc");

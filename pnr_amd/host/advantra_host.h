@@ -41,6 +41,9 @@ struct Result {
     int32_t radius_thr = 0;        // ... the threshold it used (0: the relative mode)
     long long join_bridges = 0, join_trees_in = 0, join_trees_out = 0; // --join: what pnr_join_trees reported
     double t_join = 0;
+    bool have_coverage = false;    // --mask / --residual / --coverage: the final tree rendered on the traced volume (pnr_tree_coverage)
+    pnr_coverage coverage = {};
+    double t_render = 0;
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
     double t_filter = 0;           // --median / --subtract-background: the pre-filter (part of t_setup)
@@ -89,6 +92,12 @@ struct Settings {
     bool join = false, join_keep_largest = false;
     float join_gap = 0.f;
     long long join_root_id = 0; // 0: the first soma node, if any
+    // --mask OUT, --residual OUT, --coverage: the final tree -- after --join and --measure-radius, with the f32 radius each SWC line is
+    // written from and zscale = zdist -- is rendered on the traced volume (pnr_tree_coverage): OUT receives the mask (255 under the
+    // tree) / the residual (the volume where the tree is not) as a stack (save_stack_u8), and the comment block gains a #coverage= line.
+    // The reference has no counterpart.
+    std::string mask_out, residual_out;
+    bool coverage = false;
 };
 Settings &settings();
 
@@ -124,6 +133,16 @@ bool print_tree_distance(const std::string &a, const std::string &b, const pnr_d
 // type and radius columns carried over and a #join= comment line; root_id: an SWC id of IN (0: none); keep_largest: component 0 only.
 // Prints one JSON line {"nodes", "trees_in", "trees_out", "bridges", "longest_bridge", "rounds"}.
 bool join_swc_file(const std::string &in, const std::string &out, float gap, float zscale, long long root_id, bool keep_largest, int device);
+// advantra_cli --render-swc IN.swc: the file rendered into a stack (pnr_tree_coverage on `device`).  With a stack (infiles[0]; the same
+// volume setup as tracing: channel, window, pre-filters of settings()) the tree is measured on what would be traced: `mask` / `residual`
+// (not empty) are written with save_stack_u8, `per_node` is a CSV `id,vox,fg,sum` per node under a header line, and one JSON line has
+// the fields of pnr_coverage, then "nodes" and "items".  Without a stack, raw_dims = "w,h,l" gives the grid and only the mask is
+// written (pnr_render_tree); the JSON line is {"n_vox", "n_tree", "nodes", "items"}.
+struct RenderJob {
+    std::string swc, mask, residual, per_node;
+    pnr_render_opts opts = {1.f, 1.f, 0.f, -1};
+};
+bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

@@ -78,6 +78,24 @@ BRIDGE = np.dtype([("lo", np.int32), ("hi", np.int32), ("d", np.float32)])  # pn
 PNR_JOIN_MAX_N = 1 << 22
 
 
+class RenderOpts(C.Structure):
+    """pnr_render_opts (include/pnr_hip.h): zscale > 0 (z *= zscale first), rr = max(radius * rscale + radd, 0), thr -1..255 (-1: the global mean)"""
+    _fields_ = [("zscale", C.c_float), ("rscale", C.c_float), ("radd", C.c_float), ("thr", C.c_int32)]
+
+
+class Coverage(C.Structure):
+    """pnr_coverage: the exact counts of a tree rendered on the context's volume and the three ratios derived from them"""
+    _fields_ = [("n_vox", C.c_int64), ("n_tree", C.c_int64), ("n_fg", C.c_int64), ("n_both", C.c_int64), ("sum_fg", C.c_int64), ("sum_both", C.c_int64),
+                ("thr_used", C.c_int32), ("pad", C.c_int32), ("covered", C.c_double), ("on_signal", C.c_double), ("covered_intensity", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+PNR_RENDER_MAX_N = 1 << 22
+PNR_RENDER_MAX_R = 1024
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -150,6 +168,10 @@ def load():
     L.pnr_nearest_other.argtypes = [vp, vp, vp, i64, vp, vp]
     L.pnr_join_trees.argtypes = [vp, vp, vp, i64, C.POINTER(JoinOpts), vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.pnr_join_reroot.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
+    L.pnr_render_tree.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), vp, vp]
+    L.pnr_tree_coverage.argtypes = [vp, vp, vp, vp, i64, C.POINTER(RenderOpts), C.POINTER(Coverage), vp, vp, vp, vp, vp]
+    L.pnr_render_items.argtypes = [vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), i64, i64, vp, i64, C.POINTER(i64)]
+    L.pnr_test_write_tiff.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.pnr_pair_tiles.argtypes = [i64, i64, i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_live_bytes.argtypes = [C.POINTER(i64), C.POINTER(i64)]
@@ -213,7 +235,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -222,7 +244,7 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
                    "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes"]
+                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes", "pnr_render_items", "pnr_test_write_tiff"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -419,6 +441,39 @@ class Context:
             cap = nb.value
         res = (out[0], out[1], out[2], bridges[:nb.value].copy())
         return res + ({"trees_in": t0.value, "trees_out": t1.value, "rounds": self.get_option("join_rounds")},) if counts else res
+
+    def render_tree(self, xyz, radius, parent, shape, zscale=1, rscale=1, radd=0, labels=True, mask=False):
+        """pnr_render_tree of a tree (n x 3 positions, n radii in xy voxels, parent indices with a negative value for none) on the grid
+        shape = (l, h, w) -> labels int32[l, h, w] (1 + the smallest node whose segment to its parent holds the voxel, 0: none), or the
+        mask uint8[l, h, w] (255 under the tree), or (labels, mask) when both are asked for.  Needs no volume."""
+        xyz, radius, parent = _tree_arrays("render_tree", xyz, radius, parent)
+        l, h, w = (int(v) for v in shape)
+        o = RenderOpts(float(zscale), float(rscale), float(radd), -1)
+        lab = np.empty((l, h, w), np.int32) if labels else None
+        msk = np.empty((l, h, w), np.uint8) if mask else None
+        check(self.L.pnr_render_tree(self.h, xyz.ctypes.data, radius.ctypes.data, parent.ctypes.data, len(xyz), w, h, l, C.byref(o),
+                                     lab.ctypes.data if labels else None, msk.ctypes.data if mask else None))
+        return (lab, msk) if labels and mask else lab if labels else msk
+
+    def tree_coverage(self, xyz, radius, parent, zscale=1, rscale=1, radd=0, thr=-1, per_node=False, mask=False, residual=False):
+        """pnr_tree_coverage: the tree rendered on the context's volume V -> a dict {n_vox, n_tree, n_fg, n_both, sum_fg, sum_both, thr_used,
+        covered, on_signal, covered_intensity} (foreground: V >= thr; thr = -1: the global mean); per_node adds "seg_vox", "seg_fg",
+        "seg_sum" (int64[n]: the voxels labelled with the node, the foreground among them, the sum of V over them), mask adds "mask"
+        (uint8, 255 under the tree), residual adds "residual" (V where the tree is not, else 0)"""
+        xyz, radius, parent = _tree_arrays("tree_coverage", xyz, radius, parent)
+        o = RenderOpts(float(zscale), float(rscale), float(radd), int(thr))
+        cov = Coverage()
+        out = {}
+        if per_node:
+            out.update({k: np.zeros(len(xyz), np.int64) for k in ("seg_vox", "seg_fg", "seg_sum")})
+        if mask:
+            out["mask"] = np.empty(self.shape, np.uint8)
+        if residual:
+            out["residual"] = np.empty(self.shape, np.uint8)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        check(self.L.pnr_tree_coverage(self.h, xyz.ctypes.data, radius.ctypes.data, parent.ctypes.data, len(xyz), C.byref(o), C.byref(cov), ptr("seg_vox"),
+                                       ptr("seg_fg"), ptr("seg_sum"), ptr("mask"), ptr("residual")))
+        return {**cov.as_dict(), **out}
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
@@ -846,6 +901,53 @@ def join_reroot(parent, bridges=(), root=-1):
     check(L.pnr_join_reroot(parent.ctypes.data, len(parent), bridges.ctypes.data if len(bridges) else None, len(bridges), int(root),
                             out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
     return tuple(out)
+
+
+def _tree_arrays(who, xyz, radius, parent):
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    radius = np.ascontiguousarray(radius, np.float32).reshape(-1)
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    if len(parent) != len(xyz) or len(radius) != len(xyz):
+        raise PnrError(f"{who}: one radius and one parent per node")
+    return xyz, radius, parent
+
+
+def render_items(xyz, radius, parent, shape, zscale=1, rscale=1, radd=0, piece=0, box=0):
+    """test tap pnr_render_items (pure host; no GPU needed): the work items of render_tree on the grid shape = (l, h, w) with the options
+    render_piece = piece and render_box = box -> int64[items, 7] of (segment, x0, y0, z0, x1, y1, z1), the box inclusive"""
+    L = load()
+    xyz, radius, parent = _tree_arrays("render_items", xyz, radius, parent)
+    l, h, w = (int(v) for v in shape)
+    o = RenderOpts(float(zscale), float(rscale), float(radd), -1)
+    k = C.c_int64()
+    args = (xyz.ctypes.data, radius.ctypes.data, parent.ctypes.data, len(xyz), w, h, l, C.byref(o), int(piece), int(box))
+    check(L.pnr_render_items(*args, None, 0, C.byref(k)))
+    items = np.zeros((k.value, 7), np.int64)
+    check(L.pnr_render_items(*args, items.ctypes.data, k.value, C.byref(k)))
+    return items
+
+
+def write_tiff(path, img):
+    """test tap pnr_test_write_tiff (pure host): the host's volume writer on a uint8 (l, h, w) stack -- a multi-page TIFF, or bare bytes
+    for a .raw name"""
+    img = np.ascontiguousarray(img, np.uint8)
+    l, h, w = img.shape
+    check(load().pnr_test_write_tiff(os.fsencode(path), img.ctypes.data, w, h, l))
+
+
+def read_swc_nodes(path):
+    """an SWC file with all its columns, read by the rules of read_swc -> (xyz float32[n, 3], radius float32[n], type int32[n], parent
+    int32[n] (index among the nodes, -1: none), ids int64[n])"""
+    xyz, parent, ids = read_swc(path)
+    radius, typ = [], []
+    with open(path) as f:
+        for line in f:
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            typ.append(int(float(t[1])))
+            radius.append(float(t[5]))
+    return xyz, np.array(radius, np.float64).astype(np.float32).reshape(-1), np.array(typ, np.int32).reshape(-1), parent, ids
 
 
 def read_swc(path):
