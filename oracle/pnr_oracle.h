@@ -120,6 +120,7 @@ int64_t orc_replay_soma(const float *seeds, int64_t nseeds, const int *T, const 
                         int64_t *nlinks, int64_t *ntraces_used);
 
 /* ---------- 2-D Frangi for single-slice stacks, pnr_oracle_2d.c ---------- */
+void orc_imgaussian2d(const uint8_t *I, int w, int h, float sig, float *F); /* the smoothed slice orc_hessian2d differentiates */
 void orc_hessian2d(const uint8_t *I, int w, int h, float sig, float *Dyy, float *Dxy, float *Dxx);
 void orc_frangi2d(const uint8_t *I, int w, int h, const float *sigs, int nsig, float BetaOne, float BetaTwo,
                   float *J, float *Jmin, float *Jmax, uint8_t *Vx, uint8_t *Vy, uint8_t *Vz);

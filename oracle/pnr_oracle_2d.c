@@ -39,6 +39,8 @@ static void imgaussian2d(const uint8_t *I, int w, int h, float sig, float *F)
     free(G);
 }
 
+void orc_imgaussian2d(const uint8_t *I, int w, int h, float sig, float *F) { imgaussian2d(I, w, h, sig, F); }
+
 /* derivative along y (stride w) or x (stride 1), one-sided at the borders; .5*(a-b) is an exact scaling of the f32 difference */
 static void diff_axis(const float *F, float *D, int w, int h, int along_y)
 {

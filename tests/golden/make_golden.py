@@ -112,8 +112,35 @@ def ref_cases():
     print("ref_cases", len(out), "arrays", os.path.getsize(os.path.join(HERE, "ref_cases.npz")) // 1024, "KiB")
 
 
+def ref_radii():
+    """ref_radii.npz: the reference's outputs at the Gaussian radii ref_cases.npz leaves out (test_oracle_golden.py GAUSS_RADII,
+    ERODE_RADII, ERODE_FLAT, F2D_RADII), recorded like ref_cases.npz"""
+    import test_oracle_golden as t
+    R = orc.load_ref()
+    assert R is not None, "oracle/_ref/libpnr_ref.so missing (needs the reference sources)"
+    out = {}
+
+    def put(key, d):
+        out.update({key + "__" + k: np.asarray(v) for k, v in d.items()})
+
+    for sig, zdist in t.GAUSS_RADII:
+        put("gauss_s%.4g_z%g" % (sig, zdist), t.gauss_radii_reference(R, t.gauss_radii_input(), sig, zdist))
+    for rad in t.ERODE_RADII:
+        put("erode_r%d" % rad, t.erode_reference(R, t.erode_radii_input(), rad))
+    for value, _ in t.ERODE_FLAT:
+        put("flat_%d" % value, t.erode_reference(R, np.full((4, 40, 70), value, np.uint8), 2))
+    for L in t.F2D_RADII:
+        put("h2d_L%d" % L, t.hessian2d_radii_reference(R, np.random.default_rng(12).integers(0, 256, (1, 9, 70), dtype=np.uint8), (L - 0.5) / 3))
+    np.savez_compressed(os.path.join(HERE, "ref_radii.npz"), **out)
+    print("ref_radii", len(out), "arrays", os.path.getsize(os.path.join(HERE, "ref_radii.npz")) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    # python tests/golden/make_golden.py [ref_cases]: every fixture, or ref_cases.npz alone
-    if sys.argv[1:] != ["ref_cases"]:
-        main()
-    ref_cases()
+    # python tests/golden/make_golden.py [ref_cases | ref_radii]: every fixture, or one of the two recorded-case files alone
+    if sys.argv[1:] == ["ref_radii"]:
+        ref_radii()
+    else:
+        if sys.argv[1:] != ["ref_cases"]:
+            main()
+        ref_cases()
+        ref_radii()

@@ -20,7 +20,8 @@ def _build():
 
 def load_oracle():
     path = os.path.join(ORC_DIR, "liborc.so")
-    if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(os.path.join(ORC_DIR, "pnr_oracle.c")):
+    srcs = [os.path.join(ORC_DIR, f) for f in os.listdir(ORC_DIR) if f.startswith("pnr_oracle")]
+    if not os.path.exists(path) or os.path.getmtime(path) < max(map(os.path.getmtime, srcs)):
         _build()
     L = C.CDLL(path)
     L.orc_imgaussian3d.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, f32p]
@@ -64,6 +65,7 @@ def load_oracle():
     L.orc_replay.restype = C.c_int64
     L.orc_frangi2d.argtypes = [u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float, C.c_float, f32p, C.POINTER(C.c_float), C.POINTER(C.c_float), u8p, u8p, u8p]
     L.orc_hessian2d.argtypes = [u8p, C.c_int, C.c_int, C.c_float, f32p, f32p, f32p]
+    L.orc_imgaussian2d.argtypes = [u8p, C.c_int, C.c_int, C.c_float, f32p]
     L.orc_tracker_new2.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_uint32, C.c_int]
     L.orc_tracker_new2.restype = C.c_void_p

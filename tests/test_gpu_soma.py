@@ -16,24 +16,115 @@ def _stack(shape=(32, 56, 64), seed=2, somas=((20, 28, 16, 6), (48, 20, 14, 5)))
     return synth.add_somas(synth.synth(w, h, l, seed=seed), somas)
 
 
-@pytest.mark.parametrize("shape,rad,somas", [((32, 56, 64), 3, ((20, 28, 16, 6), (48, 20, 14, 5))), ((9, 20, 23), 2, ((10, 10, 4, 4),)),
-                                             ((24, 40, 48), 4, ())])
-def test_soma_extraction_vs_oracle(oracle, shape, rad, somas):
-    img = _stack(shape, 3, somas)
+def _soma_vs_oracle(oracle, img, rad):
+    """pnr_soma on `img` equals the oracle's soma path: eroded + blurred stack, threshold, the label map as (voxel, label) pairs in
+    raster order and the four node columns; the threshold is the one of E8's histogram with every voxel counted once.  Returns
+    the oracle's (E8, threshold, node columns, foreground voxels)"""
     E8o, tho, smapo, n4o = orc.soma_extract(oracle, img, rad)
     c = pnr_amd.Context(pnr_amd.make_params(sigmas=[2.0], somaradius=rad, np_=20, ni=5), 0)
     c.set_volume(img)
     s = c.soma(want_e8=True)
+    c.close()
     assert np.array_equal(s["E8"], E8o)
     assert s["threshold"] == tho
+    hist = np.bincount(s["E8"].reshape(-1), minlength=256).astype(np.int64)
+    assert hist.sum() == img.size and oracle.orc_maxentropy_hist(hist) == s["threshold"]
+    assert oracle.orc_maxentropy_th(np.ascontiguousarray(s["E8"]).reshape(-1), img.size) == s["threshold"]
     assert len(s["nodes"]) == len(n4o)
     got4 = np.stack([s["nodes"][k] for k in ("x", "y", "z", "sig")], -1) if len(n4o) else np.zeros((0, 4), np.float32)
     assert np.array_equal(got4, n4o)
     assert np.all(s["nodes"]["type"] == 1) and np.all(s["nodes"]["corr"] == -np.finfo(np.float32).max)
     fg = np.flatnonzero(smapo.reshape(-1) > 0)
     assert np.array_equal(s["vox"], fg) and np.array_equal(s["lab"], smapo.reshape(-1)[fg])
+    return E8o, tho, n4o, fg
+
+
+@pytest.mark.parametrize("shape,rad,somas", [((32, 56, 64), 3, ((20, 28, 16, 6), (48, 20, 14, 5))), ((9, 20, 23), 2, ((10, 10, 4, 4),)),
+                                             ((24, 40, 48), 4, ())])
+def test_soma_extraction_vs_oracle(oracle, shape, rad, somas):
+    img = _stack(shape, 3, somas)
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, rad)
     if somas:
         assert len(n4o) >= 1 and len(fg) > 20
+
+
+@pytest.mark.parametrize("rad", [1, 5, 6, 8, 21])
+def test_soma_radii_vs_oracle(oracle, rad):
+    """the radii the other cases leave out, up to the largest validate() accepts, on 130 x 70 x 12: three x tiles of
+    gauss_y_trunc_hist (the last two columns wide), three ballots a row in row_count / row_compact, and -- radii 6, 12, 18 and 24
+    of the Gaussian at somaradius 2, 4, 6, 8 being the templated ones -- at 6 and 8 an interior, whole-dword tile of
+    gauss_x_u8_t<18> / <24>, which Frangi's own dispatch never hands these radii to.  Two of the three cell bodies are cut by the
+    border of the stack"""
+    img = synth.add_somas(synth.synth(130, 70, 12, seed=2), ((5, 5, 3, rad + 3), (100, 40, 6, rad + 4), (127, 66, 10, rad + 2)))
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, rad)
+    assert len(n4o) >= 2 and len(fg) > 0
+
+
+@pytest.mark.parametrize("rad", [2, 4])
+def test_soma_templated_x_pass_interior_tile(oracle, rad):
+    """gauss_x_u8_t<6> / <12> (somaradius 2 / 4; Frangi runs these radii in its fused kernels) on a stack wide enough for an
+    interior tile that reads whole dwords, with a ragged last tile and a body on the right border"""
+    img = synth.add_somas(synth.synth(130, 70, 12, seed=2), ((5, 5, 3, rad + 3), (100, 40, 6, rad + 4), (127, 66, 10, rad + 2)))
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, rad)
+    assert len(n4o) >= 2 and len(fg) > 0
+
+
+@pytest.mark.parametrize("rad", [2, 4, 6, 8])
+def test_soma_templated_x_pass_random_bytes(oracle, rad):
+    """the four radii of gauss_x_u8_t on random bytes of 90 and more: the eroded stack is nowhere zero, so every tile of the x pass
+    -- border, interior (whole dwords) and the ragged last one -- and its second, one-row tile of rows (5 x 13 = 65 rows) sums data"""
+    img = np.random.default_rng([9, rad]).integers(90, 256, (5, 13, 130), dtype=np.uint8)
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, rad)
+    assert E8o.min() > 0 and len(np.unique(E8o)) > 3
+
+
+@pytest.mark.parametrize("shape,rad", [((3, 7, 9), 8), ((2, 33, 40), 21)])
+def test_soma_window_wider_than_stack(oracle, shape, rad):
+    """erosion and blur windows wider than the stack in x and in y: most taps are clamped ones.  Each plane has a positive minimum of
+    its own, so the eroded stack is not empty -- but at radius 21 (127 taps, the running sum cut to a byte after each) the plane whose
+    minimum is 40 blurs to 0: every product is below 1"""
+    l = shape[0]
+    img = np.stack([np.random.default_rng([4, z]).integers(40 + 30 * z, 256, shape[1:], dtype=np.uint8) for z in range(l)])
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, rad)
+    assert E8o.max() > 0 and len({int(E8o[z].max()) for z in range(l)}) == l
+
+
+@pytest.mark.parametrize("w", [63, 64, 65, 129])
+def test_soma_tile_edges(oracle, w):
+    """widths around one and two x tiles of gauss_y_trunc_hist / one and two ballots of the row kernels, 33 rows: one row in the
+    second y tile, and a body on the lower right corner so that this row and the last column are foreground"""
+    img = synth.add_somas(synth.synth(w, 33, 3, seed=5), ((w - 4, 31, 1, 6), (12, 10, 1, 5)))
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, 2)
+    smap_fg = np.zeros(img.size, bool)
+    smap_fg[fg] = True
+    smap_fg = smap_fg.reshape(img.shape)
+    assert len(n4o) >= 1 and smap_fg[:, 32, :].any() and smap_fg[:, :, w - 1].any()
+
+
+def _flat(value):
+    return np.full((4, 40, 70), value, np.uint8)
+
+
+def _salt_and_pepper():
+    return (np.random.default_rng(8).integers(0, 2, (4, 40, 70)) * 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("name,make,e8,regions", [("zeros", lambda: _flat(0), 0, 0), ("full", lambda: _flat(255), 246, 1),
+                                                  ("grey", lambda: _flat(37), 31, 1), ("salt_and_pepper", _salt_and_pepper, 0, 0)])
+def test_soma_without_contrast(oracle, name, make, e8, regions):
+    """stacks whose eroded + blurred form is one value.  The y pass cuts its running sum to a byte at every tap, so a stack of
+    255s blurs to 246 and one of 37s to 31; the histogram is one bin, the threshold 0, and everything above it -- the whole stack,
+    or nothing -- is one region"""
+    img = make()
+    E8o, tho, n4o, fg = _soma_vs_oracle(oracle, img, 2)
+    assert tho == 0 and np.all(E8o == e8) and len(n4o) == regions
+    assert len(fg) == (img.size if regions else 0)
+
+
+def test_soma_radius_bound():
+    """21 is the largest somaradius (Gaussian radius 63 of at most 64 taps a side, test_soma_radii_vs_oracle runs it); 22 is refused"""
+    with pytest.raises(lib.PnrError, match="somaradius 22 too large"):
+        pnr_amd.Context(pnr_amd.make_params(sigmas=[2.0], somaradius=22, np_=20, ni=5), 0)
 
 
 def test_no_soma_when_radius_zero():

@@ -10,14 +10,15 @@ import orc
 import synth
 
 REF_CASES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cases.npz")
+REF_RADII = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_radii.npz")
 
 
-def references(ref, key, live):
-    """the reference's outputs for case `key`: as recorded in tests/golden/ref_cases.npz (make_golden.py ref_cases), and computed
-    live by `live(ref)` where oracle/_ref is built"""
-    with np.load(REF_CASES) as z:
+def references(ref, key, live, recorded=REF_CASES):
+    """the reference's outputs for case `key`: as recorded in tests/golden/ref_cases.npz (make_golden.py ref_cases; or in `recorded`),
+    and computed live by `live(ref)` where oracle/_ref is built"""
+    with np.load(recorded) as z:
         out = [{k.split("__", 1)[1]: z[k] for k in z.files if k.startswith(key + "__")}]
-    assert out[0], f"{key}: not in {REF_CASES}"
+    assert out[0], f"{key}: not in {recorded}"
     if ref is not None:
         out.append(live(ref))
     return out
@@ -186,6 +187,83 @@ def test_imerode_imgaussian_u8_vs_reference(oracle, ref, shape, rad):
         assert np.array_equal(Go, b["blurred"]) and Go.max() > 0
 
 
+# ---- the Gaussian radii the fixtures above leave out (tests/golden/ref_radii.npz: make_golden.py ref_radii) ----
+# (sigma, zdist) -> radii (xy, z): (1/6, 1) the smallest, 1 and 1; (0.3, 4) 1 and 1 with z taps of 2.5e-39, below FLT_MIN; (3.5, 3) 11
+# and 4; (10, 3) 30 and 10; (20, 1) 60 and 60, the largest sigma a context accepts -- wider than every extent of the stack
+GAUSS_RADII = [(1 / 6, 1.0), (0.3, 4.0), (3.5, 3.0), (10.0, 3.0), (20.0, 1.0)]
+
+
+def gauss_radii_input():
+    """random bytes with an empty plane and a band of values 0..3: at (0.3, 4) the empty plane's result is the neighbours' values times
+    the outer z taps alone, denormal where it comes from the band"""
+    img = np.random.default_rng(7).integers(0, 256, (7, 9, 40), dtype=np.uint8)
+    img[:, :, :8] //= 64
+    img[3] = 0
+    return img
+
+
+def gauss_radii_reference(R, img, sig, zdist):
+    l, h, w = img.shape
+    F = np.zeros(img.shape, np.float32)
+    R.ref_imgaussian3d(img.copy(), w, h, l, sig, zdist, F)
+    return dict(img=img.copy(), F=F)
+
+
+@pytest.mark.parametrize("sig,zdist", GAUSS_RADII)
+def test_imgaussian3d_radii_vs_reference(oracle, ref, sig, zdist):
+    img = gauss_radii_input()
+    l, h, w = img.shape
+    Fo = np.zeros(img.shape, np.float32)
+    oracle.orc_imgaussian3d(img, w, h, l, sig, zdist, Fo)
+    for b in references(ref, "gauss_s%.4g_z%g" % (sig, zdist), lambda R: gauss_radii_reference(R, img, sig, zdist), REF_RADII):
+        assert np.array_equal(b["img"], img)
+        assert np.array_equal(Fo, b["F"]) and Fo.max() > 0
+    if (sig, zdist) == (0.3, 4.0):
+        tiny = np.finfo(np.float32).tiny
+        assert ((Fo[3] > 0) & (Fo[3] < tiny)).sum() > 10 and (Fo[3] >= tiny).sum() > 100
+
+
+# somaradius 1, 6 and 21 (Gaussian radii 3, 18 and 63, erosion windows 3, 13 and 43) on a stack narrower than the widest window, and
+# the stacks without contrast: the byte-wise running sum of the u8 Gaussian turns 255 into 246 and 37 into 31
+ERODE_RADII = [1, 6, 21]
+ERODE_FLAT = [(255, 246), (37, 31)]
+
+
+def erode_radii_input():
+    """a noisy ramp along x, y and z, no voxel below 40: its minimum filter is a ramp again, so the eroded stack keeps a value of its
+    own in most voxels under the widest window too"""
+    z, y, x = np.meshgrid(np.arange(2), np.arange(33), np.arange(40), indexing="ij")
+    return np.clip(40 + 4 * x + 2 * y + 30 * z + np.random.default_rng(6).integers(0, 6, z.shape), 0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("rad", ERODE_RADII)
+def test_imerode_imgaussian_u8_radii_vs_reference(oracle, ref, rad):
+    img = erode_radii_input()
+    l, h, w = img.shape
+    Eo = np.zeros_like(img)
+    oracle.orc_imerode_xy(img, w, h, l, float(rad), Eo)
+    Go = Eo.copy()
+    oracle.orc_imgaussian_u8_xy(Go, w, h, l, float(rad))
+    for b in references(ref, "erode_r%d" % rad, lambda R: erode_reference(R, img, rad), REF_RADII):
+        assert np.array_equal(b["img"], img)
+        assert np.array_equal(Eo, b["eroded"]) and Eo.min() >= 40 and len(np.unique(Eo)) > 30
+        assert np.array_equal(Go, b["blurred"]) and Go.max() > 0 and len(np.unique(Go)) > 10
+
+
+@pytest.mark.parametrize("value,blurred", ERODE_FLAT)
+def test_imgaussian_u8_flat_vs_reference(oracle, ref, value, blurred):
+    img = np.full((4, 40, 70), value, np.uint8)
+    l, h, w = img.shape
+    Go = np.zeros_like(img)
+    oracle.orc_imerode_xy(img, w, h, l, 2.0, Go)
+    assert np.array_equal(Go, img)
+    oracle.orc_imgaussian_u8_xy(Go, w, h, l, 2.0)
+    assert np.all(Go == blurred)
+    for b in references(ref, "flat_%d" % value, lambda R: erode_reference(R, img, 2), REF_RADII):
+        assert np.array_equal(b["img"], img) and np.array_equal(b["eroded"], img)
+        assert np.array_equal(Go, b["blurred"])
+
+
 def test_maxentropy_and_conn3d_properties(oracle):
     """maxentropy_th / conn3d are parity-unpinned restatements (toolbox.cpp needs a Vaa3D header): check what the
     published algorithm guarantees -- threshold between two well separated modes, regions = 26-connected components
@@ -254,6 +332,28 @@ def test_frangi2d_vs_reference(oracle, ref, shape, sigs):
         assert np.array_equal(Vxo, b["Vx"]) and np.array_equal(Vyo, b["Vy"]) and np.array_equal(Vzo, b["Vz"]) and not Vzo.any()
         if min(h, w) > 16:
             assert jMo > 0.05
+
+
+# the single-slice Gaussian at the radii 24 and 40 (through the Hessian the reference's frangi.cpp exposes; ref_radii.npz)
+F2D_RADII = [24, 40]
+
+
+def hessian2d_radii_reference(R, img, sig):
+    _, h, w = img.shape
+    D = [np.zeros(img.shape, np.float32) for _ in range(3)]
+    R.ref_hessian2d(img.copy(), w, h, sig, *D)
+    return dict(img=img.copy(), D0=D[0], D1=D[1], D2=D[2])
+
+
+@pytest.mark.parametrize("L", F2D_RADII)
+def test_hessian2d_radii_vs_reference(oracle, ref, L):
+    img = np.random.default_rng(12).integers(0, 256, (1, 9, 70), dtype=np.uint8)
+    sig = (L - 0.5) / 3
+    a = [np.zeros(img.shape, np.float32) for _ in range(3)]
+    oracle.orc_hessian2d(img, 70, 9, sig, *a)
+    for b in references(ref, "h2d_L%d" % L, lambda R: hessian2d_radii_reference(R, img, sig), REF_RADII):
+        assert np.array_equal(b["img"], img)
+        assert all(np.array_equal(a[k], b["D%d" % k]) and np.abs(a[k]).max() > 0 for k in range(3))
 
 
 # ---- committed fixtures of the reference's 2-D Frangi and soma filters (tests/golden/make_golden.py) ----
