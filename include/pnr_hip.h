@@ -513,6 +513,58 @@ int pnr_tree_coverage(pnr_ctx *ctx, const float *xyz /* n x 3 */, const float *r
                       const pnr_render_opts *opts /* NULL = defaults */, pnr_coverage *cov, int64_t *seg_vox, int64_t *seg_fg, int64_t *seg_sum /* n each, nullable */,
                       uint8_t *mask_out, uint8_t *residual_out /* N each, nullable */);
 
+/* Connected components of the traced volume (beyond the reference, which has no component code outside its soma path).  Two uses:
+ * before tracing, small bright blobs that the median and the top-hat leave -- debris, hot-pixel clusters -- are cleared, as Vaa3D
+ * pipelines remove small foreground components (pnr_despeckle_volume); after tracing, the components of the residual
+ * (pnr_tree_coverage) are the list of what the trace missed (pnr_label_components).
+ * THE RULE (the contract; tests restate it in numpy).  Everything is an exact integer operation.  V is the context's traced u8 volume
+ * (w x h x l, owned or borrowed; for 16-bit input the windowed bytes, after pnr_filter_volume the filtered bytes), N = w * h * l.
+ *   Options {thr, connectivity, min_size}; opts = NULL = {-1, 26, 1}.
+ *   Foreground: V >= t.  t = thr, or for thr == -1: max(1, floor(sum(V) / N)) from the exact u64 sum -- the rule of pnr_tree_coverage
+ *     and of the radius's absolute mode (the same kernel).  thr = 0 makes every voxel foreground.  t is reported as thr_used.
+ *   Neighbours: two foreground voxels are neighbours, for connectivity = 6, when they differ by 1 in exactly one coordinate; for
+ *     connectivity = 26, when they differ by at most 1 in every coordinate and are not equal.  With l == 1 that is 4- and
+ *     8-connectivity in the plane; nothing special-cases it.
+ *   Component: a class of the transitive closure of the neighbour relation.  first = its smallest linear index x + w * (y + h * z).
+ *     The kept components (size >= min_size) are numbered 1..K in ascending first.  label(p) = that number; 0 for background and for
+ *     the voxels of components below min_size.
+ *   Per kept component a pnr_component of exact integers: first, size, sum (of V), sx, sy, sz (the sums of the voxel coordinates: the
+ *     centroid is s / size), the inclusive bounding box x0, y0, z0, x1, y1, z1 and vmax (the maximum of V).
+ *   Summary pnr_components_info: n_vox = N, n_fg, n_comp = K (kept), n_small / vox_small (the components below min_size and their
+ *     voxels), largest (the largest size; 0 without a kept component), thr_used.
+ *   Integer sums, minima and maxima do not depend on order: the rule fixes every bit, whatever the tiling, launch cut or atomic
+ *     arrival order.
+ * pnr_label_components: never writes V and leaves the pipeline state of the context alone, as pnr_tree_coverage.  info, label_out (N)
+ *   and comps are nullable; the first min(cap, n_comp) entries of comps are filled, info->n_comp is always the full count.
+ * pnr_despeckle_volume: out(p) = V(p) if p is background or belongs to a kept component, else 0: the foreground components smaller
+ *   than min_size are cleared, nothing else changes.  Afterwards the context is what pnr_filter_volume leaves: an owned volume of the
+ *   same dimensions and 2-D mode, the later pipeline state invalidated; a borrowed device volume is never written, and V is replaced
+ *   only once everything has succeeded.  min_size = 1 is a valid no-op that leaves the context alone (info, if given, is filled).
+ * Arguments (anything else: PNR_E_ARG): thr in -1..255, connectivity in {6, 26}, min_size >= 1; N at most 2^32 - 2 (the links between
+ *   voxels are u32 indices -- the largest configured stack, 2048 x 2048 x 512, has 2^31 voxels; all other index arithmetic is 64-bit);
+ *   cap >= 0; label_out with more than 2^31 - 1 kept components.  No volume in the context: PNR_E_STATE.  PNR_E_NOMEM: an allocation
+ *   failed.
+ * Both run on the context's stream (pnr_set_stream) and free every device buffer of the call before they return.  Device memory of a
+ *   call, with K_all = the components before min_size: 8 N bytes (4 N of links that become the labels, 4 N of component ids), N / 1024
+ *   bytes of counts, 72 K_all bytes of statistics, and for pnr_despeckle_volume the N bytes of the new volume, which stay.  Kernel times:
+ *   pnr_get_kernel_ms group "components" = the sum of "components_threshold" (the byte sum of thr = -1), "components_local",
+ *   "components_merge", "components_flatten", "components_number", "components_stats" and "components_finish". */
+typedef struct pnr_components_opts {
+    int32_t thr, connectivity;
+    int64_t min_size;
+} pnr_components_opts; /* NULL = {-1, 26, 1} */
+typedef struct pnr_component {
+    int64_t first, size, sum, sx, sy, sz;
+    int32_t x0, y0, z0, x1, y1, z1, vmax, pad;
+} pnr_component;
+typedef struct pnr_components_info {
+    int64_t n_vox, n_fg, n_comp, n_small, vox_small, largest;
+    int32_t thr_used, pad;
+} pnr_components_info;
+int pnr_label_components(pnr_ctx *ctx, const pnr_components_opts *opts /* NULL = defaults */, pnr_components_info *info /* nullable */,
+                         int32_t *label_out /* N, nullable */, pnr_component *comps /* nullable */, int64_t cap);
+int pnr_despeckle_volume(pnr_ctx *ctx, const pnr_components_opts *opts /* NULL = defaults */, pnr_components_info *info /* nullable */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -549,7 +601,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish").  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -14,6 +14,7 @@
 #include "join.h"
 #include "pairmin.h"
 #include "render.h"
+#include "components.h"
 #include "../host/stack_io.h"
 #include <algorithm>
 #include <cfloat>
@@ -350,6 +351,48 @@ int pnr_filter_volume(pnr_ctx *c, const pnr_filter_opts *opts)
     const int rc = pnr_filter_run(c, *opts, &out);
     if (rc) return rc;
     // what pnr_set_volume of the filtered bytes leaves: an owned volume of the same dimensions, no later pipeline state
+    c->d_img_owned.adopt(out, (size_t)c->N); // (empty while the volume was borrowed: a borrowed volume is never written or freed)
+    c->d_img = out;
+    invalidate_pipeline(c);
+    c->have_graph = false;
+    return PNR_OK;
+}
+
+// pnr_label_components / pnr_despeckle_volume (components.hip): arguments first, then the state
+static int components_args(pnr_ctx *c, const char *who, const pnr_components_opts *opts, pnr_components_opts &o)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    o = opts ? *opts : pnr_components_opts{-1, 26, 1};
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "%s: thr = %d outside [-1, 255]", who, o.thr);
+    PNR_REQUIRE(o.connectivity == 6 || o.connectivity == 26, PNR_E_ARG, "%s: connectivity = %d, not 6 or 26", who, o.connectivity);
+    PNR_REQUIRE(o.min_size >= 1, PNR_E_ARG, "%s: min_size = %lld must be at least 1", who, (long long)o.min_size);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "%s: no volume set", who);
+    PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
+    return PNR_OK;
+}
+
+int pnr_label_components(pnr_ctx *c, const pnr_components_opts *opts, pnr_components_info *info, int32_t *label_out, pnr_component *comps, int64_t cap)
+{
+    static const char *who = "pnr_label_components";
+    pnr_components_opts o;
+    PNR_REQUIRE(cap >= 0, PNR_E_ARG, "%s: cap = %lld is negative", who, (long long)cap);
+    const int rc = components_args(c, who, opts, o);
+    if (rc) return rc;
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_components_run(c, who, o, info, label_out, comps, cap, nullptr);
+}
+
+int pnr_despeckle_volume(pnr_ctx *c, const pnr_components_opts *opts, pnr_components_info *info)
+{
+    static const char *who = "pnr_despeckle_volume";
+    pnr_components_opts o;
+    int rc = components_args(c, who, opts, o);
+    if (rc) return rc;
+    PNR_HIP(hipSetDevice(c->device));
+    if (o.min_size == 1) return info ? pnr_components_run(c, who, o, info, nullptr, nullptr, 0, nullptr) : PNR_OK; // nothing can be dropped
+    uint8_t *out = nullptr;
+    if ((rc = pnr_components_run(c, who, o, info, nullptr, nullptr, 0, &out))) return rc;
+    // what pnr_filter_volume leaves: an owned volume of the same dimensions, no later pipeline state
     c->d_img_owned.adopt(out, (size_t)c->N); // (empty while the volume was borrowed: a borrowed volume is never written or freed)
     c->d_img = out;
     invalidate_pipeline(c);
@@ -1449,6 +1492,18 @@ int pnr_get_kernel_ms(pnr_ctx *c, const char *group, double *ms, int64_t *launch
         pnr_get_kernel_ms(c, "render_finish", &b, &lb);
         *ms = a + b;
         if (launches) *launches = la + lb;
+        return PNR_OK;
+    }
+    if (std::strcmp(group, "components") == 0) { // one sub-group per phase (components.hip)
+        *ms = 0;
+        if (launches) *launches = 0;
+        for (const char *g : {"components_threshold", "components_local", "components_merge", "components_flatten", "components_number", "components_stats", "components_finish"}) {
+            double a = 0;
+            int64_t la = 0;
+            pnr_get_kernel_ms(c, g, &a, &la);
+            *ms += a;
+            if (launches) *launches += la;
+        }
         return PNR_OK;
     }
     auto it = c->timers.find(group);

@@ -257,6 +257,24 @@ __global__ __launch_bounds__(NTPB) void rn_finish(FinArgs a)
 
 } // namespace
 
+// the exact sum of the N bytes at V (device) into *sum, through the zeroed device word d_sum; timed under `group`
+int pnr_byte_sum_run(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_sum, unsigned long long *sum)
+{
+    hipStream_t st = c->stream;
+    const uintptr_t addr = (uintptr_t)V;
+    const long long head = std::min<long long>(N, (long long)((16 - (addr & 15)) & 15)), nvec = (N - head) >> 4;
+    const long long work = std::max<long long>(nvec, 16);
+    const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((work + NTPB - 1) / NTPB, MAX_BLOCKS));
+    c->tic();
+    hipLaunchKernelGGL(rn_sum, dim3(nb), dim3(NTPB), 0, st, V, (long long)N, head, nvec, d_sum);
+    hipError_t e = hipGetLastError();
+    c->toc(group, 1);
+    if (e == hipSuccess) e = hipMemcpyAsync(sum, d_sum, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+    return PNR_OK;
+}
+
 int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_t w, int64_t h, int64_t l, const uint8_t *V, int thr, int32_t *label_out,
                    uint8_t *mask_out, uint8_t *residual_out, pnr_coverage *cov, int64_t *seg_vox, int64_t *seg_fg, int64_t *seg_sum)
 {
@@ -318,17 +336,8 @@ int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_
     int t_abs = thr;
     if (V && thr < 0) {
         unsigned long long sum = 0;
-        const uintptr_t addr = (uintptr_t)V;
-        const long long head = std::min<long long>(N, (long long)((16 - (addr & 15)) & 15)), nvec = (N - head) >> 4;
-        const long long work = std::max<long long>(nvec, 16);
-        const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((work + NTPB - 1) / NTPB, MAX_BLOCKS));
-        c->tic();
-        hipLaunchKernelGGL(rn_sum, dim3(nb), dim3(NTPB), 0, st, V, (long long)N, head, nvec, d_cnt);
-        e = hipGetLastError();
-        c->toc("render_finish", 1);
-        if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_cnt, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+        const int rs = pnr_byte_sum_run(c, who, "render_finish", V, N, d_cnt, &sum);
+        if (rs) return rs;
         t_abs = (int)std::max<unsigned long long>(1, sum / (unsigned long long)N);
     }
     const FinArgs fa{d_lab, V, (long long)N, t_abs, label_out ? 1 : 0, mask_out ? buf.at<uint8_t>(o_mask) : nullptr, residual_out ? buf.at<uint8_t>(o_res) : nullptr,

@@ -31,6 +31,13 @@
 //   pnr_coverage, then "nodes" and "items"; the CSV is `id,vox,fg,sum` per node.  Without -i, -d w,h,l gives the grid and only --mask is
 //   allowed.  While tracing, --mask OUT, --residual OUT and --coverage render the final tree (after --join and --measure-radius, zscale =
 //   zdist) and add #coverage=thr:T,covered:..,on_signal:..,intensity:..,tree_voxels:N to the comment block.
+//   --despeckle MIN[,THR[,CONN]]: while tracing, the foreground components (voxels >= THR, default -1: the stack's mean; CONN 6 or 26,
+//   default 26) of fewer than MIN voxels are cleared on the GPU (pnr_despeckle_volume) after --median / --subtract-background and on every
+//   rank; the comment block gains #despeckle=min:M,thr:T,conn:C,removed:K,voxels:V (T: the threshold used) behind #filter.
+//   --components -i stack [--threshold T] [--connectivity 6|26] [--min-size M] [--labels OUT.raw] [--per-component FILE.csv]: the
+//   connected components of the stack (pnr_label_components on device -g; the same volume setup as --render-swc) as one JSON line with
+//   the fields of pnr_components_info; --labels writes bare little-endian int32, --per-component one line
+//   `id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax` per kept component.  On a --residual file (.raw with -d w,h,l): what the trace missed.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -114,8 +121,60 @@ int main(int argc, char **argv)
     advantra::RenderJob render;
     std::string mask_out, residual_out;
     bool coverage = false, render_flag = false, per_node_flag = false;
+    advantra::ComponentsJob comp;
+    bool components = false, comp_flag = false;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
+        if (!strcmp(argv[i], "--components")) { components = true; continue; }
+        if (!strcmp(argv[i], "--threshold")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+            comp.opts.thr = (int32_t)v;
+            comp_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--connectivity")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 6, 26, v) || (v != 6 && v != 26)) { fprintf(stderr, "--connectivity 6|26\n"); return 1; }
+            comp.opts.connectivity = (int32_t)v;
+            comp_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--min-size")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 1, 0x7fffffffffffffffL, v)) { fprintf(stderr, "--min-size M: an integer from 1\n"); return 1; }
+            comp.opts.min_size = v;
+            comp_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--labels") || !strcmp(argv[i], "--per-component")) {
+            const bool lab = !strcmp(argv[i], "--labels");
+            const std::string name = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (name.empty() || (lab && (name.size() <= 4 || name.substr(name.size() - 4) != ".raw"))) {
+                fprintf(stderr, "%s\n", lab ? "--labels OUT.raw: a .raw file name (bare little-endian int32)" : "--per-component FILE.csv");
+                return 1;
+            }
+            (lab ? comp.labels : comp.per_component) = name;
+            comp_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--despeckle")) {
+            const std::string txt = i + 1 < argc ? argv[++i] : "";
+            std::vector<std::string> part(1);
+            for (char ch : txt) {
+                if (ch == ',') part.emplace_back();
+                else part.back() += ch;
+            }
+            long m = 0, t = -1, cn = 26;
+            if (part.size() > 3 || !parse_int(part[0].c_str(), 1, 0x7fffffffffffffffL, m) || (part.size() > 1 && !parse_int(part[1].c_str(), -1, 255, t)) ||
+                (part.size() > 2 && (!parse_int(part[2].c_str(), 6, 26, cn) || (cn != 6 && cn != 26)))) {
+                fprintf(stderr, "--despeckle MIN[,THR[,CONN]]: MIN an integer from 1, THR 0..255 or -1 for the stack's mean, CONN 6 or 26\n");
+                return 1;
+            }
+            S0.despeckle = true;
+            S0.despeckle_opts = pnr_components_opts{(int32_t)t, (int32_t)cn, m};
+            continue;
+        }
         if (!strcmp(argv[i], "--info")) { info = true; continue; }
         if (!strcmp(argv[i], "--channel") && i + 1 < argc) {
             char *end = nullptr;
@@ -290,14 +349,21 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool rendering = !render.swc.empty();
-    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering) || (zscale_flag && !distance && join_in.empty() && !rendering)) {
+    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering) || (zscale_flag && !distance && join_in.empty() && !rendering && !components)) {
         fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc; --zscale, --per-node: or --render-swc)\n");
         return 1;
     }
     if (render_flag && !rendering) { fprintf(stderr, "--radius-scale / --radius-add / --coverage-threshold need --render-swc IN.swc\n"); return 1; }
     if (join_flag && !join_given && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
+    if (comp_flag && !components) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (components) {
+        if (rendering || distance || !join_in.empty() || info || S0.despeckle) { fprintf(stderr, "--components: not with --render-swc, --distance, --join-swc, --info or --despeckle (--min-size drops the small components)\n"); return 1; }
+        if (infiles.empty()) { fprintf(stderr, "--components needs -i <stack>\n"); return 1; }
+        return advantra::components_file(comp, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 0.f, device) ? 0 : 1;
+    }
+    if (S0.despeckle && (rendering || distance || !join_in.empty() || info)) { fprintf(stderr, "--despeckle needs a tracing run\n"); return 1; }
     if (rendering) {
         if (distance || !join_in.empty() || coverage) { fprintf(stderr, "--render-swc: not with --distance, --join-swc or --coverage (the JSON line has the coverage)\n"); return 1; }
         if (infiles.empty() && (mask_out.empty() || !residual_out.empty() || !per_node.empty() || render.opts.thr != -1)) {

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <sstream>
 #include <unordered_map>
 
@@ -77,6 +78,15 @@ void print_flags()
     printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
     printf("--median 2d|3d            pre-filter: 3 x 3 median in every slice, or 3 x 3 x 3 (on the GPU, before tracing; default: off)\n");
     printf("--subtract-background R   pre-filter: top-hat with a flat box of half-width R in xy and R / zdist in z, 1..%d (after the median)\n", PNR_TOPHAT_MAX_R);
+    printf("--despeckle MIN[,THR[,CONN]]  pre-filter: foreground components (voxels >= THR, default -1: the stack's mean; CONN 6 or 26, default 26) of\n");
+    printf("                          fewer than MIN voxels are set to 0 on the GPU (after the median and the top-hat, before tracing)\n");
+    printf("--components -i stack     the connected components of the stack's foreground on the GPU (the same volume setup as tracing) as one JSON\n");
+    printf("                          line: n_vox, n_fg, n_comp, n_small, vox_small, largest, thr_used; on a --residual file: what the trace missed\n");
+    printf("  --threshold T             foreground from T on, 0..255 (default -1: the stack's mean)\n");
+    printf("  --connectivity 6|26       face neighbours only, or faces, edges and corners (default 26)\n");
+    printf("  --min-size M              components of fewer than M voxels are not counted, numbered or listed (default 1)\n");
+    printf("  --labels OUT.raw          write the label volume: little-endian int32, 0 = background, 1.. by first voxel in raster order\n");
+    printf("  --per-component FILE.csv  `id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax` per component\n");
     printf("--measure-radius          SWC radii measured from the image at the final nodes (default: SIG2RADIUS * the winning scale)\n");
     printf("--radius-rel PCT          relative mode (default, 50): background below PCT %% of the node's brightest centre voxel, 1..100\n");
     printf("--radius-threshold T      absolute mode: background below T, 0..255; -1: below the stack's mean\n");
@@ -639,6 +649,77 @@ bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, c
     return true;
 }
 
+bool components_file(const ComponentsJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    auto lib_fail = [](const char *what) {
+        fprintf(stderr, "%s: %s\n", what, pnr_last_error());
+        return false;
+    };
+    const Settings &S = settings();
+    Stack st;
+    std::string err;
+    if (!load_stack(infiles[0], raw_dims, st, err, S.channel - 1, S.raw_u16)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    if (S.windowed && st.bits != 16) {
+        fprintf(stderr, "--window / --saturate need a 16-bit stack (8-bit input is never windowed)\n");
+        return false;
+    }
+    pnr_params p;
+    pnr_default_params(&p);
+    if (zscale >= 1.f) p.zdist = zscale; // (the z half-width of --subtract-background)
+    pnr_ctx *ctx = nullptr;
+    if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+    // the volume as it would be traced: windowed to 8 bits, then pre-filtered
+    bool ok = (st.bits == 16 ? pnr_set_volume_u16(ctx, st.samples16(), st.w, st.h, st.l, 1, 0, S.windowed ? &S.window : nullptr, nullptr, nullptr)
+                             : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
+    if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
+    if (!ok) {
+        lib_fail("volume");
+        pnr_destroy(ctx);
+        return false;
+    }
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<int32_t> labels(job.labels.empty() ? 0 : N);
+    std::vector<pnr_component> comps;
+    pnr_components_info ci = {};
+    int rc = pnr_label_components(ctx, &job.opts, &ci, job.labels.empty() ? nullptr : labels.data(), nullptr, 0);
+    if (rc == PNR_OK && !job.per_component.empty() && ci.n_comp > 0) { // "n_comp > cap: call again"
+        comps.resize((size_t)ci.n_comp);
+        rc = pnr_label_components(ctx, &job.opts, &ci, nullptr, comps.data(), (int64_t)comps.size());
+    }
+    pnr_destroy(ctx);
+    if (rc != PNR_OK) return lib_fail("pnr_label_components");
+    auto write_file = [](const std::string &name, const char *mode, const std::function<void(FILE *)> &body) {
+        FILE *f = fopen(name.c_str(), mode);
+        if (!f) {
+            fprintf(stderr, "%s: cannot write the file\n", name.c_str());
+            return false;
+        }
+        body(f);
+        const bool bad = ferror(f) != 0;
+        if (fclose(f) != 0 || bad) {
+            fprintf(stderr, "%s: write failed\n", name.c_str());
+            return false;
+        }
+        return true;
+    };
+    if (!job.labels.empty() && !write_file(job.labels, "wb", [&](FILE *f) { fwrite(labels.data(), 4, N, f); })) return false; // (the hosts this builds for are little-endian)
+    if (!job.per_component.empty() && !write_file(job.per_component, "w", [&](FILE *f) {
+            fprintf(f, "id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax\n");
+            for (size_t k = 0; k < comps.size(); k++) {
+                const pnr_component &c = comps[k];
+                fprintf(f, "%lld,%lld,%lld,%.3f,%.3f,%.3f,%d,%d,%d,%d,%d,%d,%d\n", (long long)(k + 1), (long long)c.size, (long long)c.sum, (double)c.sx / (double)c.size,
+                        (double)c.sy / (double)c.size, (double)c.sz / (double)c.size, c.x0, c.y0, c.z0, c.x1, c.y1, c.z1, c.vmax);
+            }
+        }))
+        return false;
+    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_comp\": %lld, \"n_small\": %lld, \"vox_small\": %lld, \"largest\": %lld, \"thr_used\": %d}\n", (long long)ci.n_vox,
+           (long long)ci.n_fg, (long long)ci.n_comp, (long long)ci.n_small, (long long)ci.vox_small, (long long)ci.largest, (int)ci.thr_used);
+    return true;
+}
+
 Stack::~Stack()
 {
     if (view) munmap((void *)view, map_len);
@@ -776,6 +857,9 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         if (fo.tophat_r) c << fo.tophat_r;
         else c << "off";
     }
+    if (settings().despeckle && cover)
+        c << "\n#despeckle=min:" << settings().despeckle_opts.min_size << ",thr:" << cover->despeckle_thr << ",conn:" << settings().despeckle_opts.connectivity
+          << ",removed:" << cover->despeckle_removed << ",voxels:" << cover->despeckle_voxels;
     if (join) c << "\n#join=gap:" << f32_text(settings().join_gap) <<",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->" << join->join_trees_out;
     if (radius_thr) {
         const pnr_radius_opts &ro = settings().radius;
@@ -904,9 +988,22 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
                std::chrono::duration<double>(clk::now() - ts).count());
     };
     const pnr_filter_opts &fo = settings().filter;
-    const bool filtered = fo.median || fo.tophat_r;
-    auto run_filter = [&]() { // --median / --subtract-background: the context's volume is replaced by its filtered bytes
+    const bool despeckled = settings().despeckle;
+    const bool filtered = fo.median || fo.tophat_r || despeckled;
+    auto run_despeckle = [&]() { // --despeckle: the small foreground components of the (filtered) volume are cleared
+        if (!despeckled || !ok) return;
+        const auto tf = clk::now();
+        pnr_components_info ci = {};
+        ok = pnr_despeckle_volume(ctx, &settings().despeckle_opts, &ci) == PNR_OK;
+        R.t_despeckle = std::chrono::duration<double>(clk::now() - tf).count();
+        R.despeckle_removed = ci.n_small, R.despeckle_voxels = ci.vox_small, R.despeckle_thr = ci.thr_used;
+        printf("despeckle... %lld components of fewer than %lld voxels (%lld voxels) removed, threshold %d, %g sec.\n", (long long)ci.n_small,
+               (long long)settings().despeckle_opts.min_size, (long long)ci.vox_small, (int)ci.thr_used, R.t_despeckle);
+        if (settings().timing) fprintf(stderr, "[pnr host] despeckle: %.3f s\n", R.t_despeckle);
+    };
+    auto run_filter = [&]() { // --median / --subtract-background (/ --despeckle): the context's volume is replaced by its filtered bytes
         if (!filtered || !ok) return;
+        if (!fo.median && !fo.tophat_r) return run_despeckle();
         const auto tf = clk::now();
         const bool prof = settings().timing || settings().verbose;
         if (prof) pnr_set_profiling(ctx, 1);
@@ -921,6 +1018,7 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
         printf("pre-filter... median %s, top-hat %d, %g sec.\n", fo.median == 3 ? "3d" : fo.median == 2 ? "2d" : "off", (int)fo.tophat_r, R.t_filter);
         if (settings().verbose) printf("pre-filter kernels %.3f ms in %lld launches\n", ms, (long long)launches);
         if (settings().timing) fprintf(stderr, "[pnr host] filter: %.3f s, kernels %.3f ms in %lld launches\n", R.t_filter, ms, (long long)launches);
+        run_despeckle();
     };
     std::vector<pnr_seed> seeds;
     int64_t nfound = 0, nseeds = 0;

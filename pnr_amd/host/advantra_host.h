@@ -44,6 +44,9 @@ struct Result {
     bool have_coverage = false;    // --mask / --residual / --coverage: the final tree rendered on the traced volume (pnr_tree_coverage)
     pnr_coverage coverage = {};
     double t_render = 0;
+    long long despeckle_removed = 0, despeckle_voxels = 0; // --despeckle: the components and voxels pnr_despeckle_volume cleared
+    int despeckle_thr = 0;                                 // ... and the threshold it used
+    double t_despeckle = 0;                                // (part of t_setup)
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
     double t_filter = 0;           // --median / --subtract-background: the pre-filter (part of t_setup)
@@ -98,6 +101,11 @@ struct Settings {
     // The reference has no counterpart.
     std::string mask_out, residual_out;
     bool coverage = false;
+    // --despeckle MIN[,THR[,CONN]]: foreground components ({V >= THR}, -1: the mean; CONN 6 or 26) of fewer than MIN voxels are cleared on
+    // the GPU (pnr_despeckle_volume) after the pre-filters -- for 16-bit input after windowing -- and before the soma path; on every rank
+    // of --ranks N.  The SWC comment then has a #despeckle= line behind #filter.  The reference has no counterpart.
+    bool despeckle = false;
+    pnr_components_opts despeckle_opts = {-1, 26, 1};
 };
 Settings &settings();
 
@@ -143,6 +151,16 @@ struct RenderJob {
     pnr_render_opts opts = {1.f, 1.f, 0.f, -1};
 };
 bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
+// advantra_cli --components -i stack: the connected components of the stack's foreground (pnr_label_components on `device`; the same
+// volume setup as --render-swc: channel, window, pre-filters of settings(); zscale >= 1 is the zdist of --subtract-background).  One JSON
+// line with the fields of pnr_components_info; `labels` (not empty): the label volume as bare little-endian int32; `per_component` (not
+// empty): a CSV `id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax` per kept component under a header line, the centroid as %.3f of the f64
+// quotient.  Run on a file written by --residual, this lists what the trace missed.
+struct ComponentsJob {
+    pnr_components_opts opts = {-1, 26, 1};
+    std::string labels, per_component;
+};
+bool components_file(const ComponentsJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

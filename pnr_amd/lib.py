@@ -96,6 +96,24 @@ PNR_RENDER_MAX_N = 1 << 22
 PNR_RENDER_MAX_R = 1024
 
 
+class ComponentsOpts(C.Structure):
+    """pnr_components_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean), connectivity 6 or 26, min_size >= 1"""
+    _fields_ = [("thr", C.c_int32), ("connectivity", C.c_int32), ("min_size", C.c_int64)]
+
+
+class ComponentsInfo(C.Structure):
+    """pnr_components_info: the exact counts of a labelling (n_comp: the kept components; n_small / vox_small: those below min_size)"""
+    _fields_ = [("n_vox", C.c_int64), ("n_fg", C.c_int64), ("n_comp", C.c_int64), ("n_small", C.c_int64), ("vox_small", C.c_int64), ("largest", C.c_int64),
+                ("thr_used", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+# pnr_component
+COMPONENT_DT = np.dtype([(k, np.int64) for k in ("first", "size", "sum", "sx", "sy", "sz")] + [(k, np.int32) for k in ("x0", "y0", "z0", "x1", "y1", "z1", "vmax", "pad")])
+
+
 class Params(C.Structure):
     _fields_ = [("sig", C.c_float * PNR_MAX_SIGMAS), ("nsig", C.c_int), ("somaradius", C.c_int), ("tolerance", C.c_float),
                 ("znccth", C.c_float), ("kappa", C.c_float), ("step", C.c_int), ("ni", C.c_int), ("np", C.c_int),
@@ -170,6 +188,8 @@ def load():
     L.pnr_join_reroot.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
     L.pnr_render_tree.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), vp, vp]
     L.pnr_tree_coverage.argtypes = [vp, vp, vp, vp, i64, C.POINTER(RenderOpts), C.POINTER(Coverage), vp, vp, vp, vp, vp]
+    L.pnr_label_components.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo), vp, vp, i64]
+    L.pnr_despeckle_volume.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]
     L.pnr_render_items.argtypes = [vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_test_write_tiff.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
@@ -235,7 +255,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -474,6 +494,37 @@ class Context:
         check(self.L.pnr_tree_coverage(self.h, xyz.ctypes.data, radius.ctypes.data, parent.ctypes.data, len(xyz), C.byref(o), C.byref(cov), ptr("seg_vox"),
                                        ptr("seg_fg"), ptr("seg_sum"), ptr("mask"), ptr("residual")))
         return {**cov.as_dict(), **out}
+
+    def label_components(self, thr=-1, connectivity=26, min_size=1, labels=True, cap=None):
+        """pnr_label_components: the connected components of {V >= thr} (thr = -1: the global mean) of the context's volume under 6- or
+        26-connectivity -> (info dict {n_vox, n_fg, n_comp, n_small, vox_small, largest, thr_used}, labels int32[l, h, w] or None,
+        comps COMPONENT_DT[n_comp]).  The components of at least min_size voxels are numbered 1.. by their first voxel in raster order;
+        label 0 is background and the dropped components.  cap: at most this many entries of comps (info["n_comp"] stays the full count)."""
+        o = ComponentsOpts(int(thr), int(connectivity), int(min_size))
+        info = ComponentsInfo()
+        lab = np.empty(self.shape, np.int32) if labels else None
+        lp = lab.ctypes.data if labels else None
+        if cap is None:  # count first, then fetch: "n_comp > cap: call again"
+            check(self.L.pnr_label_components(self.h, C.byref(o), C.byref(info), lp, None, 0))
+            comps = np.zeros(info.n_comp, COMPONENT_DT)
+            if info.n_comp:
+                check(self.L.pnr_label_components(self.h, C.byref(o), C.byref(info), None, comps.ctypes.data, len(comps)))
+        else:
+            comps = np.zeros(int(cap), COMPONENT_DT)
+            check(self.L.pnr_label_components(self.h, C.byref(o), C.byref(info), lp, comps.ctypes.data, len(comps)))
+            comps = comps[:min(len(comps), info.n_comp)]
+        return info.as_dict(), lab, comps
+
+    def despeckle(self, min_size, thr=-1, connectivity=26):
+        """pnr_despeckle_volume: the foreground components ({V >= thr}, thr = -1: the global mean) of fewer than min_size voxels are set
+        to 0 in the traced volume -> the info dict of label_components (n_small / vox_small: what was removed).  The result is an owned
+        volume (a borrowed one is left as it was and released) and the later pipeline state is invalidated; min_size = 1 changes nothing."""
+        o = ComponentsOpts(int(thr), int(connectivity), int(min_size))
+        info = ComponentsInfo()
+        check(self.L.pnr_despeckle_volume(self.h, C.byref(o), C.byref(info)))
+        if o.min_size > 1:
+            self._keep = None
+        return info.as_dict()
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
