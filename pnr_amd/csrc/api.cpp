@@ -2,7 +2,7 @@
 // parameter validation (Advantra::dofunc, Advantra_plugin.cpp:317-326), uploads/read-backs, the
 // seed filter/sort (:2561-2586) and the host replay of the trace bookkeeping
 // (tracker.cpp:825-933 + Advantra_plugin.cpp:2602-2710).
-#include "ctx.h"
+#include "call.h"
 #include "replay.h"
 #include "stream_sched.h"
 #include "../host/reconstruct.h"
@@ -297,11 +297,7 @@ static int set_volume_u16(pnr_ctx *c, const void *img, bool host, int64_t w, int
     pnr::DevBuf<char> d_up;
     if (host) {
         const size_t bytes = (size_t)c->N * (size_t)nchan * 2;
-        if (d_up.alloc(bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("pnr_set_volume_u16: device allocation of %zu B for the 16-bit stack failed", bytes);
-            return PNR_E_NOMEM;
-        }
+        if ((rc = pnr::dev_alloc(d_up, bytes, "pnr_set_volume_u16", "for the 16-bit stack"))) return rc;
         if (hipMemcpyAsync(d_up.get(), img, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             (void)hipStreamSynchronize(c->stream);
             set_error("pnr_set_volume_u16: upload of %zu B failed", bytes);
@@ -338,6 +334,15 @@ int pnr_get_volume(pnr_ctx *c, uint8_t *img)
     return PNR_OK;
 }
 
+// what pnr_set_volume of the new bytes leaves: an owned volume of the same dimensions, no later pipeline state
+static void replace_volume(pnr_ctx *c, pnr::DevBuf<uint8_t> &&v)
+{
+    c->d_img_owned = std::move(v); // (empty while the volume was borrowed: a borrowed volume is never written or freed)
+    c->d_img = c->d_img_owned.get();
+    invalidate_pipeline(c);
+    c->have_graph = false;
+}
+
 // pnr_filter_volume: arguments first, then the state; the context changes only after the filtered volume is complete (filter.hip)
 int pnr_filter_volume(pnr_ctx *c, const pnr_filter_opts *opts)
 {
@@ -347,15 +352,10 @@ int pnr_filter_volume(pnr_ctx *c, const pnr_filter_opts *opts)
     PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_filter_volume: no volume set");
     if (!opts->median && !opts->tophat_r) return PNR_OK;
     PNR_HIP(hipSetDevice(c->device));
-    uint8_t *out = nullptr;
-    const int rc = pnr_filter_run(c, *opts, &out);
-    if (rc) return rc;
-    // what pnr_set_volume of the filtered bytes leaves: an owned volume of the same dimensions, no later pipeline state
-    c->d_img_owned.adopt(out, (size_t)c->N); // (empty while the volume was borrowed: a borrowed volume is never written or freed)
-    c->d_img = out;
-    invalidate_pipeline(c);
-    c->have_graph = false;
-    return PNR_OK;
+    pnr::DevBuf<uint8_t> out;
+    const int rc = pnr_filter_run(c, *opts, out);
+    if (!rc) replace_volume(c, std::move(out));
+    return rc;
 }
 
 // pnr_label_components / pnr_despeckle_volume (components.hip): arguments first, then the state
@@ -390,14 +390,9 @@ int pnr_despeckle_volume(pnr_ctx *c, const pnr_components_opts *opts, pnr_compon
     if (rc) return rc;
     PNR_HIP(hipSetDevice(c->device));
     if (o.min_size == 1) return info ? pnr_components_run(c, who, o, info, nullptr, nullptr, 0, nullptr) : PNR_OK; // nothing can be dropped
-    uint8_t *out = nullptr;
-    if ((rc = pnr_components_run(c, who, o, info, nullptr, nullptr, 0, &out))) return rc;
-    // what pnr_filter_volume leaves: an owned volume of the same dimensions, no later pipeline state
-    c->d_img_owned.adopt(out, (size_t)c->N); // (empty while the volume was borrowed: a borrowed volume is never written or freed)
-    c->d_img = out;
-    invalidate_pipeline(c);
-    c->have_graph = false;
-    return PNR_OK;
+    pnr::DevBuf<uint8_t> out;
+    if (!(rc = pnr_components_run(c, who, o, info, nullptr, nullptr, 0, &out))) replace_volume(c, std::move(out));
+    return rc;
 }
 
 // pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched
@@ -571,6 +566,7 @@ int pnr_join_trees(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t 
 }
 
 // ---- rendering the tree (render.hip): arguments first; pnr_render_tree needs no volume, neither call touches the pipeline state ----
+static pnr_render_opts default_render_opts(const pnr_render_opts *opts) { return opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1}; }
 static int render_grid_ok(const char *who, int64_t w, int64_t h, int64_t l)
 {
     const int64_t lim = 0x7fffffffll;
@@ -590,7 +586,7 @@ int pnr_render_tree(pnr_ctx *c, const float *xyz, const float *radius, const int
 {
     static const char *who = "pnr_render_tree";
     PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
-    const pnr_render_opts o = opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1};
+    const pnr_render_opts o = default_render_opts(opts);
     int rc = render_tree_ok(who, xyz, radius, parent, n, o);
     if (!rc) rc = render_grid_ok(who, w, h, l);
     pnr::RenderTree t;
@@ -605,7 +601,7 @@ int pnr_tree_coverage(pnr_ctx *c, const float *xyz, const float *radius, const i
 {
     static const char *who = "pnr_tree_coverage";
     PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
-    const pnr_render_opts o = opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1};
+    const pnr_render_opts o = default_render_opts(opts);
     int rc = render_tree_ok(who, xyz, radius, parent, n, o);
     pnr::RenderTree t;
     if (!rc) rc = pnr::render_prepare(who, xyz, radius, parent, n, o, t);
@@ -628,7 +624,7 @@ int pnr_render_items(const float *xyz, const float *radius, const int32_t *paren
 {
     static const char *who = "pnr_render_items";
     PNR_REQUIRE(count && piece >= 0 && box >= 0 && (cap <= 0 || items_out), PNR_E_ARG, "%s: piece and box (not negative) need a count, and items_out for cap = %lld", who, (long long)cap);
-    const pnr_render_opts o = opts ? *opts : pnr_render_opts{1.f, 1.f, 0.f, -1};
+    const pnr_render_opts o = default_render_opts(opts);
     int rc = render_tree_ok(who, xyz, radius, parent, n, o);
     if (!rc) rc = render_grid_ok(who, w, h, l);
     pnr::RenderTree t;
@@ -923,6 +919,16 @@ int pnr_get_soma(pnr_ctx *c, pnr_node *nodes, int64_t cap_nodes, int64_t *n_node
 }
 
 // ---- host replay ------------------------------------------------------------------------
+// a node graph into the caller's buffers: the counts, and as much of either array as its capacity holds
+static int put_graph(const std::vector<pnr_node> &gn, const std::vector<int32_t> &gl, pnr_node *nodes, int64_t cap_nodes, int64_t *n_nodes, int32_t *links,
+                     int64_t cap_links, int64_t *n_links)
+{
+    *n_nodes = (int64_t)gn.size();
+    *n_links = (int64_t)gl.size() / 2;
+    if (nodes) std::memcpy(nodes, gn.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_nodes));
+    if (links) std::memcpy(links, gl.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_links));
+    return PNR_OK;
+}
 int pnr_replay_traces_ctx(pnr_ctx *c, const pnr_seed *seeds, int64_t n, const int32_t *T, const pnr_xest *xc, pnr_node *nodes,
                           int64_t cap_nodes, int64_t *n_nodes, int32_t *links, int64_t cap_links, int64_t *n_links, int64_t *n_traces_used)
 {
@@ -932,12 +938,8 @@ int pnr_replay_traces_ctx(pnr_ctx *c, const pnr_seed *seeds, int64_t n, const in
     pnr::Replayer r(c->prm, c->w, c->h, c->l);
     r.set_soma(&c->soma_map, c->soma_nodes);
     r.add(seeds, n, T, xc);
-    *n_nodes = (int64_t)r.nodes.size();
-    *n_links = (int64_t)r.links.size() / 2;
-    if (nodes) std::memcpy(nodes, r.nodes.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_nodes));
-    if (links) std::memcpy(links, r.links.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_links));
     if (n_traces_used) *n_traces_used = r.trace_count;
-    return PNR_OK;
+    return put_graph(r.nodes, r.links, nodes, cap_nodes, n_nodes, links, cap_links, n_links);
 }
 
 int pnr_replay_traces(const pnr_params *p, int64_t w, int64_t h, int64_t l, const pnr_seed *seeds, int64_t n,
@@ -948,12 +950,8 @@ int pnr_replay_traces(const pnr_params *p, int64_t w, int64_t h, int64_t l, cons
     PNR_REQUIRE(w > 0 && h > 0 && l > 0, PNR_E_ARG, "bad dimensions");
     pnr::Replayer r(*p, w, h, l);
     r.add(seeds, n, T, xc);
-    *n_nodes = (int64_t)r.nodes.size();
-    *n_links = (int64_t)r.links.size() / 2;
-    if (nodes) std::memcpy(nodes, r.nodes.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_nodes));
-    if (links) std::memcpy(links, r.links.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_links));
     if (n_traces_used) *n_traces_used = r.trace_count;
-    return PNR_OK;
+    return put_graph(r.nodes, r.links, nodes, cap_nodes, n_nodes, links, cap_links, n_links);
 }
 
 // the graph of the last pnr_trace_replay / pnr_trace_replay_sharded stays in the context (pnr_get_graph): a caller whose buffers
@@ -965,23 +963,15 @@ static int store_graph(pnr_ctx *c, pnr::Replayer &r, pnr_node *nodes, int64_t ca
     c->graph_links.swap(r.links);
     c->graph_traces = r.trace_count;
     c->have_graph = true;
-    *n_nodes = (int64_t)c->graph_nodes.size();
-    *n_links = (int64_t)c->graph_links.size() / 2;
-    if (nodes) std::memcpy(nodes, c->graph_nodes.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_nodes));
-    if (links) std::memcpy(links, c->graph_links.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_links));
     if (n_traces_used) *n_traces_used = c->graph_traces;
-    return PNR_OK;
+    return put_graph(c->graph_nodes, c->graph_links, nodes, cap_nodes, n_nodes, links, cap_links, n_links);
 }
 
 int pnr_get_graph(pnr_ctx *c, pnr_node *nodes, int64_t cap_nodes, int64_t *n_nodes, int32_t *links, int64_t cap_links, int64_t *n_links)
 {
     PNR_REQUIRE(c && n_nodes && n_links, PNR_E_ARG, "null argument");
     PNR_REQUIRE(c->have_graph, PNR_E_STATE, "no node graph: pnr_trace_replay has not run");
-    *n_nodes = (int64_t)c->graph_nodes.size();
-    *n_links = (int64_t)c->graph_links.size() / 2;
-    if (nodes) std::memcpy(nodes, c->graph_nodes.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_nodes));
-    if (links) std::memcpy(links, c->graph_links.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_links));
-    return PNR_OK;
+    return put_graph(c->graph_nodes, c->graph_links, nodes, cap_nodes, n_nodes, links, cap_links, n_links);
 }
 
 int pnr_get_trace_log(pnr_ctx *c, int32_t *rec, int64_t cap, int64_t *n)
@@ -1248,10 +1238,7 @@ int pnr_sched_playback2(const pnr_params *p, int64_t w, int64_t h, int64_t l, co
     std::string err;
     const int rc = pnr::run_stream(eng, seeds, n, p->ni, o, sh, r, &st, err);
     if (rc) { set_error("%s", err.c_str()); return rc; }
-    *n_nodes = (int64_t)r.nodes.size();
-    *n_links = (int64_t)r.links.size() / 2;
-    if (nodes) std::memcpy(nodes, r.nodes.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_nodes));
-    if (links) std::memcpy(links, r.links.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_links));
+    put_graph(r.nodes, r.links, nodes, cap_nodes, n_nodes, links, cap_links, n_links);
     if (n_traces_used) *n_traces_used = r.trace_count;
     if (n_iterations) *n_iterations = st.iters;
     return PNR_OK;
@@ -1321,11 +1308,15 @@ int pnr_get_option(pnr_ctx *c, const char *key, int64_t *value)
     return PNR_E_ARG;
 }
 
-int pnr_reconstruct(const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
-                    float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min,
-                    pnr_node *out_nodes, int32_t *out_parent, int64_t cap, int64_t *n_out)
+// The one front of the four pnr_reconstruct* forms.  c (nullable): its GPU runs the two neighbour stages, else the host alone.  staged: the
+// list behind `stage` with its links (pairs) comes back; else the tree, out_links = the parents.  The plugin constants stand for values <= 0.
+static int reconstruct_front(pnr_ctx *c, bool staged, int stage, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
+                             float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min, pnr_node *out_nodes, int64_t cap_nodes,
+                             int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links, int64_t *n_out_links)
 {
-    PNR_REQUIRE(nodes && n_nodes >= 1 && n_out && (n_links == 0 || links), PNR_E_ARG, "null argument");
+    PNR_REQUIRE(nodes && n_nodes >= 1 && n_out_nodes && (!staged || n_out_links) && (n_links == 0 || links), PNR_E_ARG, "null argument");
+    PNR_REQUIRE(!staged || (stage >= advantra::RECON_N0RES && stage <= advantra::RECON_N2TREE), PNR_E_ARG, "stage %d outside [1, 4]", stage);
+    PNR_REQUIRE(!c || refine_iter <= PNR_RECON_MAX_ITER, PNR_E_ARG, "refine_iter = %d above %d", refine_iter, PNR_RECON_MAX_ITER);
     for (int64_t k = 0; k < 2 * n_links; k++) PNR_REQUIRE(links[k] >= 0 && links[k] < n_nodes, PNR_E_ARG, "link index out of range");
     advantra::ReconParams rp;
     if (trace_rsmpl > 0) rp.trace_rsmpl = trace_rsmpl;
@@ -1333,97 +1324,61 @@ int pnr_reconstruct(const pnr_node *nodes, int64_t n_nodes, const int32_t *links
     if (refine_iter > 0) rp.refine_iter = refine_iter;
     if (epsilon2 > 0) rp.epsilon2 = epsilon2;
     if (group_radius > 0) rp.group_radius = group_radius;
-    if (tree_size_min > 0) rp.tree_size_min = tree_size_min;
-    rp.single_tree = tree_size_min < 0;
-    rp.threads = pnr::host_threads(pnr::Options()); // rank 0 post-processes alone: every CPU this process may use
+    if (!staged) {
+        if (tree_size_min > 0) rp.tree_size_min = tree_size_min;
+        rp.single_tree = tree_size_min < 0;
+    }
+    if (c) {
+        rp.shift = [c](const std::vector<advantra::P4> &src, float s2r, int iters, float eps2, std::vector<advantra::P4> &res) {
+            return pnr_recon_shift(c, src, s2r, iters, eps2, res);
+        };
+        rp.balls = [c](const std::vector<advantra::P4> &pos, float rad, advantra::BallLists &out) { return pnr_recon_balls(c, pos, rad, out); };
+    } else {
+        rp.threads = pnr::host_threads(pnr::Options()); // rank 0 post-processes alone: every CPU this process may use
+    }
     std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
-    std::vector<int32_t> lk(links, links + 2 * n_links), par;
-    advantra::reconstruct(in, lk, rp, out, par);
-    *n_out = (int64_t)out.size();
-    const size_t m = (size_t)std::min<int64_t>(cap, *n_out);
+    std::vector<int32_t> lk(links, links + 2 * n_links), par, sl;
+    if (int rc = advantra::reconstruct(in, lk, rp, out, par, staged ? stage : advantra::RECON_FINAL, staged ? &sl : nullptr)) return rc;
+    if (staged) return put_graph(out, sl, out_nodes, cap_nodes, n_out_nodes, out_links, cap_links, n_out_links);
+    *n_out_nodes = (int64_t)out.size();
+    const size_t m = (size_t)std::min<int64_t>(cap_nodes, *n_out_nodes);
     if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * m);
-    if (out_parent) std::memcpy(out_parent, par.data(), 4 * m);
+    if (out_links) std::memcpy(out_links, par.data(), 4 * m);
     return PNR_OK;
+}
+
+int pnr_reconstruct(const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
+                    float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min,
+                    pnr_node *out_nodes, int32_t *out_parent, int64_t cap, int64_t *n_out)
+{
+    return reconstruct_front(nullptr, false, 0, nodes, n_nodes, links, n_links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, tree_size_min, out_nodes,
+                             cap, n_out, out_parent, cap, nullptr);
 }
 
 int pnr_reconstruct_stage(const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl, float sig2radius,
                           int refine_iter, float epsilon2, float group_radius, int stage, pnr_node *out_nodes, int64_t cap_nodes,
                           int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links, int64_t *n_out_links)
 {
-    PNR_REQUIRE(nodes && n_nodes >= 1 && n_out_nodes && n_out_links && (n_links == 0 || links), PNR_E_ARG, "null argument");
-    PNR_REQUIRE(stage >= advantra::RECON_N0RES && stage <= advantra::RECON_N2TREE, PNR_E_ARG, "stage %d outside [1, 4]", stage);
-    for (int64_t k = 0; k < 2 * n_links; k++) PNR_REQUIRE(links[k] >= 0 && links[k] < n_nodes, PNR_E_ARG, "link index out of range");
-    advantra::ReconParams rp;
-    if (trace_rsmpl > 0) rp.trace_rsmpl = trace_rsmpl;
-    if (sig2radius > 0) rp.sig2radius = sig2radius;
-    if (refine_iter > 0) rp.refine_iter = refine_iter;
-    if (epsilon2 > 0) rp.epsilon2 = epsilon2;
-    if (group_radius > 0) rp.group_radius = group_radius;
-    rp.threads = pnr::host_threads(pnr::Options());
-    std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
-    std::vector<int32_t> lk(links, links + 2 * n_links), par, sl;
-    advantra::reconstruct(in, lk, rp, out, par, stage, &sl);
-    *n_out_nodes = (int64_t)out.size();
-    *n_out_links = (int64_t)sl.size() / 2;
-    if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_out_nodes));
-    if (out_links) std::memcpy(out_links, sl.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_out_links));
-    return PNR_OK;
-}
-
-// pnr_reconstruct[_stage]_ctx: the plugin constants for values <= 0 (as pnr_reconstruct), the two neighbour stages on ctx's GPU
-static void recon_ctx_params(pnr_ctx *c, float trace_rsmpl, float sig2radius, int refine_iter, float epsilon2, float group_radius,
-                             advantra::ReconParams &rp)
-{
-    if (trace_rsmpl > 0) rp.trace_rsmpl = trace_rsmpl;
-    if (sig2radius > 0) rp.sig2radius = sig2radius;
-    if (refine_iter > 0) rp.refine_iter = refine_iter;
-    if (epsilon2 > 0) rp.epsilon2 = epsilon2;
-    if (group_radius > 0) rp.group_radius = group_radius;
-    rp.shift = [c](const std::vector<advantra::P4> &src, float s2r, int iters, float eps2, std::vector<advantra::P4> &res) {
-        return pnr_recon_shift(c, src, s2r, iters, eps2, res);
-    };
-    rp.balls = [c](const std::vector<advantra::P4> &pos, float rad, advantra::BallLists &out) { return pnr_recon_balls(c, pos, rad, out); };
+    return reconstruct_front(nullptr, true, stage, nodes, n_nodes, links, n_links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, 0, out_nodes,
+                             cap_nodes, n_out_nodes, out_links, cap_links, n_out_links);
 }
 
 int pnr_reconstruct_ctx(pnr_ctx *c, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
                         float sig2radius, int refine_iter, float epsilon2, float group_radius, int tree_size_min,
                         pnr_node *out_nodes, int32_t *out_parent, int64_t cap, int64_t *n_out)
 {
-    PNR_REQUIRE(c && nodes && n_nodes >= 1 && n_out && (n_links == 0 || links), PNR_E_ARG, "null argument");
-    PNR_REQUIRE(refine_iter <= PNR_RECON_MAX_ITER, PNR_E_ARG, "refine_iter = %d above %d", refine_iter, PNR_RECON_MAX_ITER);
-    for (int64_t k = 0; k < 2 * n_links; k++) PNR_REQUIRE(links[k] >= 0 && links[k] < n_nodes, PNR_E_ARG, "link index out of range");
-    advantra::ReconParams rp;
-    recon_ctx_params(c, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, rp);
-    if (tree_size_min > 0) rp.tree_size_min = tree_size_min;
-    rp.single_tree = tree_size_min < 0;
-    std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
-    std::vector<int32_t> lk(links, links + 2 * n_links), par;
-    if (int rc = advantra::reconstruct(in, lk, rp, out, par)) return rc;
-    *n_out = (int64_t)out.size();
-    const size_t m = (size_t)std::min<int64_t>(cap, *n_out);
-    if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * m);
-    if (out_parent) std::memcpy(out_parent, par.data(), 4 * m);
-    return PNR_OK;
+    PNR_REQUIRE(c, PNR_E_ARG, "null argument");
+    return reconstruct_front(c, false, 0, nodes, n_nodes, links, n_links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, tree_size_min, out_nodes, cap,
+                             n_out, out_parent, cap, nullptr);
 }
 
 int pnr_reconstruct_stage_ctx(pnr_ctx *c, const pnr_node *nodes, int64_t n_nodes, const int32_t *links, int64_t n_links, float trace_rsmpl,
                               float sig2radius, int refine_iter, float epsilon2, float group_radius, int stage, pnr_node *out_nodes,
                               int64_t cap_nodes, int64_t *n_out_nodes, int32_t *out_links, int64_t cap_links, int64_t *n_out_links)
 {
-    PNR_REQUIRE(c && nodes && n_nodes >= 1 && n_out_nodes && n_out_links && (n_links == 0 || links), PNR_E_ARG, "null argument");
-    PNR_REQUIRE(stage >= advantra::RECON_N0RES && stage <= advantra::RECON_N2TREE, PNR_E_ARG, "stage %d outside [1, 4]", stage);
-    PNR_REQUIRE(refine_iter <= PNR_RECON_MAX_ITER, PNR_E_ARG, "refine_iter = %d above %d", refine_iter, PNR_RECON_MAX_ITER);
-    for (int64_t k = 0; k < 2 * n_links; k++) PNR_REQUIRE(links[k] >= 0 && links[k] < n_nodes, PNR_E_ARG, "link index out of range");
-    advantra::ReconParams rp;
-    recon_ctx_params(c, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, rp);
-    std::vector<pnr_node> in(nodes, nodes + n_nodes), out;
-    std::vector<int32_t> lk(links, links + 2 * n_links), par, sl;
-    if (int rc = advantra::reconstruct(in, lk, rp, out, par, stage, &sl)) return rc;
-    *n_out_nodes = (int64_t)out.size();
-    *n_out_links = (int64_t)sl.size() / 2;
-    if (out_nodes) std::memcpy(out_nodes, out.data(), sizeof(pnr_node) * (size_t)std::min<int64_t>(cap_nodes, *n_out_nodes));
-    if (out_links) std::memcpy(out_links, sl.data(), 8 * (size_t)std::min<int64_t>(cap_links, *n_out_links));
-    return PNR_OK;
+    PNR_REQUIRE(c, PNR_E_ARG, "null argument");
+    return reconstruct_front(c, true, stage, nodes, n_nodes, links, n_links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, 0, out_nodes, cap_nodes,
+                             n_out_nodes, out_links, cap_links, n_out_links);
 }
 
 int pnr_get_table(pnr_ctx *c, const char *name, void *out, int64_t cap, int64_t *n)

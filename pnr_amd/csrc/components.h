@@ -16,7 +16,6 @@ constexpr int CC_CHUNK = 4096;
 
 // The components of {V >= t} of the context's volume under the rule of include/pnr_hip.h, on c's stream; the arguments are checked
 // by the caller.  Host outputs, all nullable: info, label_out (N), comps (the first min(cap, n_comp)).  despeckled (nullable): receives a
-// device buffer of N bytes (the caller adopts it) with the components below min_size cleared.  Every other device buffer is freed
-// before the call returns.
+// device buffer of N bytes with the components below min_size cleared.  Every other device buffer is freed before the call returns.
 int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o, pnr_components_info *info, int32_t *label_out, pnr_component *comps,
-                       int64_t cap, uint8_t **despeckled);
+                       int64_t cap, pnr::DevBuf<uint8_t> *despeckled);

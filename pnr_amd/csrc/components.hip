@@ -18,7 +18,8 @@
 //   cc_finish   label = number of the kept component of the voxel's root (0: background or dropped); despeckle: V or 0.
 // The host takes the sizes, drops what is below min_size and numbers the rest in the same order.
 #include "components.h"
-#include "render.h"
+#include "call.h"
+#include "volume.h"
 #include <cstring>
 
 namespace {
@@ -353,9 +354,8 @@ __global__ __launch_bounds__(TPB) void cc_finish(unsigned *link, const unsigned 
 } // namespace
 
 int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o, pnr_components_info *info, int32_t *label_out, pnr_component *comps,
-                       int64_t cap, uint8_t **despeckled)
+                       int64_t cap, pnr::DevBuf<uint8_t> *despeckled)
 {
-    hipStream_t st = c->stream;
     const int64_t N = c->N;
     const int w = (int)c->w, h = (int)c->h, l = (int)c->l;
     const int tiles_x = (w + CC_TX - 1) / CC_TX, tiles_y = (h + CC_TY - 1) / CC_TY, tiles_z = (l + CC_TZ - 1) / CC_TZ;
@@ -363,40 +363,29 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
     PNR_REQUIRE(tiles < (1LL << 31), PNR_E_ARG, "%s: volume extent too large", who);
     // device buffers of the call: the links (later the labels) | the ids of the roots | the chunk counts | the byte sum
     pnr::CallBuf buf; // (freed when the call returns)
-    const size_t o_link = buf.add((size_t)N * 4 + 16), o_id = buf.add((size_t)N * 4), o_cnt = buf.add((size_t)chunks * 4), o_sum = buf.add(8);
+    const auto d_link = buf.add<unsigned>((size_t)N + 4), d_id = buf.add<unsigned>((size_t)N), d_cnt = buf.add<unsigned>((size_t)chunks);
+    const auto d_sum = buf.add<unsigned long long>(1);
     int rc = buf.alloc(who);
     if (rc) return rc;
-    unsigned *const d_link = buf.at<unsigned>(o_link), *const d_id = buf.at<unsigned>(o_id), *const d_cnt = buf.at<unsigned>(o_cnt);
     pnr::DevBuf<uint8_t> d_out;
-    if (despeckled && d_out.alloc((size_t)N) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("%s: device allocation of %zu B for the despeckled volume failed", who, (size_t)N);
-        return PNR_E_NOMEM;
-    }
-    hipError_t e;
+    if (despeckled && (rc = pnr::dev_alloc(d_out, (size_t)N, who, "for the despeckled volume"))) return rc;
     int t = o.thr;
-    if (o.thr < 0) { // the global mean, from the exact sum
-        unsigned long long *d_sum = buf.at<unsigned long long>(o_sum), sum = 0;
-        if ((e = hipMemsetAsync(d_sum, 0, 8, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-        if ((rc = pnr_byte_sum_run(c, who, "components_threshold", c->d_img, N, d_sum, &sum))) return rc;
-        t = (int)std::max<unsigned long long>(1, sum / (unsigned long long)N);
-    }
+    if (o.thr < 0 && (rc = pnr_mean_threshold(c, who, "components_threshold", c->d_img, N, d_sum, &t))) return rc; // the global mean
+    pnr::Call call(c, who);
     const Tiles ta{c->d_img, d_link, w, h, l, tiles_x, tiles_y, t, o.connectivity == 26 ? 1 : 0};
     c->tic();
-    hipLaunchKernelGGL(cc_local, dim3((unsigned)tiles), dim3(TPB), 0, st, ta);
+    call.launch(cc_local, dim3((unsigned)tiles), dim3(TPB), ta);
     c->toc("components_local", 1);
     c->tic();
-    hipLaunchKernelGGL(cc_merge, dim3((unsigned)tiles), dim3(TPB), 0, st, ta);
+    call.launch(cc_merge, dim3((unsigned)tiles), dim3(TPB), ta);
     c->toc("components_merge", 1);
     c->tic();
-    hipLaunchKernelGGL(cc_flatten, dim3((unsigned)chunks), dim3(TPB), 0, st, d_link, (long long)N, d_cnt);
-    e = hipGetLastError();
+    call.launch(cc_flatten, dim3((unsigned)chunks), dim3(TPB), d_link, (long long)N, d_cnt);
     c->toc("components_flatten", 1);
     // the chunk counts become their exclusive scan
     std::vector<unsigned> cnt((size_t)chunks);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)chunks * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+    call.down(cnt.data(), d_cnt);
+    if ((rc = call.finish())) return rc;
     int64_t K = 0; // every component, the small ones included
     for (auto &v : cnt) {
         const unsigned n = v;
@@ -406,28 +395,26 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
     // the full numbering, the statistics, and what min_size keeps
     pnr::CallBuf sbuf;
     const size_t k = (size_t)K;
-    const size_t s_roots = sbuf.add(k * 4), s_new = sbuf.add(k * 4), s_zero = sbuf.add(0), s_size = sbuf.add(k * 4), s_sum = sbuf.add(k * 32), s_mx = sbuf.add(k * 12),
-                 s_vmax = sbuf.add(k * 4), s_mn = sbuf.add(k * 12), s_end = sbuf.add(0);
+    const auto s_roots = sbuf.add<unsigned>(k), s_new = sbuf.add<unsigned>(k), s_size = sbuf.add<unsigned>(k); // (zeroed from s_size up to s_mn)
+    const auto s_sum = sbuf.add<unsigned long long>(4 * k);
+    const auto s_mx = sbuf.add<unsigned>(3 * k), s_vmax = sbuf.add<unsigned>(k), s_mn = sbuf.add<unsigned>(3 * k);
     std::vector<unsigned> size, newid;
     int64_t n_fg = 0, n_comp = 0, n_small = 0, vox_small = 0, largest = 0;
     if (K > 0) {
         if ((rc = sbuf.alloc(who))) return rc;
-        const Stats sa{sbuf.at<unsigned>(s_size), sbuf.at<unsigned long long>(s_sum), sbuf.at<unsigned long long>(s_sum) + k, sbuf.at<unsigned long long>(s_sum) + 2 * k,
-                       sbuf.at<unsigned long long>(s_sum) + 3 * k, sbuf.at<unsigned>(s_mn), sbuf.at<unsigned>(s_mx), sbuf.at<unsigned>(s_vmax), (long long)K};
-        if ((e = hipMemcpyAsync(d_cnt, cnt.data(), (size_t)chunks * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-        if ((e = hipMemsetAsync(sbuf.at<char>(s_zero), 0, s_mn - s_zero, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-        if ((e = hipMemsetAsync(sbuf.at<char>(s_mn), 0xff, s_end - s_mn, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+        const Stats sa{s_size, s_sum, s_sum + k, s_sum + 2 * k, s_sum + 3 * k, s_mn, s_mx, s_vmax, (long long)K};
+        call.up(d_cnt, cnt.data());
+        call.fill((char *)s_size.get(), 0, s_mn.off - s_size.off);
+        call.fill(s_mn, 0xff);
         c->tic();
-        hipLaunchKernelGGL(cc_number, dim3((unsigned)chunks), dim3(TPB), 0, st, d_link, (long long)N, d_cnt, d_id, sbuf.at<unsigned>(s_roots));
+        call.launch(cc_number, dim3((unsigned)chunks), dim3(TPB), d_link, (long long)N, d_cnt, d_id, s_roots);
         c->toc("components_number", 1);
         c->tic();
-        hipLaunchKernelGGL(cc_stats, dim3((unsigned)tiles), dim3(TPB), 0, st, ta, d_id, sa);
-        e = hipGetLastError();
+        call.launch(cc_stats, dim3((unsigned)tiles), dim3(TPB), ta, d_id, sa);
         c->toc("components_stats", 1);
         size.resize(k);
-        if (e == hipSuccess) e = hipMemcpyAsync(size.data(), sa.size, k * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+        call.down(size.data(), s_size);
+        if ((rc = call.finish())) return rc;
         newid.resize(k);
         for (size_t i = 0; i < k; i++) {
             const int64_t n = size[i];
@@ -447,13 +434,12 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
     if (fill > 0) {
         std::vector<unsigned> roots(k), box(k * 7); // mx (3 K) | vmax (K) | mn (3 K)
         std::vector<unsigned long long> sums(k * 4);
-        e = hipMemcpyAsync(roots.data(), sbuf.at<unsigned>(s_roots), k * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), sbuf.at<char>(s_sum), k * 32, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(box.data(), sbuf.at<char>(s_mx), k * 12, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(box.data() + 3 * k, sbuf.at<char>(s_vmax), k * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(box.data() + 4 * k, sbuf.at<char>(s_mn), k * 12, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+        call.down(roots.data(), s_roots);
+        call.down(sums.data(), s_sum);
+        call.down(box.data(), s_mx);
+        call.down(box.data() + 3 * k, s_vmax);
+        call.down(box.data() + 4 * k, s_mn);
+        if ((rc = call.finish())) return rc;
         int64_t j = 0;
         for (size_t i = 0; i < k && j < fill; i++) {
             if (!newid[i]) continue;
@@ -468,18 +454,16 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
     if (!label_out && !despeckled) return PNR_OK;
     const unsigned *d_new = nullptr;
     if (n_small > 0) {
-        d_new = sbuf.at<unsigned>(s_new);
-        if ((e = hipMemcpyAsync(sbuf.at<unsigned>(s_new), newid.data(), k * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+        d_new = s_new;
+        call.up(s_new, newid.data());
     }
     const long long groups = (N + 3) >> 2;
     c->tic();
-    hipLaunchKernelGGL(cc_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((groups + TPB - 1) / TPB, MAX_BLOCKS))), dim3(TPB), 0, st, d_link, d_id, d_new,
-                       c->d_img, d_out.get(), label_out ? 1 : 0, (long long)N);
-    e = hipGetLastError();
+    call.launch(cc_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((groups + TPB - 1) / TPB, MAX_BLOCKS))), dim3(TPB), d_link, d_id, d_new, c->d_img,
+                d_out.get(), label_out ? 1 : 0, (long long)N);
     c->toc("components_finish", 1);
-    if (e == hipSuccess && label_out) e = hipMemcpyAsync(label_out, d_link, (size_t)N * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
-    if (despeckled) *despeckled = d_out.release();
+    if (label_out) call.down(label_out, d_link.get(), (size_t)N);
+    if ((rc = call.finish())) return rc;
+    if (despeckled) *despeckled = std::move(d_out);
     return PNR_OK;
 }

@@ -34,38 +34,6 @@ void set_error(const char *fmt, ...);
         }                                 \
     } while (0)
 
-// All device buffers of one call as ONE DevBuf (pnr_live_bytes sees one allocation, which ends with its owner): add() the parts --
-// each starts on a 16-byte boundary --, alloc() once, then at<T>(offset).
-class CallBuf {
-    DevBuf<char> buf_;
-    size_t bytes_ = 0;
-
-public:
-    size_t add(size_t bytes) // -> the offset of the part
-    {
-        const size_t o = bytes_;
-        bytes_ += (bytes + 15) & ~(size_t)15;
-        return o;
-    }
-    int alloc(const char *who)
-    {
-        if (buf_.alloc(bytes_) == hipSuccess) return PNR_OK;
-        (void)hipGetLastError();
-        set_error("%s: device allocation of %zu B failed", who, bytes_);
-        return PNR_E_NOMEM;
-    }
-    template <typename T>
-    T *at(size_t offset) const { return (T *)(buf_.get() + offset); }
-};
-
-// the way out of a call that has work queued on st when a HIP call fails
-inline int hip_fail(hipStream_t st, const char *who, hipError_t e)
-{
-    (void)hipStreamSynchronize(st);
-    set_error("%s: %s", who, hipGetErrorString(e));
-    return PNR_E_HIP;
-}
-
 // ---- host tables (tables.cpp): Tracker::Tracker (tracker.cpp:79-527) + Gaussian taps ----
 struct Tables {
     int sz = 0, ndir = 50, nsig = 0;

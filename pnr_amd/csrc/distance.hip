@@ -7,6 +7,7 @@
 // vector unit only does the ~25 operations of the pair.  Every pair counts, so a point whose minimum stays +inf reports the first
 // segment of the smallest slice.  Above it: tree_sample, the host's sampling of a tree.
 #include "distance.h"
+#include "call.h"
 #include "pairmin.h"
 #include <cmath>
 
@@ -91,33 +92,25 @@ struct DistRule {
 int pnr_distance_run(pnr_ctx *c, const float *pts, int64_t n, const float *seg_a, const float *seg_b, int64_t m, float *d_out, int32_t *j_out)
 {
     static const char *who = "pnr_point_segment_distance";
-    hipStream_t st = c->stream;
     pnr::CallBuf buf; // (freed when the call returns)
-    const size_t o_seg = buf.add((size_t)m * 32), o_key = buf.add((size_t)n * 8), o_pts = buf.add((size_t)n * 12), o_a = buf.add((size_t)m * 12),
-                 o_b = buf.add((size_t)m * 12), o_d = buf.add((size_t)n * 4), o_j = buf.add((size_t)n * 4);
+    const auto d_seg = buf.add<float4>((size_t)m * 2);
+    const auto d_key = buf.add<unsigned long long>((size_t)n);
+    const auto d_pts = buf.add<float>((size_t)n * 3), d_a = buf.add<float>((size_t)m * 3), d_b = buf.add<float>((size_t)m * 3), d_d = buf.add<float>((size_t)n);
+    const auto d_j = buf.add<int>((size_t)n);
     const int rc = buf.alloc(who);
     if (rc) return rc;
-    float4 *const d_seg = buf.at<float4>(o_seg);
-    unsigned long long *const d_key = buf.at<unsigned long long>(o_key);
-    float *const d_pts = buf.at<float>(o_pts);
-    hipError_t e;
-    if ((e = hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-    if ((e = hipMemcpyAsync(buf.at<float>(o_a), seg_a, (size_t)m * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-    if ((e = hipMemcpyAsync(buf.at<float>(o_b), seg_b, (size_t)m * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+    pnr::Call call(c, who);
+    call.up(d_pts, pts);
+    call.up(d_a, seg_a);
+    call.up(d_b, seg_b);
+    call.fill(d_key, 0xff);
     int launches = 0;
     c->tic();
-    hipLaunchKernelGGL(dist_prep, dim3((unsigned)((m + DTPB - 1) / DTPB)), dim3(DTPB), 0, st, (const float *)buf.at<float>(o_a), (const float *)buf.at<float>(o_b), (int)m, d_seg);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = pnr::pair_sweep(st, DistRule{d_pts, d_seg}, n, m, c->opt.dist_split, c->opt.dist_pairs_per_launch, d_key, &launches);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pnr::pair_finish, dim3((unsigned)((n + DTPB - 1) / DTPB)), dim3(DTPB), 0, st, (const unsigned long long *)d_key, (int)n, 1, buf.at<float>(o_d), buf.at<int>(o_j));
-        e = hipGetLastError();
-    }
+    call.launch(dist_prep, dim3((unsigned)((m + DTPB - 1) / DTPB)), dim3(DTPB), d_a, d_b, (int)m, d_seg);
+    if (call.ok()) call.note(pnr::pair_sweep(call.stream(), DistRule{d_pts, d_seg}, n, m, c->opt.dist_split, c->opt.dist_pairs_per_launch, d_key, &launches));
+    call.launch(pnr::pair_finish, dim3((unsigned)((n + DTPB - 1) / DTPB)), dim3(DTPB), d_key, (int)n, 1, d_d, d_j);
     c->toc("distance", 2 + launches);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, buf.at<float>(o_d), (size_t)n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && j_out) e = hipMemcpyAsync(j_out, buf.at<int>(o_j), (size_t)n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
-    return PNR_OK;
+    call.down(d_out, d_d);
+    if (j_out) call.down(j_out, d_j);
+    return call.finish();
 }

@@ -12,6 +12,6 @@ constexpr int MED_ZC = 32;
 constexpr int TH_CH = 2048;
 
 // Filters c's volume (c->d_img, never written) with the validated options `o` (at least one stage on) on c's stream into a new
-// device buffer of c->N bytes, returned in *result (the caller owns it).  At most one more buffer of N bytes lives during the
+// device buffer of c->N bytes, moved into `result`.  At most one more buffer of N bytes lives during the
 // call.  A failed allocation returns PNR_E_NOMEM; on any failure nothing is returned and the context is untouched.
-int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, uint8_t **result);
+int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, pnr::DevBuf<uint8_t> &result);

@@ -26,6 +26,7 @@
 //     once per segment: three LDS accesses and two min / max per voxel whatever r is.  A line is read r samples ahead of where it
 //     is written, so this pass works in place too.
 #include "filter.h"
+#include "call.h"
 
 namespace {
 
@@ -311,59 +312,43 @@ __global__ __launch_bounds__(TPB) void th_col(const uint8_t *src, uint8_t *dst, 
 }
 
 template <bool MAX>
-int launch_x(hipStream_t st, const uint8_t *src, uint8_t *dst, int w, i64 nrows, int r)
+int launch_x(pnr::Call &call, const uint8_t *src, uint8_t *dst, int w, i64 nrows, int r)
 {
-    hipLaunchKernelGGL(th_x<MAX>, dim3((unsigned)std::min<i64>(nrows, MAX_ROW_BLOCKS)), dim3(TPB), 0, st, src, dst, w, nrows, r);
+    call.launch(th_x<MAX>, dim3((unsigned)std::min<i64>(nrows, MAX_ROW_BLOCKS)), dim3(TPB), src, dst, w, nrows, r);
     return 1;
 }
 
 template <bool MAX>
-int launch_col(hipStream_t st, const uint8_t *src, uint8_t *dst, const uint8_t *M, i64 nlines, i64 inner, i64 outer, int n, int r)
+int launch_col(pnr::Call &call, const uint8_t *src, uint8_t *dst, const uint8_t *M, i64 nlines, i64 inner, i64 outer, int n, int r)
 {
-    const dim3 g((unsigned)((nlines + TPB - 1) / TPB));
-    if (M)
-        hipLaunchKernelGGL((th_col<MAX, true>), g, dim3(TPB), 0, st, src, dst, M, nlines, inner, outer, n, r);
-    else
-        hipLaunchKernelGGL((th_col<MAX, false>), g, dim3(TPB), 0, st, src, dst, M, nlines, inner, outer, n, r);
+    call.launch(M ? th_col<MAX, true> : th_col<MAX, false>, dim3((unsigned)((nlines + TPB - 1) / TPB)), dim3(TPB), src, dst, M, nlines, inner, outer, n, r);
     return 1;
-}
-
-int alloc_volume(size_t n, pnr::DevBuf<uint8_t> &p, const char *what)
-{
-    if (p.alloc(n) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("pnr_filter_volume: device allocation of %zu B for %s failed", n, what);
-        return PNR_E_NOMEM;
-    }
-    return PNR_OK;
 }
 
 } // namespace
 
-int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, uint8_t **result)
+int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, pnr::DevBuf<uint8_t> &result)
 {
+    static const char *who = "pnr_filter_volume";
     const int w = (int)c->w, h = (int)c->h, l = (int)c->l;
     const i64 N = c->N, plane = (i64)w * h;
     const int tiles_x = (w + MED_TX - 1) / MED_TX, tiles_y = (h + MED_TY - 1) / MED_TY;
     const i64 med_blocks = (i64)tiles_x * tiles_y * ((l + MED_ZC - 1) / MED_ZC);
     const i64 col_blocks = (std::max((i64)w * l, plane) + TPB - 1) / TPB;
-    PNR_REQUIRE(med_blocks < (1LL << 31) && col_blocks < (1LL << 31), PNR_E_ARG, "pnr_filter_volume: volume extent too large");
+    PNR_REQUIRE(med_blocks < (1LL << 31) && col_blocks < (1LL << 31), PNR_E_ARG, "%s: volume extent too large", who);
     const bool both = o.median && o.tophat_r;
-    hipStream_t st = c->stream;
     pnr::DevBuf<uint8_t> bA, bB; // A: the first stage's output; B: the top-hat's buffer behind a median
-    int rc = alloc_volume((size_t)N, bA, "the filtered volume");
-    if (!rc && both) rc = alloc_volume((size_t)N, bB, "the top-hat scratch");
+    int rc = pnr::dev_alloc(bA, (size_t)N, who, "for the filtered volume");
+    if (!rc && both) rc = pnr::dev_alloc(bB, (size_t)N, who, "for the top-hat scratch");
     if (rc) return rc;
     uint8_t *const A = bA.get(), *const B = bB.get();
     const uint8_t *V = c->d_img;
     uint8_t *out = A;
     int launches = 0;
+    pnr::Call call(c, who);
     c->tic();
     if (o.median) {
-        if (o.median == 3)
-            hipLaunchKernelGGL(median_k<true>, dim3((unsigned)med_blocks), dim3(TPB), 0, st, V, A, w, h, l, tiles_x, tiles_y);
-        else
-            hipLaunchKernelGGL(median_k<false>, dim3((unsigned)med_blocks), dim3(TPB), 0, st, V, A, w, h, l, tiles_x, tiles_y);
+        call.launch(o.median == 3 ? median_k<true> : median_k<false>, dim3((unsigned)med_blocks), dim3(TPB), V, A, w, h, l, tiles_x, tiles_y);
         launches++;
         V = A;
     }
@@ -373,20 +358,15 @@ int pnr_filter_run(pnr_ctx *c, const pnr_filter_opts &o, uint8_t **result)
         uint8_t *W = both ? B : A;
         out = W;
         const i64 nrows = (i64)h * l;
-        launches += launch_x<false>(st, V, W, w, nrows, R);
-        launches += launch_col<false>(st, W, W, nullptr, (i64)w * l, w, plane, h, R);
-        if (rz) launches += launch_col<false>(st, W, W, nullptr, plane, plane, 0, l, rz);
-        launches += launch_x<true>(st, W, W, w, nrows, R);
-        launches += launch_col<true>(st, W, W, rz ? nullptr : V, (i64)w * l, w, plane, h, R);
-        if (rz) launches += launch_col<true>(st, W, W, V, plane, plane, 0, l, rz);
+        launches += launch_x<false>(call, V, W, w, nrows, R);
+        launches += launch_col<false>(call, W, W, nullptr, (i64)w * l, w, plane, h, R);
+        if (rz) launches += launch_col<false>(call, W, W, nullptr, plane, plane, 0, l, rz);
+        launches += launch_x<true>(call, W, W, w, nrows, R);
+        launches += launch_col<true>(call, W, W, rz ? nullptr : V, (i64)w * l, w, plane, h, R);
+        if (rz) launches += launch_col<true>(call, W, W, V, plane, plane, 0, l, rz);
     }
-    hipError_t e = hipGetLastError();
     c->toc("filter", launches);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        pnr::set_error("pnr_filter_volume: %s", hipGetErrorString(e));
-        return PNR_E_HIP;
-    }
-    *result = (out == A ? bA : bB).release(); // the caller adopts it; the other buffer is freed here
+    if ((rc = call.finish())) return rc;
+    result = std::move(out == A ? bA : bB); // (the other buffer is freed here)
     return PNR_OK;
 }

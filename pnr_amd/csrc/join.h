@@ -1,6 +1,6 @@
 // join.h -- the traced forest joined into one tree (join.hip), behind pnr_nearest_other / pnr_join_trees / pnr_join_reroot.
 #pragma once
-#include "ctx.h"
+#include "call.h"
 
 namespace pnr {
 // The nearest-other search of one call (JoinRule under the pair minimum of pairmin.h): the device buffers (one CallBuf, freed with the
@@ -12,7 +12,10 @@ class JoinSearch {
     pnr_ctx *c_ = nullptr;
     int64_t n_ = 0;
     CallBuf buf_;
-    size_t o_tgt_ = 0, o_key_ = 0, o_xyz_ = 0, o_lab_ = 0, o_d_ = 0, o_j_ = 0;
+    Part<float4> tgt_;
+    Part<unsigned long long> key_;
+    Part<float> xyz_, d_;
+    Part<int> lab_, j_;
 
 public:
     int begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who);

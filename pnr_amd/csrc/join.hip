@@ -48,39 +48,32 @@ int JoinSearch::begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who)
     c_ = c;
     n_ = n;
     // device buffers of the call: the packed points | the packed minima | xyz | the labels | d | j
-    o_tgt_ = buf_.add((size_t)n * 16), o_key_ = buf_.add((size_t)n * 8), o_xyz_ = buf_.add((size_t)n * 12);
-    o_lab_ = buf_.add((size_t)n * 4), o_d_ = buf_.add((size_t)n * 4), o_j_ = buf_.add((size_t)n * 4);
+    const size_t k = (size_t)n;
+    tgt_ = buf_.add<float4>(k), key_ = buf_.add<unsigned long long>(k), xyz_ = buf_.add<float>(3 * k);
+    lab_ = buf_.add<int>(k), d_ = buf_.add<float>(k), j_ = buf_.add<int>(k);
     const int rc = buf_.alloc(who);
     if (rc) return rc;
-    const hipError_t e = hipMemcpyAsync(buf_.at<float>(o_xyz_), xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-    return e == hipSuccess ? PNR_OK : hip_fail(c->stream, who, e);
+    Call call(c, who);
+    call.up(xyz_, xyz);
+    return call.ok() ? PNR_OK : call.finish(); // (not synchronised: run() follows on the same stream)
 }
 
 int JoinSearch::run(const int32_t *label, bool root, float *d_out, int32_t *j_out, const char *who)
 {
     pnr_ctx *const c = c_;
-    hipStream_t st = c->stream;
     const long long n = n_;
-    float4 *const d_tgt = buf_.at<float4>(o_tgt_);
-    unsigned long long *const d_key = buf_.at<unsigned long long>(o_key_);
-    hipError_t e;
-    if ((e = hipMemcpyAsync(buf_.at<int>(o_lab_), label, (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(st, who, e);
-    if ((e = hipMemsetAsync(d_key, 0xff, (size_t)n * 8, st)) != hipSuccess) return hip_fail(st, who, e);
+    Call call(c, who);
+    call.up(lab_, label);
+    call.fill(key_, 0xff);
     int launches = 0;
     c->tic();
-    hipLaunchKernelGGL(join_prep, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const float *)buf_.at<float>(o_xyz_), (const int *)buf_.at<int>(o_lab_), (int)n, d_tgt);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = pair_sweep(st, JoinRule{d_tgt}, n, n, c->opt.join_split, c->opt.join_pairs_per_launch, d_key, &launches);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pair_finish, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), 0, st, (const unsigned long long *)d_key, (int)n, root ? 1 : 0, buf_.at<float>(o_d_), buf_.at<int>(o_j_));
-        e = hipGetLastError();
-    }
+    call.launch(join_prep, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), xyz_, lab_, (int)n, tgt_);
+    if (call.ok()) call.note(pair_sweep(call.stream(), JoinRule{tgt_}, n, n, c->opt.join_split, c->opt.join_pairs_per_launch, key_, &launches));
+    call.launch(pair_finish, dim3((unsigned)((n + JTPB - 1) / JTPB)), dim3(JTPB), key_, (int)n, root ? 1 : 0, d_, j_);
     c->toc("join", 2 + launches);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, buf_.at<float>(o_d_), (size_t)n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(j_out, buf_.at<int>(o_j_), (size_t)n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(st, who, e);
-    return PNR_OK;
+    call.down(d_out, d_);
+    call.down(j_out, j_);
+    return call.finish();
 }
 
 // ---- the host side ----

@@ -10,8 +10,10 @@
 // test at every shell end is wave-uniform and the wave leaves at the first failing shell -- most nodes stop within a handful of
 // shells, nothing like a (2 rmax + 1)^3 cube is ever staged.  The nodes are handed to the waves in the order of the 8^3 cells
 // their centres lie in (a host sort; the outputs stay in input order), so that neighbouring waves gather from the same lines.
-// The global mean is one grid-stride u64 reduction with one atomic per work-group.
+// The global mean is the byte sum of volume.hip (pnr_mean_threshold).
 #include "radius.h"
+#include "call.h"
+#include "volume.h"
 #include <cmath>
 #include <cstring>
 
@@ -56,31 +58,6 @@ namespace {
 constexpr int RTPB = 256;          // threads of a work-group: four waves = four nodes
 constexpr int RWAVES = RTPB / 64;
 constexpr int RUNROLL = 4;         // 64-offset groups of a shell whose gathers are issued together
-constexpr int MAX_BLOCKS = 2048;   // grid-stride loop of the sum beyond this many work-groups
-
-// sum of the bytes p[0, n): scalar head up to the first 16-byte boundary, 16-byte vectors, scalar tail
-__global__ __launch_bounds__(RTPB) void rad_sum(const uint8_t *p, long long n, long long head, long long nvec, unsigned long long *out)
-{
-    __shared__ unsigned long long part[RWAVES];
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
-    unsigned long long s = 0;
-    const uint4 *v = (const uint4 *)(p + head);
-    auto bytes = [](unsigned x) { const unsigned y = (x & 0x00ff00ffu) + ((x >> 8) & 0x00ff00ffu); return (y & 0xffffu) + (y >> 16); };
-    for (long long g = gid; g < nvec; g += stride) {
-        const uint4 q = v[g];
-        s += bytes(q.x) + bytes(q.y) + bytes(q.z) + bytes(q.w);
-    }
-    if (gid < head) s += p[gid];
-    const long long t0 = head + 16 * nvec;
-    if (gid < n - t0) s += p[t0 + gid]; // (fewer than 16 left)
-    for (int d = 32; d >= 1; d >>= 1) s += (unsigned long long)__shfl_xor((long long)s, d, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < RWAVES; k++) s += part[k];
-        if (s) atomicAdd(out, s);
-    }
-}
 
 struct RadArgs {
     const uint8_t *img;
@@ -188,31 +165,14 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
     }
     // device buffers of the call: the sum | the positions | the order of the nodes | k
     pnr::CallBuf buf; // (freed when the call returns)
-    const size_t o_sum = buf.add(8), o_xyz = buf.add((size_t)n * 12), o_ord = buf.add((size_t)n * 4), o_k = buf.add((size_t)n * 4);
-    const int rc = buf.alloc(who);
+    const auto d_sum = buf.add<unsigned long long>(1);
+    const auto d_xyz = buf.add<float>((size_t)n * 3);
+    const auto d_ord = buf.add<int>((size_t)n), d_k = buf.add<int>((size_t)n);
+    int rc = buf.alloc(who);
     if (rc) return rc;
-    hipError_t e = hipSuccess;
-    int t_abs = 0;
-    if (o.rel_pct == 0) {
-        t_abs = o.thr;
-        if (o.thr < 0) { // the global mean, from the exact sum
-            unsigned long long *d_sum = buf.at<unsigned long long>(o_sum), sum = 0;
-            const uintptr_t addr = (uintptr_t)c->d_img;
-            const long long head = std::min<long long>(c->N, (long long)((16 - (addr & 15)) & 15)), nvec = (c->N - head) >> 4;
-            const long long work = std::max<long long>(nvec, 16);
-            const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((work + RTPB - 1) / RTPB, MAX_BLOCKS));
-            if ((e = hipMemsetAsync(d_sum, 0, 8, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-            c->tic();
-            hipLaunchKernelGGL(rad_sum, dim3(nb), dim3(RTPB), 0, st, c->d_img, (long long)c->N, head, nvec, d_sum);
-            e = hipGetLastError();
-            c->toc("radius", 1);
-            if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return pnr::hip_fail(st, who, e);
-            t_abs = (int)std::max<unsigned long long>(1, sum / (unsigned long long)c->N);
-        }
-    }
-    if (thr_used) *thr_used = o.rel_pct ? 0 : t_abs;
+    int t_abs = o.rel_pct ? 0 : o.thr;
+    if (t_abs < 0 && (rc = pnr_mean_threshold(c, who, "radius", c->d_img, c->N, d_sum, &t_abs))) return rc; // the global mean
+    if (thr_used) *thr_used = t_abs;
     if (n > 0) {
         // the order of the 8^3 cells of the centres (positions that are not measured last); it changes no result
         std::vector<std::pair<uint64_t, int>> cell((size_t)n);
@@ -228,17 +188,15 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         std::sort(cell.begin(), cell.end());
         std::vector<int> order((size_t)n);
         for (int64_t i = 0; i < n; i++) order[(size_t)i] = cell[(size_t)i].second;
-        if ((e = hipMemcpyAsync(buf.at<float>(o_xyz), xyz, (size_t)n * 12, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-        if ((e = hipMemcpyAsync(buf.at<int>(o_ord), order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-        RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, d_off, d_start, buf.at<float>(o_xyz), buf.at<int>(o_ord),
-                  (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, buf.at<int>(o_k)};
+        pnr::Call call(c, who);
+        call.up(d_xyz, xyz);
+        call.up(d_ord, order.data());
+        const RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, d_off, d_start, d_xyz, d_ord, (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, d_k};
         c->tic();
-        hipLaunchKernelGGL(rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), 0, st, a);
-        e = hipGetLastError();
+        call.launch(rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), a);
         c->toc("radius", 1);
-        if (e == hipSuccess) e = hipMemcpyAsync(k_out, buf.at<int>(o_k), (size_t)n * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st); // (the host vectors above end here)
-        if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+        call.down(k_out, d_k);
+        return call.finish(); // (the host vectors above end here)
     }
     return PNR_OK;
 }

@@ -37,7 +37,3 @@ void render_items(const RenderTree &t, int64_t w, int64_t h, int64_t l, int64_t 
 // is freed before the call returns.
 int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_t w, int64_t h, int64_t l, const uint8_t *V, int thr, int32_t *label_out,
                    uint8_t *mask_out, uint8_t *residual_out, pnr_coverage *cov, int64_t *seg_vox, int64_t *seg_fg, int64_t *seg_sum);
-
-// The exact u64 sum of the N bytes at V (device memory) behind thr = -1 of the coverage and of the components: *sum, through the
-// zeroed device word d_sum, on c's stream (synchronised on return); the kernel is timed under `group`.
-int pnr_byte_sum_run(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_sum, unsigned long long *sum);

@@ -9,8 +9,10 @@
 // issues a 32-bit atomicMin of i only where the test passes and the label it just read is larger -- a minimum is order-free.  rn_finish is
 // one grid-stride pass of 16-byte label loads that turns the raw minimum into L, writes mask and residual and reduces the coverage
 // counts to one 64-bit atomic per work-group and count; the per-segment triples are integer atomics keyed by label, run-length
-// combined inside a lane.  rn_sum is the exact byte sum behind thr = -1.
+// combined inside a lane.  The exact byte sum behind thr = -1 is volume.hip's (pnr_mean_threshold).
 #include "render.h"
+#include "call.h"
+#include "volume.h"
 #include <cmath>
 #include <cstring>
 
@@ -153,30 +155,6 @@ __global__ __launch_bounds__(NTPB) void rn_scatter(ScatArgs a)
     }
 }
 
-// sum of the bytes p[0, n): scalar head up to the first 16-byte boundary, 16-byte vectors, scalar tail
-__global__ __launch_bounds__(NTPB) void rn_sum(const uint8_t *p, long long n, long long head, long long nvec, unsigned long long *out)
-{
-    __shared__ unsigned long long part[NWAVES];
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
-    unsigned long long s = 0;
-    const uint4 *v = (const uint4 *)(p + head);
-    auto bytes = [](unsigned x) { const unsigned y = (x & 0x00ff00ffu) + ((x >> 8) & 0x00ff00ffu); return (y & 0xffffu) + (y >> 16); };
-    for (long long g = gid; g < nvec; g += stride) {
-        const uint4 q = v[g];
-        s += bytes(q.x) + bytes(q.y) + bytes(q.z) + bytes(q.w);
-    }
-    if (gid < head) s += p[gid];
-    const long long t0 = head + 16 * nvec;
-    if (gid < n - t0) s += p[t0 + gid]; // (fewer than 16 left)
-    for (int d = 32; d >= 1; d >>= 1) s += (unsigned long long)__shfl_xor((long long)s, d, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < NWAVES; k++) s += part[k];
-        if (s) atomicAdd(out, s);
-    }
-}
-
 struct FinArgs {
     unsigned *lab;           // in: the raw minimum; out (write_label): L
     const uint8_t *V;        // nullable: no coverage
@@ -184,7 +162,7 @@ struct FinArgs {
     int t;                   // foreground: V >= t
     int write_label;
     uint8_t *mask, *res;     // nullable; padded to whole 4-byte words
-    unsigned long long *cnt; // [1] n_tree, [2] n_fg, [3] n_both, [4] sum_fg, [5] sum_both  ([0]: rn_sum)
+    unsigned long long *cnt; // [1] n_tree, [2] n_fg, [3] n_both, [4] sum_fg, [5] sum_both  ([0]: the byte sum)
     unsigned long long *seg; // nullable: seg_vox[n] | seg_fg[n] | seg_sum[n]
     long long n;
 };
@@ -257,28 +235,9 @@ __global__ __launch_bounds__(NTPB) void rn_finish(FinArgs a)
 
 } // namespace
 
-// the exact sum of the N bytes at V (device) into *sum, through the zeroed device word d_sum; timed under `group`
-int pnr_byte_sum_run(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_sum, unsigned long long *sum)
-{
-    hipStream_t st = c->stream;
-    const uintptr_t addr = (uintptr_t)V;
-    const long long head = std::min<long long>(N, (long long)((16 - (addr & 15)) & 15)), nvec = (N - head) >> 4;
-    const long long work = std::max<long long>(nvec, 16);
-    const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((work + NTPB - 1) / NTPB, MAX_BLOCKS));
-    c->tic();
-    hipLaunchKernelGGL(rn_sum, dim3(nb), dim3(NTPB), 0, st, V, (long long)N, head, nvec, d_sum);
-    hipError_t e = hipGetLastError();
-    c->toc(group, 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(sum, d_sum, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
-    return PNR_OK;
-}
-
 int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_t w, int64_t h, int64_t l, const uint8_t *V, int thr, int32_t *label_out,
                    uint8_t *mask_out, uint8_t *residual_out, pnr_coverage *cov, int64_t *seg_vox, int64_t *seg_fg, int64_t *seg_sum)
 {
-    hipStream_t st = c->stream;
     const int64_t N = w * h * l, n = t.n;
     const bool per_seg = (seg_vox || seg_fg || seg_sum) && n > 0;
     // the items are walked twice: counted (the size of the staging buffer; options render_items / render_pairs), then dealt out
@@ -293,69 +252,57 @@ int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_
     const size_t cap = (size_t)std::max<int64_t>(1, std::min(items, per_launch));
     // device buffers of the call: the labels | the segments | a launch's items | the counts | mask | residual | the per-segment triples
     pnr::CallBuf buf; // (freed when the call returns)
-    const size_t o_lab = buf.add((size_t)N * 4), o_seg = buf.add((size_t)n * 48), o_items = buf.add(cap * 32), o_cnt = buf.add(6 * 8),
-                 o_mask = buf.add(mask_out ? (size_t)N + 4 : 0), o_res = buf.add(residual_out ? (size_t)N + 4 : 0), o_tri = buf.add(per_seg ? (size_t)n * 24 : 0);
-    const int rc = buf.alloc(who);
+    const auto d_lab = buf.add<unsigned>((size_t)N);
+    const auto d_seg = buf.add<float4>((size_t)n * 3);
+    const auto d_items = buf.add<int4>(cap * 2);
+    const auto d_cnt = buf.add<unsigned long long>(6);
+    const auto d_mask = buf.add<uint8_t>(mask_out ? (size_t)N + 4 : 0), d_res = buf.add<uint8_t>(residual_out ? (size_t)N + 4 : 0);
+    const auto d_tri = buf.add<unsigned long long>(per_seg ? (size_t)n * 3 : 0);
+    int rc = buf.alloc(who);
     if (rc) return rc;
-    unsigned *const d_lab = buf.at<unsigned>(o_lab);
-    unsigned long long *const d_cnt = buf.at<unsigned long long>(o_cnt);
-    unsigned long long *const d_tri = per_seg ? buf.at<unsigned long long>(o_tri) : nullptr;
-    hipError_t e;
-    if ((e = hipMemsetAsync(d_lab, 0xff, (size_t)N * 4, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-    if ((e = hipMemsetAsync(d_cnt, 0, 6 * 8, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-    if (per_seg && (e = hipMemsetAsync(d_tri, 0, (size_t)n * 24, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
-    if (n > 0 && (e = hipMemcpyAsync(buf.at<float>(o_seg), t.seg.data(), (size_t)n * 48, hipMemcpyHostToDevice, st)) != hipSuccess) return pnr::hip_fail(st, who, e);
+    pnr::Call call(c, who);
+    call.fill(d_lab, 0xff);
+    call.fill(d_cnt, 0);
+    if (per_seg) call.fill(d_tri, 0);
+    if (n > 0) call.up(d_seg, t.seg.data());
     // scatter: launches of at most `cap` items; the staging vector is reused once its launch has ended
     std::vector<int32_t> stage;
     stage.reserve(cap * 8);
-    const ScatArgs sa{buf.at<int4>(o_items), buf.at<float4>(o_seg), d_lab, (int)w, (int)h, t.zscale};
-    auto launch = [&]() -> hipError_t {
+    const ScatArgs sa{d_items, d_seg, d_lab, (int)w, (int)h, t.zscale};
+    auto launch = [&]() {
         const size_t k = stage.size() / 8;
-        if (k == 0) return hipSuccess;
-        hipError_t s = hipMemcpyAsync(buf.at<int4>(o_items), stage.data(), k * 32, hipMemcpyHostToDevice, st);
-        if (s != hipSuccess) return s;
+        if (k == 0) return true;
+        call.up(d_items.get(), stage.data(), 2 * k);
         c->tic();
-        hipLaunchKernelGGL(rn_scatter, dim3((unsigned)k), dim3(NTPB), 0, st, sa);
-        s = hipGetLastError();
+        call.launch(rn_scatter, dim3((unsigned)k), dim3(NTPB), sa);
         c->toc("render_scatter", 1);
-        if (s == hipSuccess) s = hipStreamSynchronize(st);
         stage.clear();
-        return s;
+        return call.finish() == PNR_OK;
     };
-    e = hipSuccess;
     if (items > 0)
         pnr::render_items(t, w, h, l, c->opt.render_piece, c->opt.render_box, [&](const pnr::RenderItem &it) {
             const int32_t row[8] = {(int32_t)it.seg, (int32_t)it.x0, (int32_t)it.y0, (int32_t)it.z0, (int32_t)(it.x1 - it.x0 + 1), (int32_t)(it.y1 - it.y0 + 1), (int32_t)(it.z1 - it.z0 + 1), 0};
             stage.insert(stage.end(), row, row + 8);
-            if (stage.size() / 8 == cap) e = launch();
-            return e == hipSuccess;
+            return stage.size() / 8 < cap || launch();
         });
-    if (e == hipSuccess) e = launch();
-    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+    if (!call.ok() || !launch()) return call.finish();
     // the threshold of the coverage
     int t_abs = thr;
-    if (V && thr < 0) {
-        unsigned long long sum = 0;
-        const int rs = pnr_byte_sum_run(c, who, "render_finish", V, N, d_cnt, &sum);
-        if (rs) return rs;
-        t_abs = (int)std::max<unsigned long long>(1, sum / (unsigned long long)N);
-    }
-    const FinArgs fa{d_lab, V, (long long)N, t_abs, label_out ? 1 : 0, mask_out ? buf.at<uint8_t>(o_mask) : nullptr, residual_out ? buf.at<uint8_t>(o_res) : nullptr,
-                     d_cnt, d_tri, (long long)n};
+    if (V && thr < 0 && (rc = pnr_mean_threshold(c, who, "render_finish", V, N, d_cnt, &t_abs))) return rc;
+    const FinArgs fa{d_lab, V, (long long)N, t_abs, label_out ? 1 : 0, mask_out ? d_mask.get() : nullptr, residual_out ? d_res.get() : nullptr,
+                     d_cnt, per_seg ? d_tri.get() : nullptr, (long long)n};
     const long long groups = (N + 3) >> 2;
     c->tic();
-    hipLaunchKernelGGL(rn_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((groups + NTPB - 1) / NTPB, MAX_BLOCKS))), dim3(NTPB), 0, st, fa);
-    e = hipGetLastError();
+    call.launch(rn_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((groups + NTPB - 1) / NTPB, MAX_BLOCKS))), dim3(NTPB), fa);
     c->toc("render_finish", 1);
     unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
     std::vector<int64_t> tri(per_seg ? (size_t)n * 3 : 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && label_out) e = hipMemcpyAsync(label_out, d_lab, (size_t)N * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mask_out) e = hipMemcpyAsync(mask_out, fa.mask, (size_t)N, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && residual_out) e = hipMemcpyAsync(residual_out, fa.res, (size_t)N, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && per_seg) e = hipMemcpyAsync(tri.data(), d_tri, (size_t)n * 24, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return pnr::hip_fail(st, who, e);
+    call.down(cnt, d_cnt);
+    if (label_out) call.down(label_out, d_lab);
+    if (mask_out) call.down(mask_out, d_mask.get(), (size_t)N);
+    if (residual_out) call.down(residual_out, d_res.get(), (size_t)N);
+    if (per_seg) call.down(tri.data(), d_tri);
+    if ((rc = call.finish())) return rc;
     if (per_seg) {
         if (seg_vox) std::memcpy(seg_vox, tri.data(), (size_t)n * 8);
         if (seg_fg) std::memcpy(seg_fg, tri.data() + n, (size_t)n * 8);

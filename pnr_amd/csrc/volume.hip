@@ -12,7 +12,11 @@
 //
 // A histogram wave counts the voxels of one bin (the bin of the stack's first voxel: the background of a dark stack) in a register
 // instead of LDS: a wave whose 64 lanes all add to the same LDS word is serialised 64-fold.
+//
+// Below it: the exact byte sum of a u8 volume (vol_sum: one grid-stride u64 reduction, one atomic per work-group) and the threshold
+// rule "thr = -1" of the radii, the coverage and the components that rests on it (pnr_mean_threshold).
 #include "volume.h"
+#include "call.h"
 
 namespace {
 
@@ -215,6 +219,30 @@ __global__ __launch_bounds__(TPB) void vol_map(Src s, const VolState *st, unsign
     if (gid < s.n - t0) out[t0 + gid] = (uint8_t)m(s.p[(t0 + gid) * nc + s.ch]);
 }
 
+// sum of the bytes p[0, n): scalar head up to the first 16-byte boundary, 16-byte vectors, scalar tail
+__global__ __launch_bounds__(TPB) void vol_sum(const uint8_t *p, long long n, long long head, long long nvec, unsigned long long *out)
+{
+    __shared__ unsigned long long part[TPB / 64];
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    unsigned long long s = 0;
+    const uint4 *v = (const uint4 *)(p + head);
+    auto bytes = [](unsigned x) { const unsigned y = (x & 0x00ff00ffu) + ((x >> 8) & 0x00ff00ffu); return (y & 0xffffu) + (y >> 16); };
+    for (long long g = gid; g < nvec; g += stride) {
+        const uint4 q = v[g];
+        s += bytes(q.x) + bytes(q.y) + bytes(q.z) + bytes(q.w);
+    }
+    if (gid < head) s += p[gid];
+    const long long t0 = head + 16 * nvec;
+    if (gid < n - t0) s += p[t0 + gid]; // (fewer than 16 left)
+    for (int d = 32; d >= 1; d >>= 1) s += (unsigned long long)__shfl_xor((long long)s, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < TPB / 64; k++) s += part[k];
+        if (s) atomicAdd(out, s);
+    }
+}
+
 unsigned blocks_for(long long work, int tpb, int cap)
 {
     const long long b = (work + tpb - 1) / tpb;
@@ -225,26 +253,16 @@ unsigned blocks_for(long long work, int tpb, int cap)
 
 int pnr_volume_u16_run(pnr_ctx *c, const uint16_t *d_src, int nchan, int channel, const pnr_window &win, int32_t *lo_out, int32_t *hi_out)
 {
+    static const char *who = "pnr_set_volume_u16";
     const long long N = c->N;
-    hipStream_t st = c->stream;
-    if (c->d_img_owned.reserve((size_t)N) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("pnr_set_volume_u16: device allocation of %lld B for the 8-bit volume failed", N);
-        return PNR_E_NOMEM;
-    }
+    int rc = pnr::dev_alloc(c->d_img_owned, (size_t)N, who, "for the 8-bit volume");
+    if (rc) return rc;
     const bool fixed = win.lo >= 0, minmax = !fixed && win.sat_lo_ppm == 0 && win.sat_hi_ppm == 0;
     pnr::DevBuf<VolState> b_st; // (freed when the call returns: every path below has drained the stream or failed to)
-    if (!fixed && b_st.alloc(1) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("pnr_set_volume_u16: device allocation of %zu B of window state failed", sizeof(VolState));
-        return PNR_E_NOMEM;
-    }
+    if (!fixed && (rc = pnr::dev_alloc(b_st, 1, who, "of window state"))) return rc;
     VolState *d_st = b_st.get();
-    hipError_t e = d_st ? hipMemsetAsync(d_st, 0, sizeof(VolState), st) : hipSuccess;
-    if (e != hipSuccess) {
-        pnr::set_error("pnr_set_volume_u16: %s", hipGetErrorString(e));
-        return PNR_E_HIP;
-    }
+    pnr::Call call(c, who);
+    if (d_st) call.fill(d_st, 0, 1);
     Src s{d_src, N, 0, 0, nchan, channel};
     const uintptr_t addr = (uintptr_t)d_src;
     if (nchan == 1) {
@@ -252,37 +270,48 @@ int pnr_volume_u16_run(pnr_ctx *c, const uint16_t *d_src, int nchan, int channel
         s.nvec = (N - s.head) >> 3;
     }
     const long long work = nchan == 1 ? std::max(s.nvec, s.head + 8) : N; // threads' worth of work of the read passes
-    int launches = 0;
+    int launches = 1;
     c->tic();
     if (minmax) {
-        hipLaunchKernelGGL(vol_minmax, dim3(blocks_for(work, TPB, MAX_BLOCKS)), dim3(TPB), 0, st, s, d_st);
+        call.launch(vol_minmax, dim3(blocks_for(work, TPB, MAX_BLOCKS)), dim3(TPB), s, d_st);
         launches++;
     } else if (!fixed) {
         // k_lo <= k_hi < N: sat_lo_ppm + sat_hi_ppm < 1e6 (checked by the caller); N * ppm < 2^63 for any stack a device can hold
         const long long k_lo = N * (long long)win.sat_lo_ppm / 1000000, k_hi = N - 1 - N * (long long)win.sat_hi_ppm / 1000000;
         const unsigned hb = blocks_for(work, HTPB, MAX_HBLOCKS);
-        hipLaunchKernelGGL(vol_hist_coarse, dim3(hb), dim3(HTPB), 0, st, s, d_st);
-        hipLaunchKernelGGL(vol_select_coarse, dim3(1), dim3(256), 0, st, d_st, k_lo, k_hi);
-        hipLaunchKernelGGL(vol_hist_fine, dim3(hb), dim3(HTPB), 0, st, s, d_st);
-        hipLaunchKernelGGL(vol_select_fine, dim3(1), dim3(256), 0, st, d_st);
+        call.launch(vol_hist_coarse, dim3(hb), dim3(HTPB), s, d_st);
+        call.launch(vol_select_coarse, dim3(1), dim3(256), d_st, k_lo, k_hi);
+        call.launch(vol_hist_fine, dim3(hb), dim3(HTPB), s, d_st);
+        call.launch(vol_select_fine, dim3(1), dim3(256), d_st);
         launches += 4;
     }
-    const unsigned mb = blocks_for(N >> 3, TPB, MAX_BLOCKS);
-    if (nchan == 1 && (addr & 15) == 0)
-        hipLaunchKernelGGL(vol_map<true>, dim3(mb), dim3(TPB), 0, st, s, (const VolState *)d_st, (unsigned)win.lo, (unsigned)win.hi, c->d_img_owned.get());
-    else
-        hipLaunchKernelGGL(vol_map<false>, dim3(mb), dim3(TPB), 0, st, s, (const VolState *)d_st, (unsigned)win.lo, (unsigned)win.hi, c->d_img_owned.get());
-    launches++;
-    if (e == hipSuccess) e = hipGetLastError();
+    call.launch(nchan == 1 && (addr & 15) == 0 ? vol_map<true> : vol_map<false>, dim3(blocks_for(N >> 3, TPB, MAX_BLOCKS)), dim3(TPB), s, d_st, (unsigned)win.lo,
+                (unsigned)win.hi, c->d_img_owned.get());
     c->toc("volume", launches);
     unsigned w2[2] = {65535u - (unsigned)win.lo, (unsigned)win.hi};
-    if (e == hipSuccess && d_st) e = hipMemcpyAsync(w2, d_st->win, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        pnr::set_error("pnr_set_volume_u16: %s", hipGetErrorString(e));
-        return PNR_E_HIP;
-    }
+    if (d_st) call.down(w2, d_st->win, 2);
+    if ((rc = call.finish())) return rc;
     if (lo_out) *lo_out = (int32_t)(65535u - w2[0]);
     if (hi_out) *hi_out = (int32_t)w2[1];
     return PNR_OK;
+}
+
+int pnr_byte_sum_run(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_sum, unsigned long long *sum)
+{
+    const long long head = std::min<long long>(N, (long long)((16 - ((uintptr_t)V & 15)) & 15)), nvec = (N - head) >> 4;
+    pnr::Call call(c, who);
+    call.fill(d_sum, 0, 1);
+    c->tic();
+    call.launch(vol_sum, dim3(blocks_for(std::max<long long>(nvec, 16), TPB, MAX_BLOCKS)), dim3(TPB), V, (long long)N, head, nvec, d_sum);
+    c->toc(group, 1);
+    call.down(sum, d_sum, 1);
+    return call.finish();
+}
+
+int pnr_mean_threshold(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_word, int *t)
+{
+    unsigned long long sum = 0;
+    const int rc = pnr_byte_sum_run(c, who, group, V, N, d_word, &sum);
+    if (!rc) *t = (int)std::max<unsigned long long>(1, sum / (unsigned long long)N);
+    return rc;
 }
