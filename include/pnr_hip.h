@@ -565,6 +565,48 @@ int pnr_label_components(pnr_ctx *ctx, const pnr_components_opts *opts /* NULL =
                          int32_t *label_out /* N, nullable */, pnr_component *comps /* nullable */, int64_t cap);
 int pnr_despeckle_volume(pnr_ctx *ctx, const pnr_components_opts *opts /* NULL = defaults */, pnr_components_info *info /* nullable */);
 
+/* Exact anisotropic Euclidean distance transform of the traced volume (beyond the reference): every foreground voxel gets its squared
+ * distance to the nearest background voxel, in xy-voxel units with z counted zdist-fold.  pnr_measure_radii answers the same question
+ * at a list of points in whole numbers; this is the whole stack, sub-voxel: sqrt(D2) at a node's voxel is its radius, the maximum of
+ * D2 is the thickest point of the stack (where a soma is, and how large somaradius has to be), D2 over a component of the residual is
+ * how thick what the trace missed is.
+ * THE RULE (the contract; tests restate it in numpy).  V is the context's traced u8 volume (w x h x l, owned or borrowed; for 16-bit
+ * input the windowed bytes, after pnr_filter_volume / pnr_despeckle_volume the filtered bytes), N = w * h * l, zd = params.zdist (>= 1).
+ *   Options {thr, rmax}; opts = NULL = {-1, 64}.
+ *   Foreground: V >= t.  t = thr, or for thr == -1: max(1, floor(sum(V) / N)) from the exact u64 sum -- the rule of the radii, the
+ *     coverage and the components (the same kernel).  t is reported as thr_used.  Background: V < t.
+ *   Distance: for a foreground voxel p and a background voxel q INSIDE the volume, with the integer offsets (dx, dy, dz) = q - p:
+ *     d2(p, q) = (float)(dx*dx + dy*dy) + (zd*(float)dz) * (zd*(float)dz) -- the f32 expression of the radius rule's shells, single IEEE
+ *     operations (-ffp-contract=off).
+ *   Output: cap = (float)(rmax*rmax); D2(p) = min(cap, min over all background q of d2(p, q)); background voxels get D2 = 0.  Voxels
+ *     outside the volume do not exist and are not background: a stack without any background voxel has D2 = cap everywhere (the radius
+ *     rule's convention).  With l == 1 only dz = 0 occurs; nothing special-cases it.  A minimum does not depend on order: every tiling,
+ *     pass structure and launch cut gives the same bits.
+ *   Summary pnr_edt_info (exact): n_vox = N, n_fg, n_capped (foreground voxels with D2 == cap), d2_max (the maximum of D2 over the
+ *     foreground), first_max (the smallest linear index x + w * (y + h * z) that attains it; -1 and d2_max = 0 when n_fg == 0), thr_used.
+ *   Points: xyz (n x 3 f32, nullable when n == 0) -> d2_at[n] = D2 at the centre voxel of the radius rule, per coordinate
+ *     c = (int) fminf(fmaxf(v + 0.5f, 0.f), (float)(extent - 1)); -1.0f for a position with a non-finite coordinate.  Node radii are read
+ *     this way without moving 4 N bytes to the host.
+ * Arguments (anything else: PNR_E_ARG): thr in -1..255, rmax in 1..PNR_EDT_MAX_R, 0 <= n <= PNR_RADIUS_MAX_N, N at most 2^32 - 2 (as for
+ *   the components).  No volume in the context: PNR_E_STATE.  PNR_E_NOMEM: an allocation failed.  info, d2_out (N) and the points are
+ *   each optional.
+ * The call never writes V (also not a borrowed one), leaves the pipeline state of the context alone, runs on the context's stream
+ *   (pnr_set_stream), uses 64-bit voxel indices and frees every device buffer of the call before it returns.  Device memory of a call:
+ *   8 N bytes (4 N that hold the u16 row distances and then D2, 4 N that hold the row carries and then the u32 plane distances),
+ *   4 (rmax + 1) bytes of the z table, 32 bytes of sums, and 16 n bytes for the points.  Kernel times: pnr_get_kernel_ms group "edt" =
+ *   the sum of "edt_threshold" (the byte sum of thr = -1), "edt_x", "edt_y", "edt_z", "edt_stats" and "edt_sample". */
+#define PNR_EDT_MAX_R 1024
+typedef struct pnr_edt_opts {
+    int32_t thr, rmax;
+} pnr_edt_opts; /* NULL = {-1, 64} */
+typedef struct pnr_edt_info {
+    int64_t n_vox, n_fg, n_capped, first_max;
+    float d2_max;
+    int32_t thr_used;
+} pnr_edt_info;
+int pnr_distance_transform(pnr_ctx *ctx, const pnr_edt_opts *opts /* NULL = defaults */, pnr_edt_info *info /* nullable */, float *d2_out /* N, nullable */,
+                           const float *xyz /* n x 3, nullable when n == 0 */, int64_t n, float *d2_at /* n */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -601,7 +643,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample").  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -15,6 +15,7 @@
 #include "pairmin.h"
 #include "render.h"
 #include "components.h"
+#include "edt.h"
 #include "../host/stack_io.h"
 #include <algorithm>
 #include <cfloat>
@@ -393,6 +394,21 @@ int pnr_despeckle_volume(pnr_ctx *c, const pnr_components_opts *opts, pnr_compon
     pnr::DevBuf<uint8_t> out;
     if (!(rc = pnr_components_run(c, who, o, info, nullptr, nullptr, 0, &out))) replace_volume(c, std::move(out));
     return rc;
+}
+
+// pnr_distance_transform (edt.hip): arguments first, then the state; the pipeline state of the context is neither needed nor touched
+int pnr_distance_transform(pnr_ctx *c, const pnr_edt_opts *opts, pnr_edt_info *info, float *d2_out, const float *xyz, int64_t n, float *d2_at)
+{
+    static const char *who = "pnr_distance_transform";
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    const pnr_edt_opts o = opts ? *opts : pnr_edt_opts{-1, 64};
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "%s: thr = %d outside [-1, 255]", who, o.thr);
+    PNR_REQUIRE(o.rmax >= 1 && o.rmax <= PNR_EDT_MAX_R, PNR_E_ARG, "%s: rmax = %d outside [1, %d]", who, o.rmax, PNR_EDT_MAX_R);
+    PNR_REQUIRE(n >= 0 && n <= PNR_RADIUS_MAX_N && (n == 0 || (xyz && d2_at)), PNR_E_ARG, "%s: n = %lld positions (at most 2^28) need xyz and d2_at", who, (long long)n);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "%s: no volume set", who);
+    PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_edt_run(c, who, o, info, d2_out, xyz, n, d2_at);
 }
 
 // pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched
@@ -1453,6 +1469,18 @@ int pnr_get_kernel_ms(pnr_ctx *c, const char *group, double *ms, int64_t *launch
         *ms = 0;
         if (launches) *launches = 0;
         for (const char *g : {"components_threshold", "components_local", "components_merge", "components_flatten", "components_number", "components_stats", "components_finish"}) {
+            double a = 0;
+            int64_t la = 0;
+            pnr_get_kernel_ms(c, g, &a, &la);
+            *ms += a;
+            if (launches) *launches += la;
+        }
+        return PNR_OK;
+    }
+    if (std::strcmp(group, "edt") == 0) { // one sub-group per kernel (edt.hip)
+        *ms = 0;
+        if (launches) *launches = 0;
+        for (const char *g : {"edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"}) {
             double a = 0;
             int64_t la = 0;
             pnr_get_kernel_ms(c, g, &a, &la);

@@ -38,6 +38,10 @@
 //   connected components of the stack (pnr_label_components on device -g; the same volume setup as --render-swc) as one JSON line with
 //   the fields of pnr_components_info; --labels writes bare little-endian int32, --per-component one line
 //   `id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax` per kept component.  On a --residual file (.raw with -d w,h,l): what the trace missed.
+//   --edt -i stack [--threshold T] [--edt-max R] [--zscale Z] [--edt-out OUT.raw] [--at tree.swc --per-node FILE.csv]: the exact Euclidean
+//   distance transform of the stack's foreground (pnr_distance_transform on device -g; the same volume setup as --components; Z >= 1,
+//   default 1, is the context's zdist) as one JSON line n_vox, n_fg, n_capped, thr_used, rmax, zdist, d_max, max_at; --edt-out writes
+//   d = sqrtf(D2) as bare little-endian f32, --at / --per-node one line `id,d` per node of the SWC file.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -122,15 +126,36 @@ int main(int argc, char **argv)
     std::string mask_out, residual_out;
     bool coverage = false, render_flag = false, per_node_flag = false;
     advantra::ComponentsJob comp;
-    bool components = false, comp_flag = false;
+    bool components = false, comp_flag = false, thr_flag = false;
+    advantra::EdtJob edt_job;
+    bool edt = false, edt_flag = false;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--components")) { components = true; continue; }
+        if (!strcmp(argv[i], "--edt")) { edt = true; continue; }
+        if (!strcmp(argv[i], "--edt-max")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 1, PNR_EDT_MAX_R, v)) { fprintf(stderr, "--edt-max R: the largest distance looked for, an integer from 1 to %d\n", PNR_EDT_MAX_R); return 1; }
+            edt_job.opts.rmax = (int32_t)v;
+            edt_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--edt-out") || !strcmp(argv[i], "--at")) {
+            const bool out = !strcmp(argv[i], "--edt-out");
+            const std::string name = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (name.empty() || (out && (name.size() <= 4 || name.substr(name.size() - 4) != ".raw"))) {
+                fprintf(stderr, "%s\n", out ? "--edt-out OUT.raw: a .raw file name (bare little-endian float32)" : "--at tree.swc");
+                return 1;
+            }
+            (out ? edt_job.out : edt_job.at) = name;
+            edt_flag = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--threshold")) {
             long v = 0;
             if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
-            comp.opts.thr = (int32_t)v;
-            comp_flag = true;
+            comp.opts.thr = edt_job.opts.thr = (int32_t)v;
+            thr_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--connectivity")) {
@@ -349,15 +374,27 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool rendering = !render.swc.empty();
-    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering) || (zscale_flag && !distance && join_in.empty() && !rendering && !components)) {
+    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt) || (zscale_flag && !distance && join_in.empty() && !rendering && !components && !edt)) {
         fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc; --zscale, --per-node: or --render-swc)\n");
         return 1;
     }
     if (render_flag && !rendering) { fprintf(stderr, "--radius-scale / --radius-add / --coverage-threshold need --render-swc IN.swc\n"); return 1; }
     if (join_flag && !join_given && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
-    if (comp_flag && !components) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack\n"); return 1; }
+    if ((comp_flag && !components) || (thr_flag && !components && !edt)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt)\n"); return 1; }
+    if (edt_flag && !edt) { fprintf(stderr, "--edt-max / --edt-out / --at need --edt -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (edt) {
+        if (components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || !paras.empty()) {
+            fprintf(stderr, "--edt: not with a tracing run (-p), --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle or --measure-radius\n");
+            return 1;
+        }
+        if (infiles.empty()) { fprintf(stderr, "--edt needs -i <stack>\n"); return 1; }
+        if (edt_job.at.empty() != per_node.empty()) { fprintf(stderr, "--edt: --at tree.swc and --per-node FILE.csv go together\n"); return 1; }
+        if (zscale_flag && dist_opts.zscale < 1.f) { fprintf(stderr, "--edt: --zscale Z: a number, 1 or more\n"); return 1; }
+        edt_job.per_node = per_node;
+        return advantra::edt_file(edt_job, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, device) ? 0 : 1;
+    }
     if (components) {
         if (rendering || distance || !join_in.empty() || info || S0.despeckle) { fprintf(stderr, "--components: not with --render-swc, --distance, --join-swc, --info or --despeckle (--min-size drops the small components)\n"); return 1; }
         if (infiles.empty()) { fprintf(stderr, "--components needs -i <stack>\n"); return 1; }

@@ -87,6 +87,14 @@ void print_flags()
     printf("  --min-size M              components of fewer than M voxels are not counted, numbered or listed (default 1)\n");
     printf("  --labels OUT.raw          write the label volume: little-endian int32, 0 = background, 1.. by first voxel in raster order\n");
     printf("  --per-component FILE.csv  `id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax` per component\n");
+    printf("--edt -i stack            the exact Euclidean distance transform of the stack's foreground on the GPU (the same volume setup as tracing):\n");
+    printf("                          every voxel's distance d to the nearest background voxel, in xy voxels; one JSON line: n_vox, n_fg, n_capped,\n");
+    printf("                          thr_used, rmax, zdist, d_max, max_at (the thickest point: where a soma is, and how large somaradius has to be)\n");
+    printf("  --threshold T             foreground from T on, 0..255 (default -1: the stack's mean)\n");
+    printf("  --edt-max R               distances are capped at R xy voxels, 1..%d (default 64)\n", PNR_EDT_MAX_R);
+    printf("  --zscale Z                z counts Z-fold, 1 or more (default 1)\n");
+    printf("  --edt-out OUT.raw         write d of every voxel: little-endian float32\n");
+    printf("  --at tree.swc --per-node FILE.csv   `id,d` per node of the SWC file: its sub-voxel radius (-1: a position that is not finite)\n");
     printf("--measure-radius          SWC radii measured from the image at the final nodes (default: SIG2RADIUS * the winning scale)\n");
     printf("--radius-rel PCT          relative mode (default, 50): background below PCT %% of the node's brightest centre voxel, 1..100\n");
     printf("--radius-threshold T      absolute mode: background below T, 0..255; -1: below the stack's mean\n");
@@ -717,6 +725,76 @@ bool components_file(const ComponentsJob &job, const std::vector<char *> &infile
         return false;
     printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_comp\": %lld, \"n_small\": %lld, \"vox_small\": %lld, \"largest\": %lld, \"thr_used\": %d}\n", (long long)ci.n_vox,
            (long long)ci.n_fg, (long long)ci.n_comp, (long long)ci.n_small, (long long)ci.vox_small, (long long)ci.largest, (int)ci.thr_used);
+    return true;
+}
+
+bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    auto lib_fail = [](const char *what) {
+        fprintf(stderr, "%s: %s\n", what, pnr_last_error());
+        return false;
+    };
+    const Settings &S = settings();
+    Stack st;
+    std::string err;
+    if (!load_stack(infiles[0], raw_dims, st, err, S.channel - 1, S.raw_u16)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    if (S.windowed && st.bits != 16) {
+        fprintf(stderr, "--window / --saturate need a 16-bit stack (8-bit input is never windowed)\n");
+        return false;
+    }
+    SwcTree T;
+    if (!job.at.empty() && !load_swc(job.at, T, err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    pnr_params p;
+    pnr_default_params(&p);
+    p.zdist = zscale; // (also the z half-width of --subtract-background)
+    pnr_ctx *ctx = nullptr;
+    if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+    // the volume as it would be traced: windowed to 8 bits, then pre-filtered
+    bool ok = (st.bits == 16 ? pnr_set_volume_u16(ctx, st.samples16(), st.w, st.h, st.l, 1, 0, S.windowed ? &S.window : nullptr, nullptr, nullptr)
+                             : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
+    if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
+    if (!ok) {
+        lib_fail("volume");
+        pnr_destroy(ctx);
+        return false;
+    }
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<float> d(job.out.empty() ? 0 : N), at((size_t)T.n());
+    pnr_edt_info ei = {};
+    const int rc = pnr_distance_transform(ctx, &job.opts, &ei, job.out.empty() ? nullptr : d.data(), T.n() ? T.xyz.data() : nullptr, T.n(), T.n() ? at.data() : nullptr);
+    pnr_destroy(ctx);
+    if (rc != PNR_OK) return lib_fail("pnr_distance_transform");
+    auto write_file = [](const std::string &name, const char *mode, const std::function<void(FILE *)> &body) {
+        FILE *f = fopen(name.c_str(), mode);
+        if (!f) {
+            fprintf(stderr, "%s: cannot write the file\n", name.c_str());
+            return false;
+        }
+        body(f);
+        const bool bad = ferror(f) != 0;
+        if (fclose(f) != 0 || bad) {
+            fprintf(stderr, "%s: write failed\n", name.c_str());
+            return false;
+        }
+        return true;
+    };
+    for (float &v : d) v = sqrtf(v);
+    if (!job.out.empty() && !write_file(job.out, "wb", [&](FILE *f) { fwrite(d.data(), 4, N, f); })) return false; // (the hosts this builds for are little-endian)
+    if (!job.per_node.empty() && !write_file(job.per_node, "w", [&](FILE *f) {
+            fprintf(f, "id,d\n");
+            for (size_t k = 0; k < at.size(); k++) fprintf(f, "%lld,%.9g\n", T.id[k], (double)(at[k] < 0.f ? -1.f : sqrtf(at[k])));
+        }))
+        return false;
+    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_capped\": %lld, \"thr_used\": %d, \"rmax\": %d, \"zdist\": %.17g, \"d_max\": %.17g, \"max_at\": ", (long long)ei.n_vox,
+           (long long)ei.n_fg, (long long)ei.n_capped, (int)ei.thr_used, (int)job.opts.rmax, (double)zscale, (double)sqrtf(ei.d2_max));
+    if (ei.first_max < 0) printf("null}\n");
+    else printf("[%lld, %lld, %lld]}\n", (long long)(ei.first_max % st.w), (long long)(ei.first_max / st.w % st.h), (long long)(ei.first_max / (st.w * st.h)));
     return true;
 }
 

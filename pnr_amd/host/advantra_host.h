@@ -161,6 +161,16 @@ struct ComponentsJob {
     std::string labels, per_component;
 };
 bool components_file(const ComponentsJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
+// advantra_cli --edt -i stack: the exact distance transform of the stack's foreground (pnr_distance_transform on `device`; the same volume
+// setup as --components; zscale >= 1 is the context's zdist).  One JSON line {"n_vox", "n_fg", "n_capped", "thr_used", "rmax", "zdist",
+// "d_max", "max_at": [x, y, z]} (d_max = sqrtf(d2_max); max_at null without foreground); `out` (not empty): d = sqrtf(D2) of every voxel as
+// bare little-endian f32; `at` and `per_node` (both or neither): a CSV `id,d` per node of the SWC file `at` under a header line, d as %.9g
+// (-1: a position that is not finite).
+struct EdtJob {
+    pnr_edt_opts opts = {-1, 64};
+    std::string out, at, per_node;
+};
+bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

@@ -110,6 +110,22 @@ class ComponentsInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
+class EdtOpts(C.Structure):
+    """pnr_edt_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean), rmax 1..PNR_EDT_MAX_R (D2 is capped at rmax^2)"""
+    _fields_ = [("thr", C.c_int32), ("rmax", C.c_int32)]
+
+
+class EdtInfo(C.Structure):
+    """pnr_edt_info: the exact summary of a distance transform (first_max: the smallest linear index that attains d2_max, -1 without foreground)"""
+    _fields_ = [("n_vox", C.c_int64), ("n_fg", C.c_int64), ("n_capped", C.c_int64), ("first_max", C.c_int64), ("d2_max", C.c_float), ("thr_used", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+PNR_EDT_MAX_R = 1024
+
+
 # pnr_component
 COMPONENT_DT = np.dtype([(k, np.int64) for k in ("first", "size", "sum", "sx", "sy", "sz")] + [(k, np.int32) for k in ("x0", "y0", "z0", "x1", "y1", "z1", "vmax", "pad")])
 
@@ -190,6 +206,7 @@ def load():
     L.pnr_tree_coverage.argtypes = [vp, vp, vp, vp, i64, C.POINTER(RenderOpts), C.POINTER(Coverage), vp, vp, vp, vp, vp]
     L.pnr_label_components.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo), vp, vp, i64]
     L.pnr_despeckle_volume.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]
+    L.pnr_distance_transform.argtypes = [vp, C.POINTER(EdtOpts), C.POINTER(EdtInfo), vp, vp, i64, vp]
     L.pnr_render_items.argtypes = [vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_test_write_tiff.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
@@ -255,7 +272,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -525,6 +542,31 @@ class Context:
         if o.min_size > 1:
             self._keep = None
         return info.as_dict()
+
+    def distance_transform(self, thr=-1, rmax=64, volume=True, points=None, squared=True):
+        """pnr_distance_transform: the exact squared distance D2 of every voxel of {V >= thr} (thr = -1: the global mean) to the nearest
+        background voxel inside the volume, in xy voxels with z counted zdist-fold, capped at rmax^2 -> (info dict {n_vox, n_fg, n_capped,
+        first_max, d2_max, thr_used, d_max, max_at}, d2 float32[l, h, w] or None, at float32[n] or None).  points: n x 3 positions
+        (x, y, z) -> D2 at their centre voxels (-1: a position that is not finite).  squared=False: the f32 square roots of both (and -1
+        stays -1).  d_max = sqrt(d2_max); max_at = (x, y, z) of first_max, None without foreground."""
+        o = EdtOpts(int(thr), int(rmax))
+        info = EdtInfo()
+        d2 = np.empty(self.shape, np.float32) if volume else None
+        xyz = np.ascontiguousarray(points, np.float32).reshape(-1, 3) if points is not None else None
+        at = np.empty(len(xyz), np.float32) if xyz is not None else None
+        check(self.L.pnr_distance_transform(self.h, C.byref(o), C.byref(info), d2.ctypes.data if volume else None,
+                                            xyz.ctypes.data if xyz is not None and len(xyz) else None, len(xyz) if xyz is not None else 0,
+                                            at.ctypes.data if at is not None and len(at) else None))
+        out = info.as_dict()
+        out["d_max"] = float(np.sqrt(np.float32(info.d2_max)))
+        l, h, w = self.shape
+        i = info.first_max
+        out["max_at"] = (i % w, (i // w) % h, i // (w * h)) if i >= 0 else None
+        if not squared:
+            d2 = np.sqrt(d2) if volume else None
+            if at is not None:
+                at = np.where(at >= 0, np.sqrt(np.maximum(at, np.float32(0))), at).astype(np.float32)
+        return out, d2, at
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
