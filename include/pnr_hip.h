@@ -607,6 +607,76 @@ typedef struct pnr_edt_info {
 int pnr_distance_transform(pnr_ctx *ctx, const pnr_edt_opts *opts /* NULL = defaults */, pnr_edt_info *info /* nullable */, float *d2_out /* N, nullable */,
                            const float *xyz /* n x 3, nullable when n == 0 */, int64_t n, float *d2_at /* n */);
 
+/* Gray-weighted geodesic distance through the traced volume (beyond the reference): every voxel gets the cost of the cheapest 26-connected
+ * path to the nearest of n source points, where a step costs its length times the darkness of the two voxels it joins, together with the
+ * label of that source, and the path itself for a list of targets.  The tree distance, pnr_join_trees, pnr_measure_radii and the distance
+ * transform measure straight lines and ignore the image in between; this follows the signal: the cost at a fragment's node says whether the
+ * gap to the tree is a dim stretch of one neurite or background between two cells, and the path says along which voxels it attaches.
+ * THE RULE (the contract; tests restate it in numpy).  Exact integer arithmetic, but for the 26 step lengths: single IEEE f32 operations on
+ * the host.  V is the context's traced u8 volume (w x h x l, owned or borrowed, windowed or filtered as traced), N = w * h * l.
+ *   Options {thr, dmax, cost}; opts = NULL = {0, 2^31 - 1, NULL}.
+ *   Domain: a voxel is passable when V >= t.  t = thr, or for thr == -1: max(1, floor(sum(V) / N)) (the byte-sum kernel of the other calls);
+ *     t is reported as thr_used.  With the default thr = 0 every voxel is passable and the cost does the work.  Voxels outside the volume
+ *     do not exist.
+ *   Steps: the 26 offsets o = (dx, dy, dz), each component in {-1, 0, 1}, not all zero, enumerated with dz slowest, then dy, then dx, each
+ *     ascending (THE OFFSET ORDER).  len[o] = (uint32) rintf(32.0f * sqrtf((float)(dx*dx + dy*dy) + (zd*(float)dz) * (zd*(float)dz))),
+ *     zd = params.zdist.  With l == 1 only dz = 0 occurs.  len[o] = len[-o].
+ *   Cost: c(v), a table of 256 u16 entries, each >= 1; the default is c(v) = 256 - v; opts->cost (256 entries) replaces it.
+ *   Edge: for passable neighbours p, q = p + o: wt(p, q) = len[o] * (c(V(p)) + c(V(q))), symmetric.  PNR_E_ARG if
+ *     max(len) * 2 * max(c) > 2^31 - 1.
+ *   Sources: n_src points xyz (f32) with labels label[i] >= 0 (int32; src_label = NULL: label i = i).  The centre voxel of a point is that of
+ *     the radius / distance-transform rule, per coordinate c = (int) fminf(fmaxf(v + 0.5f, 0.f), (float)(extent - 1)).  A source with a
+ *     non-finite coordinate, and a source whose centre voxel is not passable, is DROPPED; dropped sources are counted in n_src_dropped.
+ *   Key: every voxel has a u64 key (D << 32) | label; NONE is all ones.  A source voxel has key = (0, the smallest label of the sources on
+ *     it).  Every other passable voxel p: key(p) = min over the passable neighbours q with D(q) + wt(q, p) <= dmax of
+ *     key(q) + (wt(q, p) << 32); NONE if there is no such neighbour.  Adding wt << 32 keeps the label, so the key is the lexicographic
+ *     minimum over all paths of (cost, source label): D is the cheapest path cost from any source, the label the smallest among the sources
+ *     that attain it.  Weights are >= 64, so the recursion is well founded and its solution unique; a path of cost <= dmax has only prefixes
+ *     of cost <= dmax, so the cap changes no kept value.  Every quantity is a minimum over a fixed set: no tiling, round structure, launch
+ *     cut or arrival order changes a bit.
+ *   Outputs: D(p) u32, 0xFFFFFFFF when unreached; L(p) int32, -1 when unreached; impassable voxels are unreached.  D / 64 is the path
+ *     length in xy voxels at the brightest cost (c = 1).
+ *   Path: for a reached voxel p with D > 0, pred(p) is the first q in the offset order with key(q) + (wt(q, p) << 32) == key(p), compared on
+ *     the full key.  Such a q exists and D strictly decreases along the walk, which therefore ends on a source voxel of label L(p) after at
+ *     most D / 64 steps.  The path of a target is p, pred(p), ..., the source voxel, as linear indices x + w * (y + h * z).
+ *   Summary pnr_geo_info (exact): n_vox = N, n_pass, n_reached, n_src (kept), n_src_dropped, d_max (the largest D over the reached voxels),
+ *     first_max (the smallest linear index that attains it; -1 and d_max = 0 when nothing is reached), thr_used, rounds (relaxation rounds
+ *     of this call: scheduling, not part of the rule).
+ *   Targets: at_xyz (m x 3 f32) -> d_at[m], label_at[m] at the centre voxel; a non-finite target gives 0xFFFFFFFF, -1 and path_len 0.
+ *     With path_cap > 0, path_len[i] = k > 0: the complete path, k voxels written to path_vox[i * path_cap ...]; 0: the target is unreached
+ *     or not finite; -path_cap: the walk was cut after path_cap voxels, and those are written.  With path_cap == 0 path_len and path_vox
+ *     are not touched.
+ * Arguments (anything else: PNR_E_ARG): thr in -1..255, 1 <= dmax <= 2^31 - 1, cost entries >= 1, labels >= 0, 0 <= n_src, m <=
+ *   PNR_RADIUS_MAX_N (with n_src = 0 everything is unreached), src_xyz when n_src > 0, at_xyz and at least one of d_at / label_at /
+ *   (path_cap > 0) when m > 0, path_cap in 0..PNR_GEO_MAX_PATH with path_len and path_vox when path_cap > 0 and m > 0, N at most 2^32 - 2.
+ *   No volume in the context: PNR_E_STATE.  PNR_E_NOMEM: an allocation failed.  info, d_out, label_out and the targets are each optional.
+ * The call never writes V (also not a borrowed one), leaves the pipeline state of the context alone, runs on the context's stream
+ *   (pnr_set_stream), uses 64-bit voxel indices and frees every device buffer of the call before it returns.  Device memory of a call: 8 N
+ *   bytes of keys, 12 bytes per tile of GEO_TX x GEO_TY x GEO_TZ voxels (two flag arrays and the list), 4 N more for each of d_out and
+ *   label_out that is asked for (split on the device), 512 bytes of cost table, 16 n_src bytes of sources, and per target 20 bytes plus
+ *   4 + 8 path_cap bytes with paths; 8 bytes of pinned host memory carry the round's tile count.
+ * Kernel times: pnr_get_kernel_ms group "geodesic" = the sum of "geodesic_threshold", "geodesic_init", "geodesic_compact",
+ *   "geodesic_relax", "geodesic_stats", "geodesic_split", "geodesic_sample" and "geodesic_paths".  pnr_get_option "geo_rounds" /
+ *   "geo_visits": the rounds and the tile visits of the last call.  pnr_set_option "geo_iters" (LDS iterations per tile visit; 0 =
+ *   automatic, 1 forces a tile to re-queue itself) and "geo_tiles_per_launch" (0 = automatic; small values force launch cuts) change no
+ *   bit: tests reach the boundaries on small stacks with them. */
+#define PNR_GEO_MAX_PATH (1 << 16)
+typedef struct pnr_geo_opts {
+    int32_t thr;
+    uint32_t dmax;
+    const uint16_t *cost;
+} pnr_geo_opts; /* NULL = {0, 2^31 - 1, NULL} */
+typedef struct pnr_geo_info {
+    int64_t n_vox, n_pass, n_reached, n_src, n_src_dropped, first_max;
+    uint32_t d_max;
+    int32_t thr_used, rounds, pad;
+} pnr_geo_info;
+int pnr_geodesic_distance(pnr_ctx *ctx, const float *src_xyz, const int32_t *src_label /* nullable */, int64_t n_src,
+                          const pnr_geo_opts *opts, pnr_geo_info *info /* nullable */,
+                          uint32_t *d_out /* N, nullable */, int32_t *label_out /* N, nullable */,
+                          const float *at_xyz /* m x 3, nullable when m == 0 */, int64_t m, uint32_t *d_at, int32_t *label_at /* m, nullable */,
+                          int32_t path_cap /* 0..PNR_GEO_MAX_PATH */, int32_t *path_len /* m */, int64_t *path_vox /* m x path_cap */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -643,7 +713,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample").  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

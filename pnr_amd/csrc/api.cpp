@@ -16,6 +16,7 @@
 #include "render.h"
 #include "components.h"
 #include "edt.h"
+#include "geodesic.h"
 #include "../host/stack_io.h"
 #include <algorithm>
 #include <cfloat>
@@ -409,6 +410,28 @@ int pnr_distance_transform(pnr_ctx *c, const pnr_edt_opts *opts, pnr_edt_info *i
     PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
     PNR_HIP(hipSetDevice(c->device));
     return pnr_edt_run(c, who, o, info, d2_out, xyz, n, d2_at);
+}
+
+// pnr_geodesic_distance (geodesic.hip): arguments first, then the state; the pipeline state of the context is neither needed nor touched
+int pnr_geodesic_distance(pnr_ctx *c, const float *src_xyz, const int32_t *src_label, int64_t n_src, const pnr_geo_opts *opts, pnr_geo_info *info, uint32_t *d_out,
+                          int32_t *label_out, const float *at_xyz, int64_t m, uint32_t *d_at, int32_t *label_at, int32_t path_cap, int32_t *path_len, int64_t *path_vox)
+{
+    static const char *who = "pnr_geodesic_distance";
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    const pnr_geo_opts o = opts ? *opts : pnr_geo_opts{0, 0x7fffffffu, nullptr};
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "%s: thr = %d outside [-1, 255]", who, o.thr);
+    PNR_REQUIRE(o.dmax >= 1 && o.dmax <= 0x7fffffffu, PNR_E_ARG, "%s: dmax = %u outside [1, 2^31 - 1]", who, o.dmax);
+    for (int v = 0; o.cost && v < 256; v++) PNR_REQUIRE(o.cost[v] >= 1, PNR_E_ARG, "%s: cost[%d] = 0, every entry is at least 1", who, v);
+    PNR_REQUIRE(n_src >= 0 && n_src <= PNR_RADIUS_MAX_N && (n_src == 0 || src_xyz), PNR_E_ARG, "%s: n_src = %lld sources (at most 2^28) need src_xyz", who, (long long)n_src);
+    for (int64_t i = 0; src_label && i < n_src; i++) PNR_REQUIRE(src_label[i] >= 0, PNR_E_ARG, "%s: label[%lld] = %d is negative", who, (long long)i, src_label[i]);
+    PNR_REQUIRE(path_cap >= 0 && path_cap <= PNR_GEO_MAX_PATH, PNR_E_ARG, "%s: path_cap = %d outside [0, %d]", who, path_cap, PNR_GEO_MAX_PATH);
+    PNR_REQUIRE(m >= 0 && m <= PNR_RADIUS_MAX_N && (m == 0 || (at_xyz && (d_at || label_at || path_cap > 0))), PNR_E_ARG,
+                "%s: m = %lld targets (at most 2^28) need at_xyz and one of d_at, label_at and path_cap > 0", who, (long long)m);
+    PNR_REQUIRE(m == 0 || path_cap == 0 || (path_len && path_vox), PNR_E_ARG, "%s: path_cap = %d needs path_len and path_vox", who, path_cap);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "%s: no volume set", who);
+    PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_geodesic_run(c, who, o, pnr_geo_call{src_xyz, src_label, n_src, info, d_out, label_out, at_xyz, m, d_at, label_at, path_cap, path_len, path_vox});
 }
 
 // pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched
@@ -1285,6 +1308,7 @@ const OptEntry OPTS[] = {
     {"join_split", &pnr::Options::join_split, nullptr, 0, 1 << 22}, {"join_pairs_per_launch", nullptr, &pnr::Options::join_pairs_per_launch, 0, 1ll << 44},
     {"render_piece", &pnr::Options::render_piece, nullptr, 0, 1 << 20}, {"render_box", nullptr, &pnr::Options::render_box, 0, 1 << 24},
     {"render_items_per_launch", nullptr, &pnr::Options::render_items_per_launch, 0, 1 << 24},
+    {"geo_iters", &pnr::Options::geo_iters, nullptr, 0, 1 << 16}, {"geo_tiles_per_launch", &pnr::Options::geo_tiles_per_launch, nullptr, 0, 1 << 24},
 };
 } // namespace
 
@@ -1312,6 +1336,8 @@ int pnr_get_option(pnr_ctx *c, const char *key, int64_t *value)
     if (std::strcmp(key, "recon_timing") == 0) { *value = advantra::recon_timing() ? 1 : 0; return PNR_OK; }
     if (std::strcmp(key, "host_threads_effective") == 0) { *value = pnr::host_threads(c->opt); return PNR_OK; }
     if (std::strcmp(key, "join_rounds") == 0) { *value = c->join_rounds; return PNR_OK; }
+    if (std::strcmp(key, "geo_rounds") == 0) { *value = c->geo_rounds; return PNR_OK; }
+    if (std::strcmp(key, "geo_visits") == 0) { *value = c->geo_visits; return PNR_OK; }
     if (std::strcmp(key, "render_items") == 0) { *value = c->render_items; return PNR_OK; }
     if (std::strcmp(key, "render_pairs") == 0) { *value = c->render_pairs; return PNR_OK; }
     if (std::strcmp(key, "frangi_recomputes") == 0) { *value = c->frangi_recomputes; return PNR_OK; } // exact Frangi re-runs so far (one pnr_frangi of GPU time each)
@@ -1481,6 +1507,18 @@ int pnr_get_kernel_ms(pnr_ctx *c, const char *group, double *ms, int64_t *launch
         *ms = 0;
         if (launches) *launches = 0;
         for (const char *g : {"edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"}) {
+            double a = 0;
+            int64_t la = 0;
+            pnr_get_kernel_ms(c, g, &a, &la);
+            *ms += a;
+            if (launches) *launches += la;
+        }
+        return PNR_OK;
+    }
+    if (std::strcmp(group, "geodesic") == 0) { // one sub-group per phase (geodesic.hip)
+        *ms = 0;
+        if (launches) *launches = 0;
+        for (const char *g : {"geodesic_threshold", "geodesic_init", "geodesic_compact", "geodesic_relax", "geodesic_stats", "geodesic_split", "geodesic_sample", "geodesic_paths"}) {
             double a = 0;
             int64_t la = 0;
             pnr_get_kernel_ms(c, g, &a, &la);

@@ -1,4 +1,4 @@
-// call.h -- the staging of one tool call (volume, radius, filter, distance, join, render, components, edt): its device buffers as typed
+// call.h -- the staging of one tool call (volume, radius, filter, distance, join, render, components, edt, geodesic): its device buffers as typed
 // parts of ONE allocation, and the chain of HIP calls on the context's stream with one sticky error.
 #pragma once
 #include "ctx.h"

@@ -42,6 +42,10 @@
 //   distance transform of the stack's foreground (pnr_distance_transform on device -g; the same volume setup as --components; Z >= 1,
 //   default 1, is the context's zdist) as one JSON line n_vox, n_fg, n_capped, thr_used, rmax, zdist, d_max, max_at; --edt-out writes
 //   d = sqrtf(D2) as bare little-endian f32, --at / --per-node one line `id,d` per node of the SWC file.
+//   --geodesic -i stack --from tree.swc [--to other.swc --per-node FILE.csv [--paths OUT.swc]] [--threshold T] [--geo-max D] [--zscale Z]
+//   [--geo-out PREFIX]: the gray-weighted geodesic distance of every voxel to the tree (pnr_geodesic_distance on device -g; the volume setup
+//   of --edt; sources: the tree's sample points labelled with their node ids) as one JSON line; --per-node writes `id,d,label` per node of
+//   other.swc, --paths every complete path as a chain of SWC nodes, --geo-out PREFIX_d.raw (u32) and PREFIX_label.raw (i32).
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -129,8 +133,29 @@ int main(int argc, char **argv)
     bool components = false, comp_flag = false, thr_flag = false;
     advantra::EdtJob edt_job;
     bool edt = false, edt_flag = false;
+    advantra::GeodesicJob geo_job;
+    bool geo = false, geo_flag = false;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
+        if (!strcmp(argv[i], "--geodesic")) { geo = true; continue; }
+        if (!strcmp(argv[i], "--geo-max")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 1, 0x7fffffffL, v)) { fprintf(stderr, "--geo-max D: the largest path cost kept, an integer from 1 to 2147483647\n"); return 1; }
+            geo_job.opts.dmax = (uint32_t)v;
+            geo_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--from") || !strcmp(argv[i], "--to") || !strcmp(argv[i], "--paths") || !strcmp(argv[i], "--geo-out")) {
+            const std::string flag = argv[i];
+            const std::string name = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (name.empty()) {
+                fprintf(stderr, "%s\n", flag == "--from" ? "--from tree.swc" : flag == "--to" ? "--to other.swc" : flag == "--paths" ? "--paths OUT.swc" : "--geo-out PREFIX");
+                return 1;
+            }
+            (flag == "--from" ? geo_job.from : flag == "--to" ? geo_job.to : flag == "--paths" ? geo_job.paths : geo_job.out) = name;
+            geo_flag = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--components")) { components = true; continue; }
         if (!strcmp(argv[i], "--edt")) { edt = true; continue; }
         if (!strcmp(argv[i], "--edt-max")) {
@@ -154,7 +179,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "--threshold")) {
             long v = 0;
             if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
-            comp.opts.thr = edt_job.opts.thr = (int32_t)v;
+            comp.opts.thr = edt_job.opts.thr = geo_job.opts.thr = (int32_t)v;
             thr_flag = true;
             continue;
         }
@@ -374,16 +399,30 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool rendering = !render.swc.empty();
-    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt) || (zscale_flag && !distance && join_in.empty() && !rendering && !components && !edt)) {
-        fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc; --zscale, --per-node: or --render-swc)\n");
+    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt && !geo) || (zscale_flag && !distance && join_in.empty() && !rendering && !components && !edt && !geo)) {
+        fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc; --zscale, --per-node: or --render-swc, --edt or --geodesic)\n");
         return 1;
     }
     if (render_flag && !rendering) { fprintf(stderr, "--radius-scale / --radius-add / --coverage-threshold need --render-swc IN.swc\n"); return 1; }
     if (join_flag && !join_given && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
-    if ((comp_flag && !components) || (thr_flag && !components && !edt)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt)\n"); return 1; }
+    if ((comp_flag && !components) || (thr_flag && !components && !edt && !geo)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt or --geodesic)\n"); return 1; }
     if (edt_flag && !edt) { fprintf(stderr, "--edt-max / --edt-out / --at need --edt -i stack\n"); return 1; }
+    if (geo_flag && !geo) { fprintf(stderr, "--from / --to / --paths / --geo-max / --geo-out need --geodesic -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (geo) {
+        if (edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || !paras.empty()) {
+            fprintf(stderr, "--geodesic: not with a tracing run (-p), --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle or --measure-radius\n");
+            return 1;
+        }
+        if (infiles.empty()) { fprintf(stderr, "--geodesic needs -i <stack>\n"); return 1; }
+        if (geo_job.from.empty()) { fprintf(stderr, "--geodesic needs --from tree.swc\n"); return 1; }
+        if (geo_job.to.empty() != per_node.empty()) { fprintf(stderr, "--geodesic: --to other.swc and --per-node FILE.csv go together\n"); return 1; }
+        if (!geo_job.paths.empty() && geo_job.to.empty()) { fprintf(stderr, "--geodesic: --paths OUT.swc needs --to other.swc\n"); return 1; }
+        if (zscale_flag && dist_opts.zscale < 1.f) { fprintf(stderr, "--geodesic: --zscale Z: a number, 1 or more\n"); return 1; }
+        geo_job.per_node = per_node;
+        return advantra::geodesic_file(geo_job, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, device) ? 0 : 1;
+    }
     if (edt) {
         if (components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || !paras.empty()) {
             fprintf(stderr, "--edt: not with a tracing run (-p), --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle or --measure-radius\n");

@@ -95,6 +95,16 @@ void print_flags()
     printf("  --zscale Z                z counts Z-fold, 1 or more (default 1)\n");
     printf("  --edt-out OUT.raw         write d of every voxel: little-endian float32\n");
     printf("  --at tree.swc --per-node FILE.csv   `id,d` per node of the SWC file: its sub-voxel radius (-1: a position that is not finite)\n");
+    printf("--geodesic -i stack --from tree.swc   the gray-weighted geodesic distance of every voxel to the tree on the GPU (the same volume setup as\n");
+    printf("                          tracing): the cheapest 26-connected path, a step costs its length times the darkness 256 - v of its two voxels;\n");
+    printf("                          one JSON line: n_vox, n_pass, n_reached, n_src, n_src_dropped, thr_used, dmax, zdist, d_max, len_max, max_at, rounds\n");
+    printf("  --threshold T             voxels below T are impassable, 0..255, -1: the stack's mean (default 0: every voxel is passable)\n");
+    printf("  --geo-max D               no path that costs more than D is kept, 1..2147483647 (default: no limit; 64 is one xy voxel at cost 1)\n");
+    printf("  --zscale Z                z counts Z-fold, 1 or more (default 1)\n");
+    printf("  --to other.swc --per-node FILE.csv   `id,d,label` per node of the SWC file: its cost and the id of the tree node it attaches to\n");
+    printf("  --paths OUT.swc           with --to: every complete path as a chain of SWC nodes that ends on the tree (paths of more than\n");
+    printf("                            min(%d, 2^26 / nodes) voxels are left out and counted on stderr)\n", PNR_GEO_MAX_PATH);
+    printf("  --geo-out PREFIX          write PREFIX_d.raw (little-endian uint32, 4294967295: unreached) and PREFIX_label.raw (int32, -1: unreached)\n");
     printf("--measure-radius          SWC radii measured from the image at the final nodes (default: SIG2RADIUS * the winning scale)\n");
     printf("--radius-rel PCT          relative mode (default, 50): background below PCT %% of the node's brightest centre voxel, 1..100\n");
     printf("--radius-threshold T      absolute mode: background below T, 0..255; -1: below the stack's mean\n");
@@ -795,6 +805,126 @@ bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::
            (long long)ei.n_fg, (long long)ei.n_capped, (int)ei.thr_used, (int)job.opts.rmax, (double)zscale, (double)sqrtf(ei.d2_max));
     if (ei.first_max < 0) printf("null}\n");
     else printf("[%lld, %lld, %lld]}\n", (long long)(ei.first_max % st.w), (long long)(ei.first_max / st.w % st.h), (long long)(ei.first_max / (st.w * st.h)));
+    return true;
+}
+
+bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    auto lib_fail = [](const char *what) {
+        fprintf(stderr, "%s: %s\n", what, pnr_last_error());
+        return false;
+    };
+    const Settings &S = settings();
+    Stack st;
+    std::string err;
+    if (!load_stack(infiles[0], raw_dims, st, err, S.channel - 1, S.raw_u16)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    if (S.windowed && st.bits != 16) {
+        fprintf(stderr, "--window / --saturate need a 16-bit stack (8-bit input is never windowed)\n");
+        return false;
+    }
+    SwcTree A, B;
+    if (!load_swc(job.from, A, err) || (!job.to.empty() && !load_swc(job.to, B, err))) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    if (A.n() == 0) {
+        fprintf(stderr, "%s: no nodes\n", job.from.c_str());
+        return false;
+    }
+    for (long long id : A.id)
+        if (id < 0 || id > 0x7fffffffLL) {
+            fprintf(stderr, "%s: node id %lld is no label (0 .. 2147483647)\n", job.from.c_str(), id);
+            return false;
+        }
+    // the sources: the sample points of the tree, labelled with their owner node's id
+    int64_t ns = 0;
+    if (pnr_tree_sample(A.xyz.data(), A.parent.data(), A.n(), 1.f, 1.f, nullptr, nullptr, 0, &ns) != PNR_OK) return lib_fail(job.from.c_str());
+    std::vector<float> src((size_t)ns * 3);
+    std::vector<int32_t> label((size_t)ns);
+    if (pnr_tree_sample(A.xyz.data(), A.parent.data(), A.n(), 1.f, 1.f, src.data(), label.data(), ns, &ns) != PNR_OK) return lib_fail(job.from.c_str());
+    for (int32_t &v : label) v = (int32_t)A.id[(size_t)v];
+    pnr_params p;
+    pnr_default_params(&p);
+    p.zdist = zscale; // (also the z half-width of --subtract-background)
+    pnr_ctx *ctx = nullptr;
+    if (pnr_create(&p, device, &ctx) != PNR_OK) return lib_fail("pnr_create");
+    // the volume as it would be traced: windowed to 8 bits, then pre-filtered
+    bool ok = (st.bits == 16 ? pnr_set_volume_u16(ctx, st.samples16(), st.w, st.h, st.l, 1, 0, S.windowed ? &S.window : nullptr, nullptr, nullptr)
+                             : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
+    if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
+    if (!ok) {
+        lib_fail("volume");
+        pnr_destroy(ctx);
+        return false;
+    }
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    const int64_t m = B.n();
+    std::vector<uint32_t> D(job.out.empty() ? 0 : N), d_at((size_t)m);
+    std::vector<int32_t> L(job.out.empty() ? 0 : N), l_at((size_t)m), plen;
+    std::vector<int64_t> pvox;
+    pnr_geo_info gi = {};
+    // the cap of the walks, fixed before the one call: a path visits a voxel at most once, no path has more than PNR_GEO_MAX_PATH voxels, and
+    // all targets together get at most 2^26 entries (512 MB here and on the device)
+    int32_t cap = 0;
+    if (!job.paths.empty() && m) {
+        cap = (int32_t)std::min<size_t>({(size_t)PNR_GEO_MAX_PATH, N, std::max<size_t>(64, ((size_t)1 << 26) / (size_t)m)});
+        plen.resize((size_t)m), pvox.resize((size_t)m * (size_t)cap);
+    }
+    const int rc = pnr_geodesic_distance(ctx, src.data(), label.data(), ns, &job.opts, &gi, job.out.empty() ? nullptr : D.data(), job.out.empty() ? nullptr : L.data(),
+                                         m ? B.xyz.data() : nullptr, m, m ? d_at.data() : nullptr, m ? l_at.data() : nullptr, cap, cap ? plen.data() : nullptr,
+                                         cap ? pvox.data() : nullptr);
+    pnr_destroy(ctx);
+    if (rc != PNR_OK) return lib_fail("pnr_geodesic_distance");
+    long long cut = 0;
+    for (int32_t n : plen) cut += n < 0;
+    if (cut) fprintf(stderr, "--paths: %lld path(s) of more than %d voxels are left out of %s\n", cut, (int)cap, job.paths.c_str());
+    auto write_file = [](const std::string &name, const char *mode, const std::function<void(FILE *)> &body) {
+        FILE *f = fopen(name.c_str(), mode);
+        if (!f) {
+            fprintf(stderr, "%s: cannot write the file\n", name.c_str());
+            return false;
+        }
+        body(f);
+        const bool bad = ferror(f) != 0;
+        if (fclose(f) != 0 || bad) {
+            fprintf(stderr, "%s: write failed\n", name.c_str());
+            return false;
+        }
+        return true;
+    };
+    if (!job.out.empty()) { // (the hosts this builds for are little-endian)
+        if (!write_file(job.out + "_d.raw", "wb", [&](FILE *f) { fwrite(D.data(), 4, N, f); })) return false;
+        if (!write_file(job.out + "_label.raw", "wb", [&](FILE *f) { fwrite(L.data(), 4, N, f); })) return false;
+    }
+    if (!job.per_node.empty() && !write_file(job.per_node, "w", [&](FILE *f) {
+            fprintf(f, "id,d,label\n");
+            for (size_t k = 0; k < (size_t)m; k++) fprintf(f, "%lld,%lld,%d\n", B.id[k], d_at[k] == 0xffffffffu ? -1LL : (long long)d_at[k], (int)l_at[k]);
+        }))
+        return false;
+    if (!job.paths.empty() && !write_file(job.paths, "w", [&](FILE *f) {
+            long long next = 1;
+            for (size_t k = 0; k < (size_t)m; k++) {
+                const int32_t n = plen[k];
+                if (n <= 0) continue; // (unreached, not finite, or cut at the cap: reported above)
+                fprintf(f, "# path %lld -> %d: %d voxels, cost %u\n", B.id[k], (int)l_at[k], (int)n, (unsigned)d_at[k]);
+                for (int32_t j = 0; j < n; j++) {
+                    const long long v = pvox[k * (size_t)cap + (size_t)j];
+                    fprintf(f, "%lld 2 %lld %lld %lld 1 %lld\n", next + j, v % st.w, v / st.w % st.h, v / (st.w * st.h), j + 1 < n ? next + j + 1 : -1LL);
+                }
+                next += n;
+            }
+        }))
+        return false;
+    printf("{\"n_vox\": %lld, \"n_pass\": %lld, \"n_reached\": %lld, \"n_src\": %lld, \"n_src_dropped\": %lld, \"thr_used\": %d, \"dmax\": %u, \"zdist\": %.17g, \"d_max\": %u, "
+           "\"len_max\": %.17g, \"max_at\": ",
+           (long long)gi.n_vox, (long long)gi.n_pass, (long long)gi.n_reached, (long long)gi.n_src, (long long)gi.n_src_dropped, (int)gi.thr_used, (unsigned)job.opts.dmax,
+           (double)zscale, (unsigned)gi.d_max, (double)gi.d_max / 64.0);
+    if (gi.first_max < 0) printf("null");
+    else printf("[%lld, %lld, %lld]", (long long)(gi.first_max % st.w), (long long)(gi.first_max / st.w % st.h), (long long)(gi.first_max / (st.w * st.h)));
+    printf(", \"rounds\": %d}\n", (int)gi.rounds);
     return true;
 }
 

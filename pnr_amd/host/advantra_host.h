@@ -171,6 +171,20 @@ struct EdtJob {
     std::string out, at, per_node;
 };
 bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
+// advantra_cli --geodesic -i stack --from tree.swc: the gray-weighted geodesic distance of every voxel of the stack to the tree
+// (pnr_geodesic_distance on `device`; the same volume setup as --edt; zscale >= 1 is the context's zdist).  Sources: the sample points of
+// `from` (pnr_tree_sample at step 1, zscale 1), each labelled with the SWC id of its owner node.  One JSON line {"n_vox", "n_pass",
+// "n_reached", "n_src", "n_src_dropped", "thr_used", "dmax", "zdist", "d_max", "len_max" (d_max / 64: xy voxels at the brightest cost),
+// "max_at": [x, y, z] (null when nothing is reached), "rounds"}.  `to` and `per_node` (both or neither): a CSV `id,d,label` per node of the
+// SWC file `to` under a header line (-1,-1: unreached or not finite); `paths` (needs `to`): every complete path as a chain of SWC nodes
+// from the target's voxel to the source voxel (the root of the chain), each chain under a comment line
+// `# path <target id> -> <label>: <k> voxels, cost <d>` (walked in the same call with a cap of min(PNR_GEO_MAX_PATH, N, max(64, 2^26 / nodes))
+// voxels; a longer path is left out, and a line on stderr says how many were); `out` (not empty): <out>_d.raw (u32) and <out>_label.raw (i32), little-endian.
+struct GeodesicJob {
+    pnr_geo_opts opts = {0, 0x7fffffffu, nullptr};
+    std::string from, to, per_node, paths, out;
+};
+bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

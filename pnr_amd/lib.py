@@ -126,6 +126,26 @@ class EdtInfo(C.Structure):
 PNR_EDT_MAX_R = 1024
 
 
+class GeoOpts(C.Structure):
+    """pnr_geo_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean; 0: every voxel is passable), dmax 1..2^31 - 1 (no path above it
+    is kept), cost: 256 u16 entries >= 1 (NULL: c(v) = 256 - v)"""
+    _fields_ = [("thr", C.c_int32), ("dmax", C.c_uint32), ("cost", C.POINTER(C.c_uint16))]
+
+
+class GeoInfo(C.Structure):
+    """pnr_geo_info: the exact summary of a geodesic distance (first_max: the smallest linear index that attains d_max, -1 when nothing is
+    reached; rounds: relaxation rounds of the call)"""
+    _fields_ = [("n_vox", C.c_int64), ("n_pass", C.c_int64), ("n_reached", C.c_int64), ("n_src", C.c_int64), ("n_src_dropped", C.c_int64), ("first_max", C.c_int64),
+                ("d_max", C.c_uint32), ("thr_used", C.c_int32), ("rounds", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+PNR_GEO_MAX_PATH = 1 << 16
+PNR_GEO_DMAX = 2**31 - 1
+
+
 # pnr_component
 COMPONENT_DT = np.dtype([(k, np.int64) for k in ("first", "size", "sum", "sx", "sy", "sz")] + [(k, np.int32) for k in ("x0", "y0", "z0", "x1", "y1", "z1", "vmax", "pad")])
 
@@ -207,6 +227,7 @@ def load():
     L.pnr_label_components.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo), vp, vp, i64]
     L.pnr_despeckle_volume.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]
     L.pnr_distance_transform.argtypes = [vp, C.POINTER(EdtOpts), C.POINTER(EdtInfo), vp, vp, i64, vp]
+    L.pnr_geodesic_distance.argtypes = [vp, vp, vp, i64, C.POINTER(GeoOpts), C.POINTER(GeoInfo), vp, vp, vp, i64, vp, vp, i32, vp, vp]
     L.pnr_render_items.argtypes = [vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_test_write_tiff.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
@@ -272,7 +293,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_geodesic_distance", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -567,6 +588,50 @@ class Context:
             if at is not None:
                 at = np.where(at >= 0, np.sqrt(np.maximum(at, np.float32(0))), at).astype(np.float32)
         return out, d2, at
+
+    def geodesic(self, sources, labels=None, thr=0, dmax=PNR_GEO_DMAX, cost=None, volume=True, targets=None, path_cap=0):
+        """pnr_geodesic_distance: the gray-weighted geodesic distance D of every passable voxel (V >= thr; thr = -1: the global mean) to the
+        nearest of the sources (n x 3 positions (x, y, z); labels int32 >= 0, None: 0 .. n - 1) along 26-connected paths whose steps cost
+        len * (c(V(p)) + c(V(q))), c = cost (256 u16 >= 1; None: 256 - v), and the label L of that source -> (info dict {n_vox, n_pass,
+        n_reached, n_src, n_src_dropped, first_max, d_max, thr_used, rounds, max_at}, D uint32[l, h, w] or None (0xFFFFFFFF: unreached),
+        L int32[l, h, w] or None (-1: unreached), at or None).  targets: m x 3 positions -> at = {"d": uint32[m], "label": int32[m]} at
+        their centre voxels, and with path_cap > 0 also {"path_len": int32[m], "paths": a list of m int64 arrays of linear voxel indices
+        from the target to its source voxel}: path_len k > 0 is a complete path, 0 an unreached or non-finite target (an empty array),
+        -path_cap a walk cut after path_cap voxels (those are in the array)."""
+        src = np.ascontiguousarray(sources, np.float32).reshape(-1, 3)
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1) if labels is not None else None
+        if lab is not None and len(lab) != len(src):
+            raise ValueError("geodesic: %d labels for %d sources" % (len(lab), len(src)))
+        tab = np.ascontiguousarray(cost, np.uint16).reshape(-1) if cost is not None else None
+        if tab is not None and len(tab) != 256:
+            raise ValueError("geodesic: the cost table has 256 entries")
+        o = GeoOpts(int(thr), int(dmax), tab.ctypes.data_as(C.POINTER(C.c_uint16)) if tab is not None else None)
+        info = GeoInfo()
+        D = np.empty(self.shape, np.uint32) if volume else None
+        Lv = np.empty(self.shape, np.int32) if volume else None
+        xyz = np.ascontiguousarray(targets, np.float32).reshape(-1, 3) if targets is not None else None
+        m = len(xyz) if xyz is not None else 0
+        cap = int(path_cap)
+        d_at, l_at = (np.empty(m, np.uint32), np.empty(m, np.int32)) if xyz is not None else (None, None)
+        plen = np.zeros(m, np.int32) if m and cap > 0 else None
+        pvox = np.empty((m, cap), np.int64) if plen is not None else None
+        check(self.L.pnr_geodesic_distance(self.h, src.ctypes.data if len(src) else None, lab.ctypes.data if lab is not None and len(lab) else None, len(src),
+                                           C.byref(o), C.byref(info), D.ctypes.data if volume else None, Lv.ctypes.data if volume else None,
+                                           xyz.ctypes.data if m else None, m, d_at.ctypes.data if m else None, l_at.ctypes.data if m else None,
+                                           cap, plen.ctypes.data if plen is not None else None, pvox.ctypes.data if pvox is not None else None))
+        out = info.as_dict()
+        l, h, w = self.shape
+        i = info.first_max
+        out["max_at"] = (i % w, (i // w) % h, i // (w * h)) if i >= 0 else None
+        at = None
+        if xyz is not None:
+            at = {"d": d_at, "label": l_at}
+            if cap > 0:
+                if plen is None:
+                    plen = np.zeros(0, np.int32)
+                at["path_len"] = plen
+                at["paths"] = [pvox[k, :abs(int(n))].copy() for k, n in enumerate(plen)]
+        return out, D, Lv, at
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
