@@ -1,0 +1,352 @@
+// tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc, --render-swc, --components, --edt and
+// --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+#include "host_internal.h"
+#include <algorithm>
+#include <cmath>
+#include <functional>
+
+namespace advantra {
+
+// `name` opened with `mode`, written by `body` and closed: false after a message on stderr
+static bool write_file(const std::string &name, const char *mode, const std::function<void(FILE *)> &body)
+{
+    FILE *f = fopen(name.c_str(), mode);
+    if (!f) {
+        fprintf(stderr, "%s: cannot write the file\n", name.c_str());
+        return false;
+    }
+    body(f);
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) {
+        fprintf(stderr, "%s: write failed\n", name.c_str());
+        return false;
+    }
+    return true;
+}
+
+// the volume as it would be traced: windowed to 8 bits, then pre-filtered (never despeckled)
+static bool set_traced_volume(pnr_ctx *ctx, const Stack &st)
+{
+    const Settings &S = settings();
+    bool ok = (st.bits == 16 ? pnr_set_volume_u16(ctx, st.samples16(), st.w, st.h, st.l, 1, 0, S.windowed ? &S.window : nullptr, nullptr, nullptr)
+                             : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
+    if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
+    return ok || lib_fail("volume");
+}
+
+// the JSON value of a voxel index in a stack of w x h pixels per plane: [x, y, z], or null for none
+static void print_max_at(int64_t first_max, long long w, long long h)
+{
+    if (first_max < 0) printf("null");
+    else printf("[%lld, %lld, %lld]", (long long)(first_max % w), (long long)(first_max / w % h), (long long)(first_max / (w * h)));
+}
+
+bool print_tree_distance(const std::string &a, const std::string &b, const pnr_distance_opts &opts, int device, const std::string &per_node)
+{
+    SwcTree A, B;
+    if (!read_swc(a, A) || !read_swc(b, B)) return false;
+    for (const auto &side : {std::make_pair(&a, &A), std::make_pair(&b, &B)})
+        if (side.second->n() == 0) {
+            fprintf(stderr, "%s: no nodes\n", side.first->c_str());
+            return false;
+        }
+    // the sample points of either side first: the sizes of the per-point arrays (and an empty or malformed tree before any GPU work)
+    int64_t na = 0, nb = 0;
+    if (pnr_tree_sample(A.xyz.data(), A.parent.data(), A.n(), opts.zscale, opts.step, nullptr, nullptr, 0, &na) != PNR_OK) return lib_fail(a.c_str());
+    if (pnr_tree_sample(B.xyz.data(), B.parent.data(), B.n(), opts.zscale, opts.step, nullptr, nullptr, 0, &nb) != PNR_OK) return lib_fail(b.c_str());
+    pnr_params p;
+    pnr_default_params(&p);
+    Ctx ctx;
+    if (!ctx.create(p, device)) return false;
+    std::vector<float> da((size_t)na), db((size_t)nb);
+    std::vector<int32_t> oa((size_t)na), ob((size_t)nb);
+    pnr_distance_result r;
+    if (pnr_tree_distance(ctx, A.xyz.data(), A.parent.data(), A.n(), B.xyz.data(), B.parent.data(), B.n(), &opts, &r, da.data(), oa.data(), na, db.data(), ob.data(),
+                          nb) != PNR_OK)
+        return lib_fail("pnr_tree_distance");
+    auto csv = [&](const char *tag, const SwcTree &t, const std::vector<float> &d, const std::vector<int32_t> &o) {
+        return write_file(per_node + tag, "w", [&](FILE *f) {
+            fprintf(f, "id,d\n");
+            for (size_t k = 0; k < d.size(); k++) fprintf(f, "%lld,%.9g\n", t.id[(size_t)o[k]], (double)d[k]);
+        });
+    };
+    if (!per_node.empty() && (!csv("_ab.csv", A, da, oa) || !csv("_ba.csv", B, db, ob))) return false;
+    auto dir = [](const char *k, const pnr_distance_dir &d) {
+        printf("\"%s\": {\"n\": %lld, \"n_big\": %lld, \"mean\": %.17g, \"ssd\": %.17g, \"pct\": %.17g, \"max\": %.17g}, ", k, (long long)d.n, (long long)d.n_big, d.mean,
+               d.ssd, d.pct, d.max);
+    };
+    printf("{\"zscale\": %.9g, \"step\": %.9g, \"thr\": %.9g, \"nodes_a\": %lld, \"nodes_b\": %lld, ", (double)opts.zscale, (double)opts.step, (double)opts.thr, A.n(), B.n());
+    dir("ab", r.ab);
+    dir("ba", r.ba);
+    printf("\"sd\": %.17g, \"ssd\": %.17g, \"pct\": %.17g, \"hausdorff\": %.17g}\n", r.sd, r.ssd, r.pct, r.hausdorff);
+    return true;
+}
+
+bool join_swc_file(const std::string &in, const std::string &out, float gap, float zscale, long long root_id, bool keep_largest, int device)
+{
+    SwcTree T;
+    if (!read_swc(in, T)) return false;
+    const int64_t n = T.n();
+    if (n == 0) {
+        fprintf(stderr, "%s: no nodes\n", in.c_str());
+        return false;
+    }
+    int64_t root = -1;
+    if (root_id > 0) {
+        const auto it = std::find(T.id.begin(), T.id.end(), root_id);
+        if (it == T.id.end()) {
+            fprintf(stderr, "--join-root %lld: %s has no node with this id\n", root_id, in.c_str());
+            return false;
+        }
+        root = it - T.id.begin();
+    }
+    pnr_params p;
+    pnr_default_params(&p);
+    Ctx ctx;
+    if (!ctx.create(p, device)) return false;
+    const pnr_join_opts jo = {zscale, gap, (int32_t)root};
+    std::vector<int32_t> par_out((size_t)n), order((size_t)n), comp((size_t)n);
+    std::vector<pnr_bridge> bridges((size_t)n);
+    int64_t nb = 0, t_in = 0, t_out = 0, rounds = 0;
+    const int rc = pnr_join_trees(ctx, T.xyz.data(), T.parent.data(), n, &jo, par_out.data(), order.data(), comp.data(), bridges.data(), n, &nb, &t_in, &t_out);
+    pnr_get_option(ctx, "join_rounds", &rounds);
+    if (rc != PNR_OK) return lib_fail("pnr_join_trees");
+    int64_t written = 0;
+    if (!write_file(out, "w", [&](FILE *f) {
+            fprintf(f, "#join=gap:%s,bridges:%lld,trees:%lld->%lld\n##n,type,x,y,z,radius,parent\n", f32_text(gap).c_str(), (long long)nb, (long long)t_in, (long long)t_out);
+            std::vector<int64_t> pos((size_t)n, -1);
+            for (int64_t k = 0; k < n; k++) {
+                const size_t v = (size_t)order[(size_t)k];
+                if (keep_largest && comp[v] != 0) break;
+                pos[v] = ++written;
+                fprintf(f, "%lld %d %s %s %s %s %lld\n", (long long)written, T.type[v], f32_text(T.xyz[3 * v]).c_str(), f32_text(T.xyz[3 * v + 1]).c_str(),
+                        f32_text(T.xyz[3 * v + 2]).c_str(), f32_text(T.radius[v]).c_str(), par_out[v] < 0 ? -1LL : (long long)pos[(size_t)par_out[v]]);
+            }
+        }))
+        return false;
+    printf("{\"nodes\": %lld, \"trees_in\": %lld, \"trees_out\": %lld, \"bridges\": %lld, \"longest_bridge\": %.9g, \"rounds\": %lld}\n", (long long)written,
+           (long long)t_in, (long long)t_out, (long long)nb, nb ? (double)bridges[(size_t)nb - 1].d : 0.0, (long long)rounds);
+    return true;
+}
+
+// --render-swc without -i: the mask alone, on the grid of -d
+static bool render_mask_on_grid(const RenderJob &job, const SwcTree &T, const pnr_params &p, const std::string &raw_dims, int device)
+{
+    long long w = 0, h = 0, l = 0;
+    if (sscanf(raw_dims.c_str(), "%lld,%lld,%lld", &w, &h, &l) != 3 || w <= 0 || h <= 0 || l <= 0) {
+        fprintf(stderr, "--render-swc without -i needs the grid: -d w,h,l\n");
+        return false;
+    }
+    std::string e;
+    if (job.mask.size() > 4 && job.mask.substr(job.mask.size() - 4) != ".raw" && tiff_u8_bytes(w, h, l) < 0 && !save_stack_u8(job.mask, nullptr, w, h, l, e)) {
+        fprintf(stderr, "%s\n", e.c_str()); // (refused from the dimensions, before any GPU work)
+        return false;
+    }
+    Ctx ctx;
+    if (!ctx.create(p, device)) return false;
+    std::vector<unsigned char> mask((size_t)(w * h * l));
+    int64_t items = 0;
+    const int rc = pnr_render_tree(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), T.n(), w, h, l, &job.opts, nullptr, mask.data());
+    pnr_get_option(ctx, "render_items", &items);
+    if (rc != PNR_OK) return lib_fail("pnr_render_tree");
+    if (!write_stack(job.mask, mask.data(), w, h, l)) return false;
+    long long n_tree = 0;
+    for (unsigned char v : mask) n_tree += v != 0;
+    printf("{\"n_vox\": %lld, \"n_tree\": %lld, \"nodes\": %lld, \"items\": %lld}\n", w * h * l, n_tree, T.n(), (long long)items);
+    return true;
+}
+
+bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device)
+{
+    SwcTree T;
+    if (!read_swc(job.swc, T)) return false;
+    const int64_t n = T.n();
+    pnr_params p;
+    pnr_default_params(&p);
+    if (job.opts.zscale >= 1.f) p.zdist = job.opts.zscale; // (the z half-width of --subtract-background)
+    if (infiles.empty()) return render_mask_on_grid(job, T, p, raw_dims, device);
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<unsigned char> mask(job.mask.empty() ? 0 : N), residual(job.residual.empty() ? 0 : N);
+    std::vector<int64_t> vox, fg, sum;
+    if (!job.per_node.empty()) vox.assign((size_t)n, 0), fg.assign((size_t)n, 0), sum.assign((size_t)n, 0);
+    pnr_coverage c;
+    int64_t items = 0;
+    const int rc = pnr_tree_coverage(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), n, &job.opts, &c, job.per_node.empty() ? nullptr : vox.data(),
+                                     job.per_node.empty() ? nullptr : fg.data(), job.per_node.empty() ? nullptr : sum.data(),
+                                     job.mask.empty() ? nullptr : mask.data(), job.residual.empty() ? nullptr : residual.data());
+    pnr_get_option(ctx, "render_items", &items);
+    if (rc != PNR_OK) return lib_fail("pnr_tree_coverage");
+    if (!job.mask.empty() && !write_stack(job.mask, mask.data(), st.w, st.h, st.l)) return false;
+    if (!job.residual.empty() && !write_stack(job.residual, residual.data(), st.w, st.h, st.l)) return false;
+    if (!job.per_node.empty() && !write_file(job.per_node, "w", [&](FILE *f) {
+            fprintf(f, "id,vox,fg,sum\n");
+            for (size_t k = 0; k < (size_t)n; k++) fprintf(f, "%lld,%lld,%lld,%lld\n", T.id[k], (long long)vox[k], (long long)fg[k], (long long)sum[k]);
+        }))
+        return false;
+    printf("{\"n_vox\": %lld, \"n_tree\": %lld, \"n_fg\": %lld, \"n_both\": %lld, \"sum_fg\": %lld, \"sum_both\": %lld, \"thr_used\": %d, \"covered\": %.17g, "
+           "\"on_signal\": %.17g, \"covered_intensity\": %.17g, \"nodes\": %lld, \"items\": %lld}\n",
+           (long long)c.n_vox, (long long)c.n_tree, (long long)c.n_fg, (long long)c.n_both, (long long)c.sum_fg, (long long)c.sum_both, (int)c.thr_used, c.covered,
+           c.on_signal, c.covered_intensity, (long long)n, (long long)items);
+    return true;
+}
+
+bool components_file(const ComponentsJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    if (zscale >= 1.f) p.zdist = zscale; // (the z half-width of --subtract-background)
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<int32_t> labels(job.labels.empty() ? 0 : N);
+    std::vector<pnr_component> comps;
+    pnr_components_info ci = {};
+    int rc = pnr_label_components(ctx, &job.opts, &ci, job.labels.empty() ? nullptr : labels.data(), nullptr, 0);
+    if (rc == PNR_OK && !job.per_component.empty() && ci.n_comp > 0) { // "n_comp > cap: call again"
+        comps.resize((size_t)ci.n_comp);
+        rc = pnr_label_components(ctx, &job.opts, &ci, nullptr, comps.data(), (int64_t)comps.size());
+    }
+    if (rc != PNR_OK) return lib_fail("pnr_label_components");
+    if (!job.labels.empty() && !write_file(job.labels, "wb", [&](FILE *f) { fwrite(labels.data(), 4, N, f); })) return false; // (the hosts this builds for are little-endian)
+    if (!job.per_component.empty() && !write_file(job.per_component, "w", [&](FILE *f) {
+            fprintf(f, "id,size,sum,cx,cy,cz,x0,y0,z0,x1,y1,z1,vmax\n");
+            for (size_t k = 0; k < comps.size(); k++) {
+                const pnr_component &c = comps[k];
+                fprintf(f, "%lld,%lld,%lld,%.3f,%.3f,%.3f,%d,%d,%d,%d,%d,%d,%d\n", (long long)(k + 1), (long long)c.size, (long long)c.sum, (double)c.sx / (double)c.size,
+                        (double)c.sy / (double)c.size, (double)c.sz / (double)c.size, c.x0, c.y0, c.z0, c.x1, c.y1, c.z1, c.vmax);
+            }
+        }))
+        return false;
+    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_comp\": %lld, \"n_small\": %lld, \"vox_small\": %lld, \"largest\": %lld, \"thr_used\": %d}\n", (long long)ci.n_vox,
+           (long long)ci.n_fg, (long long)ci.n_comp, (long long)ci.n_small, (long long)ci.vox_small, (long long)ci.largest, (int)ci.thr_used);
+    return true;
+}
+
+bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    SwcTree T;
+    if (!job.at.empty() && !read_swc(job.at, T)) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    p.zdist = zscale; // (also the z half-width of --subtract-background)
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<float> d(job.out.empty() ? 0 : N), at((size_t)T.n());
+    pnr_edt_info ei = {};
+    if (pnr_distance_transform(ctx, &job.opts, &ei, job.out.empty() ? nullptr : d.data(), T.n() ? T.xyz.data() : nullptr, T.n(), T.n() ? at.data() : nullptr) != PNR_OK)
+        return lib_fail("pnr_distance_transform");
+    for (float &v : d) v = sqrtf(v);
+    if (!job.out.empty() && !write_file(job.out, "wb", [&](FILE *f) { fwrite(d.data(), 4, N, f); })) return false; // (the hosts this builds for are little-endian)
+    if (!job.per_node.empty() && !write_file(job.per_node, "w", [&](FILE *f) {
+            fprintf(f, "id,d\n");
+            for (size_t k = 0; k < at.size(); k++) fprintf(f, "%lld,%.9g\n", T.id[k], (double)(at[k] < 0.f ? -1.f : sqrtf(at[k])));
+        }))
+        return false;
+    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_capped\": %lld, \"thr_used\": %d, \"rmax\": %d, \"zdist\": %.17g, \"d_max\": %.17g, \"max_at\": ", (long long)ei.n_vox,
+           (long long)ei.n_fg, (long long)ei.n_capped, (int)ei.thr_used, (int)job.opts.rmax, (double)zscale, (double)sqrtf(ei.d2_max));
+    print_max_at(ei.first_max, st.w, st.h);
+    printf("}\n");
+    return true;
+}
+
+// the sources of --geodesic: the sample points of the tree (step 1, zscale 1), each labelled with the id of its owner node
+static bool geodesic_sources(const std::string &from, const SwcTree &A, std::vector<float> &src, std::vector<int32_t> &label)
+{
+    if (A.n() == 0) {
+        fprintf(stderr, "%s: no nodes\n", from.c_str());
+        return false;
+    }
+    for (long long id : A.id)
+        if (id < 0 || id > 0x7fffffffLL) {
+            fprintf(stderr, "%s: node id %lld is no label (0 .. 2147483647)\n", from.c_str(), id);
+            return false;
+        }
+    int64_t ns = 0;
+    if (pnr_tree_sample(A.xyz.data(), A.parent.data(), A.n(), 1.f, 1.f, nullptr, nullptr, 0, &ns) != PNR_OK) return lib_fail(from.c_str());
+    src.resize((size_t)ns * 3), label.resize((size_t)ns);
+    if (pnr_tree_sample(A.xyz.data(), A.parent.data(), A.n(), 1.f, 1.f, src.data(), label.data(), ns, &ns) != PNR_OK) return lib_fail(from.c_str());
+    for (int32_t &v : label) v = (int32_t)A.id[(size_t)v];
+    return true;
+}
+
+// --paths: every complete path (plen[k] voxels, the first of the `cap` that pvox keeps per target) as a chain of SWC nodes from the
+// target's voxel to the source voxel
+static void write_paths(FILE *f, const SwcTree &B, const std::vector<uint32_t> &d_at, const std::vector<int32_t> &l_at, const std::vector<int32_t> &plen,
+                        const std::vector<int64_t> &pvox, int32_t cap, long long w, long long h)
+{
+    long long next = 1;
+    for (size_t k = 0; k < plen.size(); k++) {
+        const int32_t n = plen[k];
+        if (n <= 0) continue; // (unreached, not finite, or cut at the cap: reported on stderr)
+        fprintf(f, "# path %lld -> %d: %d voxels, cost %u\n", B.id[k], (int)l_at[k], (int)n, (unsigned)d_at[k]);
+        for (int32_t j = 0; j < n; j++) {
+            const long long v = pvox[k * (size_t)cap + (size_t)j];
+            fprintf(f, "%lld 2 %lld %lld %lld 1 %lld\n", next + j, v % w, v / w % h, v / (w * h), j + 1 < n ? next + j + 1 : -1LL);
+        }
+        next += n;
+    }
+}
+
+bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    SwcTree A, B;
+    if (!read_swc(job.from, A) || (!job.to.empty() && !read_swc(job.to, B))) return false;
+    std::vector<float> src;
+    std::vector<int32_t> label;
+    if (!geodesic_sources(job.from, A, src, label)) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    p.zdist = zscale; // (also the z half-width of --subtract-background)
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    const int64_t m = B.n();
+    std::vector<uint32_t> D(job.out.empty() ? 0 : N), d_at((size_t)m);
+    std::vector<int32_t> L(job.out.empty() ? 0 : N), l_at((size_t)m), plen;
+    std::vector<int64_t> pvox;
+    pnr_geo_info gi = {};
+    // the cap of the walks, fixed before the one call: a path visits a voxel at most once, no path has more than PNR_GEO_MAX_PATH voxels, and
+    // all targets together get at most 2^26 entries (512 MB here and on the device)
+    int32_t cap = 0;
+    if (!job.paths.empty() && m) {
+        cap = (int32_t)std::min<size_t>({(size_t)PNR_GEO_MAX_PATH, N, std::max<size_t>(64, ((size_t)1 << 26) / (size_t)m)});
+        plen.resize((size_t)m), pvox.resize((size_t)m * (size_t)cap);
+    }
+    if (pnr_geodesic_distance(ctx, src.data(), label.data(), (int64_t)label.size(), &job.opts, &gi, job.out.empty() ? nullptr : D.data(), job.out.empty() ? nullptr : L.data(),
+                              m ? B.xyz.data() : nullptr, m, m ? d_at.data() : nullptr, m ? l_at.data() : nullptr, cap, cap ? plen.data() : nullptr,
+                              cap ? pvox.data() : nullptr) != PNR_OK)
+        return lib_fail("pnr_geodesic_distance");
+    long long cut = 0;
+    for (int32_t n : plen) cut += n < 0;
+    if (cut) fprintf(stderr, "--paths: %lld path(s) of more than %d voxels are left out of %s\n", cut, (int)cap, job.paths.c_str());
+    if (!job.out.empty()) { // (the hosts this builds for are little-endian)
+        if (!write_file(job.out + "_d.raw", "wb", [&](FILE *f) { fwrite(D.data(), 4, N, f); })) return false;
+        if (!write_file(job.out + "_label.raw", "wb", [&](FILE *f) { fwrite(L.data(), 4, N, f); })) return false;
+    }
+    if (!job.per_node.empty() && !write_file(job.per_node, "w", [&](FILE *f) {
+            fprintf(f, "id,d,label\n");
+            for (size_t k = 0; k < (size_t)m; k++) fprintf(f, "%lld,%lld,%d\n", B.id[k], d_at[k] == 0xffffffffu ? -1LL : (long long)d_at[k], (int)l_at[k]);
+        }))
+        return false;
+    if (!job.paths.empty() && !write_file(job.paths, "w", [&](FILE *f) { write_paths(f, B, d_at, l_at, plen, pvox, cap, st.w, st.h); })) return false;
+    printf("{\"n_vox\": %lld, \"n_pass\": %lld, \"n_reached\": %lld, \"n_src\": %lld, \"n_src_dropped\": %lld, \"thr_used\": %d, \"dmax\": %u, \"zdist\": %.17g, \"d_max\": %u, "
+           "\"len_max\": %.17g, \"max_at\": ",
+           (long long)gi.n_vox, (long long)gi.n_pass, (long long)gi.n_reached, (long long)gi.n_src, (long long)gi.n_src_dropped, (int)gi.thr_used, (unsigned)job.opts.dmax,
+           (double)zscale, (unsigned)gi.d_max, (double)gi.d_max / 64.0);
+    print_max_at(gi.first_max, st.w, st.h);
+    printf(", \"rounds\": %d}\n", (int)gi.rounds);
+    return true;
+}
+
+} // namespace advantra
