@@ -677,6 +677,86 @@ int pnr_geodesic_distance(pnr_ctx *ctx, const float *src_xyz, const int32_t *src
                           const float *at_xyz /* m x 3, nullable when m == 0 */, int64_t m, uint32_t *d_at, int32_t *label_at /* m, nullable */,
                           int32_t path_cap /* 0..PNR_GEO_MAX_PATH */, int32_t *path_len /* m */, int64_t *path_vox /* m x path_cap */);
 
+/* Joining the traced forest along the signal (beyond the reference): the composition of the geodesic distance and the join.  pnr_join_trees
+ * bridges fragments whose closest nodes lie within a straight-line gap and never looks at the image in between; this takes the forest and
+ * the stack and returns the unique minimum spanning forest of the fragments under gray-weighted path cost, every bridge as the voxel path
+ * it follows.  One geodesic pass suffices (Mehlhorn 1988): a minimum spanning tree of the graph whose edges are the places where the
+ * geodesic Voronoi cells of the trees touch, weighted D(p) + wt(p, q) + D(q), is one of the complete graph of pairwise geodesic distances.
+ * THE RULE (the contract; tests restate it in numpy).  Exact integer arithmetic on top of the geodesic rule above; every output bit is fixed.
+ *   Input.  n nodes xyz (f32, voxel indices as in pnr_node) and parent[i] in [-1, n), any negative value = none: the layout of
+ *     pnr_join_trees.  PNR_E_ARG: a cycle, a parent >= n, a coordinate that is not finite.  The context's traced u8 volume V,
+ *     zd = params.zdist.  Options {thr, limit, step, cost}; opts = NULL = {0, 0, 1, NULL}; limit == 0: no limit; thr and cost are
+ *     those of pnr_geo_opts.
+ *   Trees and sources.  The input trees are the components of the parent links; the label of a tree is its smallest node index.  The
+ *     sources are the sample points of pnr_tree_sample(xyz, parent, n, zscale = 1, step), in its order, each labelled with the tree of
+ *     its owner node (step = 0: the nodes only).  D and L are the outputs of the geodesic rule for these sources with dmax = limit, or
+ *     2^31 - 1 when limit is 0 or above 2^31 - 1.  A tree all of whose sources are dropped or share their centre voxel with a source of
+ *     a smaller label takes no part, is never bridged and is counted in n_trees_lost.
+ *   Meet edges.  For every voxel p and every offset o among the last 13 of THE OFFSET ORDER (indices 13..25: q = p + o has the larger
+ *     linear index, every unordered pair of 26-neighbours occurs once): if both voxels are reached and L(p) != L(q),
+ *     W(p, o) = D(p) + wt(p, q) + D(q), a u64 (it can exceed 2^32), wt the edge weight of the geodesic rule.  The edge exists iff
+ *     limit == 0 or W <= limit (W >= D(p), D(q): capping D at limit drops no edge that the limit keeps).  Its key is the triple
+ *     (W, p, o - 13), compared lexicographically; no two edges share a key.
+ *   Bridges.  The edges of the UNIQUE minimum spanning forest of the graph whose vertices are the trees and whose edges are the meet
+ *     edges, under that key order: what Kruskal's algorithm over the ascending keys gives, and what Boruvka's rounds give in any order
+ *     -- independent of tiling, launch cuts, round structure and atomic arrival order.  Reported in ascending key order.
+ *   Path and attachment of a bridge (W, p, o).  path(p) and path(q) are the walks along pred() of the geodesic rule; they end on source
+ *     voxels s_a, s_b of labels L(p), L(q).  The bridge's voxel chain is reverse(path(p)) followed by path(q): s_a .. p, q .. s_b, at
+ *     least 2 voxels.  Node a is the owner of the first sample point, in sample order, of tree L(p) whose centre voxel is s_a; node b
+ *     likewise on s_b.
+ *   Expansion (pnr_join_expand, pure host).  The k interior voxels of a chain (all but s_a and s_b) become new nodes n, n + 1, ...,
+ *     appended bridge after bridge in bridge order, each at its voxel's integer coordinates, each the child of the previous node of the
+ *     chain, the first one of a.  The bridge handed to the re-rooting is (the last new node, b), or (a, b) when k = 0, as
+ *     pnr_bridge {lo = the smaller index, hi, d = W / 64}.  A negative parent is written as -1.  Re-rooting, numbering and order are
+ *     pnr_join_reroot on the n + sum(k) nodes, exactly as for pnr_join_trees.
+ *   Summary pnr_geojoin_info (exact): n_trees_in, n_trees_lost, n_trees_out (= n_trees_in - n_bridges), n_bridges, n_inserted (sum(k)),
+ *     n_src / n_src_dropped (the geodesic's), w_max (the largest bridge W, 0 without one), thr_used, rounds (Boruvka rounds of this
+ *     call: scheduling, not part of the rule).
+ * pnr_geodesic_bridges: the geodesic pass, then Boruvka's rounds on the device over the settled keys, which never cross to the host:
+ *   per round two sweeps of the key volume give every current component its minimum meet edge under the full key, the host unites; a
+ *   component without an edge within the limit leaves the search.  The bridges' p and q voxels then go through the path stage of the
+ *   geodesic call.  bridges_out (cap_bridges entries) and path_vox (cap_path entries: the chains one after the other, bridge k at
+ *   path_off, path_len voxels) are nullable; *n_bridges > cap_bridges or *n_path > cap_path: call again, as pnr_join_trees.
+ *   PNR_E_ARG also for: thr outside -1..255, step < 0 or not finite, a cost entry of 0, n outside 1..PNR_JOIN_MAX_N, more than 2^28
+ *   sample points, N above 2^32 - 2, an extent of 2^24 or more (voxel coordinates must be exact in f32), and a bridge whose walk to its
+ *   tree has more than PNR_GEO_MAX_PATH voxels (the message says that it was cut).  No volume in the context: PNR_E_STATE.  The call
+ *   never writes V (also not a borrowed one), leaves the pipeline state alone, runs on the context's stream, uses 64-bit voxel indices
+ *   and frees every device buffer before it returns.  Device memory: that of the geodesic call without d_out / label_out, 20 bytes per
+ *   tree during the rounds, then per bridge 2 (24 + 8 * 256) bytes, and 8 path_cap more for every walk of more than 256 voxels,
+ *   path_cap = min(PNR_GEO_MAX_PATH, w_max / the smallest edge + 2); 20 bytes per source.
+ * pnr_join_expand: the expansion alone, pure host, no context; the grid w x h x l turns a voxel into coordinates.  *n_nodes = n + sum(k);
+ *   xyz_out, parent_out (cap_nodes entries), bridge_of (cap_nodes - n entries: for every new node its bridge) are nullable and written
+ *   only when *n_nodes <= cap_nodes: else call again.  join_out (nb entries, nullable): the bridges for pnr_join_reroot.  PNR_E_ARG: a
+ *   bridge node outside [0, n) or a == b, a path outside [0, n_path) or of fewer than 2 voxels, a voxel outside the grid, more than
+ *   PNR_JOIN_MAX_N nodes in all.
+ * Kernel times: pnr_get_kernel_ms group "geojoin" = "geojoin_meet_w" + "geojoin_meet_e"; the relaxation counts under "geodesic".
+ *   pnr_get_option "geojoin_rounds": the rounds of the last call.  pnr_set_option "geojoin_tiles_per_launch" (0 = automatic) cuts the
+ *   launches of a sweep and changes no bit. */
+typedef struct pnr_geojoin_opts {
+    int32_t thr;
+    uint64_t limit;
+    float step;
+    const uint16_t *cost;
+} pnr_geojoin_opts; /* NULL = {0, 0, 1, NULL} */
+typedef struct pnr_geo_bridge {
+    int32_t a, b;
+    int64_t p;
+    int32_t o, path_len;
+    uint64_t w;
+    int64_t path_off;
+} pnr_geo_bridge;
+typedef struct pnr_geojoin_info {
+    int64_t n_trees_in, n_trees_lost, n_trees_out, n_bridges, n_inserted, n_src, n_src_dropped;
+    uint64_t w_max;
+    int32_t thr_used, rounds;
+} pnr_geojoin_info;
+int pnr_geodesic_bridges(pnr_ctx *ctx, const float *xyz /* n x 3 */, const int32_t *parent /* n */, int64_t n, const pnr_geojoin_opts *opts /* NULL = defaults */,
+                         pnr_geojoin_info *info /* nullable */, pnr_geo_bridge *bridges_out, int64_t cap_bridges, int64_t *n_bridges, int64_t *path_vox,
+                         int64_t cap_path, int64_t *n_path);
+int pnr_join_expand(const float *xyz /* n x 3 */, const int32_t *parent /* n */, int64_t n, const pnr_geo_bridge *bridges, int64_t nb, const int64_t *path_vox,
+                    int64_t n_path, int64_t w, int64_t h, int64_t l, float *xyz_out, int32_t *parent_out, int32_t *bridge_of, int64_t cap_nodes, int64_t *n_nodes,
+                    pnr_bridge *join_out /* nb */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -704,6 +784,7 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   join_split (0 = automatic), join_pairs_per_launch (0 = automatic: 2^34): the same for the targets and the (point, target) pairs of pnr_nearest_other / pnr_join_trees (the same bits) |
  *   render_piece (0 = automatic: 16) xy voxels of a segment's axis per work item of pnr_render_tree / pnr_tree_coverage | render_box (0 = automatic: 2^15) voxels per item, larger boxes are cut |
  *   render_items_per_launch (0 = automatic: 2^18) items per launch (the same bits -- tests reach piece, box and launch boundaries with them on small inputs) |
+ *   geo_iters, geo_tiles_per_launch (0 = automatic) of pnr_geodesic_distance and geojoin_tiles_per_launch (0 = automatic: 2^20) tiles per launch of a sweep of pnr_geodesic_bridges (the same bits) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
  *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
@@ -713,7 +794,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e").  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -17,6 +17,7 @@
 #include "components.h"
 #include "edt.h"
 #include "geodesic.h"
+#include "geojoin.h"
 #include "../host/stack_io.h"
 #include <algorithm>
 #include <cfloat>
@@ -602,6 +603,46 @@ int pnr_join_trees(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t 
     if (n_trees_in) *n_trees_in = trees_in;
     if (n_trees_out) *n_trees_out = trees_out;
     return PNR_OK;
+}
+
+// ---- joining the forest along the signal (geojoin.hip): arguments first, then the state; the pipeline state is neither needed nor touched ----
+int pnr_geodesic_bridges(pnr_ctx *c, const float *xyz, const int32_t *parent, int64_t n, const pnr_geojoin_opts *opts, pnr_geojoin_info *info, pnr_geo_bridge *bridges_out,
+                         int64_t cap_bridges, int64_t *n_bridges, int64_t *path_vox, int64_t cap_path, int64_t *n_path)
+{
+    static const char *who = "pnr_geodesic_bridges";
+    PNR_REQUIRE(c && n_bridges && n_path, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(n >= 1 && n <= PNR_JOIN_MAX_N && xyz && parent, PNR_E_ARG, "%s: n = %lld nodes (1 to 2^22) need xyz and parent", who, (long long)n);
+    const pnr_geojoin_opts o = opts ? *opts : pnr_geojoin_opts{0, 0, 1.f, nullptr};
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "%s: thr = %d outside [-1, 255]", who, o.thr);
+    PNR_REQUIRE(std::isfinite(o.step) && o.step >= 0.f, PNR_E_ARG, "%s: step = %g must not be negative", who, (double)o.step);
+    for (int v = 0; o.cost && v < 256; v++) PNR_REQUIRE(o.cost[v] >= 1, PNR_E_ARG, "%s: cost[%d] = 0, every entry is at least 1", who, v);
+    PNR_REQUIRE(cap_bridges >= 0 && (cap_bridges == 0 || bridges_out), PNR_E_ARG, "%s: cap_bridges = %lld needs bridges_out", who, (long long)cap_bridges);
+    PNR_REQUIRE(cap_path >= 0 && (cap_path == 0 || path_vox), PNR_E_ARG, "%s: cap_path = %lld needs path_vox", who, (long long)cap_path);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "%s: no volume set", who);
+    PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
+    PNR_HIP(hipSetDevice(c->device));
+    std::vector<pnr_geo_bridge> bridges;
+    std::vector<int64_t> chain;
+    const int rc = pnr_geojoin_run(c, xyz, parent, n, o, info, bridges, chain);
+    if (rc) return rc;
+    *n_bridges = (int64_t)bridges.size();
+    *n_path = (int64_t)chain.size();
+    if (bridges_out) std::memcpy(bridges_out, bridges.data(), sizeof(pnr_geo_bridge) * (size_t)std::min<int64_t>(cap_bridges, *n_bridges));
+    if (path_vox) std::memcpy(path_vox, chain.data(), sizeof(int64_t) * (size_t)std::min<int64_t>(cap_path, *n_path));
+    return PNR_OK;
+}
+
+int pnr_join_expand(const float *xyz, const int32_t *parent, int64_t n, const pnr_geo_bridge *bridges, int64_t nb, const int64_t *path_vox, int64_t n_path, int64_t w, int64_t h,
+                    int64_t l, float *xyz_out, int32_t *parent_out, int32_t *bridge_of, int64_t cap_nodes, int64_t *n_nodes, pnr_bridge *join_out)
+{
+    static const char *who = "pnr_join_expand";
+    PNR_REQUIRE(n >= 1 && n <= PNR_JOIN_MAX_N && xyz && parent && n_nodes, PNR_E_ARG, "%s: n = %lld nodes (1 to 2^22) need xyz, parent and n_nodes", who, (long long)n);
+    PNR_REQUIRE(nb >= 0 && nb < n && (nb == 0 || bridges), PNR_E_ARG, "%s: %lld bridges (0 to n - 1) need bridges", who, (long long)nb);
+    PNR_REQUIRE(n_path >= 0 && (nb == 0 || path_vox) && cap_nodes >= 0, PNR_E_ARG, "%s: %lld bridges need path_vox", who, (long long)nb);
+    PNR_REQUIRE(w >= 1 && h >= 1 && l >= 1 && w < (1 << 24) && h < (1 << 24) && l < (1 << 24), PNR_E_ARG, "%s: the grid %lld x %lld x %lld needs sides from 1 and below 2^24", who,
+                (long long)w, (long long)h, (long long)l);
+    for (int64_t i = 0; i < n; i++) PNR_REQUIRE(parent[i] < n, PNR_E_ARG, "%s: parent[%lld] = %d outside [-1, %lld)", who, (long long)i, parent[i], (long long)n);
+    return pnr_geojoin_expand(xyz, parent, n, bridges, nb, path_vox, n_path, w, h, l, xyz_out, parent_out, bridge_of, cap_nodes, n_nodes, join_out);
 }
 
 // ---- rendering the tree (render.hip): arguments first; pnr_render_tree needs no volume, neither call touches the pipeline state ----
@@ -1309,6 +1350,7 @@ const OptEntry OPTS[] = {
     {"render_piece", &pnr::Options::render_piece, nullptr, 0, 1 << 20}, {"render_box", nullptr, &pnr::Options::render_box, 0, 1 << 24},
     {"render_items_per_launch", nullptr, &pnr::Options::render_items_per_launch, 0, 1 << 24},
     {"geo_iters", &pnr::Options::geo_iters, nullptr, 0, 1 << 16}, {"geo_tiles_per_launch", &pnr::Options::geo_tiles_per_launch, nullptr, 0, 1 << 24},
+    {"geojoin_tiles_per_launch", &pnr::Options::geojoin_tiles_per_launch, nullptr, 0, 1 << 24},
 };
 } // namespace
 
@@ -1338,6 +1380,7 @@ int pnr_get_option(pnr_ctx *c, const char *key, int64_t *value)
     if (std::strcmp(key, "join_rounds") == 0) { *value = c->join_rounds; return PNR_OK; }
     if (std::strcmp(key, "geo_rounds") == 0) { *value = c->geo_rounds; return PNR_OK; }
     if (std::strcmp(key, "geo_visits") == 0) { *value = c->geo_visits; return PNR_OK; }
+    if (std::strcmp(key, "geojoin_rounds") == 0) { *value = c->geojoin_rounds; return PNR_OK; }
     if (std::strcmp(key, "render_items") == 0) { *value = c->render_items; return PNR_OK; }
     if (std::strcmp(key, "render_pairs") == 0) { *value = c->render_pairs; return PNR_OK; }
     if (std::strcmp(key, "frangi_recomputes") == 0) { *value = c->frangi_recomputes; return PNR_OK; } // exact Frangi re-runs so far (one pnr_frangi of GPU time each)
@@ -1525,6 +1568,15 @@ int pnr_get_kernel_ms(pnr_ctx *c, const char *group, double *ms, int64_t *launch
             *ms += a;
             if (launches) *launches += la;
         }
+        return PNR_OK;
+    }
+    if (std::strcmp(group, "geojoin") == 0) { // the two passes of a Boruvka round (geojoin.hip)
+        double a = 0, b = 0;
+        int64_t la = 0, lb = 0;
+        pnr_get_kernel_ms(c, "geojoin_meet_w", &a, &la);
+        pnr_get_kernel_ms(c, "geojoin_meet_e", &b, &lb);
+        *ms = a + b;
+        if (launches) *launches = la + lb;
         return PNR_OK;
     }
     auto it = c->timers.find(group);

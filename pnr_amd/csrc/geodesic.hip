@@ -21,7 +21,10 @@
 //   geo_stats    n_pass, n_reached and the maximum of (D << 32) | ~index over the reached voxels (one 64-bit atomic maximum per
 //                work-group): the largest D and the smallest index that attains it.
 //   geo_split    D and L from the keys where the caller asks for the volumes.
-//   geo_sample / geo_paths   a thread per target: the key at its centre voxel; the walk along pred() of at most path_cap voxels.
+//   geo_sample / geo_paths   a thread per target: the key at its centre voxel; the walk along pred() of at most path_cap voxels
+//                (pnr_geo_targets: the stage with its own buffers, after the statistics and the split).
+//   hook         a caller's function that runs once the keys have settled (geodesic.h): it sees the device keys, may run the target
+//                stage itself and may replace the targets of the call (geojoin.hip: the bridges between the sources' trees).
 #include "geodesic.h"
 #include "call.h"
 #include "volume.h"
@@ -45,12 +48,8 @@ constexpr int AUTO_TILES = 1 << 20;   // tiles per launch (option geo_tiles_per_
 static_assert(RTPB % 64 == 0 && RTPB <= 1024 && GEO_TPB % 64 == 0, "whole waves");
 static_assert(GEO_TX >= 2 && GEO_TY >= 2 && GEO_TZ >= 2, "a voxel is on at most one of the two faces of an axis");
 
-struct Dims {
-    int w, h, l, ntx, nty, ntz;
-};
-struct Lens {
-    unsigned v[27]; // by (dz + 1) 9 + (dy + 1) 3 + (dx + 1): the offset order with the centre (0) in the middle
-};
+using Dims = pnr::GeoDims;
+using Lens = pnr::GeoLens;
 
 __device__ inline bool finite3(float x, float y, float z)
 {
@@ -301,8 +300,42 @@ __global__ __launch_bounds__(GEO_TPB) void geo_paths(PathArgs a)
 
 } // namespace
 
-int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const pnr_geo_call &g)
+int pnr_geo_targets(pnr_ctx *c, const char *who, const pnr_geo_keys &k, const pnr_geo_call &g)
 {
+    if (g.m <= 0) return PNR_OK;
+    const int64_t m_path = g.path_cap > 0 ? g.m - g.m_no_path : 0;
+    const bool paths = m_path > 0;
+    pnr::CallBuf buf; // (freed when the stage returns)
+    const auto d_axyz = buf.add<float>((size_t)g.m * 3);
+    const auto d_dat = buf.add<unsigned>((size_t)g.m);
+    const auto d_lat = buf.add<int>((size_t)g.m);
+    const auto d_plen = buf.add<int>(paths ? (size_t)m_path : 0);
+    const auto d_pvox = buf.add<long long>(paths ? (size_t)m_path * (size_t)g.path_cap : 0);
+    const int rc = buf.alloc(who);
+    if (rc) return rc;
+    pnr::Call call(c, who);
+    call.up(d_axyz, g.at_xyz);
+    if (g.d_at || g.label_at) {
+        c->tic();
+        call.launch(geo_sample, dim3((unsigned)((g.m + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB), k.key, (const float *)d_axyz.get(), (long long)g.m, k.d, d_dat.get(), d_lat.get());
+        c->toc("geodesic_sample", 1);
+        if (g.d_at) call.down(g.d_at, d_dat);
+        if (g.label_at) call.down(g.label_at, d_lat);
+    }
+    if (paths) {
+        c->tic();
+        call.launch(geo_paths, dim3((unsigned)((m_path + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB),
+                    PathArgs{k.V, k.key, k.ctab, (const float *)d_axyz.get(), (long long)m_path, k.d, g.path_cap, d_plen.get(), d_pvox.get(), k.len});
+        c->toc("geodesic_paths", 1);
+        call.down(g.path_len, d_plen);
+        call.down(g.path_vox, d_pvox);
+    }
+    return call.finish();
+}
+
+int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const pnr_geo_call &g_in)
+{
+    pnr_geo_call g = g_in; // (the hook may replace the targets)
     const int64_t N = c->N;
     const Dims d{(int)c->w, (int)c->h, (int)c->l, (int)((c->w + GEO_TX - 1) / GEO_TX), (int)((c->h + GEO_TY - 1) / GEO_TY), (int)((c->l + GEO_TZ - 1) / GEO_TZ)};
     const int64_t tiles = (int64_t)d.ntx * d.nty * d.ntz, vblocks = (N + GEO_TPB - 1) / GEO_TPB;
@@ -322,7 +355,7 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
         lmax = std::max(lmax, len.v[k]);
     }
     PNR_REQUIRE((uint64_t)lmax * 2 * cmax <= 0x7fffffffull, PNR_E_ARG, "%s: the largest edge %u * 2 * %u is above 2^31 - 1 (zdist = %g)", who, lmax, cmax, (double)zd);
-    const bool paths = g.m > 0 && g.path_cap > 0, split_d = g.d_out != nullptr, split_l = g.label_out != nullptr;
+    const bool split_d = g.d_out != nullptr, split_l = g.label_out != nullptr;
     pnr::CallBuf buf; // (freed when the call returns)
     const auto d_key = buf.add<u64>((size_t)N);
     const auto d_flag = buf.add<int>((size_t)tiles * 2), d_list = buf.add<int>((size_t)tiles);
@@ -332,11 +365,6 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
     const auto d_slab = buf.add<int>(g.src_label ? (size_t)g.n_src : 0);
     const auto d_dv = buf.add<unsigned>(split_d ? (size_t)N : 0);
     const auto d_lv = buf.add<int>(split_l ? (size_t)N : 0);
-    const auto d_axyz = buf.add<float>((size_t)g.m * 3);
-    const auto d_dat = buf.add<unsigned>((size_t)g.m);
-    const auto d_lat = buf.add<int>((size_t)g.m);
-    const auto d_plen = buf.add<int>(paths ? (size_t)g.m : 0);
-    const auto d_pvox = buf.add<long long>(paths ? (size_t)g.m * (size_t)g.path_cap : 0);
     int rc = buf.alloc(who);
     if (rc) return rc;
     pnr::PinBuf<u64> h_count;
@@ -387,6 +415,8 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
     }
     if (!call.ok()) return call.finish();
     c->geo_rounds = rounds, c->geo_visits = visits;
+    const pnr_geo_keys keys{c->d_img, d_key.get(), d_ctab.get(), t, d, len};
+    if (g.hook && (rc = g.hook(g.hook_user, c, who, keys, g))) return rc;
     u64 st[3] = {0, 0, 0}, dropped = 0;
     call.down(&dropped, d_drop);
     if (g.info) {
@@ -404,24 +434,9 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
         if (split_d) call.down(g.d_out, d_dv);
         if (split_l) call.down(g.label_out, d_lv);
     }
-    if (g.m > 0) {
-        call.up(d_axyz, g.at_xyz);
-        if (g.d_at || g.label_at) {
-            c->tic();
-            call.launch(geo_sample, dim3((unsigned)((g.m + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB), (const u64 *)d_key.get(), (const float *)d_axyz.get(), (long long)g.m, d,
-                        d_dat.get(), d_lat.get());
-            c->toc("geodesic_sample", 1);
-            if (g.d_at) call.down(g.d_at, d_dat);
-            if (g.label_at) call.down(g.label_at, d_lat);
-        }
-        if (paths) {
-            c->tic();
-            call.launch(geo_paths, dim3((unsigned)((g.m + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB),
-                        PathArgs{c->d_img, d_key.get(), (const uint16_t *)d_ctab.get(), (const float *)d_axyz.get(), (long long)g.m, d, g.path_cap, d_plen.get(), d_pvox.get(), len});
-            c->toc("geodesic_paths", 1);
-            call.down(g.path_len, d_plen);
-            call.down(g.path_vox, d_pvox);
-        }
+    if ((rc = pnr_geo_targets(c, who, keys, g))) { // (the same stream: behind the statistics and the split)
+        (void)hipStreamSynchronize(c->stream); // (the downloads above write into this frame)
+        return rc;
     }
     if ((rc = call.finish())) return rc;
     if (g.info) {

@@ -1,6 +1,9 @@
 // join.h -- the traced forest joined into one tree (join.hip), behind pnr_nearest_other / pnr_join_trees / pnr_join_reroot.
 #pragma once
 #include "call.h"
+#include <numeric>
+#include <utility>
+#include <vector>
 
 namespace pnr {
 // The nearest-other search of one call (JoinRule under the pair minimum of pairmin.h): the device buffers (one CallBuf, freed with the
@@ -20,6 +23,25 @@ class JoinSearch {
 public:
     int begin(pnr_ctx *c, const float *xyz, int64_t n, const char *who);
     int run(const int32_t *label, bool root, float *d_out, int32_t *j_out, const char *who);
+};
+
+// disjoint sets over 0 .. n - 1 (the host side of the Boruvka rounds of join.hip and geojoin.hip)
+struct UnionFind {
+    std::vector<int32_t> up;
+    explicit UnionFind(int64_t n) : up((size_t)n) { std::iota(up.begin(), up.end(), 0); }
+    int32_t find(int32_t a)
+    {
+        while (up[(size_t)a] != a) a = up[(size_t)a] = up[(size_t)up[(size_t)a]];
+        return a;
+    }
+    bool unite(int32_t a, int32_t b) // the smaller index stays the representative
+    {
+        a = find(a), b = find(b);
+        if (a == b) return false;
+        if (a > b) std::swap(a, b);
+        up[(size_t)b] = a;
+        return true;
+    }
 };
 
 // parent[i] in [-1, n) (any negative value = none) without a cycle, or PNR_E_ARG; comp_out[i] (nullable) = the smallest node index of

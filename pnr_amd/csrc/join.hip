@@ -78,23 +78,6 @@ int JoinSearch::run(const int32_t *label, bool root, float *d_out, int32_t *j_ou
 
 // ---- the host side ----
 namespace {
-struct UnionFind {
-    std::vector<int32_t> up;
-    explicit UnionFind(int64_t n) : up((size_t)n) { std::iota(up.begin(), up.end(), 0); }
-    int32_t find(int32_t a)
-    {
-        while (up[(size_t)a] != a) a = up[(size_t)a] = up[(size_t)up[(size_t)a]];
-        return a;
-    }
-    bool unite(int32_t a, int32_t b) // the smaller index stays the representative
-    {
-        a = find(a), b = find(b);
-        if (a == b) return false;
-        if (a > b) std::swap(a, b);
-        up[(size_t)b] = a;
-        return true;
-    }
-};
 // the parent links as a union-find; a link inside one set closes a cycle (every node has at most one link of its own)
 int link_trees(const int32_t *parent, int64_t n, UnionFind &uf, const char *who)
 {

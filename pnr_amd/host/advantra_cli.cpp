@@ -23,6 +23,10 @@
 //   --join GAP [--join-root soma|ID] [--join-keep-largest]: while tracing, the reconstructed forest is joined into one tree on the GPU
 //   (pnr_join_trees with zscale = zdist; GAP in xy voxels, 0 = any distance), re-rooted (default: at the first soma node, if any; ID = a
 //   node id of the file without --join) and written in tree order; the comment block gains #join=gap:G,bridges:K,trees:T0->T1.
+//   --join-geodesic D [--join-threshold T] [--join-root soma|ID] [--join-keep-largest] in the place of --join GAP: the forest is joined along
+//   the signal (pnr_geodesic_bridges: the minimum spanning forest of the fragments under gray-weighted path cost, no bridge heavier than D,
+//   0 = no limit), the bridges' voxels become nodes; the comment block gains #join=geodesic:D,thr:T,bridges:K,trees:T0->T1,inserted:M.
+//   --join-swc IN.swc OUT.swc --join-geodesic D -i stack [--zscale Z] [--join-threshold T]: the same on a file and a stack; one JSON line.
 //   --join-swc IN.swc OUT.swc [--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]: the same on a file (device -g); one JSON
 //   line {"nodes","trees_in","trees_out","bridges","longest_bridge","rounds"}.
 //   --render-swc IN.swc -i stack [--mask OUT] [--residual OUT] [--per-node FILE.csv] [--zscale Z] [--radius-scale S] [--radius-add A]
@@ -49,6 +53,7 @@
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -125,6 +130,9 @@ int main(int argc, char **argv)
     bool zscale_flag = false, join_flag = false, join_root_soma = false, join_given = false, join_keep_largest = false;
     float join_gap = 0.f;
     long join_root_id = 0;
+    bool join_geodesic = false, join_thr_flag = false;
+    unsigned long long join_limit = 0;
+    int join_thr = 0;
     std::string join_in, join_out;
     advantra::RenderJob render;
     std::string mask_out, residual_out;
@@ -287,6 +295,22 @@ int main(int argc, char **argv)
             join_gap = v;
             continue;
         }
+        if (!strcmp(argv[i], "--join-geodesic")) {
+            const char *txt = i + 1 < argc ? argv[++i] : "";
+            char *end = nullptr;
+            errno = 0;
+            join_limit = strtoull(txt, &end, 10);
+            if (!*txt || *txt == '-' || *end || errno) { fprintf(stderr, "--join-geodesic D: the largest bridge weight, an integer, 0 (no limit) or more\n"); return 1; }
+            join_geodesic = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--join-threshold")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--join-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+            join_thr = (int)v;
+            join_thr_flag = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--join-root")) {
             const char *txt = i + 1 < argc ? argv[++i] : "";
             long v = 0;
@@ -404,14 +428,16 @@ int main(int argc, char **argv)
         return 1;
     }
     if (render_flag && !rendering) { fprintf(stderr, "--radius-scale / --radius-add / --coverage-threshold need --render-swc IN.swc\n"); return 1; }
-    if (join_flag && !join_given && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP or --join-swc IN.swc OUT.swc\n"); return 1; }
+    if (join_geodesic && join_given) { fprintf(stderr, "--join GAP and --join-geodesic D: one or the other\n"); return 1; }
+    if (join_thr_flag && !join_geodesic) { fprintf(stderr, "--join-threshold needs --join-geodesic D\n"); return 1; }
+    if (join_flag && !join_given && !join_geodesic && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP, --join-geodesic D or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
     if ((comp_flag && !components) || (thr_flag && !components && !edt && !geo)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt or --geodesic)\n"); return 1; }
     if (edt_flag && !edt) { fprintf(stderr, "--edt-max / --edt-out / --at need --edt -i stack\n"); return 1; }
     if (geo_flag && !geo) { fprintf(stderr, "--from / --to / --paths / --geo-max / --geo-out need --geodesic -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
     if (geo) {
-        if (edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || !paras.empty()) {
+        if (edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic || !paras.empty()) {
             fprintf(stderr, "--geodesic: not with a tracing run (-p), --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle or --measure-radius\n");
             return 1;
         }
@@ -424,7 +450,7 @@ int main(int argc, char **argv)
         return advantra::geodesic_file(geo_job, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, device) ? 0 : 1;
     }
     if (edt) {
-        if (components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || !paras.empty()) {
+        if (components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic || !paras.empty()) {
             fprintf(stderr, "--edt: not with a tracing run (-p), --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle or --measure-radius\n");
             return 1;
         }
@@ -451,8 +477,15 @@ int main(int argc, char **argv)
     }
     if ((!mask_out.empty() || !residual_out.empty() || coverage) && (distance || !join_in.empty() || info)) { fprintf(stderr, "--mask / --residual / --coverage need a tracing run or --render-swc IN.swc\n"); return 1; }
     S0.mask_out = mask_out, S0.residual_out = residual_out, S0.coverage = coverage;
+    if (!join_in.empty() && join_geodesic) {
+        if (infiles.empty()) { fprintf(stderr, "--join-swc --join-geodesic needs -i <stack>\n"); return 1; }
+        if (zscale_flag && dist_opts.zscale < 1.f) { fprintf(stderr, "--join-geodesic: --zscale Z: a number, 1 or more\n"); return 1; }
+        const pnr_geojoin_opts go = {join_thr, join_limit, 1.f, nullptr};
+        return advantra::join_swc_geodesic_file(join_in, join_out, go, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, join_root_id, join_keep_largest, device) ? 0 : 1;
+    }
     if (!join_in.empty()) return advantra::join_swc_file(join_in, join_out, join_gap, dist_opts.zscale, join_root_id, join_keep_largest, device) ? 0 : 1;
     if (join_given) S0.join = true, S0.join_gap = join_gap, S0.join_root_id = join_root_id, S0.join_keep_largest = join_keep_largest;
+    if (join_geodesic) S0.join = S0.join_geodesic = true, S0.join_limit = join_limit, S0.join_thr = join_thr, S0.join_root_id = join_root_id, S0.join_keep_largest = join_keep_largest;
     if (distance) return advantra::print_tree_distance(dist_a, dist_b, dist_opts, device, per_node) ? 0 : 1;
     if (info) {
         if (infiles.empty()) { fprintf(stderr, "--info needs -i <inimg_file>\n"); return 1; }

@@ -57,6 +57,12 @@ void print_flags()
     printf("  --join-root soma|ID       the root: the first soma node if there is one (default), or the node with this id in the file without --join\n");
     printf("  --join-keep-largest       write only the largest component (the root's, if a root is given)\n");
     printf("--join-swc IN.swc OUT.swc the same on an SWC file ([--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]); one JSON line\n");
+    printf("--join-geodesic D         in the place of --join GAP: join the traced forest along the signal on the GPU -- the minimum spanning forest of the\n");
+    printf("                          fragments under gray-weighted path cost; no bridge that weighs more than D is made (0: no limit; 64 is one xy voxel\n");
+    printf("                          at cost 1); the bridges' voxels become nodes ([--join-threshold T] [--join-root soma|ID] [--join-keep-largest])\n");
+    printf("  --join-threshold T        voxels below T are impassable, 0..255, -1: the stack's mean (default 0: every voxel is passable)\n");
+    printf("--join-swc IN.swc OUT.swc --join-geodesic D -i stack   the same on an SWC file and a stack (the volume setup of --geodesic; [--zscale Z]\n");
+    printf("                          [--join-threshold T] [--join-root ID] [--join-keep-largest]); one JSON line with the summary\n");
     printf("--render-swc IN.swc       render an SWC file into the stack given with -i (the same volume setup as tracing) on the GPU; one JSON line with\n");
     printf("                          the coverage counts: how much of the foreground the tree covers, how much of the tree lies on signal\n");
     printf("  --mask OUT                write the mask (255 under the tree) as a multi-page 8-bit TIFF, or bare bytes for a .raw name\n");
@@ -179,7 +185,10 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
     if (settings().despeckle && cover)
         c << "\n#despeckle=min:" << settings().despeckle_opts.min_size << ",thr:" << cover->despeckle_thr << ",conn:" << settings().despeckle_opts.connectivity
           << ",removed:" << cover->despeckle_removed << ",voxels:" << cover->despeckle_voxels;
-    if (join) c << "\n#join=gap:" << f32_text(settings().join_gap) <<",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->" << join->join_trees_out;
+    if (join && settings().join_geodesic)
+        c << "\n#join=geodesic:" << settings().join_limit << ",thr:" << join->join_thr_used << ",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->"
+          << join->join_trees_out << ",inserted:" << join->join_inserted;
+    else if (join) c << "\n#join=gap:" << f32_text(settings().join_gap) <<",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->" << join->join_trees_out;
     if (radius_thr) {
         const pnr_radius_opts &ro = settings().radius;
         c << "\n#radius=measured,thr=";
@@ -556,6 +565,7 @@ struct Pipeline {
             fprintf(stderr, "--join-root %lld: the tree has %lld nodes\n", S.join_root_id, (long long)n);
             return false;
         }
+        if (S.join_geodesic) return join_geodesic(tj, T, n, root);
         const pnr_join_opts jo = {p.zdist, S.join_gap, (int32_t)root};
         std::vector<int32_t> par_out((size_t)n), order((size_t)n), comp((size_t)n);
         int64_t nb = 0, t_in = 0, t_out = 0;
@@ -582,6 +592,45 @@ struct Pipeline {
             prof.end();
             pnr_get_option(ctx, "join_rounds", &rounds);
             fprintf(stderr, "[pnr host] join: %.3f s, %lld rounds, kernels %.3f ms in %lld launches\n", R.t_join, (long long)rounds, prof.ms, (long long)prof.launches);
+        }
+        return true;
+    }
+
+    // --join-geodesic: the fragments are joined along the signal (pnr_geodesic_bridges), the bridges' voxels become nodes, and the tree
+    // list is rewritten in tree order
+    bool join_geodesic(clk::time_point tj, const TreeArrays &T, int64_t n, int64_t root)
+    {
+        const pnr_geojoin_opts go = {S.join_thr, S.join_limit, 1.f, nullptr};
+        GeoJoined J;
+        Profile prof(ctx, "geojoin", S.timing);
+        if (!geodesic_join(ctx, T.xyz.data() + 3, T.par.data() + 1, n, go, root, w, h, l, J)) return false;
+        const pnr_geojoin_info &gi = J.info;
+        R.join_bridges = gi.n_bridges, R.join_trees_in = gi.n_trees_in, R.join_trees_out = gi.n_trees_out, R.join_inserted = gi.n_inserted, R.join_thr_used = gi.thr_used;
+        std::vector<int32_t> pos((size_t)J.n2(), -1); // node -> its line; component 0 comes first in the order
+        std::vector<pnr_node> tree(1, R.tree[0]);
+        std::vector<int32_t> parent(1, R.parent[0]);
+        for (int64_t k = 0; k < J.n2(); k++) {
+            const int32_t v = J.order[(size_t)k];
+            if (S.join_keep_largest && J.comp[(size_t)v] != 0) break;
+            pos[(size_t)v] = (int32_t)tree.size();
+            if (v < n) tree.push_back(R.tree[(size_t)v + 1]);
+            else { // an inserted node: node a of its bridge moved onto the voxel, with the smaller radius of a and b
+                const pnr_geo_bridge &b = J.bridges[(size_t)J.bridge_of[(size_t)(v - n)]];
+                pnr_node nd = R.tree[(size_t)b.a + 1];
+                nd.x = J.xyz[3 * (size_t)v], nd.y = J.xyz[3 * (size_t)v + 1], nd.z = J.xyz[3 * (size_t)v + 2];
+                nd.sig = std::min(nd.sig, R.tree[(size_t)b.b + 1].sig);
+                tree.push_back(nd);
+            }
+            parent.push_back(J.par_out[(size_t)v] < 0 ? -1 : pos[(size_t)J.par_out[(size_t)v]]); // (the parent was written before)
+        }
+        R.tree.swap(tree);
+        R.parent.swap(parent);
+        R.t_join = secs(tj, clk::now());
+        printf("join... geodesic %llu, %lld bridges, %lld -> %lld trees, %lld nodes inserted, %zu nodes written, %g sec.\n", S.join_limit, (long long)gi.n_bridges,
+               (long long)gi.n_trees_in, (long long)gi.n_trees_out, (long long)gi.n_inserted, R.tree.size() - 1, R.t_join);
+        if (S.timing) {
+            prof.end();
+            fprintf(stderr, "[pnr host] join: %.3f s, %d rounds, meet kernels %.3f ms in %lld launches\n", R.t_join, (int)gi.rounds, prof.ms, (long long)prof.launches);
         }
         return true;
     }

@@ -40,6 +40,8 @@ struct Result {
     std::vector<int32_t> radius_k; // --measure-radius: k* of pnr_measure_radii per tree node (index 0 dummy: -1), else empty
     int32_t radius_thr = 0;        // ... the threshold it used (0: the relative mode)
     long long join_bridges = 0, join_trees_in = 0, join_trees_out = 0; // --join: what pnr_join_trees reported
+    long long join_inserted = 0;   // --join-geodesic: the nodes pnr_join_expand inserted
+    int join_thr_used = 0;         // ... and the threshold pnr_geodesic_bridges used
     double t_join = 0;
     bool have_coverage = false;    // --mask / --residual / --coverage: the final tree rendered on the traced volume (pnr_tree_coverage)
     pnr_coverage coverage = {};
@@ -92,8 +94,14 @@ struct Settings {
     // and the SWC written in tree order (every parent before its children) with a #join= comment line.  --join-root soma (the default:
     // the first soma node, type 1, if there is one) or ID (a node id of the file without --join); --join-keep-largest: only component
     // 0 is written.  The reference has no counterpart (ENFORCE_SINGLE_TREE throws the other trees away).
-    bool join = false, join_keep_largest = false;
+    // --join-geodesic D [--join-threshold T] in the place of --join GAP: the fragments are joined along the signal of the traced volume
+    // (pnr_geodesic_bridges; D: the largest bridge weight, 0: no limit; T as --geodesic's --threshold), the bridges' voxels become nodes
+    // (the type of the bridge's node a, the smaller radius of its two nodes) and the comment line is
+    // #join=geodesic:D,thr:T,bridges:K,trees:T0->T1,inserted:M.
+    bool join = false, join_keep_largest = false, join_geodesic = false;
     float join_gap = 0.f;
+    unsigned long long join_limit = 0;
+    int join_thr = 0;
     long long join_root_id = 0; // 0: the first soma node, if any
     // --mask OUT, --residual OUT, --coverage: the final tree -- after --join and --measure-radius, with the f32 radius each SWC line is
     // written from and zscale = zdist -- is rendered on the traced volume (pnr_tree_coverage): OUT receives the mask (255 under the
@@ -141,6 +149,14 @@ bool print_tree_distance(const std::string &a, const std::string &b, const pnr_d
 // type and radius columns carried over and a #join= comment line; root_id: an SWC id of IN (0: none); keep_largest: component 0 only.
 // Prints one JSON line {"nodes", "trees_in", "trees_out", "bridges", "longest_bridge", "rounds"}.
 bool join_swc_file(const std::string &in, const std::string &out, float gap, float zscale, long long root_id, bool keep_largest, int device);
+// advantra_cli --join-swc IN.swc OUT.swc --join-geodesic D -i stack: the fragments of the file joined along the signal of the stack
+// (pnr_geodesic_bridges on `device`; the volume setup of --geodesic, zscale >= 1 is the context's zdist; opts.limit = D, 0: no limit),
+// the bridges' voxels inserted as nodes (pnr_join_expand: the type of the bridge's node a, the smaller radius of its two nodes) and the
+// result re-rooted (pnr_join_reroot); OUT.swc as --join-swc writes it, with #join=geodesic:D,thr:T,bridges:K,trees:T0->T1,inserted:M.
+// Prints one JSON line {"nodes", "n_trees_in", "n_trees_lost", "n_trees_out", "n_bridges", "n_inserted", "w_max", "thr_used", "n_src",
+// "n_src_dropped", "limit", "zdist", "rounds"}.
+bool join_swc_geodesic_file(const std::string &in, const std::string &out, const pnr_geojoin_opts &opts, const std::vector<char *> &infiles, const std::string &raw_dims,
+                            float zscale, long long root_id, bool keep_largest, int device);
 // advantra_cli --render-swc IN.swc: the file rendered into a stack (pnr_tree_coverage on `device`).  With a stack (infiles[0]; the same
 // volume setup as tracing: channel, window, pre-filters of settings()) the tree is measured on what would be traced: `mask` / `residual`
 // (not empty) are written with save_stack_u8, `per_node` is a CSV `id,vox,fg,sum` per node under a header line, and one JSON line has

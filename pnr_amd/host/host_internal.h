@@ -3,6 +3,7 @@
 #include "advantra_host.h"
 #include "stack_io.h"
 #include <cstdio>
+#include <vector>
 
 namespace advantra {
 
@@ -38,6 +39,19 @@ struct Ctx {
 // stack; either failure is reported on stderr
 enum class Loaded { ok, unreadable, not_windowable };
 Loaded load_input_stack(const std::string &path, const std::string &raw_dims, Stack &out);
+
+// tools.cpp: the forest joined along the signal on ctx's volume -- pnr_geodesic_bridges, pnr_join_expand, then pnr_join_reroot on the
+// n + inserted nodes (root: a node index, or negative for none); false after lib_fail
+struct GeoJoined {
+    pnr_geojoin_info info = {};
+    std::vector<pnr_geo_bridge> bridges;
+    std::vector<float> xyz;                    // n2 x 3: the n nodes, then the inserted ones
+    std::vector<int32_t> bridge_of;            // per inserted node: its bridge
+    std::vector<int32_t> par_out, order, comp; // of pnr_join_reroot, n2 entries each
+    int64_t n2() const { return (int64_t)par_out.size(); }
+};
+bool geodesic_join(pnr_ctx *ctx, const float *xyz, const int32_t *parent, int64_t n, const pnr_geojoin_opts &opts, int64_t root, long long w, long long h, long long l,
+                   GeoJoined &out);
 
 // swc_io.cpp: load_swc with its message on stderr; the shortest decimal text without an exponent (nine digits at the most) that reads
 // back as the same f32

@@ -1,5 +1,5 @@
-// tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc, --render-swc, --components, --edt and
-// --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+// tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc (by gap, or --join-geodesic), --render-swc,
+// --components, --edt and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
 #include "host_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -126,6 +126,84 @@ bool join_swc_file(const std::string &in, const std::string &out, float gap, flo
         return false;
     printf("{\"nodes\": %lld, \"trees_in\": %lld, \"trees_out\": %lld, \"bridges\": %lld, \"longest_bridge\": %.9g, \"rounds\": %lld}\n", (long long)written,
            (long long)t_in, (long long)t_out, (long long)nb, nb ? (double)bridges[(size_t)nb - 1].d : 0.0, (long long)rounds);
+    return true;
+}
+
+bool geodesic_join(pnr_ctx *ctx, const float *xyz, const int32_t *parent, int64_t n, const pnr_geojoin_opts &opts, int64_t root, long long w, long long h, long long l,
+                   GeoJoined &out)
+{
+    std::vector<int64_t> vox;
+    int64_t nb = 0, np = 0;
+    for (;;) { // "*n_bridges > cap_bridges or *n_path > cap_path: call again"
+        const int64_t cap_b = (int64_t)out.bridges.size(), cap_p = (int64_t)vox.size();
+        if (pnr_geodesic_bridges(ctx, xyz, parent, n, &opts, &out.info, out.bridges.data(), cap_b, &nb, vox.data(), cap_p, &np) != PNR_OK) return lib_fail("pnr_geodesic_bridges");
+        if (nb <= cap_b && np <= cap_p) break;
+        out.bridges.resize((size_t)nb), vox.resize((size_t)np);
+    }
+    out.bridges.resize((size_t)nb);
+    int64_t n2 = 0;
+    std::vector<pnr_bridge> join((size_t)nb);
+    if (pnr_join_expand(xyz, parent, n, out.bridges.data(), nb, vox.data(), np, w, h, l, nullptr, nullptr, nullptr, 0, &n2, nullptr) != PNR_OK) return lib_fail("pnr_join_expand");
+    std::vector<int32_t> par((size_t)n2);
+    out.xyz.resize((size_t)n2 * 3), out.bridge_of.resize((size_t)(n2 - n));
+    out.par_out.resize((size_t)n2), out.order.resize((size_t)n2), out.comp.resize((size_t)n2);
+    if (pnr_join_expand(xyz, parent, n, out.bridges.data(), nb, vox.data(), np, w, h, l, out.xyz.data(), par.data(), out.bridge_of.data(), n2, &n2, join.data()) != PNR_OK)
+        return lib_fail("pnr_join_expand");
+    if (pnr_join_reroot(par.data(), n2, join.data(), nb, root, out.par_out.data(), out.order.data(), out.comp.data()) != PNR_OK) return lib_fail("pnr_join_reroot");
+    return true;
+}
+
+bool join_swc_geodesic_file(const std::string &in, const std::string &out, const pnr_geojoin_opts &opts, const std::vector<char *> &infiles, const std::string &raw_dims,
+                            float zscale, long long root_id, bool keep_largest, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    SwcTree T;
+    if (!read_swc(in, T)) return false;
+    const int64_t n = T.n();
+    if (n == 0) {
+        fprintf(stderr, "%s: no nodes\n", in.c_str());
+        return false;
+    }
+    int64_t root = -1;
+    if (root_id > 0) {
+        const auto it = std::find(T.id.begin(), T.id.end(), root_id);
+        if (it == T.id.end()) {
+            fprintf(stderr, "--join-root %lld: %s has no node with this id\n", root_id, in.c_str());
+            return false;
+        }
+        root = it - T.id.begin();
+    }
+    pnr_params p;
+    pnr_default_params(&p);
+    p.zdist = zscale; // (also the z half-width of --subtract-background)
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    GeoJoined J;
+    if (!geodesic_join(ctx, T.xyz.data(), T.parent.data(), n, opts, root, st.w, st.h, st.l, J)) return false;
+    const pnr_geojoin_info &gi = J.info;
+    int64_t written = 0;
+    if (!write_file(out, "w", [&](FILE *f) {
+            fprintf(f, "#join=geodesic:%llu,thr:%d,bridges:%lld,trees:%lld->%lld,inserted:%lld\n##n,type,x,y,z,radius,parent\n", (unsigned long long)opts.limit, (int)gi.thr_used,
+                    (long long)gi.n_bridges, (long long)gi.n_trees_in, (long long)gi.n_trees_out, (long long)gi.n_inserted);
+            std::vector<int64_t> pos((size_t)J.n2(), -1);
+            for (int64_t k = 0; k < J.n2(); k++) {
+                const size_t v = (size_t)J.order[(size_t)k];
+                if (keep_largest && J.comp[v] != 0) break;
+                pos[v] = ++written;
+                // an inserted node: the type of its bridge's node a, the smaller radius of a and b
+                const pnr_geo_bridge *b = (int64_t)v >= n ? &J.bridges[(size_t)J.bridge_of[v - (size_t)n]] : nullptr;
+                const int type = T.type[b ? (size_t)b->a : v];
+                const float radius = b ? std::min(T.radius[(size_t)b->a], T.radius[(size_t)b->b]) : T.radius[v];
+                fprintf(f, "%lld %d %s %s %s %s %lld\n", (long long)written, type, f32_text(J.xyz[3 * v]).c_str(), f32_text(J.xyz[3 * v + 1]).c_str(),
+                        f32_text(J.xyz[3 * v + 2]).c_str(), f32_text(radius).c_str(), J.par_out[v] < 0 ? -1LL : (long long)pos[(size_t)J.par_out[v]]);
+            }
+        }))
+        return false;
+    printf("{\"nodes\": %lld, \"n_trees_in\": %lld, \"n_trees_lost\": %lld, \"n_trees_out\": %lld, \"n_bridges\": %lld, \"n_inserted\": %lld, \"w_max\": %llu, \"thr_used\": %d, "
+           "\"n_src\": %lld, \"n_src_dropped\": %lld, \"limit\": %llu, \"zdist\": %.17g, \"rounds\": %d}\n",
+           (long long)written, (long long)gi.n_trees_in, (long long)gi.n_trees_lost, (long long)gi.n_trees_out, (long long)gi.n_bridges, (long long)gi.n_inserted,
+           (unsigned long long)gi.w_max, (int)gi.thr_used, (long long)gi.n_src, (long long)gi.n_src_dropped, (unsigned long long)opts.limit, (double)zscale, (int)gi.rounds);
     return true;
 }
 

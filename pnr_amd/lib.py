@@ -146,6 +146,25 @@ PNR_GEO_MAX_PATH = 1 << 16
 PNR_GEO_DMAX = 2**31 - 1
 
 
+class GeoJoinOpts(C.Structure):
+    """pnr_geojoin_opts (include/pnr_hip.h): thr and cost as in pnr_geo_opts, limit (0: none) the largest bridge weight W, step the spacing
+    of the sample points along the segments (0: the nodes only)"""
+    _fields_ = [("thr", C.c_int32), ("limit", C.c_uint64), ("step", C.c_float), ("cost", C.POINTER(C.c_uint16))]
+
+
+class GeoJoinInfo(C.Structure):
+    """pnr_geojoin_info: the exact summary of pnr_geodesic_bridges (rounds: Boruvka rounds of the call)"""
+    _fields_ = [(k, C.c_int64) for k in ("n_trees_in", "n_trees_lost", "n_trees_out", "n_bridges", "n_inserted", "n_src", "n_src_dropped")] + [
+        ("w_max", C.c_uint64), ("thr_used", C.c_int32), ("rounds", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+# pnr_geo_bridge: the attachment nodes, the meet voxel p and offset o (13..25 of the offset order), the weight W and the bridge's voxel chain
+GEO_BRIDGE = np.dtype([("a", np.int32), ("b", np.int32), ("p", np.int64), ("o", np.int32), ("path_len", np.int32), ("w", np.uint64), ("path_off", np.int64)])
+
+
 # pnr_component
 COMPONENT_DT = np.dtype([(k, np.int64) for k in ("first", "size", "sum", "sx", "sy", "sz")] + [(k, np.int32) for k in ("x0", "y0", "z0", "x1", "y1", "z1", "vmax", "pad")])
 
@@ -228,6 +247,8 @@ def load():
     L.pnr_despeckle_volume.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]
     L.pnr_distance_transform.argtypes = [vp, C.POINTER(EdtOpts), C.POINTER(EdtInfo), vp, vp, i64, vp]
     L.pnr_geodesic_distance.argtypes = [vp, vp, vp, i64, C.POINTER(GeoOpts), C.POINTER(GeoInfo), vp, vp, vp, i64, vp, vp, i32, vp, vp]
+    L.pnr_geodesic_bridges.argtypes = [vp, vp, vp, i64, C.POINTER(GeoJoinOpts), C.POINTER(GeoJoinInfo), vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
+    L.pnr_join_expand.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, C.POINTER(i64), vp]
     L.pnr_render_items.argtypes = [vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_test_write_tiff.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
@@ -293,7 +314,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_geodesic_distance", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_geodesic_distance", "pnr_geodesic_bridges", "pnr_join_expand", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -632,6 +653,34 @@ class Context:
                 at["path_len"] = plen
                 at["paths"] = [pvox[k, :abs(int(n))].copy() for k, n in enumerate(plen)]
         return out, D, Lv, at
+
+    def join_trees_geodesic(self, xyz, parent, limit=0, thr=0, step=1, cost=None):
+        """pnr_geodesic_bridges of a forest (n x 3 voxel positions, parent indices with a negative value for none) through the context's
+        volume: the unique minimum spanning forest of the fragments under gray-weighted path cost (bridges heavier than `limit` are not
+        made; 0: no limit; thr, cost as in geodesic(); step: the spacing of the sources along the segments) -> (bridges GEO_BRIDGE[k] in
+        ascending key order, paths {"vox": int64[...] the bridges' voxel chains s_a .. p, q .. s_b one after the other (bridge k:
+        vox[path_off : path_off + path_len]), "shape": (l, h, w)}, info dict {n_trees_in, n_trees_lost, n_trees_out, n_bridges,
+        n_inserted, n_src, n_src_dropped, w_max, thr_used, rounds}).  join_expand() turns the result into nodes for join_reroot()."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        if len(parent) != len(xyz):
+            raise PnrError("join_trees_geodesic: one parent per node")
+        tab = np.ascontiguousarray(cost, np.uint16).reshape(-1) if cost is not None else None
+        if tab is not None and len(tab) != 256:
+            raise ValueError("join_trees_geodesic: the cost table has 256 entries")
+        o = GeoJoinOpts(int(thr), int(limit), float(step), tab.ctypes.data_as(C.POINTER(C.c_uint16)) if tab is not None else None)
+        info = GeoJoinInfo()
+        nb, npath = C.c_int64(), C.c_int64()
+        cap_b, cap_p = 64, 4096
+        while True:  # "*n_bridges > cap_bridges or *n_path > cap_path: call again"
+            bridges = np.empty(cap_b, GEO_BRIDGE)
+            vox = np.empty(cap_p, np.int64)
+            check(self.L.pnr_geodesic_bridges(self.h, xyz.ctypes.data, parent.ctypes.data, len(xyz), C.byref(o), C.byref(info), bridges.ctypes.data, cap_b, C.byref(nb),
+                                              vox.ctypes.data, cap_p, C.byref(npath)))
+            if nb.value <= cap_b and npath.value <= cap_p:
+                break
+            cap_b, cap_p = max(cap_b, nb.value), max(cap_p, npath.value)
+        return bridges[:nb.value].copy(), {"vox": vox[:npath.value].copy(), "shape": tuple(int(v) for v in self.shape)}, info.as_dict()
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
@@ -1059,6 +1108,28 @@ def join_reroot(parent, bridges=(), root=-1):
     check(L.pnr_join_reroot(parent.ctypes.data, len(parent), bridges.ctypes.data if len(bridges) else None, len(bridges), int(root),
                             out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
     return tuple(out)
+
+
+def join_expand(xyz, parent, bridges, paths):
+    """pnr_join_expand (pure host; no GPU needed): the interior voxels of the bridges' chains as new nodes n, n + 1, ... behind the n nodes
+    of the forest; bridges, paths: what Context.join_trees_geodesic returned -> (xyz float32[n2, 3], parent int32[n2], bridge_of
+    int32[n2 - n] the bridge of every new node, join BRIDGE[k] for join_reroot(parent, join))"""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    if len(parent) != len(xyz):
+        raise PnrError("join_expand: one parent per node")
+    bridges = np.ascontiguousarray(bridges, GEO_BRIDGE)
+    vox = np.ascontiguousarray(paths["vox"], np.int64).reshape(-1)
+    l, h, w = (int(v) for v in paths["shape"])
+    n, nb = len(xyz), len(bridges)
+    join = np.zeros(nb, BRIDGE)
+    n2 = C.c_int64()
+    args = (xyz.ctypes.data, parent.ctypes.data, n, bridges.ctypes.data if nb else None, nb, vox.ctypes.data if len(vox) else None, len(vox), w, h, l)
+    check(L.pnr_join_expand(*args, None, None, None, 0, C.byref(n2), None))
+    xyz2, parent2, of = np.empty((n2.value, 3), np.float32), np.empty(n2.value, np.int32), np.empty(n2.value - n, np.int32)
+    check(L.pnr_join_expand(*args, xyz2.ctypes.data, parent2.ctypes.data, of.ctypes.data if len(of) else None, n2.value, C.byref(n2), join.ctypes.data if nb else None))
+    return xyz2, parent2, of, join
 
 
 def _tree_arrays(who, xyz, radius, parent):
