@@ -20,6 +20,18 @@ int pnr_hessian(pnr_ctx *ctx, float sig, float *Dzz, float *Dyy, float *Dyz, flo
  * tested in isolation exactly like SeedExtractor::extractSeeds(tolerance,J8,...,Vx,Vy,Vz). */
 int pnr_set_j8_v(pnr_ctx *ctx, const uint8_t *J8, const uint8_t *Vx, const uint8_t *Vy, const uint8_t *Vz);
 
+/* What the GPU half of pnr_extract_seeds_range hands to the host's flood fill for the layers [z0, z1) of the context's J8 (same
+ * argument rules), nl = z1 - z0 layers: the stage runs as it does there (extremes, bitmap and row counts, row prefix, keys and
+ * compacted values, the chunked download on the second stream), then both streams are waited for.  Per layer: vmin / vmax [nl] the
+ * extremes as the device computed them; ltot [nl] the pixels above the minimum; key_off [nl + 1] and keys, the candidate keys
+ * ((int)((v - vmin) * vFactor) << 32 | y * w + x, seed.cpp:616-632) sorted ascending inside each layer -- *n_keys receives their
+ * number, they are written only if it is <= cap_keys (*n_keys > cap_keys: call again); layers [nl][h][w] the layer as the fill's own
+ * loader rebuilds it from the downloaded bits and values; restored [nl] 1 where the loader's image is uniformly the layer minimum
+ * again after its restore step (one loader takes all the layers in turn, as a fill thread does: a pixel a restore misses shows in
+ * the next layer as well).  Any output may be NULL.  Neither the seed list of the context nor a later pnr_extract_seeds changes. */
+int pnr_seed_handover(pnr_ctx *ctx, int64_t z0, int64_t z1, int32_t *vmin, int32_t *vmax, int64_t *ltot, int64_t *key_off,
+                      int64_t *keys, int64_t cap_keys, int64_t *n_keys, uint8_t *layers, int32_t *restored);
+
 /* Tracker tables for parity tests: name in {"p","u","w0","w0_cws","v","w","w_cws","rng",
  * "model_vuw<s>","model_wgt<s>","model_avg","gauss_xy<s>","gauss_z<s>"}.  Copies up to cap
  * 4-byte words into out; *n receives the element count. */

@@ -913,6 +913,14 @@ int pnr_extract_seeds(pnr_ctx *c, const pnr_seed **seeds, int64_t *n)
     return pnr_extract_seeds_range(c, 0, c->l, seeds, n);
 }
 
+int pnr_seed_handover(pnr_ctx *c, int64_t z0, int64_t z1, int32_t *vmin, int32_t *vmax, int64_t *ltot, int64_t *key_off, int64_t *keys,
+                      int64_t cap_keys, int64_t *n_keys, uint8_t *layers, int32_t *restored)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_seed_handover_run(c, z0, z1, vmin, vmax, ltot, key_off, keys, cap_keys, n_keys, layers, restored);
+}
+
 int pnr_zncc_batch(pnr_ctx *c, const float *pos_dir, int64_t n, float *corr, float *sig)
 {
     PNR_REQUIRE(c && (n == 0 || (pos_dir && corr)), PNR_E_ARG, "null argument");

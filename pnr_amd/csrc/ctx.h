@@ -299,6 +299,8 @@ int pnr_j8_run(pnr_ctx *c, float jmin, float jmax);
 int pnr_gaussian_run(pnr_ctx *c, float sig, float *d_out /*device N floats*/);
 int pnr_hessian_run(pnr_ctx *c, float sig, float *const d_out[6]);
 int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1);
+int pnr_seed_handover_run(pnr_ctx *c, int64_t z0, int64_t z1, int32_t *vmin, int32_t *vmax, int64_t *ltot, int64_t *key_off, int64_t *keys,
+                          int64_t cap_keys, int64_t *n_keys, uint8_t *layers, int32_t *restored); // test tap (pnr_hip_test.h)
 int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold);
 int pnr_gauss_x_u8_launch(pnr_ctx *c, const uint8_t *src, float *dst, const float *d_taps, int L);
 int pnr_ensure_tmpA(pnr_ctx *c); // the second Gaussian scratch volume / the direction volumes: allocated where they are used (frangi.hip)

@@ -370,19 +370,23 @@ struct LayerFinder {
     }
 };
 
-} // namespace
+// What the GPU half of the seed stage leaves for the host's flood fill: the per-layer tables, the candidate keys (unsorted, layer k
+// in [off[k], off[k + 1])) and the sparse J8 in the context's pinned buffers (layer k: bitmap rows from k * h, values from voff[k]).
+struct SeedHandover {
+    int wpr = 0, per_chunk = 1; // bitmap words per row; layers per download chunk (layer k waits for j8_ev[k / per_chunk])
+    std::vector<int> vmin, vmax;
+    std::vector<unsigned int> cnt, ltot;
+    std::vector<i64> off, voff, keys;
+    const unsigned long long *h_bits = nullptr;
+    const unsigned char *h_vals = nullptr;
+};
 
-int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
+// The GPU half for the nl >= 1 layers from z0.  On return the context's stream has been waited for; the bitmap and the values may
+// still be on their way on the copy stream.  Without a candidate in any layer the fill needs no value and none is compacted or
+// downloaded -- unless all_values asks for them (the test tap).
+int seeds_gpu_stage(pnr_ctx *c, int64_t z0, int nl, bool all_values, SeedHandover &H)
 {
-    PNR_REQUIRE(c->have_j8, PNR_E_STATE, "pnr_extract_seeds: run pnr_frangi (or pnr_set_j8_v) first");
-    PNR_REQUIRE(z0 >= 0 && z1 <= c->l && z0 <= z1, PNR_E_ARG, "layer range [%lld,%lld) outside [0,%lld)", (long long)z0, (long long)z1, (long long)c->l);
-    c->seeds.clear();
-    const bool timing = c->opt.seed_timing != 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
     const int w = (int)c->w, h = (int)c->h;
-    const int nl = (int)(z1 - z0);
-    if (nl == 0) return PNR_OK;
     const i64 wh = (i64)w * h;
 
     int *d_min = nullptr, *d_max = nullptr;
@@ -404,10 +408,14 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
     if (!rc) rc = c->scratch_get("seed_rowoff", nrows, &d_rowoff);
     if (!rc) rc = c->scratch_get("seed_bits", nwords, &d_bits);
     if (rc) return rc;
-    std::vector<int> vmin(nl), vmax(nl);
-    std::vector<unsigned int> cnt(nl), ltot(nl);
+    H.wpr = wpr;
+    std::vector<int> &vmin = H.vmin, &vmax = H.vmax;
+    std::vector<unsigned int> &cnt = H.cnt, &ltot = H.ltot;
+    std::vector<i64> &off = H.off, &voff = H.voff, &keys = H.keys;
+    vmin.assign(nl, 0); vmax.assign(nl, 0);
+    cnt.assign(nl, 0u); ltot.assign(nl, 0u);
     std::vector<float> vf(nl);
-    std::vector<i64> off(nl + 1, 0), voff(nl + 1, 0);
+    off.assign(nl + 1, 0); voff.assign(nl + 1, 0);
 
     // The host's flood fill gets J8 in sparse form: one bit per pixel (above its layer's minimum or not) and the values of the
     // set pixels in raster order -- on a second stream, in chunks of layers with an event each, so that the fill of a layer only
@@ -426,8 +434,8 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
     };
     rc = pinned(c->h_j8, nwords * 8);
     if (rc) return rc;
-    const unsigned long long *h_bits = (const unsigned long long *)c->h_j8.get();
-    const int per_chunk = (nl + NCH - 1) / NCH;
+    H.h_bits = (const unsigned long long *)c->h_j8.get();
+    const int per_chunk = H.per_chunk = (nl + NCH - 1) / NCH;
 
     c->tic();
     PNR_HIP(hipMemsetAsync(d_min, 0x7f, nl * 4, c->stream));
@@ -457,11 +465,11 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
         vf[k] = (float)(2e9 / ((float)vmax[k] - (float)vmin[k])); // seed.cpp:616 (inf on flat layers: no maxima there)
     }
     const i64 total = off[nl], nvals = voff[nl];
-    std::vector<i64> keys((size_t)total);
+    keys.assign((size_t)total, 0);
     rc = pinned(c->h_j8v, (size_t)std::max<i64>(nvals, 1));
     if (rc) return rc;
-    const unsigned char *h_vals = c->h_j8v.get();
-    if (total > 0) { // (no candidate anywhere: nothing to fill, nothing to hand over)
+    H.h_vals = c->h_j8v.get();
+    if (total > 0 || all_values) { // (no candidate anywhere: nothing to fill, nothing to hand over)
         rc = c->scratch_get("seed_keys", (size_t)total, &d_keys);
         if (!rc) rc = c->scratch_get("seed_vals", (size_t)std::max<i64>(nvals, 1), &d_vals);
         if (rc) return rc;
@@ -474,7 +482,7 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
         hipLaunchKernelGGL(layer_maxima<true>, dim3(nblk), dim3(256), 0, c->stream, c->d_J8.get(), w, h, (int)z0, tiles_x, d_min,
                            d_vf, d_cnt, d_off, d_keys, SP);
         c->toc("seed_maxima", 1);
-        PNR_HIP(hipMemcpyAsync(keys.data(), d_keys, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
+        if (total > 0) PNR_HIP(hipMemcpyAsync(keys.data(), d_keys, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
         // the values follow the bitmap on the copy stream, in chunks of layers
         PNR_HIP(hipEventRecord(c->j8_start, c->stream));
         PNR_HIP(hipStreamWaitEvent(c->copy_stream, c->j8_start, 0));
@@ -487,6 +495,35 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
     }
     PNR_HIP(hipGetLastError());
     PNR_HIP(hipStreamSynchronize(c->stream));
+    return PNR_OK;
+}
+
+} // namespace
+
+int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
+{
+    PNR_REQUIRE(c->have_j8, PNR_E_STATE, "pnr_extract_seeds: run pnr_frangi (or pnr_set_j8_v) first");
+    PNR_REQUIRE(z0 >= 0 && z1 <= c->l && z0 <= z1, PNR_E_ARG, "layer range [%lld,%lld) outside [0,%lld)", (long long)z0, (long long)z1, (long long)c->l);
+    c->seeds.clear();
+    const bool timing = c->opt.seed_timing != 0;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_start = now();
+    const int w = (int)c->w, h = (int)c->h;
+    const int nl = (int)(z1 - z0);
+    if (nl == 0) return PNR_OK;
+    const i64 wh = (i64)w * h;
+
+    SeedHandover H;
+    int rc = seeds_gpu_stage(c, z0, nl, false, H);
+    if (rc) return rc;
+    const std::vector<int> &vmin = H.vmin;
+    const std::vector<unsigned int> &cnt = H.cnt;
+    const std::vector<i64> &off = H.off, &voff = H.voff;
+    std::vector<i64> &keys = H.keys;
+    const int wpr = H.wpr, per_chunk = H.per_chunk;
+    const unsigned long long *h_bits = H.h_bits;
+    const unsigned char *h_vals = H.h_vals;
+    const i64 total = off[nl];
 
     const double t_gpu = now();
     // host: per-layer flood-fill on a thread pool; results kept per layer to preserve z-major order
@@ -554,5 +591,44 @@ int pnr_seeds_run(pnr_ctx *c, int64_t z0, int64_t z1)
     if (timing)
         fprintf(stderr, "[pnr seeds] kernels + keys %.1f ms (J8 download overlapped), host fill %.1f ms (%u threads, %lld candidates), dirs+free %.1f ms\n",
                 1e3 * (t_gpu - t_start), 1e3 * (t_fill - t_gpu), (unsigned)pnr::host_threads(c->opt), (long long)total, 1e3 * (now() - t_fill));
+    return PNR_OK;
+}
+
+// test tap (pnr_hip_test.h): the GPU half alone, then every layer through the fill's own loader
+int pnr_seed_handover_run(pnr_ctx *c, int64_t z0, int64_t z1, int32_t *vmin, int32_t *vmax, int64_t *ltot, int64_t *key_off, int64_t *keys,
+                          int64_t cap_keys, int64_t *n_keys, uint8_t *layers, int32_t *restored)
+{
+    PNR_REQUIRE(c->have_j8, PNR_E_STATE, "pnr_seed_handover: run pnr_frangi (or pnr_set_j8_v) first");
+    PNR_REQUIRE(z0 >= 0 && z1 <= c->l && z0 <= z1, PNR_E_ARG, "layer range [%lld,%lld) outside [0,%lld)", (long long)z0, (long long)z1, (long long)c->l);
+    PNR_REQUIRE(cap_keys >= 0 && (keys || cap_keys == 0), PNR_E_ARG, "cap_keys = %lld without a key array", (long long)cap_keys);
+    const int w = (int)c->w, h = (int)c->h;
+    const int nl = (int)(z1 - z0);
+    if (key_off) key_off[0] = 0;
+    if (n_keys) *n_keys = 0;
+    if (nl == 0) return PNR_OK;
+    const size_t wh = (size_t)w * h;
+
+    SeedHandover H;
+    const int rc = seeds_gpu_stage(c, z0, nl, true, H);
+    if (rc) return rc;
+    PNR_HIP(hipStreamSynchronize(c->copy_stream));
+    const i64 total = H.off[nl];
+    if (n_keys) *n_keys = total;
+    const bool put_keys = keys && total <= cap_keys;
+    LayerFinder lf(w, h); // one for all the layers, as on a fill thread
+    for (int k = 0; k < nl; k++) {
+        if (vmin) vmin[k] = H.vmin[k];
+        if (vmax) vmax[k] = H.vmax[k];
+        if (ltot) ltot[k] = (int64_t)H.ltot[k];
+        if (key_off) key_off[k + 1] = H.off[k + 1];
+        i64 *kb = H.keys.data() + H.off[k];
+        std::sort(kb, kb + H.cnt[k]);
+        if (put_keys && H.cnt[k]) std::memcpy(keys + H.off[k], kb, (size_t)H.cnt[k] * 8);
+        const unsigned long long *lb = H.h_bits + (size_t)k * h * H.wpr;
+        const unsigned char *L8 = lf.load(lb, H.wpr, H.h_vals + H.voff[k], H.vmin[k]);
+        if (layers) std::memcpy(layers + (size_t)k * wh, L8, wh);
+        lf.restore(lb, H.wpr);
+        if (restored) restored[k] = std::count(lf.img.begin(), lf.img.end(), (unsigned char)lf.img_fill) == (std::ptrdiff_t)wh ? 1 : 0;
+    }
     return PNR_OK;
 }

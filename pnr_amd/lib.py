@@ -259,6 +259,7 @@ def load():
     L.pnr_gaussian.argtypes = [vp, C.c_float, vp]
     L.pnr_hessian.argtypes = [vp, C.c_float] + [vp] * 6
     L.pnr_set_j8_v.argtypes = [vp] + [vp] * 4
+    L.pnr_seed_handover.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
     L.pnr_extract_seeds.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.pnr_extract_seeds_range.argtypes = [vp, i64, i64, C.POINTER(vp), C.POINTER(i64)]
     L.pnr_zncc_batch.argtypes = [vp, vp, i64, vp, vp]
@@ -323,7 +324,8 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
                    "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes", "pnr_render_items", "pnr_test_write_tiff"]
+                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes", "pnr_render_items", "pnr_test_write_tiff",
+                "pnr_seed_handover"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -741,6 +743,26 @@ class Context:
             return np.zeros(0, SEED_DT)
         buf = (C.c_char * (n.value * SEED_DT.itemsize)).from_address(ptr.value)
         return np.frombuffer(buf, SEED_DT).copy()
+
+    def seed_handover(self, z0=None, z1=None):
+        """test tap pnr_seed_handover: what the GPU half of extract_seeds(z0, z1) hands to the host's flood fill -- per layer vmin,
+        vmax, ltot (pixels above the minimum), the candidate keys sorted inside each layer with key_off [nl + 1], the layers as the
+        fill's loader rebuilds them (nl, h, w) and restored (1: the loader's image is uniform again after its restore)"""
+        l, h, w = self.shape
+        z0, z1 = (0, l) if z0 is None else (int(z0), int(z1))
+        nl = max(z1 - z0, 0)
+        out = dict(vmin=np.zeros(nl, np.int32), vmax=np.zeros(nl, np.int32), ltot=np.zeros(nl, np.int64), key_off=np.zeros(nl + 1, np.int64),
+                   layers=np.zeros((nl, h, w), np.uint8), restored=np.zeros(nl, np.int32))
+        keys, n = np.zeros(0, np.int64), C.c_int64()
+        while True:
+            check(self.L.pnr_seed_handover(self.h, z0, z1, out["vmin"].ctypes.data, out["vmax"].ctypes.data, out["ltot"].ctypes.data,
+                                           out["key_off"].ctypes.data, keys.ctypes.data, len(keys), C.byref(n), out["layers"].ctypes.data,
+                                           out["restored"].ctypes.data))
+            if n.value <= len(keys):
+                break
+            keys = np.zeros(n.value, np.int64)
+        out["keys"] = keys[:n.value]
+        return out
 
     def zncc(self, pos_dir):
         pd = np.ascontiguousarray(pos_dir, np.float32).reshape(-1, 6)

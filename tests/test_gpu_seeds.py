@@ -5,6 +5,7 @@ import pytest
 import orc
 import synth
 import pnr_amd
+import seeds_ref as sr
 from pnr_amd import SeedExtractor
 
 pytestmark = pytest.mark.gpu
@@ -85,3 +86,62 @@ def test_zslab_sharding_equals_whole_stack(world):
     assert len(got) == len(want) > 20
     for k in want.dtype.names:
         assert np.array_equal(got[k], want[k], equal_nan=True), k
+
+
+# ---- end to end on the stacks of the hand-over tests (tests/seeds_ref.py): the shapes at which the index arithmetic of the seed
+# kernels changes, and the tolerances around the fill's early break (a 255 over a minimum of 0 survives 254, nothing survives 255) ----
+E2E_CASES = [(s, k) for s in sr.SHAPES for k in sr.E2E_KINDS]
+_e2e_ctx = {}
+
+
+def e2e_context(tol, shape):
+    """one context per tolerance for the whole sweep, moved from stack to stack"""
+    if tol not in _e2e_ctx:
+        _e2e_ctx[tol] = pnr_amd.Context(pnr_amd.make_params(tolerance=tol), 0)
+    c = _e2e_ctx[tol]
+    w, h, l = shape
+    if c.shape != (l, h, w):
+        c.set_volume(np.zeros((l, h, w), np.uint8))  # dimensions only
+    return c
+
+
+@pytest.mark.parametrize("shape,kind", E2E_CASES, ids=["%s-%s" % (sr.shape_id(s), k) for s, k in E2E_CASES])
+def test_seeds_at_kernel_edge_shapes(oracle, shape, kind):
+    J8, V = sr.stack(shape, kind), sr.directions(shape)
+    if shape[0] < 2 or shape[1] < 2:  # no volume under 2 x 2 x 1: the library refuses it, the oracle finds nothing in it
+        with pytest.raises(pnr_amd.PnrError, match="at least 2x2x1"):
+            e2e_context(5, shape)
+        assert all(len(sr.oracle_seeds(oracle, shape, kind, tol)) == 0 for tol in sr.TOLERANCES)
+        return
+    for tol in sr.TOLERANCES:
+        want = sr.oracle_seeds(oracle, shape, kind, tol)
+        c = e2e_context(tol, shape)
+        c.set_j8_v(J8, *V)
+        assert np.array_equal(as_mat(c.extract_seeds()), want, equal_nan=True), (tol, len(want))
+        if not sr.has_interior(shape):
+            assert len(want) == 0
+        if tol == 5:  # one fill thread, and three: more than some of the layer counts, fewer than others
+            before = c.get_option("host_threads")
+            for nt in (1, 3):
+                c.set_option("host_threads", nt)
+                got = as_mat(c.extract_seeds())
+                c.set_option("host_threads", before)
+                assert np.array_equal(got, want, equal_nan=True), ("host_threads", nt)
+
+
+def test_edge_shape_sweep_is_not_vacuous(oracle):
+    """the sweep above compares seed lists: it must contain seeds -- for every shape with an interior, and at tolerance 254 (the last
+    one in front of the fill's early break) in at least three shapes"""
+    n254 = 0
+    for shape in sr.SHAPES:
+        counts = {tol: sum(len(sr.oracle_seeds(oracle, shape, k, tol)) for k in sr.E2E_KINDS) for tol in sr.TOLERANCES}
+        if sr.has_interior(shape):
+            assert max(counts.values()) > 0, shape
+        else:
+            assert max(counts.values()) == 0, shape
+        assert counts[255] == 0 and counts[1000] == 0, shape
+        n254 += counts[254] > 0
+    assert n254 >= 3
+    for c in _e2e_ctx.values():
+        c.close()
+    _e2e_ctx.clear()
