@@ -187,7 +187,8 @@ int pnr_replay_traces(const pnr_params *p, int64_t w, int64_t h, int64_t l, cons
  * (toolbox.cpp:657), binarise at > threshold, conn3d (toolbox.cpp:245) -> one SOMA node (x, y, z, sig = mean radius,
  * corr = -FLT_MAX, type 1) per 26-connected region and the map voxel -> node index the seed filter, the replay and the
  * trace kernels' early stop use.  Must run after pnr_set_volume and before pnr_frangi (it uses the Frangi scratch) whenever
- * somaradius > 0; with somaradius = 0 it records "no soma".  E8 (nullable, N bytes) receives the eroded + blurred stack. */
+ * somaradius > 0; with somaradius = 0 it records "no soma".  E8 (nullable, N bytes) receives the eroded + blurred stack.  The call's
+ * own device buffers (taps, histogram, row tables, the compacted voxels) are freed before it returns; PNR_E_NOMEM: an allocation failed. */
 int pnr_soma(pnr_ctx *ctx, uint8_t *E8, int32_t *threshold, int64_t *n_soma);
 /* soma nodes (in node-list order, index k+1) and the sparse label map: foreground voxels in raster order with their node index */
 int pnr_get_soma(pnr_ctx *ctx, pnr_node *nodes, int64_t cap_nodes, int64_t *n_nodes, int64_t *vox, int32_t *label,

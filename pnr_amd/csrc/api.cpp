@@ -63,50 +63,22 @@ int host_threads(const Options &o)
 
 using pnr::set_error;
 
-template <typename T>
-static int upload(pnr::DevBuf<T> &dst, const std::vector<T> &src, hipStream_t s)
-{
-    PNR_HIP(dst.alloc(src.size()));
-    if (!src.empty()) PNR_HIP(hipMemcpyAsync(dst.get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    return PNR_OK;
-}
-
-template <typename T>
-static int download(pnr_ctx *c, T *dst, const T *src, size_t n)
-{
-    if (!dst) return PNR_OK;
-    PNR_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
-    return PNR_OK;
-}
-
 // tracker tables for the 3-D (default) or the 2-D (single-slice stack, P == 1) branch of Tracker::Tracker: built on the host,
 // resident on the device.  Rebuilt when pnr_set_volume changes the dimensionality.
 static int load_tables(pnr_ctx *c, bool is2d)
 {
     pnr::build_tables(c->prm, is2d, c->tab);
     const pnr::Tables &t = c->tab;
-    std::vector<float> sig(c->prm.sig, c->prm.sig + c->prm.nsig);
-    int rc = upload(c->d_p, t.p, c->stream);
-    if (!rc) rc = upload(c->d_u, t.u, c->stream);
-    if (!rc) rc = upload(c->d_w0, t.w0, c->stream);
-    if (!rc) rc = upload(c->d_w0cws, t.w0_cws, c->stream);
-    if (!rc) rc = upload(c->d_v, t.v, c->stream);
-    if (!rc) rc = upload(c->d_w, t.w, c->stream);
-    if (!rc) rc = upload(c->d_wcws, t.w_cws, c->stream);
-    if (!rc) rc = upload(c->d_tmpl, t.tmpl, c->stream);
-    if (!rc) rc = upload(c->d_corrc, t.corrc, c->stream);
-    if (!rc) rc = upload(c->d_sig, sig, c->stream);
-    if (!rc) rc = upload(c->d_M, t.M, c->stream);
-    if (!rc) rc = upload(c->d_moff, t.moff, c->stream);
-    if (!rc) rc = upload(c->d_rng, t.rng, c->stream);
-    if (!rc) rc = upload(c->d_grid, t.grid, c->stream);
-    if (!rc) rc = upload(c->d_axes, t.axes, c->stream);
-    if (!rc) rc = upload(c->d_axes_off, t.axes_off, c->stream);
-    if (!rc) rc = upload(c->d_wd, t.wd, c->stream);
-    if (!rc) rc = upload(c->d_share, t.share_tab, c->stream);
-    if (!rc) rc = upload(c->d_grows, t.grows, c->stream);
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = PNR_E_HIP;
-    return rc;
+    const std::vector<float> sig(c->prm.sig, c->prm.sig + c->prm.nsig);
+    pnr::Call call(c, "tracker tables");
+    auto up = [&call](auto &dst, const auto &src) { // a device buffer of exactly the table's size (PNR_E_HIP without one), and its upload
+        if (call.ok()) call.note(dst.alloc(src.size()));
+        if (!src.empty()) call.up(dst.get(), src.data(), src.size());
+    };
+    up(c->d_p, t.p), up(c->d_u, t.u), up(c->d_w0, t.w0), up(c->d_w0cws, t.w0_cws), up(c->d_v, t.v), up(c->d_w, t.w), up(c->d_wcws, t.w_cws);
+    up(c->d_tmpl, t.tmpl), up(c->d_corrc, t.corrc), up(c->d_sig, sig), up(c->d_M, t.M), up(c->d_moff, t.moff), up(c->d_rng, t.rng);
+    up(c->d_grid, t.grid), up(c->d_axes, t.axes), up(c->d_axes_off, t.axes_off), up(c->d_wd, t.wd), up(c->d_share, t.share_tab), up(c->d_grows, t.grows);
+    return call.finish(); // (sig ends here)
 }
 
 extern "C" {
@@ -260,9 +232,10 @@ int pnr_set_volume(pnr_ctx *c, const uint8_t *img, int64_t w, int64_t h, int64_t
     int rc = set_dims(c, w, h, l);
     if (rc) return rc;
     c->d_img = nullptr; // never leave the context pointing at a freed image if the allocation below fails
-    PNR_HIP(c->d_img_owned.reserve((size_t)c->N));
-    PNR_HIP(hipMemcpyAsync(c->d_img_owned.get(), img, (size_t)c->N, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipStreamSynchronize(c->stream));
+    pnr::Call call(c, "pnr_set_volume");
+    call.note(c->d_img_owned.reserve((size_t)c->N));
+    call.up(c->d_img_owned.get(), img, (size_t)c->N);
+    if ((rc = call.finish())) return rc;
     c->d_img = c->d_img_owned.get();
     return PNR_OK;
 }
@@ -301,11 +274,9 @@ static int set_volume_u16(pnr_ctx *c, const void *img, bool host, int64_t w, int
     if (host) {
         const size_t bytes = (size_t)c->N * (size_t)nchan * 2;
         if ((rc = pnr::dev_alloc(d_up, bytes, "pnr_set_volume_u16", "for the 16-bit stack"))) return rc;
-        if (hipMemcpyAsync(d_up.get(), img, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);
-            set_error("pnr_set_volume_u16: upload of %zu B failed", bytes);
-            return PNR_E_HIP;
-        }
+        pnr::Call call(c, "pnr_set_volume_u16");
+        call.up(d_up.get(), img, bytes);
+        if (!call.ok()) return call.finish();
         src = (const uint16_t *)d_up.get();
     }
     rc = pnr_volume_u16_run(c, src, nchan, channel, wd, lo_out, hi_out);
@@ -332,9 +303,9 @@ int pnr_get_volume(pnr_ctx *c, uint8_t *img)
     PNR_REQUIRE(c && img, PNR_E_ARG, "null argument");
     PNR_REQUIRE(c->d_img, PNR_E_STATE, "pnr_get_volume: no volume set");
     PNR_HIP(hipSetDevice(c->device));
-    PNR_HIP(hipMemcpyAsync(img, c->d_img, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
-    PNR_HIP(hipStreamSynchronize(c->stream));
-    return PNR_OK;
+    pnr::Call call(c, "pnr_get_volume");
+    call.down(img, c->d_img, (size_t)c->N);
+    return call.finish();
 }
 
 // what pnr_set_volume of the new bytes leaves: an owned volume of the same dimensions, no later pipeline state
@@ -829,14 +800,14 @@ int pnr_get_frangi(pnr_ctx *c, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, 
         if (rc) return rc;
     }
     if (Vx || Vy || Vz) rc = pnr_frangi_materialise_v(c); // the pipeline itself only needs the directions at the seeds
-    if (!rc) rc = download(c, J, c->d_J.get(), n);
-    if (!rc) rc = download(c, J8, c->d_J8.get(), n);
-    if (!rc) rc = download(c, Vx, c->d_Vx.get(), n);
-    if (!rc) rc = download(c, Vy, c->d_Vy.get(), n);
-    if (!rc) rc = download(c, Vz, c->d_Vz.get(), n);
     if (rc) return rc;
-    PNR_HIP(hipStreamSynchronize(c->stream));
-    return PNR_OK;
+    pnr::Call call(c, "pnr_get_frangi");
+    if (J) call.down(J, c->d_J.get(), n);
+    if (J8) call.down(J8, c->d_J8.get(), n);
+    if (Vx) call.down(Vx, c->d_Vx.get(), n);
+    if (Vy) call.down(Vy, c->d_Vy.get(), n);
+    if (Vz) call.down(Vz, c->d_Vz.get(), n);
+    return call.finish();
 }
 
 int pnr_gaussian(pnr_ctx *c, float sig, float *F)
@@ -848,8 +819,9 @@ int pnr_gaussian(pnr_ctx *c, float sig, float *F)
     if (rc) return rc;
     rc = pnr_gaussian_run(c, sig, c->d_tmpA.get());
     if (rc) return rc;
-    PNR_HIP(hipMemcpy(F, c->d_tmpA.get(), (size_t)c->N * 4, hipMemcpyDeviceToHost));
-    return PNR_OK;
+    pnr::Call call(c, "pnr_gaussian");
+    call.down(F, c->d_tmpA.get(), (size_t)c->N);
+    return call.finish();
 }
 
 int pnr_hessian(pnr_ctx *c, float sig, float *Dzz, float *Dyy, float *Dyz, float *Dxx, float *Dxy, float *Dxz)
@@ -859,19 +831,18 @@ int pnr_hessian(pnr_ctx *c, float sig, float *Dzz, float *Dyy, float *Dyz, float
     PNR_REQUIRE(sig > 0, PNR_E_ARG, "sigma must be positive");
     int rc = pnr_ensure_frangi_buffers(c);
     if (rc) return rc;
-    pnr::DevBuf<float> own[6];
+    pnr::CallBuf buf; // the six volumes (freed when the call returns)
+    pnr::Part<float> part[6];
+    for (auto &p : part) p = buf.add<float>((size_t)c->N);
+    if ((rc = buf.alloc("pnr_hessian"))) return rc;
     float *d[6];
-    for (int k = 0; k < 6; k++) {
-        if (own[k].alloc((size_t)c->N) != hipSuccess) {
-            set_error("hipMalloc failed for Hessian tap");
-            return PNR_E_NOMEM;
-        }
-        d[k] = own[k].get();
-    }
+    for (int k = 0; k < 6; k++) d[k] = part[k];
     rc = pnr_hessian_run(c, sig, d);
     float *hst[6] = {Dzz, Dyy, Dyz, Dxx, Dxy, Dxz};
+    pnr::Call call(c, "pnr_hessian");
     for (int k = 0; k < 6 && !rc; k++)
-        if (hst[k] && hipMemcpy(hst[k], d[k], (size_t)c->N * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = PNR_E_HIP;
+        if (hst[k]) call.down(hst[k], part[k]);
+    if (!rc) rc = call.finish();
     c->have_j8 = false; // tmp buffers were reused
     return rc;
 }
@@ -884,11 +855,12 @@ int pnr_set_j8_v(pnr_ctx *c, const uint8_t *J8, const uint8_t *Vx, const uint8_t
     if (!rc) rc = pnr_ensure_v(c);
     if (rc) return rc;
     const size_t n = (size_t)c->N;
-    PNR_HIP(hipMemcpyAsync(c->d_J8.get(), J8, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipMemcpyAsync(c->d_Vx.get(), Vx, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipMemcpyAsync(c->d_Vy.get(), Vy, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipMemcpyAsync(c->d_Vz.get(), Vz, n, hipMemcpyHostToDevice, c->stream));
-    PNR_HIP(hipStreamSynchronize(c->stream));
+    pnr::Call call(c, "pnr_set_j8_v");
+    call.up(c->d_J8.get(), J8, n);
+    call.up(c->d_Vx.get(), Vx, n);
+    call.up(c->d_Vy.get(), Vy, n);
+    call.up(c->d_Vz.get(), Vz, n);
+    if ((rc = call.finish())) return rc;
     c->have_j8 = true;
     c->have_v = true;
     c->have_scale = false;

@@ -1,5 +1,7 @@
-// call.h -- the staging of one tool call (volume, radius, filter, distance, join, render, components, edt, geodesic): its device buffers as typed
-// parts of ONE allocation, and the chain of HIP calls on the context's stream with one sticky error.
+// call.h -- the staging of one bounded call on the context's stream: its device buffers as typed parts of ONE allocation, and the chain
+// of HIP calls with one sticky error.  Users: the volume and tree tools (volume, radius, filter, distance, join, render, components, edt,
+// geodesic, geojoin), the side stages (recon, soma), the test taps (frangi.hip: eigen, hessian, gaussian, the direction volumes; smc.hip:
+// expf) and the uploads and read-backs of api.cpp.
 #pragma once
 #include "ctx.h"
 
@@ -82,13 +84,16 @@ public:
     void fill(T *dst, int byte, size_t count) { if (ok()) e_ = hipMemsetAsync(dst, byte, count * sizeof(T), st_); }
     template <typename T>
     void fill(const Part<T> &dst, int byte) { fill(dst.get(), byte, dst.count); }
+    struct Lds { size_t bytes; }; // dynamic LDS of a launch, in front of the kernel's arguments
     template <typename... P, typename... A>
-    void launch(void (*kernel)(P...), dim3 grid, dim3 block, const A &...args)
+    void launch(void (*kernel)(P...), dim3 grid, dim3 block, Lds lds, const A &...args)
     {
         if (!ok()) return;
-        hipLaunchKernelGGL(kernel, grid, block, 0, st_, args...);
+        hipLaunchKernelGGL(kernel, grid, block, lds.bytes, st_, args...);
         e_ = hipGetLastError();
     }
+    template <typename... P, typename... A>
+    void launch(void (*kernel)(P...), dim3 grid, dim3 block, const A &...args) { launch(kernel, grid, block, Lds{0}, args...); }
     // synchronises the stream: PNR_OK, or the first failure through hip_fail
     int finish()
     {

@@ -202,6 +202,13 @@ struct pnr_ctx {
     int64_t geojoin_rounds = 0; // Boruvka rounds of the last pnr_geodesic_bridges (pnr_get_option "geojoin_rounds")
     std::vector<int32_t> graph_log; // 5 ints per replayed trace (option "trace_log")
 
+    // shell table of pnr_measure_radii (radius.hip): one per context, rebuilt when what it was built for changes (reallocated with rmax)
+    pnr::DevBuf<uint32_t> d_rad_off;
+    pnr::DevBuf<int> d_rad_start;
+    int rad_rmax = 0; // (0: no table)
+    uint32_t rad_zbits = 0; // the bits of zdist
+    bool rad_2d = false;
+
     // profiling: HIP event pairs recorded on the ctx stream around each kernel group, resolved
     // lazily (no host sync inside the timed region)
     bool profiling = false;

@@ -16,7 +16,7 @@
 // Build: hipcc --offload-arch=gfx950 -ffp-contract=off : every f32/f64 operation is the IEEE
 // operation the reference's scalar loop performs, in the same order, so Gaussian / Hessian /
 // eigenvectors are bit-identical; only exp() (fp64, ocml vs glibc, <1 ulp each) can differ.
-#include "ctx.h"
+#include "call.h"
 #include "smc_device.h" // expf_libm: the device expf that equals the host libm value
 #include <cfloat>
 #include <cmath>
@@ -1604,8 +1604,8 @@ int pnr_gaussian_run(pnr_ctx *c, float sig, float *d_out)
     pnr::gaussian_taps(sig, gxy);
     pnr::gaussian_taps(sig / c->prm.zdist, gz);
     rc = gaussian3d(c, gxy, gz, c->d_taps.get(), d_out);
-    hipStreamSynchronize(c->stream);
-    return rc;
+    const int rs = pnr::Call(c, "pnr_gaussian").finish();
+    return rc ? rc : rs;
 }
 
 // launches of the Hessian stencil over the z-chunk [zc0, zc1)
@@ -1626,11 +1626,10 @@ int pnr_hessian_run(pnr_ctx *c, float sig, float *const d_out[6])
     int tiles_x, tiles_y;
     unsigned blocks;
     tile_grid(c, 0, l, tiles_x, tiles_y, blocks);
-    hipLaunchKernelGGL(hessian_tile<true>, dim3(blocks), dim3(HT_THREADS), 0, c->stream, (const float *)c->d_tmpA.get(), w, h, l, tiles_x, tiles_y, 0, l,
-                       sig * sig, HessQueue{}, (unsigned int *)nullptr, 1, 0, l, dump, 0.f, 0);
-    PNR_HIP(hipGetLastError());
-    PNR_HIP(hipStreamSynchronize(c->stream));
-    return PNR_OK;
+    pnr::Call call(c, "pnr_hessian");
+    call.launch(hessian_tile<true>, dim3(blocks), dim3(HT_THREADS), (const float *)c->d_tmpA.get(), w, h, l, tiles_x, tiles_y, 0, l, sig * sig, HessQueue{},
+                (unsigned int *)nullptr, 1, 0, l, dump, 0.f, 0);
+    return call.finish();
 }
 
 // Vx / Vy / Vz of the whole volume (pnr_get_frangi asking for them): not needed by the pipeline, which takes the directions at
@@ -1642,10 +1641,10 @@ int pnr_frangi_materialise_v(pnr_ctx *c)
     { const int rcv = pnr_ensure_v(c); if (rcv) return rcv; }
     ScaleVols SV{};
     for (int s = 0; s < c->prm.nsig; s++) { SV.F[s] = c->d_F[s].get(); SV.s2[s] = c->prm.sig[s] * c->prm.sig[s]; }
-    hipLaunchKernelGGL(vdir_points, dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, SV, (const unsigned char *)c->d_scale.get(), (const i64 *)nullptr,
-                       (i64)c->N, (int)c->w, (int)c->h, (int)c->l, c->d_Vx.get(), c->d_Vy.get(), c->d_Vz.get(), 0);
-    PNR_HIP(hipGetLastError());
-    PNR_HIP(hipStreamSynchronize(c->stream));
+    pnr::Call call(c, "pnr_get_frangi");
+    call.launch(vdir_points, dim3((unsigned)((c->N + 255) / 256)), dim3(256), SV, (const unsigned char *)c->d_scale.get(), (const i64 *)nullptr, (i64)c->N,
+                (int)c->w, (int)c->h, (int)c->l, c->d_Vx.get(), c->d_Vy.get(), c->d_Vz.get(), 0);
+    if (const int rc = call.finish()) return rc;
     c->have_v = true;
     return PNR_OK;
 }
@@ -1672,22 +1671,18 @@ int pnr_seed_dirs(pnr_ctx *c, const long long *d_idx, int n, unsigned char *d_di
 int pnr_eigen_run(pnr_ctx *c, const double *A, int64_t n, double *V, double *d)
 {
     if (n == 0) return PNR_OK;
-    pnr::DevBuf<double> bA, bV, bd; // (freed on every path, after the synchronise below on the good one)
-    PNR_HIP(bA.alloc((size_t)n * 9));
-    hipError_t e = bd.alloc((size_t)n * 3);
-    if (e == hipSuccess && V) e = bV.alloc((size_t)n * 9);
-    double *dA = bA.get(), *dV = bV.get(), *dd = bd.get();
-    if (e == hipSuccess) e = hipMemcpyAsync(dA, A, (size_t)n * 72, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        if (V) hipLaunchKernelGGL(eigen_kat<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dA, (i64)n, dV, dd);
-        else hipLaunchKernelGGL(eigen_kat<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dA, (i64)n, dV, dd);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(d, dd, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && V) e = hipMemcpyAsync(V, dV, (size_t)n * 72, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    PNR_HIP(e);
-    return PNR_OK;
+    static const char *who = "pnr_eigen_batch";
+    pnr::CallBuf buf; // the matrices | the eigenvalues | the eigenvectors, if asked for (freed when the call returns)
+    const auto dA = buf.add<double>((size_t)n * 9), dd = buf.add<double>((size_t)n * 3), dV = buf.add<double>(V ? (size_t)n * 9 : 0);
+    if (const int rc = buf.alloc(who)) return rc;
+    pnr::Call call(c, who);
+    call.up(dA, A);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (V) call.launch(eigen_kat<true>, grid, dim3(256), (const double *)dA, (i64)n, dV.get(), dd.get());
+    else call.launch(eigen_kat<false>, grid, dim3(256), (const double *)dA, (i64)n, (double *)nullptr, dd.get());
+    call.down(d, dd);
+    if (V) call.down(V, dV);
+    return call.finish();
 }
 
 // J -> J8 with the given extremes (Advantra_plugin.cpp:2499-2512)

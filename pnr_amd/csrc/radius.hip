@@ -137,39 +137,32 @@ __global__ __launch_bounds__(RTPB) void rad_measure(RadArgs a)
 int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opts &o, int32_t *k_out, int32_t *thr_used)
 {
     static const char *who = "pnr_measure_radii";
-    hipStream_t st = c->stream;
+    pnr::Call call(c, who);
     const bool is2d = c->l == 1;
-    // the shells of (rmax, zdist, 2-D), kept in the context's named device scratch.  Which table that is, is the NAME of an empty
-    // scratch entry beside it ("radius_key/..."): the context's own structure (ctx.h) stays as it is.
+    // the shells of (rmax, zdist, 2-D), kept in the context: the table of the last call, or a new one.  Another rmax gets buffers of
+    // exactly its size; the 2-D and the 3-D table of one rmax share what the larger needs (dev_alloc only grows), so a change of
+    // volume alone frees nothing
     uint32_t zbits;
     std::memcpy(&zbits, &c->prm.zdist, 4);
-    char key[64];
-    snprintf(key, sizeof(key), "radius_key/%d/%08x/%d", o.rmax, zbits, is2d ? 1 : 0);
-    uint32_t *d_off = nullptr;
-    int *d_start = nullptr;
-    if (c->scratch.find(key) == c->scratch.end()) {
-        for (auto it = c->scratch.begin(); it != c->scratch.end();)
-            it = it->first.compare(0, 11, "radius_key/") == 0 ? c->scratch.erase(it) : std::next(it);
+    int rc = PNR_OK;
+    if (c->rad_rmax != o.rmax || c->rad_zbits != zbits || c->rad_2d != is2d) {
         pnr::RadiusTable t;
         pnr::build_radius_table(c->prm.zdist, o.rmax, is2d, t);
-        int rc = c->scratch_get("radius_off", t.off.size(), &d_off);
-        if (rc == PNR_OK) rc = c->scratch_get("radius_start", t.start.size(), &d_start);
-        if (rc) return rc;
-        PNR_HIP(hipMemcpyAsync(d_off, t.off.data(), t.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        PNR_HIP(hipMemcpyAsync(d_start, t.start.data(), t.start.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        PNR_HIP(hipStreamSynchronize(st)); // (the host table ends here)
-        c->scratch[key];
-    } else {
-        d_off = (uint32_t *)c->scratch["radius_off"].get();
-        d_start = (int *)c->scratch["radius_start"].get();
+        if (c->rad_rmax != o.rmax) c->d_rad_off.reset(), c->d_rad_start.reset();
+        c->rad_rmax = 0;
+        if ((rc = pnr::dev_alloc(c->d_rad_off, t.off.size(), who, "for the shell table"))) return rc;
+        if ((rc = pnr::dev_alloc(c->d_rad_start, t.start.size(), who, "for the shell table"))) return rc;
+        call.up(c->d_rad_off.get(), t.off.data(), t.off.size());
+        call.up(c->d_rad_start.get(), t.start.data(), t.start.size());
+        if ((rc = call.finish())) return rc; // (the host table ends here)
+        c->rad_rmax = o.rmax, c->rad_zbits = zbits, c->rad_2d = is2d;
     }
     // device buffers of the call: the sum | the positions | the order of the nodes | k
     pnr::CallBuf buf; // (freed when the call returns)
     const auto d_sum = buf.add<unsigned long long>(1);
     const auto d_xyz = buf.add<float>((size_t)n * 3);
     const auto d_ord = buf.add<int>((size_t)n), d_k = buf.add<int>((size_t)n);
-    int rc = buf.alloc(who);
-    if (rc) return rc;
+    if ((rc = buf.alloc(who))) return rc;
     int t_abs = o.rel_pct ? 0 : o.thr;
     if (t_abs < 0 && (rc = pnr_mean_threshold(c, who, "radius", c->d_img, c->N, d_sum, &t_abs))) return rc; // the global mean
     if (thr_used) *thr_used = t_abs;
@@ -188,10 +181,9 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         std::sort(cell.begin(), cell.end());
         std::vector<int> order((size_t)n);
         for (int64_t i = 0; i < n; i++) order[(size_t)i] = cell[(size_t)i].second;
-        pnr::Call call(c, who);
         call.up(d_xyz, xyz);
         call.up(d_ord, order.data());
-        const RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, d_off, d_start, d_xyz, d_ord, (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, d_k};
+        const RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, c->d_rad_off.get(), c->d_rad_start.get(), d_xyz, d_ord, (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, d_k};
         c->tic();
         call.launch(rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), a);
         c->toc("radius", 1);

@@ -12,6 +12,7 @@
 // ball with more than CAP members is left to a second kernel, where a work-group marks the members in a bitmap over the node
 // indices and walks it in ascending order: same members, same order, no bound on the ball.
 #include "recon.h"
+#include "call.h"
 #include <climits>
 #include <cmath>
 
@@ -399,54 +400,20 @@ __global__ __launch_bounds__(BIG) void k_balls_big(const float4 *pos, Geom g, co
 // ---- host side ----
 using advantra::P4;
 static_assert(sizeof(P4) == sizeof(float4), "P4 is uploaded as float4");
+const char *const who = "reconstruct";
 
-// device buffers of one call (the work on them goes to the context's stream); the stream is drained and they are freed when the
-// call returns
-struct Bufs {
-    hipStream_t s;
-    std::vector<pnr::DevBuf<char>> p;
-    explicit Bufs(hipStream_t s_) : s(s_) {}
-    ~Bufs() { (void)hipStreamSynchronize(s); } // (then p frees them)
-    template <class T>
-    int get(T **out, size_t count, const char *what)
-    {
-        pnr::DevBuf<char> b;
-        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        if (b.alloc(bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            pnr::set_error("reconstruct: device allocation of %zu B for %s failed", bytes, what);
-            return PNR_E_NOMEM;
-        }
-        *out = (T *)b.get();
-        p.push_back(std::move(b));
-        return PNR_OK;
-    }
-    void release(void *q)
-    {
-        for (auto &e : p)
-            if (e.get() == q) {
-                (void)hipStreamSynchronize(s);
-                e = std::move(p.back()); // (frees q)
-                p.pop_back();
-                return;
-            }
-    }
-};
-
-#define RC(call)                 \
-    do {                         \
-        if (int rc_ = (call)) return rc_; \
-    } while (0)
-
+// the grid of a call: its geometry (host) and its arrays, parts of the call's buffer
 struct DevGrid {
     Geom g;
-    int *start = nullptr; // [ncell + 1]
-    float4 *gp = nullptr; // [n - 1]
+    int ncell = 0;
+    pnr::Part<int> cell, count, cursor; // [n] [ncell] [ncell]
+    pnr::Part<int> start;               // [ncell + 1]
+    pnr::Part<float4> gp;               // [n - 1]
 };
 
-// the grid over nodes 1 .. n-1 of d_pos (pos: the same on the host), cells of at least `cell` (larger where the box would need
-// more than max(4096, 4n) of them)
-int build_grid(pnr_ctx *c, Bufs &B, const float4 *d_pos, const std::vector<P4> &pos, float cell, DevGrid &G)
+// the grid over nodes 1 .. n-1 of pos, cells of at least `cell` (larger where the box would need more than max(4096, 4n) of them): the
+// geometry, and the arrays as parts of buf
+void plan_grid(pnr::CallBuf &buf, const std::vector<P4> &pos, float cell, DevGrid &G)
 {
     const int n = (int)pos.size();
     double mn[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, mx[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
@@ -468,21 +435,22 @@ int build_grid(pnr_ctx *c, Bufs &B, const float4 *d_pos, const std::vector<P4> &
     } else cs = 1; // one cell: every query visits it
     Geom &g = G.g;
     g = Geom{(float)mn[0], (float)mn[1], (float)mn[2], (float)cs, (int)dim[0], (int)dim[1], (int)dim[2]};
-    const int ncell = g.nx * g.ny * g.nz;
-    hipStream_t st = c->stream;
-    int *d_cell = nullptr, *d_count = nullptr, *d_cursor = nullptr;
-    RC(B.get(&d_cell, n, "cell ids"));
-    RC(B.get(&d_count, ncell, "cell counts"));
-    RC(B.get(&d_cursor, ncell, "cell cursors"));
-    RC(B.get(&G.start, (size_t)ncell + 1, "cell starts"));
-    RC(B.get(&G.gp, n - 1, "packed nodes"));
-    PNR_HIP(hipMemsetAsync(d_count, 0, (size_t)ncell * 4, st));
+    G.ncell = g.nx * g.ny * g.nz;
+    G.cell = buf.add<int>((size_t)n);
+    G.count = buf.add<int>((size_t)G.ncell);
+    G.cursor = buf.add<int>((size_t)G.ncell);
+    G.start = buf.add<int>((size_t)G.ncell + 1);
+    G.gp = buf.add<float4>((size_t)n - 1);
+}
+
+// fills the grid from the n positions d_pos (the ones plan_grid saw): three launches
+void build_grid(pnr::Call &call, const float4 *d_pos, int n, const DevGrid &G)
+{
+    call.fill(G.count, 0);
     const unsigned nb = (unsigned)((n - 1 + 255) / 256);
-    hipLaunchKernelGGL(k_bin, dim3(nb), dim3(256), 0, st, d_pos, n, g, d_cell, d_count);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const int *)d_count, ncell, G.start, d_cursor);
-    hipLaunchKernelGGL(k_scatter, dim3(nb), dim3(256), 0, st, d_pos, n, (const int *)d_cell, d_cursor, G.gp);
-    PNR_HIP(hipGetLastError());
-    return PNR_OK;
+    call.launch(k_bin, dim3(nb), dim3(256), d_pos, n, G.g, G.cell.get(), G.count.get());
+    call.launch(k_scan, dim3(1), dim3(1024), (const int *)G.count, G.ncell, G.start.get(), G.cursor.get());
+    call.launch(k_scatter, dim3(nb), dim3(256), d_pos, n, (const int *)G.cell, G.cursor.get(), G.gp.get());
 }
 
 // work-groups of a bitmap kernel for `balls` large balls over n nodes, and its bitmap words per work-group
@@ -503,47 +471,45 @@ int pnr_recon_shift(pnr_ctx *c, const std::vector<P4> &src, float s2r, int maxit
     PNR_REQUIRE(n64 < (1 << 28), PNR_E_ARG, "reconstruct: %lld nodes, at most 2^28 on the device", (long long)n64);
     const int n = (int)n64;
     PNR_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     // cells of about the mean ball radius (the candidate boxes stay a few cells wide)
     double ssum = 0;
     int64_t sn = 0;
     for (int i = 1; i < n; i++)
         if (std::isfinite(src[i].s) && src[i].s > 0) { ssum += src[i].s; sn++; }
     const float cell = std::max(1.0f, s2r * (float)(sn ? ssum / (double)sn : 1.0));
-    Bufs B(st);
-    float4 *d_src = nullptr, *d_res = nullptr;
-    int *d_ovf = nullptr, *d_novf = nullptr;
-    RC(B.get(&d_src, n, "mean-shift input"));
-    RC(B.get(&d_res, n, "mean-shift result"));
-    RC(B.get(&d_ovf, n, "large balls"));
-    RC(B.get(&d_novf, 1, "large-ball count"));
-    PNR_HIP(hipMemcpyAsync(d_src, src.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
-    PNR_HIP(hipMemsetAsync(d_novf, 0, 4, st));
-    c->tic();
+    // device buffers of the call: input | result | the large balls and their number | the grid
+    pnr::CallBuf buf; // (freed when the call returns)
+    const auto d_src = buf.add<float4>((size_t)n), d_res = buf.add<float4>((size_t)n);
+    const auto d_ovf = buf.add<int>((size_t)n), d_novf = buf.add<int>(1);
     DevGrid G;
-    RC(build_grid(c, B, d_src, src, cell, G));
-    hipLaunchKernelGGL(k_shift, dim3(n - 1), dim3(64), 0, st, (const float4 *)d_src, n, G.g, (const int *)G.start, (const float4 *)G.gp, s2r,
-                       maxiter, eps2, d_res, d_ovf, d_novf);
-    PNR_HIP(hipGetLastError());
+    plan_grid(buf, src, cell, G);
+    int rc = buf.alloc(who);
+    if (rc) return rc;
+    pnr::Call call(c, who);
+    call.up(d_src, src.data());
+    call.fill(d_novf, 0);
+    c->tic();
+    build_grid(call, d_src, n, G);
+    call.launch(k_shift, dim3(n - 1), dim3(64), (const float4 *)d_src, n, G.g, (const int *)G.start, (const float4 *)G.gp, s2r, maxiter, eps2,
+                d_res.get(), d_ovf.get(), d_novf.get());
     c->toc("recon", 4);
     int novf = 0;
-    PNR_HIP(hipMemcpyAsync(&novf, d_novf, 4, hipMemcpyDeviceToHost, st));
-    PNR_HIP(hipStreamSynchronize(st));
+    call.down(&novf, d_novf);
+    if ((rc = call.finish())) return rc;
+    pnr::CallBuf bm; // the bitmaps, sized by the read-back
     if (novf > 0) {
         int groups = 0, nw = 0;
         bitmap_shape(novf, n, groups, nw);
-        unsigned *d_bm = nullptr;
-        RC(B.get(&d_bm, (size_t)groups * nw, "mean-shift bitmaps"));
-        PNR_HIP(hipMemsetAsync(d_bm, 0, (size_t)groups * nw * 4, st));
+        const auto d_bm = bm.add<unsigned>((size_t)groups * nw);
+        if ((rc = bm.alloc(who))) return rc;
+        call.fill(d_bm, 0);
         c->tic();
-        hipLaunchKernelGGL(k_shift_big, dim3(groups), dim3(BIG), 0, st, (const float4 *)d_src, G.g, (const int *)G.start, (const float4 *)G.gp,
-                           s2r, maxiter, eps2, d_res, (const int *)d_ovf, (const int *)d_novf, d_bm, nw);
-        PNR_HIP(hipGetLastError());
+        call.launch(k_shift_big, dim3(groups), dim3(BIG), (const float4 *)d_src, G.g, (const int *)G.start, (const float4 *)G.gp, s2r, maxiter, eps2,
+                    d_res.get(), (const int *)d_ovf, (const int *)d_novf, d_bm.get(), nw);
         c->toc("recon", 1);
     }
-    PNR_HIP(hipMemcpyAsync(res.data() + 1, d_res + 1, (size_t)(n - 1) * 16, hipMemcpyDeviceToHost, st));
-    PNR_HIP(hipStreamSynchronize(st));
-    return PNR_OK;
+    call.down(res.data() + 1, d_res.get() + 1, (size_t)n - 1);
+    return call.finish();
 }
 
 int pnr_recon_balls(pnr_ctx *c, const std::vector<P4> &pos, float rad, advantra::BallLists &out)
@@ -556,62 +522,57 @@ int pnr_recon_balls(pnr_ctx *c, const std::vector<P4> &pos, float rad, advantra:
     PNR_REQUIRE(n64 < (1 << 28), PNR_E_ARG, "reconstruct: %lld nodes, at most 2^28 on the device", (long long)n64);
     const int n = (int)n64;
     PNR_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    Bufs B(st);
-    float4 *d_pos = nullptr;
-    long long *d_off = nullptr;
-    int *d_cnt = nullptr, *d_ovf = nullptr, *d_novf = nullptr;
-    unsigned long long *d_cursor = nullptr;
-    RC(B.get(&d_pos, n, "grouping positions"));
-    RC(B.get(&d_off, n, "ball offsets"));
-    RC(B.get(&d_cnt, n, "ball sizes"));
-    RC(B.get(&d_ovf, n, "large balls"));
-    RC(B.get(&d_novf, 1, "large-ball count"));
-    RC(B.get(&d_cursor, 1, "ball cursor"));
-    PNR_HIP(hipMemcpyAsync(d_pos, pos.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
-    c->tic();
+    // device buffers of the call: positions | offset and size of every ball | the large balls and their number | the list cursor | the grid
+    pnr::CallBuf buf; // (freed when the call returns)
+    const auto d_pos = buf.add<float4>((size_t)n);
+    const auto d_off = buf.add<long long>((size_t)n);
+    const auto d_cnt = buf.add<int>((size_t)n), d_ovf = buf.add<int>((size_t)n), d_novf = buf.add<int>(1);
+    const auto d_cursor = buf.add<unsigned long long>(1);
     DevGrid G;
-    RC(build_grid(c, B, d_pos, pos, std::max(2.0f, rad), G));
+    plan_grid(buf, pos, std::max(2.0f, rad), G);
+    int rc = buf.alloc(who);
+    if (rc) return rc;
+    pnr::Call call(c, who);
+    call.up(d_pos, pos.data());
+    c->tic();
+    build_grid(call, d_pos, n, G);
     c->toc("recon", 3);
     long long cap = std::max<long long>(1 << 20, 16LL * n);
-    unsigned long long used = 0;
-    int *d_list = nullptr;
     for (int pass = 0;; pass++) {
-        RC(B.get(&d_list, (size_t)cap, "ball lists"));
-        PNR_HIP(hipMemsetAsync(d_novf, 0, 4, st));
-        PNR_HIP(hipMemsetAsync(d_cursor, 0, 8, st));
+        pnr::CallBuf lists, bm; // of this pass: a list that was too small and the bitmaps are gone before the next one
+        const auto d_list = lists.add<int>((size_t)cap);
+        if ((rc = lists.alloc(who))) return rc;
+        call.fill(d_novf, 0);
+        call.fill(d_cursor, 0);
         c->tic();
-        hipLaunchKernelGGL(k_balls, dim3(n - 1), dim3(64), 0, st, (const float4 *)d_pos, n, G.g, (const int *)G.start, (const float4 *)G.gp, rad,
-                           d_off, d_cnt, d_list, cap, d_cursor, d_ovf, d_novf);
-        PNR_HIP(hipGetLastError());
+        call.launch(k_balls, dim3(n - 1), dim3(64), (const float4 *)d_pos, n, G.g, (const int *)G.start, (const float4 *)G.gp, rad, d_off.get(),
+                    d_cnt.get(), d_list.get(), cap, d_cursor.get(), d_ovf.get(), d_novf.get());
         c->toc("recon", 1);
         int novf = 0;
-        PNR_HIP(hipMemcpyAsync(&novf, d_novf, 4, hipMemcpyDeviceToHost, st));
-        PNR_HIP(hipStreamSynchronize(st));
+        call.down(&novf, d_novf);
+        if ((rc = call.finish())) return rc;
         if (novf > 0) {
             int groups = 0, nw = 0;
             bitmap_shape(novf, n, groups, nw);
-            unsigned *d_bm = nullptr;
-            RC(B.get(&d_bm, (size_t)groups * nw, "ball bitmaps"));
-            PNR_HIP(hipMemsetAsync(d_bm, 0, (size_t)groups * nw * 4, st));
+            const auto d_bm = bm.add<unsigned>((size_t)groups * nw);
+            if ((rc = bm.alloc(who))) return rc;
+            call.fill(d_bm, 0);
             c->tic();
-            hipLaunchKernelGGL(k_balls_big, dim3(groups), dim3(BIG), 0, st, (const float4 *)d_pos, G.g, (const int *)G.start, (const float4 *)G.gp,
-                               rad, d_off, d_cnt, d_list, cap, d_cursor, (const int *)d_ovf, (const int *)d_novf, d_bm, nw);
-            PNR_HIP(hipGetLastError());
+            call.launch(k_balls_big, dim3(groups), dim3(BIG), (const float4 *)d_pos, G.g, (const int *)G.start, (const float4 *)G.gp, rad, d_off.get(),
+                        d_cnt.get(), d_list.get(), cap, d_cursor.get(), (const int *)d_ovf, (const int *)d_novf, d_bm.get(), nw);
             c->toc("recon", 1);
-            B.release(d_bm);
         }
-        PNR_HIP(hipMemcpyAsync(&used, d_cursor, 8, hipMemcpyDeviceToHost, st));
-        PNR_HIP(hipStreamSynchronize(st));
-        if ((long long)used <= cap) break;
+        unsigned long long used = 0;
+        call.down(&used, d_cursor);
+        if ((rc = call.finish())) return rc;
+        if ((long long)used <= cap) {
+            out.list.resize((size_t)used);
+            call.down(out.off.data() + 1, d_off.get() + 1, (size_t)n - 1);
+            call.down(out.cnt.data() + 1, d_cnt.get() + 1, (size_t)n - 1);
+            if (used) call.down(out.list.data(), d_list.get(), (size_t)used);
+            return call.finish();
+        }
         PNR_REQUIRE(pass == 0, PNR_E_STATE, "reconstruct: ball lists need %llu entries after resizing to %lld", used, cap);
-        B.release(d_list); // too small: sized to what this pass needed, and run again
-        cap = (long long)used;
+        cap = (long long)used; // too small: sized to what this pass needed, and run again
     }
-    out.list.resize((size_t)used);
-    PNR_HIP(hipMemcpyAsync(out.off.data() + 1, d_off + 1, (size_t)(n - 1) * 8, hipMemcpyDeviceToHost, st));
-    PNR_HIP(hipMemcpyAsync(out.cnt.data() + 1, d_cnt + 1, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, st));
-    if (used) PNR_HIP(hipMemcpyAsync(out.list.data(), d_list, (size_t)used * 4, hipMemcpyDeviceToHost, st));
-    PNR_HIP(hipStreamSynchronize(st));
-    return PNR_OK;
 }

@@ -14,7 +14,7 @@
 //   * template offsets / weights are wave-uniform: one coalesced load per row + v_readlane.
 //   * the centroid's own ZNCC rides along as S extra chains of the next iteration.
 //   * early DENSITY stop against the node-density map of earlier seed batches (pnr_trace_replay).
-#include "ctx.h"
+#include "call.h"
 #include "replay.h"
 #include <algorithm>
 #include <cfloat>
@@ -734,14 +734,13 @@ int pnr_density_update(pnr_ctx *c, const pnr::Replayer &r, hipStream_t on)
 int pnr_expf_run(pnr_ctx *c, const float *x, int64_t n, float *y)
 {
     if (n == 0) return PNR_OK;
-    pnr::DevBuf<float> bx, by;
-    PNR_HIP(bx.alloc((size_t)n));
-    PNR_HIP(by.alloc((size_t)n));
-    float *dx = bx.get(), *dy = by.get();
-    PNR_HIP(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(expf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dx, (i64)n, dy);
-    PNR_HIP(hipGetLastError());
-    PNR_HIP(hipMemcpyAsync(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    PNR_HIP(hipStreamSynchronize(c->stream));
-    return PNR_OK;
+    static const char *who = "pnr_expf_batch";
+    pnr::CallBuf buf; // (freed when the call returns)
+    const auto dx = buf.add<float>((size_t)n), dy = buf.add<float>((size_t)n);
+    if (const int rc = buf.alloc(who)) return rc;
+    pnr::Call call(c, who);
+    call.up(dx, x);
+    call.launch(expf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), dx.get(), (i64)n, dy.get());
+    call.down(y, dy);
+    return call.finish();
 }

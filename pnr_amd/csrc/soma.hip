@@ -12,7 +12,7 @@
 // The four kernels are streaming u8 / f32 passes.  Results: one SOMA node per region, a
 // sparse voxel -> node-index map used by the seed filter (:2561-2564), by the replay (tracker.cpp:858-869) and -- written
 // as "saturated" into the GPU density map -- by the trace kernels' early stop.
-#include "ctx.h"
+#include "call.h"
 #include "replay.h"
 #include <algorithm>
 #include <cfloat>
@@ -232,6 +232,7 @@ void grow_regions(const std::vector<i64> &vox, int w, int h, int l, std::vector<
 
 int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold)
 {
+    static const char *who = "pnr_soma";
     c->soma_nodes.clear(); c->soma_vox.clear(); c->soma_lab.clear(); c->soma_map.clear();
     c->have_soma = false;
     if (threshold) *threshold = 0;
@@ -248,64 +249,61 @@ int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold)
     const int Le = (int)std::ceil(rad);
     std::vector<float> G;
     const int Lg = pnr::gaussian_taps(rad, G); // same kernel formula as the 3-D filter (frangi.cpp:791-803)
-    hipStream_t st = c->stream;
-    pnr::DevBuf<float> b_G; // (all freed when the call returns, on every path)
-    pnr::DevBuf<unsigned long long> b_hist;
-    pnr::DevBuf<int> b_cnt;
-    pnr::DevBuf<i64> b_off, b_vox;
     { // a +0 in front of the taps and one behind: the register-tiled x pass reads the neighbours of a tap pairwise (gauss_sums_packed)
         std::vector<float> Gp(G.size() + 2, 0.f);
         std::copy(G.begin(), G.end(), Gp.begin() + 1);
         G.swap(Gp);
     }
-    PNR_HIP(b_G.alloc(G.size()));
-    PNR_HIP(b_hist.alloc(256));
-    PNR_HIP(b_cnt.alloc((size_t)rows));
-    PNR_HIP(b_off.alloc((size_t)rows));
-    float *const d_G = b_G.get();
-    unsigned long long *const d_hist = b_hist.get();
-    int *const d_cnt = b_cnt.get();
-    i64 *const d_off = b_off.get();
-    PNR_HIP(hipMemcpyAsync(d_G, G.data(), G.size() * 4, hipMemcpyHostToDevice, st));
-    PNR_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, st));
+    // device buffers of the call: taps | histogram | foreground voxels per row | their offsets
+    pnr::CallBuf buf; // (freed when the call returns)
+    const auto d_G = buf.add<float>(G.size());
+    const auto d_hist = buf.add<unsigned long long>(256);
+    const auto d_cnt = buf.add<int>((size_t)rows);
+    const auto d_off = buf.add<i64>((size_t)rows);
+    if ((rc = buf.alloc(who))) return rc;
+    pnr::Call call(c, who);
+    call.up(d_G, G.data());
+    call.fill(d_hist, 0);
     unsigned char *d_K = c->d_Vx.get(), *d_E = c->d_Vy.get();
     c->have_v = false; // the direction volumes serve as scratch here
     const unsigned nb = (unsigned)((n + SOMA_BLOCK - 1) / SOMA_BLOCK);
     c->tic();
-    hipLaunchKernelGGL(erode_x, dim3(nb), dim3(SOMA_BLOCK), 0, st, c->d_img, d_K, w, n, Le);
-    hipLaunchKernelGGL(erode_y, dim3(nb), dim3(SOMA_BLOCK), 0, st, (const unsigned char *)d_K, d_E, w, h, n, Le);
-    rc = pnr_gauss_x_u8_launch(c, d_E, c->d_tmpA.get(), d_G + 1, Lg); // K[i0] += I[i1] * G[...], taps ascending, clamp-to-edge (frangi.cpp:806-836)
-    if (rc) return rc;
+    call.launch(erode_x, dim3(nb), dim3(SOMA_BLOCK), c->d_img, d_K, w, n, Le);
+    call.launch(erode_y, dim3(nb), dim3(SOMA_BLOCK), (const unsigned char *)d_K, d_E, w, h, n, Le);
+    if (call.ok() && (rc = pnr_gauss_x_u8_launch(c, d_E, c->d_tmpA.get(), d_G.get() + 1, Lg))) { // K[i0] += I[i1] * G[...], taps ascending, clamp-to-edge (frangi.cpp:806-836)
+        (void)call.finish(); // (its own code and message; the taps' upload is queued)
+        return rc;
+    }
     {
         const int tiles_x = (w + 63) / 64, tiles_y = (h + TYS - 1) / TYS;
         const size_t sm = ((size_t)(TYS + 2 * Lg) * 64 + 2 * Lg + 1) * 4 + 8 * 256 * 4;
-        hipLaunchKernelGGL(gauss_y_trunc_hist, dim3((unsigned)((i64)tiles_x * tiles_y * l)), dim3(256), sm, st, (const float *)c->d_tmpA.get(), d_E,
-                           (const float *)(d_G + 1), w, h, tiles_x, tiles_y, Lg, d_hist);
+        call.launch(gauss_y_trunc_hist, dim3((unsigned)((i64)tiles_x * tiles_y * l)), dim3(256), pnr::Call::Lds{sm}, (const float *)c->d_tmpA.get(), d_E,
+                    (const float *)d_G.get() + 1, w, h, tiles_x, tiles_y, Lg, d_hist.get());
     }
     c->toc("soma", 4);
     unsigned long long hist[256];
-    PNR_HIP(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
-    if (E8_out) PNR_HIP(hipMemcpyAsync(E8_out, d_E, (size_t)n, hipMemcpyDeviceToHost, st));
-    PNR_HIP(hipStreamSynchronize(st));
+    call.down(hist, d_hist);
+    if (E8_out) call.down(E8_out, d_E, (size_t)n);
+    if ((rc = call.finish())) return rc;
     const int th = maxentropy_from_hist(hist);
     if (threshold) *threshold = th;
-    hipLaunchKernelGGL(row_count, dim3((unsigned)rows), dim3(64), 0, st, (const unsigned char *)d_E, w, th, d_cnt);
+    call.launch(row_count, dim3((unsigned)rows), dim3(64), (const unsigned char *)d_E, w, th, d_cnt.get());
     std::vector<int> cnt((size_t)rows);
-    PNR_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-    PNR_HIP(hipStreamSynchronize(st));
+    call.down(cnt.data(), d_cnt);
+    if ((rc = call.finish())) return rc;
     std::vector<i64> off((size_t)rows);
     i64 K = 0;
     for (i64 r = 0; r < rows; r++) { off[(size_t)r] = K; K += cnt[(size_t)r]; }
     c->soma_vox.resize((size_t)K);
     if (K > 0) {
-        PNR_REQUIRE(b_vox.alloc((size_t)K) == hipSuccess, PNR_E_HIP, "out of device memory for %lld soma voxels", (long long)K);
-        i64 *d_vox = b_vox.get();
-        PNR_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)rows * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(row_compact, dim3((unsigned)rows), dim3(64), 0, st, (const unsigned char *)d_E, w, th, (const i64 *)d_off, d_vox);
-        PNR_HIP(hipMemcpyAsync(c->soma_vox.data(), d_vox, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-        PNR_HIP(hipStreamSynchronize(st));
+        pnr::CallBuf vbuf; // the K compacted voxels
+        const auto d_vox = vbuf.add<i64>((size_t)K);
+        if ((rc = vbuf.alloc(who))) return rc;
+        call.up(d_off, off.data());
+        call.launch(row_compact, dim3((unsigned)rows), dim3(64), (const unsigned char *)d_E, w, th, (const i64 *)d_off, d_vox.get());
+        call.down(c->soma_vox.data(), d_vox);
+        if ((rc = call.finish())) return rc;
     }
-    PNR_HIP(hipGetLastError());
     std::vector<i64> vox(c->soma_vox.begin(), c->soma_vox.end());
     grow_regions(vox, w, h, l, c->soma_lab, c->soma_nodes);
     c->soma_map.reserve((size_t)K * 2 + 16);

@@ -60,6 +60,8 @@ def _touch_every_owner(c, img, driver):
     c.reconstruct(nodes, links)
     k, _ = c.measure_radii(np.stack([nodes["x"], nodes["y"], nodes["z"]], 1)[1:])
     assert len(k) == len(nodes) - 1
+    k, _ = c.measure_radii(np.stack([nodes["x"], nodes["y"], nodes["z"]], 1)[1:], rmax=7)  # another shell table: the cached one is rebuilt
+    assert len(k) == len(nodes) - 1
     c.gaussian(2.0)
     c.hessian(2.0)
     A = np.eye(3)[None].repeat(5, 0)

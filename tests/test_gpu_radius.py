@@ -226,6 +226,48 @@ def test_windowed_u16_volume_stream_and_timer():
     ctx.close()
 
 
+def test_shell_table_cache():
+    """one context keeps one shell table: rmax 8, 12, 8 again, then the 2-D table of a one-slice volume and the 3-D one once more, each
+    call equal to a fresh context's that does only that call; the third call holds the device bytes of the first (one table, nothing
+    else left behind), and close returns everything"""
+    import gc
+
+    def live():
+        gc.collect()
+        return lib.live_bytes()[0]
+
+    V = synth.synth(40, 40, 40, seed=6)
+    S = np.ascontiguousarray(V[20:21])
+    rng = np.random.default_rng(12)
+    xyz = rng.random((50, 3)).astype(F) * F(40) - F(0.5)
+    opts = dict(thr=-1, rel_pct=0, bg_permille=800)  # balls that grow until four fifths of them lie below the mean: the tables differ in k
+
+    def fresh(vol, rmax):
+        c = context()
+        c.set_volume(vol)
+        k, t = c.measure_radii(xyz, rmax=rmax, **opts)
+        c.close()
+        return k, t
+
+    want = {(name, rmax): fresh(vol, rmax) for name, vol, rmax in (("3d", V, 8), ("3d", V, 12), ("2d", S, 8))}
+    print({key: np.bincount(k, minlength=13).tolist() for key, (k, _) in want.items()})
+    assert not np.array_equal(want["3d", 8][0], want["3d", 12][0]) and not np.array_equal(want["3d", 8][0], want["2d", 8][0])
+    d0 = live()
+    ctx = context()
+    ctx.set_volume(V)
+    held = []
+    for name, vol, rmax in (("3d", None, 8), ("3d", None, 12), ("3d", None, 8), ("2d", S, 8), ("3d", V, 8)):
+        if vol is not None:
+            ctx.set_volume(vol)
+        k, t = ctx.measure_radii(xyz, rmax=rmax, **opts)
+        held.append(live() - d0)
+        print(f"{name} rmax={rmax}: device bytes held {held[-1]}")
+        assert t == want[name, rmax][1] and np.array_equal(k, want[name, rmax][0]), (name, rmax)
+    assert held[2] == held[0]
+    ctx.close()
+    assert live() == d0
+
+
 def test_errors_leave_the_context_working():
     """no volume: PNR_E_STATE; every option outside its range: PNR_E_ARG; after each the context measures as before"""
     L = lib.load()

@@ -216,6 +216,38 @@ def test_balls_larger_than_the_lds_lists(ctx):
     _same_stages(ctx, allnodes, alllinks)
 
 
+def test_resize_and_bitmap_passes_take_the_same_launches(ctx):
+    """1100 nodes in one unit cube: every grouping ball holds the other 1099, so the lists need 1100 x 1099 > max(2^20, 16 n) entries
+    and the resize pass runs, and both stages leave their large balls to the bitmap kernels.  Same bits as the host, and the launches
+    the timer group "recon" counts are those of the passes, one by one."""
+    rng = np.random.default_rng(13)
+    nodes, links = _chain(200, rng)
+    m = 1100
+    blob = np.zeros(m, lib.NODE_DT)
+    blob["x"] = 40 + rng.random(m).astype(np.float32)
+    blob["y"] = 20 + rng.random(m).astype(np.float32)
+    blob["z"] = 6 + rng.random(m).astype(np.float32)
+    blob["sig"] = rng.choice([2.0, 3.0], m).astype(np.float32)
+    blob["corr"] = rng.uniform(0.3, 0.95, m).astype(np.float32)
+    blob["type"] = 3
+    n0 = len(nodes)
+    allnodes = np.concatenate([nodes, blob])
+    bl = np.stack([np.arange(n0, n0 + m - 1), np.arange(n0 + 1, n0 + m)], 1).astype(np.int32)
+    alllinks = np.concatenate([links, bl, np.array([(n0 - 1, n0)], np.int32)])
+    ctx.set_profiling(True)
+    try:
+        ctx.reset_kernel_ms()
+        _both(ctx, allnodes, alllinks, tree_size_min=2)
+        _, launches = ctx.kernel_ms("recon")
+    finally:
+        ctx.set_profiling(False)
+    print(f"recon launches of one reconstruct: {launches}")
+    # pnr_recon_shift: toc("recon", 4) the grid's bin, scan and scatter with k_shift, toc("recon", 1) k_shift_big           = 5
+    # pnr_recon_balls: toc("recon", 3) the grid; then per pass toc("recon", 1) k_balls and toc("recon", 1) k_balls_big,
+    #                  and there are two passes, the first with too small a list                                           = 3 + 2 * 2
+    assert launches == 12
+
+
 def test_large_traced_stack_matches_host():
     """the full trace loop on a 384^3 synthetic stack: balls span many grid cells, as on the CLI's full stacks"""
     import torch
