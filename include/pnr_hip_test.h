@@ -32,9 +32,34 @@ int pnr_set_j8_v(pnr_ctx *ctx, const uint8_t *J8, const uint8_t *Vx, const uint8
 int pnr_seed_handover(pnr_ctx *ctx, int64_t z0, int64_t z1, int32_t *vmin, int32_t *vmax, int64_t *ltot, int64_t *key_off,
                       int64_t *keys, int64_t cap_keys, int64_t *n_keys, uint8_t *layers, int32_t *restored);
 
+/* The likelihood half of one step of the phased SMC driver (smc_phased.hip) over nt traces whose poses the caller gives, all in one
+ * step list: the placement, fast words and duplicate search of ph_predict (compiled in a form that takes the particles as they are
+ * instead of drawing them), ph_cube (option "cube_copy"), ph_sample and ph_sums, launched as a production step of nt traces launches
+ * them, with the context's options "split_x10", "max_split", "cube_copy", "sums_deep", "share_scales", "share_min".  np = the
+ * context's particle count, S its number of scales, np_pad = (np + 1 + 63) / 64 * 64.
+ *   poses [nt][np][6] the particles (x, y, z, vx, vy, vz), exact duplicates allowed; centroids [nt][6] the pending centroid;
+ *   modes [nt]: PNR_PHL_FIRST no pending centroid, as at iteration 0 (the closing chain reads zeros; centroids[j] is not used),
+ *               PNR_PHL_REGULAR particles and centroid, PNR_PHL_TAIL the centroid only (one chain; poses[j] is not used).
+ * NaN and out-of-volume poses are legal, as in a trace.  Outputs (host, any may be NULL): corr [nt][S][np_pad] the correlation per
+ * scale and CHAIN (0 beyond a trace's chains); uidx [nt][np_pad] chain -> particle (np = the centroid, which closes the list; -1
+ * beyond); cmap [nt][np_pad] particle -> chain (-1 beyond np, and in a tail pass); flags [nt][PNR_PHL_FLAGS] the trace's flag words
+ * (PNR_PHL_OX.. below); info [8]: np_pad, S, sampling work-groups per trace, 1 if guest scales read their hosts' stash, 1 for the
+ * deep form of the sums, 1 if ph_cube ran, chain groups per trace of the sums launch, rounds the traces were evaluated in (1 unless
+ * the sample stash does not hold them all; the forms are those of the first round).
+ * PNR_E_ARG: nt < 1, no volume, not the phased driver, ni < 2, a mode out of range. */
+enum { PNR_PHL_FIRST = 0, PNR_PHL_REGULAR = 1, PNR_PHL_TAIL = 2 };
+enum { PNR_PHL_FLAGS = 16,                   /* words per trace; those the step's likelihood half writes: */
+       PNR_PHL_OX = 5, PNR_PHL_OY = 6, PNR_PHL_OZ = 7, /* the cube's origin in the volume */
+       PNR_PHL_Y0 = 8, PNR_PHL_Y1 = 9, PNR_PHL_Z0 = 10, PNR_PHL_Z1 = 11, /* rows / planes of the cube that are staged: [y0, y1) x [z0, z1) */
+       PNR_PHL_FAST = 12,                    /* bit s: all templates of scale s inside cube and volume; bit 8 + s: inside the volume */
+       PNR_PHL_NCH = 13 };                   /* chains: distinct particle poses + 1 (1 in a tail pass) */
+int pnr_phased_likelihood(pnr_ctx *ctx, int64_t nt, const float *poses, const float *centroids, const int32_t *modes, float *corr,
+                          int32_t *uidx, int32_t *cmap, int32_t *flags, int32_t *info);
+
 /* Tracker tables for parity tests: name in {"p","u","w0","w0_cws","v","w","w_cws","rng",
- * "model_vuw<s>","model_wgt<s>","model_avg","gauss_xy<s>","gauss_z<s>"}.  Copies up to cap
- * 4-byte words into out; *n receives the element count. */
+ * "model_vuw<s>","model_wgt<s>","model_avg","gauss_xy<s>","gauss_z<s>","scale_share"}.  Copies up to cap
+ * 4-byte words into out; *n receives the element count.  "scale_share" (int32): [0, 8) the scale whose stash scale s reads under
+ * option "share_scales" (its host; -1: s samples on its own), [8, 16) s's first entry in the row table. */
 int pnr_get_table(pnr_ctx *ctx, const char *name, void *out, int64_t cap, int64_t *n);
 
 /* expf used for the particle likelihood exp(Kc*corr) (tracker.cpp:1029,1136), exposed so the

@@ -864,8 +864,8 @@ float orc_interp(float _x, float _y, float _z, const uint8_t *img, int width, in
 /* ====================================================================== */
 /*  T1  Tracker::znccBBB                           tracker.cpp:1891-1964  */
 /* ====================================================================== */
-float orc_zncc(orc_tracker *t, float _x, float _y, float _z, float _vx, float _vy, float _vz,
-               const uint8_t *img, int w, int h, int l, float *sig_out)
+float orc_zncc_scales(orc_tracker *t, float _x, float _y, float _z, float _vx, float _vy, float _vz,
+                      const uint8_t *img, int w, int h, int l, float *sig_out, float *per_scale)
 {
     float ux, uy, uz, wx, wy, wz;
     float nrm = (float)sqrt((double)_vx * (double)_vx + (double)_vy * (double)_vy); /* pow(f,2) is f64 */
@@ -911,6 +911,7 @@ float orc_zncc(orc_tracker *t, float _x, float _y, float _z, float _vx, float _v
             corrc = (float)(corrc + (double)dw * (double)dw);
         }
         float corr_val = (corrb * corrc > FLT_MIN) ? corra / sqrtf(corrb * corrc) : 0;
+        if (per_scale) per_scale[s] = corr_val;
         if (corr_val > out_corr) {
             out_corr = corr_val;
             *sig_out = t->sig[s];
@@ -918,6 +919,23 @@ float orc_zncc(orc_tracker *t, float _x, float _y, float _z, float _vx, float _v
     }
     return out_corr;
 }
+
+float orc_zncc(orc_tracker *t, float _x, float _y, float _z, float _vx, float _vy, float _vz,
+               const uint8_t *img, int w, int h, int l, float *sig_out)
+{
+    return orc_zncc_scales(t, _x, _y, _z, _vx, _vy, _vz, img, w, h, l, sig_out, NULL);
+}
+
+void orc_zncc_scales_batch(orc_tracker *t, const float *pd, int64_t n, const uint8_t *img, int w, int h, int l,
+                           float *corr, float *sig, float *per_scale)
+{
+    for (int64_t i = 0; i < n; i++) {
+        const float *q = pd + 6 * i;
+        corr[i] = orc_zncc_scales(t, q[0], q[1], q[2], q[3], q[4], q[5], img, w, h, l, &sig[i], per_scale + (size_t)i * t->nsig);
+    }
+}
+
+int orc_tracker_nsig(const orc_tracker *t) { return t->nsig; }
 
 /* ====================================================================== */
 /*  T3-T7  iter0New / iterINew                     tracker.cpp:1001-1198  */

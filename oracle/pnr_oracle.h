@@ -77,6 +77,13 @@ void orc_glibc_rand(uint32_t seed, int n, uint32_t *out);
 float orc_interp(float x, float y, float z, const uint8_t *img, int w, int h, int l);
 float orc_zncc(orc_tracker *t, float x, float y, float z, float vx, float vy, float vz,
                const uint8_t *img, int w, int h, int l, float *sig_out);
+/* the same, and the correlation of every scale (the values its loop takes the first maximum of) into per_scale[nsig] */
+float orc_zncc_scales(orc_tracker *t, float x, float y, float z, float vx, float vy, float vz,
+                      const uint8_t *img, int w, int h, int l, float *sig_out, float *per_scale);
+/* orc_zncc_scales for n poses pos_dir[n][6]: corr[n], sig[n], per_scale[n][nsig] */
+void orc_zncc_scales_batch(orc_tracker *t, const float *pos_dir, int64_t n, const uint8_t *img, int w, int h, int l,
+                           float *corr, float *sig, float *per_scale);
+int orc_tracker_nsig(const orc_tracker *t);
 
 /* Map-independent part of trackPos: run the particle filter from a seed until
  * iter0New/iterINew returns false or niter is reached.

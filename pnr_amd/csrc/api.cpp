@@ -893,6 +893,16 @@ int pnr_seed_handover(pnr_ctx *c, int64_t z0, int64_t z1, int32_t *vmin, int32_t
     return pnr_seed_handover_run(c, z0, z1, vmin, vmax, ltot, key_off, keys, cap_keys, n_keys, layers, restored);
 }
 
+int pnr_phased_likelihood(pnr_ctx *c, int64_t nt, const float *poses, const float *centroids, const int32_t *modes, float *corr,
+                          int32_t *uidx, int32_t *cmap, int32_t *flags, int32_t *info)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    PNR_REQUIRE(nt >= 1, PNR_E_ARG, "pnr_phased_likelihood: bad number of traces");
+    PNR_REQUIRE(poses && centroids && modes, PNR_E_ARG, "null argument");
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_phased_likelihood_run(c, nt, poses, centroids, modes, corr, uidx, cmap, flags, info);
+}
+
 int pnr_zncc_batch(pnr_ctx *c, const float *pos_dir, int64_t n, float *corr, float *sig)
 {
     PNR_REQUIRE(c && (n == 0 || (pos_dir && corr)), PNR_E_ARG, "null argument");
@@ -1464,6 +1474,7 @@ int pnr_get_table(pnr_ctx *c, const char *name, void *out, int64_t cap, int64_t 
     else if (nm == "w_cws") fv(t.w_cws);
     else if (nm == "model_avg") fv(t.mavg);
     else if (nm == "rng") { src = t.rng.data(); cnt = t.rng.size(); }
+    else if (nm == "scale_share") { src = t.share_tab.data(); cnt = t.share_tab.size(); } // int32 words
     else if (nm.rfind("model_vuw", 0) == 0 || nm.rfind("model_wgt", 0) == 0 || nm.rfind("gauss_xy", 0) == 0 ||
              nm.rfind("gauss_z", 0) == 0) {
         const size_t pre = (nm[0] == 'm') ? 9 : (nm[6] == 'x' ? 8 : 7);

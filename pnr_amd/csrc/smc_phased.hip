@@ -28,6 +28,8 @@
 namespace {
 
 enum { FL_RES = 0, FL_STOP = 1, FL_T = 2, FL_IT = 3, FL_DONE = 4, FL_OX = 5, FL_OY = 6, FL_OZ = 7, FL_Y0 = 8, FL_Y1 = 9, FL_Z0 = 10, FL_Z1 = 11, FL_FAST = 12, FL_NCH = 13, FL_PAUSE = 14, FL_N = 16 };
+static_assert(FL_N == PNR_PHL_FLAGS && FL_OX == PNR_PHL_OX && FL_OY == PNR_PHL_OY && FL_OZ == PNR_PHL_OZ && FL_Y0 == PNR_PHL_Y0 && FL_Y1 == PNR_PHL_Y1 &&
+              FL_Z0 == PNR_PHL_Z0 && FL_Z1 == PNR_PHL_Z1 && FL_FAST == PNR_PHL_FAST && FL_NCH == PNR_PHL_NCH, "the flag words the test tap names (pnr_hip_test.h)");
 constexpr int PH_THREADS = 1024; // sampling work-group: 16 waves (<= 128 VGPRs each)
 constexpr int PH_CS = 54; // the sampling kernel holds nothing but the cube in LDS: 54 x 54 rows of 56 bytes = 163 296 B of the 160 KB (53 costs 1.5 %)
 constexpr int PH_PITCH = 56; // row pitch: a multiple of 4, so that every staged dword lands with one aligned ds_write_b32
@@ -141,6 +143,9 @@ __device__ unsigned long long g_pu_fine[8]; // ph_predict, thread 0: [0] until t
 #define PU_STAMP(var)
 #endif
 
+// GIVEN (the test tap pnr_phased_likelihood only): the particles of the iteration are in P.part already and are taken as they are --
+// nothing is drawn, no prior is written; placement, fast words and the duplicate search run as in production (GIVEN = false)
+template <bool GIVEN>
 __global__ __launch_bounds__(256) void ph_predict(Tab T, TabX X, PhState P, const float *__restrict__ seeds6, Vol V, int np, int ni, int it_arg,
                                                    int lp, int CS, int tbl)
 {
@@ -187,7 +192,9 @@ __global__ __launch_bounds__(256) void ph_predict(Tab T, TabX X, PhState P, cons
         } else {
             if (tail) continue;
             float *q = cur + k * PSTRIDE;
-            if (it == 0) { // iter0New: systematic sample of the isotropic prior (tracker.cpp:1006-1024)
+            if constexpr (GIVEN) {
+                // (the tap wrote the pose)
+            } else if (it == 0) { // iter0New: systematic sample of the isotropic prior (tracker.cpp:1006-1024)
                 const float stepw = T.w0cws[T.sz - 1] / np;
                 const float u1 = stepw * ((float)T.rng[0] / (float)2147483647);
                 const float ui = u1 + k * stepw;
@@ -1150,7 +1157,7 @@ static void smc_step(pnr_ctx *c, const PhEnv &E, hipStream_t st, const PhState &
     auto tic = [&] { if (tm.on) c->tic(st, chain); chain = tm.chain_rest; };
     auto toc = [&](const char *group) { if (tm.on) c->toc(group, 1, st, tm.weight); };
     tic();
-    hipLaunchKernelGGL(ph_predict, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)E.h->d_s6.get(), E.V, np, ni, it, lp, PH_CS, ph_tbl(np));
+    hipLaunchKernelGGL(ph_predict<false>, dim3(active), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)E.h->d_s6.get(), E.V, np, ni, it, lp, PH_CS, ph_tbl(np));
     toc("smc_predict");
     if (P.cubes) {
         tic();
@@ -1350,6 +1357,76 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
         if (O.idxres) PNR_HIP(hipMemcpyAsync(idxres + t0 * dbg_iters * np, O.idxres, (size_t)nt * dbg_iters * np * 4, hipMemcpyDeviceToHost, st));
         if (O.neff) PNR_HIP(hipMemcpyAsync(neff + t0 * dbg_iters, O.neff, (size_t)nt * dbg_iters * 4, hipMemcpyDeviceToHost, st));
         PNR_HIP(hipStreamSynchronize(st));
+    }
+    return PNR_OK;
+}
+
+// Test tap (pnr_hip_test.h pnr_phased_likelihood): the likelihood half of ONE step over nt traces whose particles and pending
+// centroids the caller gives -- ph_predict<true> (placement, fast words, duplicate search; nothing drawn), ph_cube, ph_sample and
+// ph_sums through the launchers and with the launch forms smc_step would pick for a step of this many traces.  No ph_update: the
+// per-scale, per-chain correlations are read back as the sums left them.
+int pnr_phased_likelihood_run(pnr_ctx *c, int64_t nt_all, const float *poses, const float *centroids, const int32_t *modes, float *corr,
+                              int32_t *uidx, int32_t *cmap, int32_t *flags_out, int32_t *info)
+{
+    PNR_REQUIRE(nt_all >= 1 && nt_all < (1LL << 30), PNR_E_ARG, "pnr_phased_likelihood: bad number of traces");
+    PNR_REQUIRE(c->d_img, PNR_E_ARG, "pnr_phased_likelihood: no volume set (pnr_set_volume)");
+    PNR_REQUIRE(c->smc_driver == 0, PNR_E_ARG, "pnr_phased_likelihood: the phased driver only (pnr_set_smc_driver)");
+    PNR_REQUIRE(c->prm.ni >= 2, PNR_E_ARG, "pnr_phased_likelihood: needs ni >= 2 (a regular step is iteration 1 or 2)");
+    for (int64_t j = 0; j < nt_all; j++)
+        PNR_REQUIRE(modes[j] >= PNR_PHL_FIRST && modes[j] <= PNR_PHL_TAIL, PNR_E_ARG, "pnr_phased_likelihood: mode %d of trace %lld", (int)modes[j], (long long)j);
+    PhEnv E;
+    int rc = phased_env(c, nt_all, 0, false, false, false, E);
+    if (rc) return rc;
+    const PhState &P = E.P;
+    const int np = E.np, ni = E.ni, S = E.S, np_pad = E.np_pad;
+    hipStream_t st = c->stream;
+    std::vector<float> part, xcs;
+    std::vector<int> flags, list0;
+    for (int64_t t0 = 0; t0 < nt_all; t0 += E.NT) {
+        const int nt = (int)std::min<int64_t>(E.NT, nt_all - t0);
+        part.assign((size_t)nt * 2 * np * PSTRIDE, 0.f);
+        xcs.assign((size_t)nt * 16, 0.f);
+        flags.assign((size_t)nt * FL_N, 0);
+        list0.resize((size_t)nt);
+        for (int j = 0; j < nt; j++) {
+            const int mode = modes[t0 + j];
+            // a first step is iteration 0; the others alternate between iterations 1 and 2, so that both halves of part / xcs are read
+            const int it = mode == PNR_PHL_FIRST ? 0 : ((ni > 2 && ((t0 + j) & 1)) ? 2 : 1);
+            float *cur = &part[((size_t)j * 2 + (it & 1)) * np * PSTRIDE];
+            const float *q = poses + (size_t)(t0 + j) * np * 6;
+            for (int k = 0; k < np; k++)
+                for (int a = 0; a < 6; a++) cur[(size_t)k * PSTRIDE + a] = q[(size_t)k * 6 + a];
+            if (mode != PNR_PHL_FIRST) // (before the first centroid exists the closing chain reads zeros)
+                for (int a = 0; a < 6; a++) xcs[(size_t)j * 16 + ((it & 1) ^ 1) * 8 + a] = centroids[(size_t)(t0 + j) * 6 + a];
+            int *fl = &flags[(size_t)j * FL_N];
+            fl[FL_IT] = it; fl[FL_T] = ni; fl[FL_STOP] = mode == PNR_PHL_TAIL ? 2 : 0;
+            list0[(size_t)j] = j;
+        }
+        const int cnt0[2] = {nt, 0};
+        PNR_HIP(hipMemcpyAsync(P.part, part.data(), part.size() * 4, hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemcpyAsync(P.xcs, xcs.data(), xcs.size() * 4, hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemcpyAsync(P.flags, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemcpyAsync(P.list, list0.data(), list0.size() * 4, hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemcpyAsync(P.cnt, cnt0, sizeof(cnt0), hipMemcpyHostToDevice, st));
+        PNR_HIP(hipMemsetAsync(P.corr, 0, (size_t)nt * S * np_pad * 4, st)); // chains a trace does not have stay 0 / -1
+        PNR_HIP(hipMemsetAsync(P.uidx, 0xff, (size_t)nt * np_pad * 4, st));
+        PNR_HIP(hipMemsetAsync(P.cmap, 0xff, (size_t)nt * np_pad * 4, st));
+        const int nsplit = pick_nsplit(nt, E.ncu, E.max_split, c->opt.split_x10), share = share_scales(c, nt);
+        const bool deep = sums_deep(c, nt, 1);
+        hipLaunchKernelGGL(ph_predict<true>, dim3(nt), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)E.h->d_s6.get(), E.V, np, ni, -1, 0, PH_CS, ph_tbl(np));
+        if (P.cubes) hipLaunchKernelGGL(ph_cube, dim3((unsigned)(nt * PH_CUBE_SPLIT)), dim3(PH_CUBE_THREADS), 0, st, E.V, P, 0, nt);
+        launch_sample(st, E.V, E.T, E.X, P, np, ni, -1, 0, nt, nsplit, E.cube_bytes, share);
+        launch_sums(st, E.T, E.X, P, np, np_pad, ni, -1, 0, nt, E.ng, deep, share);
+        PNR_HIP(hipGetLastError());
+        if (corr) PNR_HIP(hipMemcpyAsync(corr + (size_t)t0 * S * np_pad, P.corr, (size_t)nt * S * np_pad * 4, hipMemcpyDeviceToHost, st));
+        if (uidx) PNR_HIP(hipMemcpyAsync(uidx + (size_t)t0 * np_pad, P.uidx, (size_t)nt * np_pad * 4, hipMemcpyDeviceToHost, st));
+        if (cmap) PNR_HIP(hipMemcpyAsync(cmap + (size_t)t0 * np_pad, P.cmap, (size_t)nt * np_pad * 4, hipMemcpyDeviceToHost, st));
+        if (flags_out) PNR_HIP(hipMemcpyAsync(flags_out + (size_t)t0 * FL_N, P.flags, (size_t)nt * FL_N * 4, hipMemcpyDeviceToHost, st));
+        PNR_HIP(hipStreamSynchronize(st)); // (the uploads come from pageable host vectors reused in the next round)
+        if (info && t0 == 0) { // the launch forms of the first (normally the only) round
+            info[0] = np_pad; info[1] = S; info[2] = nsplit; info[3] = share; info[4] = deep ? 1 : 0; info[5] = P.cubes ? 1 : 0;
+            info[6] = E.ng; info[7] = (int)((nt_all + E.NT - 1) / E.NT);
+        }
     }
     return PNR_OK;
 }

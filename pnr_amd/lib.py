@@ -260,6 +260,7 @@ def load():
     L.pnr_hessian.argtypes = [vp, C.c_float] + [vp] * 6
     L.pnr_set_j8_v.argtypes = [vp] + [vp] * 4
     L.pnr_seed_handover.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
+    L.pnr_phased_likelihood.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pnr_extract_seeds.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.pnr_extract_seeds_range.argtypes = [vp, i64, i64, C.POINTER(vp), C.POINTER(i64)]
     L.pnr_zncc_batch.argtypes = [vp, vp, i64, vp, vp]
@@ -325,7 +326,7 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
                 "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes", "pnr_render_items", "pnr_test_write_tiff",
-                "pnr_seed_handover"]
+                "pnr_seed_handover", "pnr_phased_likelihood"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -349,6 +350,11 @@ def make_params(sigmas=(2, 4, 6), somaradius=0, tolerance=5, znccth=0.3, kappa=3
     for k, v in const.items():
         setattr(p, k, v)
     return p
+
+
+# pnr_phased_likelihood (include/pnr_hip_test.h): modes and the flag words it returns
+PHL_FIRST, PHL_REGULAR, PHL_TAIL = 0, 1, 2
+PHL_OX, PHL_OY, PHL_OZ, PHL_Y0, PHL_Y1, PHL_Z0, PHL_Z1, PHL_FAST, PHL_NCH = 5, 6, 7, 8, 9, 10, 11, 12, 13
 
 
 # what a new Context starts with (tests run every case with both SMC drivers by patching this; the library itself reads no
@@ -764,6 +770,26 @@ class Context:
         out["keys"] = keys[:n.value]
         return out
 
+    def phased_likelihood(self, poses, centroids, modes):
+        """test tap pnr_phased_likelihood: the likelihood half of one phased SMC step over the given traces -- poses (nt, np, 6),
+        centroids (nt, 6), modes (nt,) in PHL_FIRST / PHL_REGULAR / PHL_TAIL.  Returns corr (nt, S, np_pad) per scale and chain, uidx
+        and cmap (nt, np_pad), flags (nt, 16) (PHL_OX .. PHL_NCH) and info: the launch forms the step took"""
+        n_p, S = int(self.p.np), int(self.p.nsig)
+        poses = np.ascontiguousarray(poses, np.float32)
+        cen = np.ascontiguousarray(centroids, np.float32)
+        modes = np.ascontiguousarray(modes, np.int32)
+        nt = len(modes)
+        if poses.shape != (nt, n_p, 6) or cen.shape != (nt, 6):
+            raise PnrError(f"poses {poses.shape} / centroids {cen.shape} for {nt} traces of {n_p} particles")
+        np_pad = (n_p + 1 + 63) // 64 * 64
+        out = dict(corr=np.zeros((nt, S, np_pad), np.float32), uidx=np.zeros((nt, np_pad), np.int32), cmap=np.zeros((nt, np_pad), np.int32),
+                   flags=np.zeros((nt, 16), np.int32))
+        info = np.zeros(8, np.int32)
+        check(self.L.pnr_phased_likelihood(self.h, nt, poses.ctypes.data, cen.ctypes.data, modes.ctypes.data, out["corr"].ctypes.data,
+                                           out["uidx"].ctypes.data, out["cmap"].ctypes.data, out["flags"].ctypes.data, info.ctypes.data))
+        out["info"] = dict(zip(("np_pad", "S", "nsplit", "share", "deep", "cube_copy", "ng", "rounds"), (int(v) for v in info)))
+        return out
+
     def zncc(self, pos_dir):
         pd = np.ascontiguousarray(pos_dir, np.float32).reshape(-1, 6)
         corr = np.empty(len(pd), np.float32)
@@ -900,7 +926,7 @@ class Context:
     def table(self, name):
         n = C.c_int64()
         check(self.L.pnr_get_table(self.h, name.encode(), None, 0, C.byref(n)))
-        out = np.empty(n.value, np.uint32 if name == "rng" else np.float32)
+        out = np.empty(n.value, np.uint32 if name == "rng" else np.int32 if name == "scale_share" else np.float32)
         check(self.L.pnr_get_table(self.h, name.encode(), out.ctypes.data, n.value, C.byref(n)))
         return out
 

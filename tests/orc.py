@@ -57,6 +57,10 @@ def load_oracle():
     L.orc_interp.restype = C.c_float
     L.orc_zncc.argtypes = [C.c_void_p] + [C.c_float] * 6 + [u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.orc_zncc.restype = C.c_float
+    L.orc_zncc_scales.argtypes = [C.c_void_p] + [C.c_float] * 6 + [u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), f32p]
+    L.orc_zncc_scales.restype = C.c_float
+    L.orc_zncc_scales_batch.argtypes = [C.c_void_p, f32p, C.c_int64, u8p, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p]
+    L.orc_zncc_scales_batch.restype = None
     L.orc_trace.argtypes = [C.c_void_p, f32p, u8p, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_int), C.c_int,
                             C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_trace.restype = C.c_int
@@ -195,6 +199,17 @@ class Tracker:
             corr[i] = self.L.orc_zncc(self.h, *[float(v) for v in q], img, w, h, l, C.byref(s))
             sig[i] = s.value
         return corr, sig
+
+    def zncc_scales(self, img, pos_dir):
+        """orc_zncc and the correlation of every scale: corr [n], sig [n], per_scale [n][nsig] (orc_zncc's corr is the first maximum
+        over per_scale, its sigma that scale's)"""
+        l, h, w = img.shape
+        pd = np.ascontiguousarray(np.asarray(pos_dir, np.float32).reshape(-1, 6))
+        corr = np.zeros(len(pd), np.float32)
+        sig = np.zeros(len(pd), np.float32)
+        per = np.zeros((len(pd), len(self.sigs)), np.float32)
+        self.L.orc_zncc_scales_batch(self.h, pd, len(pd), np.ascontiguousarray(img, np.uint8), w, h, l, corr, sig, per)
+        return corr, sig, per
 
     def trace(self, img, seed6, max_dbg=0):
         l, h, w = img.shape

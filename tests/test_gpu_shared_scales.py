@@ -43,7 +43,9 @@ def _seeds(p, img, n):
     return s[:: max(1, len(s) // n)][:n]
 
 
-# np + 1 chains: 51 (last group 64 wide), 41, 21 (32), 11 (16), 64 + 1 (a full group and a last one of one chain)
+# AT MOST np + 1 chains -- 51 (last group 64 wide), 41, 21 (32), 11 (16), 64 + 1 (a full group and a last one of one chain): exact
+# duplicates among the particles share a chain, so what a step really has is whatever the resampling left.  The chain counts and
+# stash strides themselves are pinned, as inputs, by tests/test_gpu_phased_likelihood.py.
 @pytest.mark.parametrize("sigs,np_", [((2.0, 4.0, 6.0), 50), ((2.0, 4.0, 6.0), 40), ((2.0, 4.0), 20), ((4.0, 2.0), 10),
                                       ((2.0, 4.0, 6.0), 64), ((2.0, 3.0, 4.0), 30)])
 def test_trace_batch_per_chain_corr(sigs, np_):

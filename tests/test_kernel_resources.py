@@ -60,7 +60,8 @@ def test_register_and_scratch_budgets(compiled):
     assert deep["VGPRs"] <= 128 and deep["ScratchSize"] == 0, deep          # 4 x 96 + 128 = 512
     own, _ = find(usage, "ph_sampleILi54ELb0ELb0EE")  # option cube_copy = 0: every work-group stages its cube from the image
     assert own["VGPRs"] <= 96 and own["ScratchSize"] <= 32, own
-    for frag in ("ph_predict", "ph_update", "ph_cube"):
+    # ph_predict<false> is the production kernel; <true> (the particles are given: test tap pnr_phased_likelihood) only drops code
+    for frag in ("ph_predictILb0EE", "ph_predictILb1EE", "ph_update", "ph_cube"):
         u, _ = find(usage, frag)
         assert u["ScratchSize"] == 0 and u["VGPRs"] <= 128, (frag, u)
 
