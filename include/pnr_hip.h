@@ -608,6 +608,63 @@ typedef struct pnr_edt_info {
 int pnr_distance_transform(pnr_ctx *ctx, const pnr_edt_opts *opts /* NULL = defaults */, pnr_edt_info *info /* nullable */, float *d2_out /* N, nullable */,
                            const float *xyz /* n x 3, nullable when n == 0 */, int64_t n, float *d2_at /* n */);
 
+/* Thinning the foreground of the traced volume to a curve skeleton (beyond the reference, which has no thinning): the step of a
+ * Vaa3D-style pipeline that turns a binary object into a one-voxel-wide centre line and reads that as a tree.  Two uses: a second,
+ * topological trace of the same stack that shares no code or parameter with the particle tracer (to score against, pnr_tree_distance),
+ * and the residual of a trace (pnr_tree_coverage) as SWC fragments that pnr_geodesic_bridges can attach to it.
+ * THE RULE (the contract; tests restate it in numpy).  Everything is an exact integer operation.  V is the context's traced u8 volume
+ * (w x h x l, owned or borrowed; windowed and filtered as traced), N = w * h * l.  Options {thr, max_rounds}; opts = NULL = {-1, 0}.
+ *   Object: V >= t.  t = thr, or for thr == -1: max(1, floor(sum(V) / N)) from the exact u64 sum (the same kernel as the radii, the
+ *     coverage, the components and the distance transform).  t is reported as thr_used.  Voxels outside the volume are background.
+ *     params.zdist plays no part: thinning is topological.
+ *   Neighbourhoods of a voxel p: N6, N18 and N26 are the voxels that differ from p by at most 1 in every coordinate and in exactly 1, at
+ *     most 2, at most 3 coordinates; none contains p.  Connectivity is (26, 6): 26 for the object, 6 for the background.
+ *   Simple point (Malandain-Bertrand): p is simple when (a) the object voxels of N26(p) are non-empty and form exactly one 26-connected
+ *     set within N26(p), and (b) the background voxels of N6(p) are non-empty and all lie in one 6-connected set of the background
+ *     voxels of N18(p).  Deleting a simple point changes neither the object's 26-components, nor the background's 6-components, nor the
+ *     tunnels.
+ *   End point: exactly one voxel of N26(p) is object.
+ *   Subfield: s(p) = (x & 1) | (y & 1) << 1 | (z & 1) << 2 of p = (x, y, z).  Two voxels of one subfield are never 26-adjacent.
+ *   One round: first the object voxels with a background voxel in N6 are marked as candidates, taken at the round's start.  Then for
+ *     s = 0..7 in order one pass: every candidate of subfield s that is still object is deleted if, in the image as it stands at the
+ *     start of that pass, it is simple and not an end point; all deletions of a pass happen at once.  Rounds repeat until a round
+ *     deletes nothing or max_rounds rounds have run (0: no limit).  rounds counts the rounds run, the last, empty one included.
+ *   Why the rule is exact: within a pass no deleted voxel lies in another's N26, so the simultaneous deletion equals a sequential one in
+ *     any order; topology is preserved exactly, and the rule fixes every bit whatever the tiling or launch cut.  A pass runs in place: a
+ *     thread reads voxels of other subfields, which do not change during the pass, and writes only its own.  The marking runs in place
+ *     too: it only switches object voxels between two non-zero states.
+ *   Output: skel(p) = 255 for what is left of the object, else 0.  The skeleton voxels in ascending linear index x + w * (y + h * z)
+ *     with their degree, the number of skeleton voxels in N26.  Summary pnr_thin_info (exact): n_vox = N, n_fg, n_skel, n_end / n_branch
+ *     / n_isolated (the skeleton voxels of degree 1, >= 3 and 0), tiles (the work-group tiles of the volume), tile_visits (the tiles the
+ *     passes visited: 8 * tiles in the first round; later a tile is visited only if it or one of its 26 neighbour tiles deleted
+ *     something during the previous round or the completed passes of this one -- decided from completed passes only, so the count is
+ *     deterministic; it is a property of the implementation, not of the rule), rounds, thr_used.
+ * pnr_skeletonize: never writes V (also not a borrowed one) and leaves the pipeline state of the context alone.  info, skel_out (N),
+ *   vox_out and deg_out are nullable; the first min(cap, n_skel) entries of vox_out and deg_out are filled, info->n_skel is always the
+ *   full count.  Arguments (anything else: PNR_E_ARG): thr in -1..255, max_rounds >= 0, cap >= 0, N at most 2^32 - 2 (as for the
+ *   components).  No volume in the context: PNR_E_STATE.  PNR_E_NOMEM: an allocation failed.  It runs on the context's stream
+ *   (pnr_set_stream), uses 64-bit voxel indices and frees every device buffer of the call before it returns.  Device memory of a call:
+ *   N bytes of state, 8 bytes per tile of 32 x 8 x 8 voxels (stamps and the visit list), N / 1024 bytes of chunk counts, 64 bytes of
+ *   counters, and 5 n_skel bytes for the list.  Kernel times: pnr_get_kernel_ms group "thin" = the sum of "thin_threshold" (the byte sum
+ *   of thr = -1), "thin_init", "thin_mark", "thin_pass" (with the visit plans between the passes), "thin_list" and "thin_finish".
+ * pnr_skeleton_forest: the skeleton as a forest, pure host, no context.  Nodes are the k voxels vox (distinct linear indices of a
+ *   w x h x l grid, any order); edges are the 26-adjacent pairs.  The output is the unique minimum spanning forest under the total order
+ *   (squared step length 1 / 2 / 3, then lo, then hi) as pnr_bridge {lo, hi, d = sqrtf(len2)} with lo < hi node indices, sorted by
+ *   (lo, hi): short links win, so junction triangles open at their diagonal.  *n_edges = k - components, always the full count; the
+ *   first min(cap, *n_edges) entries of edges_out (nullable) are filled.  Feeding the edges to pnr_join_reroot with an all-roots parent
+ *   gives parents and tree order.  PNR_E_ARG: k < 0 or above 2^31 - 1, a grid extent below 1, an index outside the grid or listed
+ *   twice, cap < 0. */
+typedef struct pnr_thin_opts {
+    int32_t thr, max_rounds;
+} pnr_thin_opts; /* NULL = {-1, 0} */
+typedef struct pnr_thin_info {
+    int64_t n_vox, n_fg, n_skel, n_end, n_branch, n_isolated, tiles, tile_visits;
+    int32_t rounds, thr_used;
+} pnr_thin_info;
+int pnr_skeletonize(pnr_ctx *ctx, const pnr_thin_opts *opts /* NULL = defaults */, pnr_thin_info *info /* nullable */, uint8_t *skel_out /* N, 0 / 255, nullable */,
+                    int64_t *vox_out /* linear indices, ascending, nullable */, uint8_t *deg_out /* nullable */, int64_t cap);
+int pnr_skeleton_forest(const int64_t *vox /* k */, int64_t k, int64_t w, int64_t h, int64_t l, pnr_bridge *edges_out /* nullable */, int64_t cap, int64_t *n_edges);
+
 /* Gray-weighted geodesic distance through the traced volume (beyond the reference): every voxel gets the cost of the cheapest 26-connected
  * path to the nearest of n source points, where a step costs its length times the darkness of the two voxels it joins, together with the
  * label of that source, and the path itself for a list of targets.  The tree distance, pnr_join_trees, pnr_measure_radii and the distance

@@ -16,6 +16,7 @@
 #include "render.h"
 #include "components.h"
 #include "edt.h"
+#include "thin.h"
 #include "geodesic.h"
 #include "geojoin.h"
 #include "../host/stack_io.h"
@@ -382,6 +383,78 @@ int pnr_distance_transform(pnr_ctx *c, const pnr_edt_opts *opts, pnr_edt_info *i
     PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
     PNR_HIP(hipSetDevice(c->device));
     return pnr_edt_run(c, who, o, info, d2_out, xyz, n, d2_at);
+}
+
+// pnr_skeletonize (thin.hip): arguments first, then the state; the pipeline state of the context is neither needed nor touched
+int pnr_skeletonize(pnr_ctx *c, const pnr_thin_opts *opts, pnr_thin_info *info, uint8_t *skel_out, int64_t *vox_out, uint8_t *deg_out, int64_t cap)
+{
+    static const char *who = "pnr_skeletonize";
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    const pnr_thin_opts o = opts ? *opts : pnr_thin_opts{-1, 0};
+    PNR_REQUIRE(o.thr >= -1 && o.thr <= 255, PNR_E_ARG, "%s: thr = %d outside [-1, 255]", who, o.thr);
+    PNR_REQUIRE(o.max_rounds >= 0, PNR_E_ARG, "%s: max_rounds = %d is negative", who, o.max_rounds);
+    PNR_REQUIRE(cap >= 0, PNR_E_ARG, "%s: cap = %lld is negative", who, (long long)cap);
+    PNR_REQUIRE(c->d_img, PNR_E_STATE, "%s: no volume set", who);
+    PNR_REQUIRE(c->N <= 0xfffffffeLL, PNR_E_ARG, "%s: %lld voxels, at most 2^32 - 2", who, (long long)c->N);
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_thin_run(c, who, o, info, skel_out, vox_out, deg_out, cap);
+}
+
+// pnr_skeleton_forest: pure host.  Kruskal over the 26-adjacent pairs under (len2, lo, hi); every key is distinct, so the forest is unique
+int pnr_skeleton_forest(const int64_t *vox, int64_t k, int64_t w, int64_t h, int64_t l, pnr_bridge *edges_out, int64_t cap, int64_t *n_edges)
+{
+    static const char *who = "pnr_skeleton_forest";
+    PNR_REQUIRE(n_edges, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(k >= 0 && k <= 0x7fffffffLL && (k == 0 || vox), PNR_E_ARG, "%s: k = %lld voxels (0 to 2^31 - 1) need vox", who, (long long)k);
+    PNR_REQUIRE(w >= 1 && h >= 1 && l >= 1 && w < (1LL << 31) && h < (1LL << 31) && l < (1LL << 31) && w * h <= (1LL << 40) / l, PNR_E_ARG, "%s: grid %lld x %lld x %lld", who,
+                (long long)w, (long long)h, (long long)l);
+    PNR_REQUIRE(cap >= 0, PNR_E_ARG, "%s: cap = %lld is negative", who, (long long)cap);
+    const int64_t N = w * h * l;
+    std::vector<std::pair<int64_t, int32_t>> at((size_t)k); // (voxel, node), sorted by voxel
+    for (int64_t i = 0; i < k; i++) {
+        PNR_REQUIRE(vox[i] >= 0 && vox[i] < N, PNR_E_ARG, "%s: voxel %lld of node %lld is outside the grid", who, (long long)vox[i], (long long)i);
+        at[(size_t)i] = {vox[i], (int32_t)i};
+    }
+    std::sort(at.begin(), at.end());
+    for (int64_t i = 1; i < k; i++) PNR_REQUIRE(at[(size_t)i].first != at[(size_t)i - 1].first, PNR_E_ARG, "%s: voxel %lld is listed twice", who, (long long)at[(size_t)i].first);
+    struct Edge {
+        int32_t len2, lo, hi;
+    };
+    std::vector<Edge> edges;
+    for (int64_t i = 0; i < k; i++) {
+        const int64_t v = at[(size_t)i].first, x = v % w, y = v / w % h, z = v / (w * h);
+        for (int dz = 0; dz <= 1; dz++)
+            for (int dy = -1; dy <= 1; dy++)
+                for (int dx = -1; dx <= 1; dx++) {
+                    if (!(dz > 0 || dy > 0 || (dy == 0 && dx > 0))) continue; // the 13 forward neighbours
+                    const int64_t nx = x + dx, ny = y + dy, nz = z + dz;
+                    if (nx < 0 || nx >= w || ny < 0 || ny >= h || nz >= l) continue;
+                    const int64_t u = (nz * h + ny) * w + nx;
+                    const auto it = std::lower_bound(at.begin() + i + 1, at.end(), std::make_pair(u, (int32_t)0));
+                    if (it == at.end() || it->first != u) continue;
+                    const int32_t a = at[(size_t)i].second, b = it->second;
+                    edges.push_back(Edge{dx * dx + dy * dy + dz * dz, std::min(a, b), std::max(a, b)});
+                }
+    }
+    std::sort(edges.begin(), edges.end(), [](const Edge &p, const Edge &q) { return p.len2 != q.len2 ? p.len2 < q.len2 : p.lo != q.lo ? p.lo < q.lo : p.hi < q.hi; });
+    std::vector<int32_t> up((size_t)k);
+    for (int64_t i = 0; i < k; i++) up[(size_t)i] = (int32_t)i;
+    auto find = [&](int32_t a) {
+        while (up[(size_t)a] != a) a = up[(size_t)a] = up[(size_t)up[(size_t)a]];
+        return a;
+    };
+    std::vector<Edge> kept;
+    for (const Edge &e : edges) {
+        const int32_t a = find(e.lo), b = find(e.hi);
+        if (a == b) continue;
+        up[(size_t)std::max(a, b)] = std::min(a, b);
+        kept.push_back(e);
+    }
+    std::sort(kept.begin(), kept.end(), [](const Edge &p, const Edge &q) { return p.lo != q.lo ? p.lo < q.lo : p.hi < q.hi; });
+    *n_edges = (int64_t)kept.size();
+    const size_t fill = edges_out ? (size_t)std::min<int64_t>(cap, *n_edges) : 0;
+    for (size_t i = 0; i < fill; i++) edges_out[i] = pnr_bridge{kept[i].lo, kept[i].hi, sqrtf((float)kept[i].len2)};
+    return PNR_OK;
 }
 
 // pnr_geodesic_distance (geodesic.hip): arguments first, then the state; the pipeline state of the context is neither needed nor touched
@@ -1541,6 +1614,18 @@ int pnr_get_kernel_ms(pnr_ctx *c, const char *group, double *ms, int64_t *launch
         *ms = 0;
         if (launches) *launches = 0;
         for (const char *g : {"edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"}) {
+            double a = 0;
+            int64_t la = 0;
+            pnr_get_kernel_ms(c, g, &a, &la);
+            *ms += a;
+            if (launches) *launches += la;
+        }
+        return PNR_OK;
+    }
+    if (std::strcmp(group, "thin") == 0) { // one sub-group per phase (thin.hip)
+        *ms = 0;
+        if (launches) *launches = 0;
+        for (const char *g : {"thin_threshold", "thin_init", "thin_mark", "thin_pass", "thin_list", "thin_finish"}) {
             double a = 0;
             int64_t la = 0;
             pnr_get_kernel_ms(c, g, &a, &la);

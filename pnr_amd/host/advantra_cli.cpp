@@ -50,6 +50,11 @@
 //   [--geo-out PREFIX]: the gray-weighted geodesic distance of every voxel to the tree (pnr_geodesic_distance on device -g; the volume setup
 //   of --edt; sources: the tree's sample points labelled with their node ids) as one JSON line; --per-node writes `id,d,label` per node of
 //   other.swc, --paths every complete path as a chain of SWC nodes, --geo-out PREFIX_d.raw (u32) and PREFIX_label.raw (i32).
+//   --skeleton -i stack [--threshold T] [--skeleton-rounds R] [--zscale Z] [--skeleton-out OUT.tif|.raw] [--swc OUT.swc]: the stack's foreground
+//   thinned to a one-voxel-wide curve skeleton (pnr_skeletonize on device -g; the volume setup of --components) as one JSON line with the
+//   fields of pnr_thin_info and "trees"; --skeleton-out writes the 0 / 255 volume, --swc the skeleton as a tree (pnr_skeleton_forest, then
+//   pnr_join_reroot at the thickest voxel; radius = the distance transform at the voxel with zdist = Z; the comment block ends in
+//   #skeleton=thr:T,rounds:R,voxels:K,trees:C): an independent baseline for --distance, and fragments for --join-swc --join-geodesic.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -143,6 +148,8 @@ int main(int argc, char **argv)
     bool edt = false, edt_flag = false;
     advantra::GeodesicJob geo_job;
     bool geo = false, geo_flag = false;
+    advantra::SkeletonJob skel_job;
+    bool skeleton = false, skel_flag = false;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--geodesic")) { geo = true; continue; }
@@ -162,6 +169,22 @@ int main(int argc, char **argv)
             }
             (flag == "--from" ? geo_job.from : flag == "--to" ? geo_job.to : flag == "--paths" ? geo_job.paths : geo_job.out) = name;
             geo_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--skeleton")) { skeleton = true; continue; }
+        if (!strcmp(argv[i], "--skeleton-rounds")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 0, 0x7fffffffL, v)) { fprintf(stderr, "--skeleton-rounds R: the thinning rounds run at the most, an integer, 0 (until nothing is deleted) or more\n"); return 1; }
+            skel_job.opts.max_rounds = (int32_t)v;
+            skel_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--skeleton-out") || !strcmp(argv[i], "--swc")) {
+            const bool out = !strcmp(argv[i], "--skeleton-out");
+            const std::string name = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (name.empty()) { fprintf(stderr, "%s\n", out ? "--skeleton-out OUT: a .tif or .raw file name" : "--swc OUT.swc"); return 1; }
+            (out ? skel_job.out : skel_job.swc) = name;
+            skel_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--components")) { components = true; continue; }
@@ -187,7 +210,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "--threshold")) {
             long v = 0;
             if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
-            comp.opts.thr = edt_job.opts.thr = geo_job.opts.thr = (int32_t)v;
+            comp.opts.thr = edt_job.opts.thr = geo_job.opts.thr = skel_job.opts.thr = (int32_t)v;
             thr_flag = true;
             continue;
         }
@@ -423,8 +446,8 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool rendering = !render.swc.empty();
-    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt && !geo) || (zscale_flag && !distance && join_in.empty() && !rendering && !components && !edt && !geo)) {
-        fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc; --zscale, --per-node: or --render-swc, --edt or --geodesic)\n");
+    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt && !geo) || (zscale_flag && !distance && join_in.empty() && !rendering && !components && !edt && !geo && !skeleton)) {
+        fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc or --skeleton; --zscale, --per-node: or --render-swc, --edt or --geodesic)\n");
         return 1;
     }
     if (render_flag && !rendering) { fprintf(stderr, "--radius-scale / --radius-add / --coverage-threshold need --render-swc IN.swc\n"); return 1; }
@@ -432,10 +455,21 @@ int main(int argc, char **argv)
     if (join_thr_flag && !join_geodesic) { fprintf(stderr, "--join-threshold needs --join-geodesic D\n"); return 1; }
     if (join_flag && !join_given && !join_geodesic && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP, --join-geodesic D or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
-    if ((comp_flag && !components) || (thr_flag && !components && !edt && !geo)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt or --geodesic)\n"); return 1; }
+    if ((comp_flag && !components) || (thr_flag && !components && !edt && !geo && !skeleton)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt, --geodesic or --skeleton)\n"); return 1; }
+    if (skel_flag && !skeleton) { fprintf(stderr, "--skeleton-rounds / --skeleton-out / --swc need --skeleton -i stack\n"); return 1; }
     if (edt_flag && !edt) { fprintf(stderr, "--edt-max / --edt-out / --at need --edt -i stack\n"); return 1; }
     if (geo_flag && !geo) { fprintf(stderr, "--from / --to / --paths / --geo-max / --geo-out need --geodesic -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (skeleton) {
+        if (geo || geo_flag || edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic ||
+            per_node_flag || !paras.empty()) {
+            fprintf(stderr, "--skeleton: not with a tracing run (-p), --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius or --per-node\n");
+            return 1;
+        }
+        if (infiles.empty()) { fprintf(stderr, "--skeleton needs -i <stack>\n"); return 1; }
+        if (zscale_flag && dist_opts.zscale < 1.f) { fprintf(stderr, "--skeleton: --zscale Z: a number, 1 or more\n"); return 1; }
+        return advantra::skeleton_file(skel_job, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, device) ? 0 : 1;
+    }
     if (geo) {
         if (edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic || !paras.empty()) {
             fprintf(stderr, "--geodesic: not with a tracing run (-p), --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle or --measure-radius\n");

@@ -103,6 +103,15 @@ void print_flags()
     printf("  --paths OUT.swc           with --to: every complete path as a chain of SWC nodes that ends on the tree (paths of more than\n");
     printf("                            min(%d, 2^26 / nodes) voxels are left out and counted on stderr)\n", PNR_GEO_MAX_PATH);
     printf("  --geo-out PREFIX          write PREFIX_d.raw (little-endian uint32, 4294967295: unreached) and PREFIX_label.raw (int32, -1: unreached)\n");
+    printf("--skeleton -i stack       the stack's foreground thinned to a one-voxel-wide curve skeleton on the GPU (the same volume setup as tracing;\n");
+    printf("                          topology-preserving: simple points that are no end points go, subfield by subfield); one JSON line: n_vox, n_fg,\n");
+    printf("                          n_skel, n_end, n_branch, n_isolated, tiles, tile_visits, rounds, thr_used, trees\n");
+    printf("  --threshold T             foreground from T on, 0..255 (default -1: the stack's mean)\n");
+    printf("  --skeleton-rounds R       at most R thinning rounds (default 0: until nothing is deleted)\n");
+    printf("  --zscale Z                z counts Z-fold in the radii of --swc, 1 or more (default 1)\n");
+    printf("  --skeleton-out OUT        write the skeleton (255) as a multi-page 8-bit TIFF, or bare bytes for a .raw name\n");
+    printf("  --swc OUT.swc             write the skeleton as a tree rooted at its thickest voxel: radius = the distance to the background, type 2,\n");
+    printf("                            every parent before its children; the comment block ends in #skeleton=thr:T,rounds:R,voxels:K,trees:C\n");
     printf("--measure-radius          SWC radii measured from the image at the final nodes (default: SIG2RADIUS * the winning scale)\n");
     printf("--radius-rel PCT          relative mode (default, 50): background below PCT %% of the node's brightest centre voxel, 1..100\n");
     printf("--radius-threshold T      absolute mode: background below T, 0..255; -1: below the stack's mean\n");

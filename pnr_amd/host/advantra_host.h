@@ -201,6 +201,18 @@ struct GeodesicJob {
     std::string from, to, per_node, paths, out;
 };
 bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
+// advantra_cli --skeleton -i stack: the stack's foreground thinned to a one-voxel-wide curve skeleton (pnr_skeletonize on `device`; the same
+// volume setup as --components; zscale >= 1 is the context's zdist, which only the radii see).  One JSON line with the fields of
+// pnr_thin_info, then "trees": the 26-components of the skeleton.  `out` (not empty): the 0 / 255 volume as a TIFF, or bare bytes for a .raw
+// name.  `swc` (not empty): the skeleton as a tree -- pnr_skeleton_forest, then pnr_join_reroot at the voxel with the largest D2 (the
+// smallest index on ties); coordinates = the voxel's x, y, z, radius = sqrtf(D2) of pnr_distance_transform at those points (thr = thr_used,
+// rmax = 64), type 2, ids 1..n in tree order with every parent before its children; the comment block ends in
+// #skeleton=thr:T,rounds:R,voxels:K,trees:C.
+struct SkeletonJob {
+    pnr_thin_opts opts = {-1, 0};
+    std::string out, swc;
+};
+bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

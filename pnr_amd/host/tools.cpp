@@ -1,5 +1,5 @@
 // tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc (by gap, or --join-geodesic), --render-swc,
-// --components, --edt and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+// --components, --edt, --skeleton and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
 #include "host_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -333,6 +333,61 @@ bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::
            (long long)ei.n_fg, (long long)ei.n_capped, (int)ei.thr_used, (int)job.opts.rmax, (double)zscale, (double)sqrtf(ei.d2_max));
     print_max_at(ei.first_max, st.w, st.h);
     printf("}\n");
+    return true;
+}
+
+bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    p.zdist = zscale; // (the radii of --swc; also the z half-width of --subtract-background)
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    std::vector<unsigned char> skel(job.out.empty() ? 0 : N);
+    pnr_thin_info ti = {};
+    if (pnr_skeletonize(ctx, &job.opts, &ti, nullptr, nullptr, nullptr, 0) != PNR_OK) return lib_fail("pnr_skeletonize"); // "n_skel > cap: call again"
+    const int64_t n = ti.n_skel;
+    std::vector<int64_t> vox((size_t)n);
+    std::vector<uint8_t> deg((size_t)n);
+    if ((n > 0 || !job.out.empty()) && pnr_skeletonize(ctx, &job.opts, &ti, job.out.empty() ? nullptr : skel.data(), vox.data(), deg.data(), n) != PNR_OK)
+        return lib_fail("pnr_skeletonize");
+    std::vector<pnr_bridge> edges((size_t)std::max<int64_t>(n - 1, 0));
+    int64_t ne = 0;
+    if (pnr_skeleton_forest(vox.data(), n, st.w, st.h, st.l, edges.data(), (int64_t)edges.size(), &ne) != PNR_OK) return lib_fail("pnr_skeleton_forest");
+    const int64_t trees = n - ne;
+    if (!job.swc.empty()) {
+        std::vector<float> xyz((size_t)n * 3), d2((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t v = vox[(size_t)i];
+            xyz[(size_t)(3 * i)] = (float)(v % st.w), xyz[(size_t)(3 * i + 1)] = (float)(v / st.w % st.h), xyz[(size_t)(3 * i + 2)] = (float)(v / (st.w * st.h));
+        }
+        std::vector<int32_t> par((size_t)n, -1), par_out((size_t)n), order((size_t)n), comp((size_t)n);
+        if (n > 0) {
+            const pnr_edt_opts eo = {ti.thr_used, 64};
+            if (pnr_distance_transform(ctx, &eo, nullptr, nullptr, xyz.data(), n, d2.data()) != PNR_OK) return lib_fail("pnr_distance_transform");
+            const int64_t root = std::max_element(d2.begin(), d2.end()) - d2.begin(); // (the first of the largest: the soma guess of --edt)
+            if (pnr_join_reroot(par.data(), n, edges.data(), ne, root, par_out.data(), order.data(), comp.data()) != PNR_OK) return lib_fail("pnr_join_reroot");
+        }
+        if (!write_file(job.swc, "w", [&](FILE *f) {
+                fprintf(f, "##n,type,x,y,z,radius,parent\n#skeleton=thr:%d,rounds:%d,voxels:%lld,trees:%lld\n", (int)ti.thr_used, (int)ti.rounds, (long long)n, (long long)trees);
+                std::vector<int64_t> pos((size_t)n, -1);
+                for (int64_t k = 0; k < n; k++) {
+                    const size_t v = (size_t)order[(size_t)k];
+                    pos[v] = k + 1;
+                    fprintf(f, "%lld 2 %s %s %s %s %lld\n", (long long)(k + 1), f32_text(xyz[3 * v]).c_str(), f32_text(xyz[3 * v + 1]).c_str(), f32_text(xyz[3 * v + 2]).c_str(),
+                            f32_text(sqrtf(d2[v])).c_str(), par_out[v] < 0 ? -1LL : (long long)pos[(size_t)par_out[v]]);
+                }
+            }))
+            return false;
+    }
+    if (!job.out.empty() && !write_stack(job.out, skel.data(), st.w, st.h, st.l)) return false;
+    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_skel\": %lld, \"n_end\": %lld, \"n_branch\": %lld, \"n_isolated\": %lld, \"tiles\": %lld, \"tile_visits\": %lld, "
+           "\"rounds\": %d, \"thr_used\": %d, \"trees\": %lld}\n",
+           (long long)ti.n_vox, (long long)ti.n_fg, (long long)ti.n_skel, (long long)ti.n_end, (long long)ti.n_branch, (long long)ti.n_isolated, (long long)ti.tiles,
+           (long long)ti.tile_visits, (int)ti.rounds, (int)ti.thr_used, (long long)trees);
     return true;
 }
 

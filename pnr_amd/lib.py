@@ -126,6 +126,20 @@ class EdtInfo(C.Structure):
 PNR_EDT_MAX_R = 1024
 
 
+class ThinOpts(C.Structure):
+    """pnr_thin_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean), max_rounds >= 0 (0: until nothing is deleted)"""
+    _fields_ = [("thr", C.c_int32), ("max_rounds", C.c_int32)]
+
+
+class ThinInfo(C.Structure):
+    """pnr_thin_info: the exact summary of a thinning (tile_visits: the work of the passes, a property of the implementation)"""
+    _fields_ = [("n_vox", C.c_int64), ("n_fg", C.c_int64), ("n_skel", C.c_int64), ("n_end", C.c_int64), ("n_branch", C.c_int64), ("n_isolated", C.c_int64),
+                ("tiles", C.c_int64), ("tile_visits", C.c_int64), ("rounds", C.c_int32), ("thr_used", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class GeoOpts(C.Structure):
     """pnr_geo_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean; 0: every voxel is passable), dmax 1..2^31 - 1 (no path above it
     is kept), cost: 256 u16 entries >= 1 (NULL: c(v) = 256 - v)"""
@@ -246,6 +260,8 @@ def load():
     L.pnr_label_components.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo), vp, vp, i64]
     L.pnr_despeckle_volume.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]
     L.pnr_distance_transform.argtypes = [vp, C.POINTER(EdtOpts), C.POINTER(EdtInfo), vp, vp, i64, vp]
+    L.pnr_skeletonize.argtypes = [vp, C.POINTER(ThinOpts), C.POINTER(ThinInfo), vp, vp, vp, i64]
+    L.pnr_skeleton_forest.argtypes = [vp, i64, i64, i64, i64, vp, i64, C.POINTER(i64)]
     L.pnr_geodesic_distance.argtypes = [vp, vp, vp, i64, C.POINTER(GeoOpts), C.POINTER(GeoInfo), vp, vp, vp, i64, vp, vp, i32, vp, vp]
     L.pnr_geodesic_bridges.argtypes = [vp, vp, vp, i64, C.POINTER(GeoJoinOpts), C.POINTER(GeoJoinInfo), vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
     L.pnr_join_expand.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, C.POINTER(i64), vp]
@@ -316,7 +332,7 @@ def load():
 
 # the drop-in boundary (include/pnr_hip.h)
 PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_geodesic_distance", "pnr_geodesic_bridges", "pnr_join_expand", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
+                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_skeletonize", "pnr_skeleton_forest", "pnr_geodesic_distance", "pnr_geodesic_bridges", "pnr_join_expand", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
                    "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
                    "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
                    "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
@@ -617,6 +633,27 @@ class Context:
             if at is not None:
                 at = np.where(at >= 0, np.sqrt(np.maximum(at, np.float32(0))), at).astype(np.float32)
         return out, d2, at
+
+    def skeletonize(self, thr=-1, max_rounds=0, volume=True, voxels=True, cap=None):
+        """pnr_skeletonize: {V >= thr} (thr = -1: the global mean) of the context's volume thinned to a one-voxel-wide curve skeleton under
+        the rule of include/pnr_hip.h -> (info dict {n_vox, n_fg, n_skel, n_end, n_branch, n_isolated, tiles, tile_visits, rounds,
+        thr_used}, skel uint8[l, h, w] of 0 / 255 or None, vox int64[n_skel] ascending linear indices or None, deg uint8[n_skel] the
+        skeleton voxels in N26 or None).  max_rounds: stop after this many rounds (0: when nothing is deleted).  cap: at most this many
+        entries of vox and deg (info["n_skel"] stays the full count)."""
+        o = ThinOpts(int(thr), int(max_rounds))
+        info = ThinInfo()
+        skel = np.empty(self.shape, np.uint8) if volume else None
+        sp = skel.ctypes.data if volume else None
+        if not voxels:
+            check(self.L.pnr_skeletonize(self.h, C.byref(o), C.byref(info), sp, None, None, 0))
+            return info.as_dict(), skel, None, None
+        if cap is None:  # count first, then fetch
+            check(self.L.pnr_skeletonize(self.h, C.byref(o), C.byref(info), None, None, None, 0))
+            cap = info.n_skel
+        vox, deg = np.zeros(max(int(cap), 0), np.int64), np.zeros(max(int(cap), 0), np.uint8)
+        check(self.L.pnr_skeletonize(self.h, C.byref(o), C.byref(info), sp, vox.ctypes.data if len(vox) else None, deg.ctypes.data if len(deg) else None, int(cap)))
+        k = min(len(vox), info.n_skel)
+        return info.as_dict(), skel, vox[:k], deg[:k]
 
     def geodesic(self, sources, labels=None, thr=0, dmax=PNR_GEO_DMAX, cost=None, volume=True, targets=None, path_cap=0):
         """pnr_geodesic_distance: the gray-weighted geodesic distance D of every passable voxel (V >= thr; thr = -1: the global mean) to the
@@ -1156,6 +1193,19 @@ def join_reroot(parent, bridges=(), root=-1):
     check(L.pnr_join_reroot(parent.ctypes.data, len(parent), bridges.ctypes.data if len(bridges) else None, len(bridges), int(root),
                             out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
     return tuple(out)
+
+
+def skeleton_forest(vox, shape):
+    """pnr_skeleton_forest (pure host; no GPU needed): the k voxels vox (linear indices of a stack of shape (l, h, w)) as a forest -- the
+    unique minimum spanning forest of their 26-adjacent pairs under (squared step length, lo, hi) -> BRIDGE[k - components] sorted by
+    (lo, hi), d = the step length; join_reroot(np.full(k, -1), edges) gives parents and tree order"""
+    L = load()
+    vox = np.ascontiguousarray(vox, np.int64).reshape(-1)
+    l, h, w = (int(v) for v in shape)
+    edges = np.zeros(max(len(vox) - 1, 0), BRIDGE)
+    n = C.c_int64()
+    check(L.pnr_skeleton_forest(vox.ctypes.data if len(vox) else None, len(vox), w, h, l, edges.ctypes.data if len(edges) else None, len(edges), C.byref(n)))
+    return edges[:n.value]
 
 
 def join_expand(xyz, parent, bridges, paths):
