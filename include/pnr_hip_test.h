@@ -56,6 +56,39 @@ enum { PNR_PHL_FLAGS = 16,                   /* words per trace; those the step'
 int pnr_phased_likelihood(pnr_ctx *ctx, int64_t nt, const float *poses, const float *centroids, const int32_t *modes, float *corr,
                           int32_t *uidx, int32_t *cmap, int32_t *flags, int32_t *info);
 
+/* The decision half of one step of the phased SMC driver over nt traces whose whole state the caller gives, all in the step list
+ * `lp`: ph_update (pending centroid and its stop test, maximum over the scales, weights, N_eff, CDF, centroid, stop tests, systematic
+ * resampling, the hand-over into the next list), then ph_predict of the FOLLOWING step on the list ph_update filled (the drawing of
+ * the next particles, priors, duplicate search) -- the production kernels with the launch parameters of a production step, every
+ * trace at its own iteration.  np, S, ni, Kc, znccth, neff_ratio, nodepervol = the context's; np_pad = (np + 1 + 63) / 64 * 64.
+ * Inputs, in the device's layout (host arrays):
+ *   flags [nt][PNR_PHL_FLAGS]: PNR_PHL_IT the trace's iteration (0..ni), PNR_PHL_RES whether the step before resampled, PNR_PHL_STOP /
+ *     PNR_PHL_T / PNR_PHL_PAUSE on entry, PNR_PHL_NCH the chains of corr (the centroid's is the last); seeds [nt][6];
+ *   part [nt][2][np][9]: half it & 1 the particles of the iteration (x, y, z, vx, vy, vz, then w, corr, sig), the other half those of
+ *     it - 1; prior [nt][np]; idxres [nt][np] the resampling of the step before (0..np-1 each, read only with PNR_PHL_RES);
+ *   xcs [nt][2][8]: half (it & 1) ^ 1 the pending centroid; corr [nt][S][np_pad] the GIVEN correlations per scale and chain, cmap
+ *     [nt][np_pad] particle -> chain (several particles may share one); draws [np + 1] instead of the context's rand() stream, or
+ *     NULL; den [w * h * l] a density map for the DENSITY stop, or NULL for none.
+ * Outputs (host, any may be NULL), after ph_update: part_u, xcs_u, idxres_u, prior_u, flags_u as the inputs; neff [nt][ni] (row it;
+ * 0 where not written); oxc [nt][ni][8] the records of the pending iterations (0 elsewhere); oT / ostop [nt] (-1 where not written);
+ * cnt_next and list_next [nt] the next step's list (-1 beyond).  After ph_predict: part_p, prior_p, flags_p, uidx [nt][np_pad] (-1
+ * where not written), cmap_p (the same), cnt_p [2] both list counters.
+ * mode PNR_PHD_PREDICT runs ph_predict alone, on the list `lp` and at the traces' own iterations -- the only way to iter0New's draw,
+ * which no ph_update precedes: the outputs after ph_update are then not written.
+ * PNR_E_ARG: nt < 1 or more traces than the state holds, no volume, not the phased driver, lp, mode, an iteration, a chain count, a
+ * chain or a resampling index out of range. */
+enum { PNR_PHD_STEP = 0, PNR_PHD_PREDICT = 1 };
+enum { PNR_PHL_RES = 0, PNR_PHL_STOP = 1, PNR_PHL_T = 2, PNR_PHL_IT = 3, PNR_PHL_DONE = 4, PNR_PHL_PAUSE = 14 };
+typedef struct {
+    const int32_t *flags; const float *seeds, *part, *prior; const int32_t *idxres; const float *xcs, *corr; const int32_t *cmap;
+    const uint32_t *draws; const uint8_t *den; int32_t lp, mode;
+} pnr_phd_in;
+typedef struct {
+    float *part_u, *neff, *xcs_u, *oxc; int32_t *oT, *ostop, *idxres_u; float *prior_u; int32_t *flags_u, *cnt_next, *list_next;
+    float *part_p, *prior_p; int32_t *flags_p, *uidx, *cmap_p, *cnt_p;
+} pnr_phd_out;
+int pnr_phased_decide(pnr_ctx *ctx, int64_t nt, const pnr_phd_in *in, pnr_phd_out *out);
+
 /* Tracker tables for parity tests: name in {"p","u","w0","w0_cws","v","w","w_cws","rng",
  * "model_vuw<s>","model_wgt<s>","model_avg","gauss_xy<s>","gauss_z<s>","scale_share"}.  Copies up to cap
  * 4-byte words into out; *n receives the element count.  "scale_share" (int32): [0, 8) the scale whose stash scale s reads under

@@ -954,28 +954,105 @@ static int getdirection(const orc_tracker *t, float vx, float vy, float vz)
     return idx;
 }
 
-/* shared tail of iter0New/iterINew: normalise, N_eff, CDF, centroid, stop tests, resampling.
- * `prevw` NULL => weights start from 1/np. rdraw = RNG draw used for resampling. */
-static int smc_finish(orc_tracker *t, int it, const float *prevw, float wnorm_prior,
-                      const uint8_t *img, int w, int h, int l, uint32_t rdraw, int *stop)
+/* (int)r as the reference's build converts it: x86-64's cvttss2si gives INT_MIN ("integer indefinite") for NaN and for anything
+ * outside int -- written out so that the oracle does not lean on undefined behaviour for the non-finite centroid */
+static int f2i_x86(float r) { return (r >= -2147483648.0f && r < 2147483648.0f) ? (int)r : (-2147483647 - 1); }
+
+void orc_tracker_set_rng(orc_tracker *t, const uint32_t *draws, int n)
+{
+    for (int i = 0; i < n && i <= t->npcles; i++) t->rng[i] = draws[i];
+}
+
+/* The drawing of iter0New (tracker.cpp:1006-1024) / iterINew (:1104-1132): the pose words of xf [np][9] and prior [np].  xp = the
+ * particles of it - 1 [np][9], read through idxp when that step resampled.  A parent whose direction has no maximum (getdirection
+ * -1: a NaN direction; the reference then indexes w_cws with -1) has no reference value: it is drawn with direction 0 and counted
+ * in the return value.  nodir [np] (may be NULL) receives the direction index, -1 for such a parent (0 at iteration 0); s_out [np]
+ * (may be NULL) the prediction offset drawn. */
+static int smc_draw(const orc_tracker *t, int it, const float seed[6], const float *xp, int resampled, const int *idxp,
+                    float *xf, float *prior, int *nodir, int *s_out)
+{
+    int np = t->npcles, sz = t->sz, bad = 0;
+    if (it == 0) {
+        float u1 = (t->w0_cws[sz - 1] / np) * ((float)t->rng[0] / ORC_RAND_MAX);
+        int s = 0;
+        for (int i = 0; i < np; ++i) {
+            float ui = u1 + i * (t->w0_cws[sz - 1] / np);
+            while (ui > t->w0_cws[s] && s < (sz - 1)) s++;
+            float *q = xf + i * 9;
+            q[XF_X] = seed[0] + t->p[3 * s + 0];
+            q[XF_Y] = seed[1] + t->p[3 * s + 1];
+            q[XF_Z] = seed[2] + t->p[3 * s + 2];
+            q[XF_VX] = isnan(seed[3]) ? t->u[3 * s + 0] : seed[3];
+            q[XF_VY] = isnan(seed[4]) ? t->u[3 * s + 1] : seed[4];
+            q[XF_VZ] = isnan(seed[5]) ? t->u[3 * s + 2] : seed[5];
+            prior[i] = t->w0[s];
+            if (nodir) nodir[i] = 0;
+            if (s_out) s_out[i] = s;
+        }
+        return 0;
+    }
+    for (int k = 0; k < np; ++k) {
+        int k1 = resampled ? idxp[k] : k;
+        const float *par = xp + k1 * 9;
+        int vi = getdirection(t, par[XF_VX], par[XF_VY], par[XF_VZ]);
+        if (nodir) nodir[k] = vi; /* (-1: none) */
+        if (vi < 0) { vi = 0; bad++; }
+        const float *cws = t->w_cws + (size_t)vi * sz;
+        float u1 = (cws[sz - 1]) * ((float)t->rng[k] / ORC_RAND_MAX);
+        int s = 0;
+        while (u1 > cws[s] && s < sz - 1) s++;
+        float *q = xf + k * 9;
+        q[XF_X] = par[XF_X] + t->p[3 * s + 0];
+        q[XF_Y] = par[XF_Y] + t->p[3 * s + 1];
+        q[XF_Z] = par[XF_Z] + t->p[3 * s + 2];
+        q[XF_VX] = t->u[3 * s + 0];
+        q[XF_VY] = t->u[3 * s + 1];
+        q[XF_VZ] = t->u[3 * s + 2];
+        prior[k] = t->w[(size_t)vi * sz + s];
+        if (s_out) s_out[k] = s;
+    }
+    return bad;
+}
+
+/* the first maximum over the scales, as orc_zncc_scales' loop takes it (strict >: the first scale wins a tie, a NaN never wins);
+ * *sig keeps its value if no scale wins */
+static float max_scales(const orc_tracker *t, const float *cs, int stride, float *sig)
+{
+    float best = -FLT_MAX;
+    for (int s = 0; s < t->nsig; ++s)
+        if (cs[(size_t)s * stride] > best) { best = cs[(size_t)s * stride]; *sig = t->sig[s]; }
+    return best;
+}
+
+/* Weights, N_eff, CDF, centroid and the border test of one iteration on GIVEN correlations cs [nsig][np] of the particles whose
+ * poses xf [np][9] holds (tracker.cpp:1028-1071, :1136-1178): writes XF_CORR / XF_SIG / XF_W of xf, *neff, csw [np], xc [0..6]
+ * (XC_SIG = the weighted sum of the particles' sigmas, as the reference leaves it in front of the centroid's znccBBB), xyz1 [3] the
+ * rounded centroid.  `prevw` NULL => weights start from 1/np.  Returns 1 if the centroid left the volume (stop 1). */
+static int smc_weights(const orc_tracker *t, float *xf, const float *prior, const float *prevw, const float *cs,
+                       int w, int h, int l, float *lhood, float *neff_out, float *csw, float *xc, int *xyz1)
 {
     int np = t->npcles;
-    float *xf = t->xfilt + (size_t)it * np * 9;
-    float *xc = t->xc + (size_t)it * 8;
+    float wnorm_prior = 0;
+    for (int k = 0; k < np; ++k) {
+        float *q = xf + k * 9;
+        wnorm_prior += prior[k];
+        q[XF_CORR] = max_scales(t, cs + k, np, &q[XF_SIG]);
+        lhood[k] = expf(t->Kc * q[XF_CORR]);
+    }
     float wnorm_posterior = 0;
     for (int k = 0; k < np; ++k) {
         double base = prevw ? (double)prevw[k] : (1.0 / np);
-        xf[k * 9 + XF_W] = (float)(base * (t->prior[k] / wnorm_prior) * t->lhood[k]);
+        xf[k * 9 + XF_W] = (float)(base * (prior[k] / wnorm_prior) * lhood[k]);
         wnorm_posterior += xf[k * 9 + XF_W];
     }
     float neff = 0;
     for (int k = 0; k < np; ++k) {
         xf[k * 9 + XF_W] /= wnorm_posterior;
         neff = (float)(neff + (double)xf[k * 9 + XF_W] * (double)xf[k * 9 + XF_W]);
-        t->res_csw[k] = xf[k * 9 + XF_W] + ((k > 0) ? t->res_csw[k - 1] : 0);
+        csw[k] = xf[k * 9 + XF_W] + ((k > 0) ? csw[k - 1] : 0);
     }
     neff = (float)(1.0 / neff);
-    t->neff[it] = neff;
+    *neff_out = neff;
 
     for (int c = 0; c < 8; c++) xc[c] = 0;
     for (int k = 0; k < np; ++k) {
@@ -992,87 +1069,101 @@ static int smc_finish(orc_tracker *t, int it, const float *prevw, float wnorm_pr
     xc[XC_VX] /= vnorm;
     xc[XC_VY] /= vnorm;
     xc[XC_VZ] /= vnorm;
-    xc[XC_CORR] = orc_zncc(t, xc[XC_X], xc[XC_Y], xc[XC_Z], xc[XC_VX], xc[XC_VY], xc[XC_VZ], img, w, h, l, &xc[XC_SIG]);
+    int x1 = f2i_x86(roundf(xc[XC_X])), y1 = f2i_x86(roundf(xc[XC_Y])), z1 = f2i_x86(roundf(xc[XC_Z]));
+    if (xyz1) { xyz1[0] = x1; xyz1[1] = y1; xyz1[2] = z1; }
+    return (x1 < 0 || x1 >= w || y1 < 0 || y1 >= h || z1 < 0 || z1 >= l);
+}
 
-    int x1 = (int)roundf(xc[XC_X]), y1 = (int)roundf(xc[XC_Y]), z1 = (int)roundf(xc[XC_Z]);
-    if (x1 < 0 || x1 >= w || y1 < 0 || y1 >= h || z1 < 0 || z1 >= l) { *stop = 1; return 0; }
-    if (xc[XC_CORR] < t->znccth) { *stop = 2; return 0; }
-
-    if (neff / np < t->neff_ratio) {
-        float u1 = (float)((1.0 / np) * ((float)rdraw / ORC_RAND_MAX));
-        int s = 0;
-        int *idx = t->idxres + (size_t)it * np;
-        for (int k = 0; k < np; ++k) {
-            float ui = (float)(u1 + k * (1.0 / np));
-            while (ui > t->res_csw[s] && s < np - 1) s++; /* clamp: documented divergence */
-            idx[k] = s;
-        }
+/* systematic resampling (tracker.cpp:1082-1090, :1187-1195) if neff / np < neff_ratio: idx [np]; returns whether it resampled */
+static int smc_resample(const orc_tracker *t, float neff, const float *csw, uint32_t rdraw, int *idx, float *ui_out)
+{
+    int np = t->npcles;
+    if (!(neff / np < t->neff_ratio)) return 0;
+    float u1 = (float)((1.0 / np) * ((float)rdraw / ORC_RAND_MAX));
+    int s = 0;
+    for (int k = 0; k < np; ++k) {
+        float ui = (float)(u1 + k * (1.0 / np));
+        while (ui > csw[s] && s < np - 1) s++; /* clamp: documented divergence */
+        idx[k] = s;
+        if (ui_out) ui_out[k] = ui;
     }
     return 1;
 }
 
-static int iter0(orc_tracker *t, const float seed[6], const uint8_t *img, int w, int h, int l, int *stop)
+/* the centroid's own test (tracker.cpp:1072-1079) from its per-scale correlations cs [nsig]: *best, *sig (on entry the weighted
+ * sum smc_weights left; kept if no scale wins); returns best < znccth */
+int orc_smc_pending(const orc_tracker *t, const float *cs, float *best, float *sig)
 {
-    int np = t->npcles, sz = t->sz;
-    float *xf = t->xfilt;
-    float wnorm_prior = 0;
-    float u1 = (t->w0_cws[sz - 1] / np) * ((float)t->rng[0] / ORC_RAND_MAX);
-    int s = 0;
-    for (int i = 0; i < np; ++i) {
-        float ui = u1 + i * (t->w0_cws[sz - 1] / np);
-        while (ui > t->w0_cws[s] && s < (sz - 1)) s++;
-        float *q = xf + i * 9;
-        q[XF_X] = seed[0] + t->p[3 * s + 0];
-        q[XF_Y] = seed[1] + t->p[3 * s + 1];
-        q[XF_Z] = seed[2] + t->p[3 * s + 2];
-        q[XF_VX] = isnan(seed[3]) ? t->u[3 * s + 0] : seed[3];
-        q[XF_VY] = isnan(seed[4]) ? t->u[3 * s + 1] : seed[4];
-        q[XF_VZ] = isnan(seed[5]) ? t->u[3 * s + 2] : seed[5];
-        t->prior[i] = t->w0[s];
-        wnorm_prior += t->prior[i];
-        q[XF_CORR] = orc_zncc(t, q[XF_X], q[XF_Y], q[XF_Z], q[XF_VX], q[XF_VY], q[XF_VZ], img, w, h, l, &q[XF_SIG]);
-        t->lhood[i] = expf(t->Kc * q[XF_CORR]);
-    }
-    return smc_finish(t, 0, NULL, wnorm_prior, img, w, h, l, t->rng[1], stop);
+    *best = max_scales(t, cs, 1, sig);
+    return *best < t->znccth;
 }
 
-static int iterI(orc_tracker *t, int it, const uint8_t *img, int w, int h, int l, int *stop)
+int orc_smc_draw(const orc_tracker *t, int it, const float seed[6], const float *prev, int resampled_prev, const int *idxres_prev,
+                 float *poses, float *prior, int *dir, int *s_out)
 {
-    int np = t->npcles, sz = t->sz;
-    const float *xp = t->xfilt + (size_t)(it - 1) * np * 9;
+    int np = t->npcles;
+    float *xf = (float *)calloc((size_t)np * 9, sizeof(float));
+    int bad = smc_draw(t, it, seed, prev, resampled_prev, idxres_prev, xf, prior, dir, s_out);
+    for (int k = 0; k < np; k++) memcpy(poses + (size_t)k * 6, xf + (size_t)k * 9, sizeof(float) * 6);
+    free(xf);
+    return bad;
+}
+
+int orc_smc_decide(const orc_tracker *t, int it, const float *poses, const float *prior, const float *prevw, const float *cs,
+                   int w, int h, int l, float *xf, float *neff, float *csw, float *xc7, int *xyz1, int *resampled, int *idxres, float *ui)
+{
+    int np = t->npcles;
+    float xc[8];
+    float *lhood = (float *)malloc(sizeof(float) * (size_t)np);
+    for (int k = 0; k < np; k++) {
+        memcpy(xf + (size_t)k * 9, poses + (size_t)k * 6, sizeof(float) * 6);
+        xf[k * 9 + XF_W] = xf[k * 9 + XF_CORR] = xf[k * 9 + XF_SIG] = 0;
+    }
+    int border = smc_weights(t, xf, prior, prevw, cs, w, h, l, lhood, neff, csw, xc, xyz1);
+    free(lhood);
+    memcpy(xc7, xc, sizeof(float) * 7);
+    *resampled = border ? 0 : smc_resample(t, *neff, csw, t->rng[(it == 0) ? 1 : np], idxres, ui);
+    return border;
+}
+
+/* one iteration of orc_trace through the pieces above: draw, znccBBB per scale, weights, the centroid's test, resampling */
+static int smc_iter(orc_tracker *t, int it, const float seed[6], const uint8_t *img, int w, int h, int l, int *stop)
+{
+    int np = t->npcles, S = t->nsig;
     float *xf = t->xfilt + (size_t)it * np * 9;
-    const int *idxp = t->idxres + (size_t)(it - 1) * np;
-    int resampled = (t->neff[it - 1] / np < t->neff_ratio);
-    float wnorm_prior = 0;
+    float *xc = t->xc + (size_t)it * 8;
+    const float *xp = (it > 0) ? t->xfilt + (size_t)(it - 1) * np * 9 : NULL;
+    int resampled = (it > 0) && (t->neff[it - 1] / np < t->neff_ratio);
+    smc_draw(t, it, seed, xp, resampled, (it > 0) ? t->idxres + (size_t)(it - 1) * np : NULL, xf, t->prior, NULL, NULL);
+    float *cs = (float *)malloc(sizeof(float) * (size_t)np * S), ps[16], dummy;
     for (int k = 0; k < np; ++k) {
-        int k1 = resampled ? idxp[k] : k;
-        const float *par = xp + k1 * 9;
-        int vi = getdirection(t, par[XF_VX], par[XF_VY], par[XF_VZ]);
-        const float *cws = t->w_cws + (size_t)vi * sz;
-        float u1 = (cws[sz - 1]) * ((float)t->rng[k] / ORC_RAND_MAX);
-        int s = 0;
-        while (u1 > cws[s] && s < sz - 1) s++;
-        float *q = xf + k * 9;
-        q[XF_X] = par[XF_X] + t->p[3 * s + 0];
-        q[XF_Y] = par[XF_Y] + t->p[3 * s + 1];
-        q[XF_Z] = par[XF_Z] + t->p[3 * s + 2];
-        q[XF_VX] = t->u[3 * s + 0];
-        q[XF_VY] = t->u[3 * s + 1];
-        q[XF_VZ] = t->u[3 * s + 2];
-        t->prior[k] = t->w[(size_t)vi * sz + s];
-        wnorm_prior += t->prior[k];
-        q[XF_CORR] = orc_zncc(t, q[XF_X], q[XF_Y], q[XF_Z], q[XF_VX], q[XF_VY], q[XF_VZ], img, w, h, l, &q[XF_SIG]);
-        t->lhood[k] = expf(t->Kc * q[XF_CORR]);
+        const float *q = xf + k * 9;
+        orc_zncc_scales(t, q[XF_X], q[XF_Y], q[XF_Z], q[XF_VX], q[XF_VY], q[XF_VZ], img, w, h, l, &dummy, ps);
+        for (int s = 0; s < S; s++) cs[(size_t)s * np + k] = ps[s];
     }
     /* previous weights: of slot k, used only when step it-1 did not resample (tracker.cpp:1143) */
     float *prevw = NULL;
-    if (!resampled) {
+    if (it > 0 && !resampled) {
         prevw = (float *)malloc(sizeof(float) * (size_t)np);
         for (int k = 0; k < np; k++) prevw[k] = xp[k * 9 + XF_W];
     }
-    int ok = smc_finish(t, it, prevw, wnorm_prior, img, w, h, l, t->rng[np], stop);
+    int border = smc_weights(t, xf, t->prior, prevw, cs, w, h, l, t->lhood, &t->neff[it], t->res_csw, xc, NULL);
     free(prevw);
-    return ok;
+    free(cs);
+    /* A centroid that is not finite (wsum == 0 or NaN, a zero direction) has no reference correlation: Tracker::interp converts the
+     * NaN coordinate to an int and indexes the image with it (INT_MIN on x86: the reference itself faults).  Its record carries NaN. */
+    int low = 0, finite = 1;
+    for (int c = 0; c < 6; c++) finite = finite && isfinite(xc[c]);
+    if (finite) {
+        orc_zncc_scales(t, xc[XC_X], xc[XC_Y], xc[XC_Z], xc[XC_VX], xc[XC_VY], xc[XC_VZ], img, w, h, l, &dummy, ps);
+        low = orc_smc_pending(t, ps, &xc[XC_CORR], &xc[XC_SIG]);
+    } else {
+        xc[XC_CORR] = NAN;
+    }
+    if (border) { *stop = 1; return 0; }
+    if (low) { *stop = 2; return 0; }
+    smc_resample(t, t->neff[it], t->res_csw, t->rng[(it == 0) ? 1 : np], t->idxres + (size_t)it * np, NULL);
+    return 1;
 }
 
 int orc_trace(orc_tracker *t, const float seed[6], const uint8_t *img, int w, int h, int l,
@@ -1081,7 +1172,7 @@ int orc_trace(orc_tracker *t, const float seed[6], const uint8_t *img, int w, in
 {
     int T = t->niter, st = 0, np = t->npcles;
     for (int i = 0; i < t->niter; ++i) {
-        int ok = (i == 0) ? iter0(t, seed, img, w, h, l, &st) : iterI(t, i, img, w, h, l, &st);
+        int ok = smc_iter(t, i, seed, img, w, h, l, &st);
         memcpy(xc_out + (size_t)i * 8, t->xc + (size_t)i * 8, sizeof(float) * 8);
         if (i < max_dbg) {
             if (xfilt_out) memcpy(xfilt_out + (size_t)i * np * 9, t->xfilt + (size_t)i * np * 9, sizeof(float) * 9 * (size_t)np);

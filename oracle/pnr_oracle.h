@@ -91,6 +91,8 @@ int orc_tracker_nsig(const orc_tracker *t);
  *                (row T holds the failing estimate when T < niter)
  *   returns T  = number of successful iterations (ti_limit of a map-free run)
  *   stop       : 0 = niter reached, 1 = out of volume, 2 = corr < znccth
+ *                (a centroid that is not finite is out of volume -- the x86 conversion of NaN is INT_MIN -- and has no reference
+ *                correlation: the reference indexes the image with that INT_MIN; its record carries corr = NaN)
  * Optional debug dumps (may be NULL), sized for max_dbg iterations:
  *   xfilt_out  : max_dbg x npcles x 9 (x,y,z,vx,vy,vz,w,corr,sig)
  *   idxres_out : max_dbg x npcles (only meaningful where neff/np < neff_ratio)
@@ -99,6 +101,28 @@ int orc_tracker_nsig(const orc_tracker *t);
 int orc_trace(orc_tracker *t, const float seed[6], const uint8_t *img, int w, int h, int l,
               float *xc_out, int *stop, int max_dbg, float *xfilt_out, int *idxres_out,
               float *neff_out);
+
+/* ---------- one SMC step in pieces: what orc_trace chains, with the ZNCC evaluation supplied by the caller ---------- */
+/* replace the first n (<= npcles + 1) draws of the tracker's rand() stream */
+void orc_tracker_set_rng(orc_tracker *t, const uint32_t *draws, int n);
+/* The particles of iteration `it`: poses [np][6] and prior [np].  it == 0: from seed[6] (draw 0); it >= 1: from prev [np][9], the
+ * particles of it - 1, read through idxres_prev [np] if resampled_prev (draw k for particle k).  A parent with a NaN direction has
+ * no reference value (the reference indexes w_cws with -1): it is drawn with direction 0; returns the number of such particles.
+ * dir [np] (may be NULL): the direction index of every parent, -1 for such a one; s_out [np] (may be NULL): the offset drawn. */
+int orc_smc_draw(const orc_tracker *t, int it, const float seed[6], const float *prev, int resampled_prev, const int *idxres_prev,
+                 float *poses, float *prior, int *dir, int *s_out);
+/* Weights, N_eff, CDF, centroid, border test and resampling of iteration `it` on GIVEN per-scale correlations cs [nsig][np] of the
+ * particles poses [np][6] (the maximum over the scales is orc_zncc_scales': strict >, the first scale wins a tie): prevw [np] the
+ * previous weights to carry, or NULL for 1/np.  Outputs: xf [np][9] (x,y,z,vx,vy,vz,w,corr,sig), *neff, csw [np], xc7 (x,y,z,vx,vy,
+ * vz and the weighted sum of the sigmas), xyz1 [3] the rounded centroid (INT_MIN where the x86 conversion gives it), *resampled
+ * and idxres [np] (draw 1 at iteration 0, draw np later; not resampled when the centroid left the volume) with ui [np] (may be
+ * NULL) the positions the resampling looked up in csw.  Returns 1 for that
+ * border stop.  The centroid's own correlation test is orc_smc_pending: the product evaluates it one step late. */
+int orc_smc_decide(const orc_tracker *t, int it, const float *poses, const float *prior, const float *prevw, const float *cs,
+                   int w, int h, int l, float *xf, float *neff, float *csw, float *xc7, int *xyz1, int *resampled, int *idxres, float *ui);
+/* the centroid's test from its per-scale correlations cs [nsig]: *best, *sig (in: the weighted sum of xc7[6], kept if no scale
+ * wins); returns best < znccth (stop 2) */
+int orc_smc_pending(const orc_tracker *t, const float *cs, float *best, float *sig);
 
 /* ---------- host bookkeeping (tracker.cpp:825-933, Advantra_plugin.cpp:2602-2710) ---------- */
 typedef struct {

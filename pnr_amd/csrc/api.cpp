@@ -976,6 +976,15 @@ int pnr_phased_likelihood(pnr_ctx *c, int64_t nt, const float *poses, const floa
     return pnr_phased_likelihood_run(c, nt, poses, centroids, modes, corr, uidx, cmap, flags, info);
 }
 
+int pnr_phased_decide(pnr_ctx *c, int64_t nt, const pnr_phd_in *in, pnr_phd_out *out)
+{
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    PNR_REQUIRE(nt >= 1, PNR_E_ARG, "pnr_phased_decide: bad number of traces");
+    PNR_REQUIRE(in && out && in->flags && in->seeds && in->part && in->prior && in->idxres && in->xcs && in->corr && in->cmap, PNR_E_ARG, "null argument");
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_phased_decide_run(c, nt, in, out);
+}
+
 int pnr_zncc_batch(pnr_ctx *c, const float *pos_dir, int64_t n, float *corr, float *sig)
 {
     PNR_REQUIRE(c && (n == 0 || (pos_dir && corr)), PNR_E_ARG, "null argument");

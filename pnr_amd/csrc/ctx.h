@@ -323,6 +323,7 @@ int pnr_trace_run_phased(pnr_ctx *c, const pnr_seed *seeds, int64_t n, int32_t *
                          float *xfilt, int32_t *idxres, float *neff, int use_density);
 int pnr_phased_likelihood_run(pnr_ctx *c, int64_t nt, const float *poses, const float *centroids, const int32_t *modes, float *corr,
                               int32_t *uidx, int32_t *cmap, int32_t *flags, int32_t *info); // test tap (pnr_hip_test.h)
+int pnr_phased_decide_run(pnr_ctx *c, int64_t nt, const pnr_phd_in *in, pnr_phd_out *out); // test tap (pnr_hip_test.h)
 void pnr_phased_destroy(pnr_phased *h);
 int pnr_trace_replay_stream(pnr_ctx *c, const pnr_seed *seeds, int64_t n, pnr::Replayer &r, const pnr::ShardSpec &sh, int64_t *iters);
 int pnr_density_reset(pnr_ctx *c);                       // zero the device density map (allocating it on first use)

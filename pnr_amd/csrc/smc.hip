@@ -429,7 +429,9 @@ __global__ __launch_bounds__(768) void smc_trace(Vol V, Tab T, TabX X, const flo
             if (it < O.dbg_iters && O.neff) O.neff[(i64)tr * O.dbg_iters + it] = neff;
             const int x1 = (int)roundf(cx), y1 = (int)roundf(cy), z1 = (int)roundf(cz);
             int res = 0;
-            if (x1 < 0 || x1 >= V.w || y1 < 0 || y1 >= V.h || z1 < 0 || z1 >= V.l) {
+            // (a NaN centroid leaves the volume, as the reference's x86 conversion of the rounded NaN to INT_MIN has it: ph_update)
+            const bool nonfinite = cx != cx || cy != cy || cz != cz;
+            if (nonfinite || x1 < 0 || x1 >= V.w || y1 < 0 || y1 >= V.h || z1 < 0 || z1 >= V.l) {
                 sflag[1] = 1; // left the volume: the centroid's corr is still evaluated (tail pass) for the record
                 sflag[2] = it;
             } else if (den && (int)den[(i64)z1 * V.wh + (i64)y1 * V.w + x1] >= nodepervol) {

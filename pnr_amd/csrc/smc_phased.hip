@@ -29,7 +29,9 @@ namespace {
 
 enum { FL_RES = 0, FL_STOP = 1, FL_T = 2, FL_IT = 3, FL_DONE = 4, FL_OX = 5, FL_OY = 6, FL_OZ = 7, FL_Y0 = 8, FL_Y1 = 9, FL_Z0 = 10, FL_Z1 = 11, FL_FAST = 12, FL_NCH = 13, FL_PAUSE = 14, FL_N = 16 };
 static_assert(FL_N == PNR_PHL_FLAGS && FL_OX == PNR_PHL_OX && FL_OY == PNR_PHL_OY && FL_OZ == PNR_PHL_OZ && FL_Y0 == PNR_PHL_Y0 && FL_Y1 == PNR_PHL_Y1 &&
-              FL_Z0 == PNR_PHL_Z0 && FL_Z1 == PNR_PHL_Z1 && FL_FAST == PNR_PHL_FAST && FL_NCH == PNR_PHL_NCH, "the flag words the test tap names (pnr_hip_test.h)");
+              FL_Z0 == PNR_PHL_Z0 && FL_Z1 == PNR_PHL_Z1 && FL_FAST == PNR_PHL_FAST && FL_NCH == PNR_PHL_NCH && FL_RES == PNR_PHL_RES &&
+              FL_STOP == PNR_PHL_STOP && FL_T == PNR_PHL_T && FL_IT == PNR_PHL_IT && FL_DONE == PNR_PHL_DONE && FL_PAUSE == PNR_PHL_PAUSE,
+              "the flag words the test taps name (pnr_hip_test.h)");
 constexpr int PH_THREADS = 1024; // sampling work-group: 16 waves (<= 128 VGPRs each)
 constexpr int PH_CS = 54; // the sampling kernel holds nothing but the cube in LDS: 54 x 54 rows of 56 bytes = 163 296 B of the 160 KB (53 costs 1.5 %)
 constexpr int PH_PITCH = 56; // row pitch: a multiple of 4, so that every staged dword lands with one aligned ds_write_b32
@@ -866,7 +868,10 @@ __global__ __launch_bounds__(256) void ph_update(Vol V, Tab T, PhState P, int np
         if (it < O.dbg_iters && O.neff) O.neff[(i64)tr * O.dbg_iters + it] = neff;
         const int x1 = (int)roundf(cx), y1 = (int)roundf(cy), z1 = (int)roundf(cz);
         int res = 0;
-        if (x1 < 0 || x1 >= V.w || y1 < 0 || y1 >= V.h || z1 < 0 || z1 >= V.l) {
+        // A NaN centroid (wsum == 0 or NaN: every weight is NaN) leaves the volume: the reference's build converts the rounded NaN
+        // with x86's cvttss2si, which gives INT_MIN; the conversion here gives 0, a voxel inside.
+        const bool nonfinite = cx != cx || cy != cy || cz != cz;
+        if (nonfinite || x1 < 0 || x1 >= V.w || y1 < 0 || y1 >= V.h || z1 < 0 || z1 >= V.l) {
             fl[FL_STOP] = 1;
             fl[FL_T] = it;
         } else if (den && (int)den[(i64)z1 * V.wh + (i64)y1 * V.w + x1] >= nodepervol) {
@@ -1428,6 +1433,105 @@ int pnr_phased_likelihood_run(pnr_ctx *c, int64_t nt_all, const float *poses, co
             info[6] = E.ng; info[7] = (int)((nt_all + E.NT - 1) / E.NT);
         }
     }
+    return PNR_OK;
+}
+
+// Test tap (pnr_hip_test.h pnr_phased_decide): the decision half of ONE step over nt traces whose whole state the caller gives --
+// ph_update on the step list `lp` (the correlations are in P.corr / P.cmap / FL_NCH as the sums would have left them), then
+// ph_predict<false> of the following step on the list ph_update filled, both launched as smc_step launches them, every trace at its
+// own iteration (it = -1).  The kernels are the production ones; the tap only decides what is in memory beforehand, a private copy
+// of the np + 1 draws and of the density map included.
+int pnr_phased_decide_run(pnr_ctx *c, int64_t nt_all, const pnr_phd_in *in, pnr_phd_out *out)
+{
+    PNR_REQUIRE(nt_all >= 1 && nt_all < (1LL << 30), PNR_E_ARG, "pnr_phased_decide: bad number of traces");
+    PNR_REQUIRE(c->d_img, PNR_E_ARG, "pnr_phased_decide: no volume set (pnr_set_volume)");
+    PNR_REQUIRE(c->smc_driver == 0, PNR_E_ARG, "pnr_phased_decide: the phased driver only (pnr_set_smc_driver)");
+    PNR_REQUIRE(in->lp == 0 || in->lp == 1, PNR_E_ARG, "pnr_phased_decide: step list %d", (int)in->lp);
+    PNR_REQUIRE(in->mode == PNR_PHD_STEP || in->mode == PNR_PHD_PREDICT, PNR_E_ARG, "pnr_phased_decide: mode %d", (int)in->mode);
+    PhEnv E;
+    int rc = phased_env(c, nt_all, c->prm.ni, false, false, true, E, 1); // (nothing is sampled: one stash row)
+    if (rc) return rc;
+    PNR_REQUIRE(nt_all <= E.NT, PNR_E_ARG, "pnr_phased_decide: %lld traces, room for %lld", (long long)nt_all, (long long)E.NT);
+    const PhState &P = E.P;
+    const int nt = (int)nt_all, np = E.np, ni = E.ni, S = E.S, np_pad = E.np_pad, lp = in->lp;
+    for (int j = 0; j < nt; j++) { // everything the kernels index with
+        const int *fl = in->flags + (size_t)j * FL_N;
+        PNR_REQUIRE(fl[FL_IT] >= 0 && fl[FL_IT] <= ni, PNR_E_ARG, "pnr_phased_decide: iteration %d of trace %d", fl[FL_IT], j);
+        PNR_REQUIRE(fl[FL_NCH] >= 1 && fl[FL_NCH] <= np + 1, PNR_E_ARG, "pnr_phased_decide: %d chains of trace %d", fl[FL_NCH], j);
+        for (int k = 0; k < np; k++) {
+            const int cm = in->cmap[(size_t)j * np_pad + k], ix = in->idxres[(size_t)j * np + k];
+            PNR_REQUIRE(cm >= 0 && cm < fl[FL_NCH], PNR_E_ARG, "pnr_phased_decide: particle %d of trace %d on chain %d", k, j, cm);
+            PNR_REQUIRE(ix >= 0 && ix < np, PNR_E_ARG, "pnr_phased_decide: resampling index %d of trace %d", ix, j);
+        }
+    }
+    hipStream_t st = c->stream;
+    pnr::DevBuf<unsigned int> d_draws;
+    pnr::DevBuf<unsigned char> d_den;
+    if (in->draws) {
+        PNR_HIP(d_draws.alloc((size_t)np + 1));
+        PNR_HIP(hipMemcpyAsync(d_draws.get(), in->draws, ((size_t)np + 1) * 4, hipMemcpyHostToDevice, st));
+        E.T.rng = d_draws.get();
+    }
+    if (in->den) {
+        PNR_HIP(d_den.alloc((size_t)c->N));
+        PNR_HIP(hipMemcpyAsync(d_den.get(), in->den, (size_t)c->N, hipMemcpyHostToDevice, st));
+    }
+    std::vector<int> list0((size_t)nt);
+    for (int j = 0; j < nt; j++) list0[(size_t)j] = j;
+    int cnt0[2] = {0, 0}; // (the other list's counter: zero, as the step's own ph_predict leaves it for ph_update)
+    cnt0[lp] = nt;
+    TraceOut O = E.h->O;
+    O.dbg_iters = E.dbg_iters;
+    O.xfilt = nullptr; O.idxres = nullptr;
+    PNR_HIP(hipMemcpyAsync(E.h->d_s6.get(), in->seeds, (size_t)nt * 6 * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.part, in->part, (size_t)nt * 2 * np * PSTRIDE * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.prior, in->prior, (size_t)nt * np * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.idxres, in->idxres, (size_t)nt * np * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.xcs, in->xcs, (size_t)nt * 16 * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.corr, in->corr, (size_t)nt * S * np_pad * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.cmap, in->cmap, (size_t)nt * np_pad * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.flags, in->flags, (size_t)nt * FL_N * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemcpyAsync(P.list + (size_t)lp * P.cap, list0.data(), (size_t)nt * 4, hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemsetAsync(P.list + (size_t)(lp ^ 1) * P.cap, 0xff, (size_t)nt * 4, st));
+    PNR_HIP(hipMemcpyAsync(P.cnt, cnt0, sizeof(cnt0), hipMemcpyHostToDevice, st));
+    PNR_HIP(hipMemsetAsync(P.uidx, 0xff, (size_t)nt * np_pad * 4, st));
+    PNR_HIP(hipMemsetAsync(O.T, 0xff, (size_t)nt * 4, st)); // -1: not written
+    PNR_HIP(hipMemsetAsync(O.stop, 0xff, (size_t)nt * 4, st));
+    PNR_HIP(hipMemsetAsync(O.xc, 0, (size_t)nt * ni * 32, st));
+    PNR_HIP(hipMemsetAsync(O.neff, 0, (size_t)nt * E.dbg_iters * 4, st));
+    auto down = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    int lpp = lp; // the list ph_predict runs on
+    if (in->mode == PNR_PHD_STEP) {
+        lpp = lp ^ 1;
+        hipLaunchKernelGGL(ph_update, dim3(nt), dim3(256), E.upd_lds, st, E.V, E.T, P, np, np_pad, ni, -1, lp, c->prm.Kc, c->prm.znccth, c->prm.neff_ratio,
+                           (const unsigned char *)(in->den ? d_den.get() : nullptr), c->prm.nodepervol, O);
+        PNR_HIP(hipGetLastError());
+        PNR_HIP(down(out->part_u, P.part, (size_t)nt * 2 * np * PSTRIDE * 4));
+        PNR_HIP(down(out->neff, O.neff, (size_t)nt * E.dbg_iters * 4));
+        PNR_HIP(down(out->xcs_u, P.xcs, (size_t)nt * 16 * 4));
+        PNR_HIP(down(out->oxc, O.xc, (size_t)nt * ni * 32));
+        PNR_HIP(down(out->oT, O.T, (size_t)nt * 4));
+        PNR_HIP(down(out->ostop, O.stop, (size_t)nt * 4));
+        PNR_HIP(down(out->idxres_u, P.idxres, (size_t)nt * np * 4));
+        PNR_HIP(down(out->prior_u, P.prior, (size_t)nt * np * 4));
+        PNR_HIP(down(out->flags_u, P.flags, (size_t)nt * FL_N * 4));
+        PNR_HIP(down(out->cnt_next, P.cnt + (lp ^ 1), 4));
+        PNR_HIP(down(out->list_next, P.list + (size_t)(lp ^ 1) * P.cap, (size_t)nt * 4));
+        PNR_HIP(hipStreamSynchronize(st));
+    }
+    // the following step's ph_predict, over as many work-groups as the step before had traces (the host's upper bound, as in a trace)
+    // -- or, PNR_PHD_PREDICT, the ph_predict of the traces' own step on the list given
+    PNR_HIP(hipMemsetAsync(P.cmap, 0xff, (size_t)nt * np_pad * 4, st));
+    hipLaunchKernelGGL(ph_predict<false>, dim3(nt), dim3(256), ph_predict_lds(np, P.dedup), st, E.T, E.X, P, (const float *)E.h->d_s6.get(), E.V, np, ni, -1, lpp, PH_CS,
+                       ph_tbl(np));
+    PNR_HIP(hipGetLastError());
+    PNR_HIP(down(out->part_p, P.part, (size_t)nt * 2 * np * PSTRIDE * 4));
+    PNR_HIP(down(out->prior_p, P.prior, (size_t)nt * np * 4));
+    PNR_HIP(down(out->flags_p, P.flags, (size_t)nt * FL_N * 4));
+    PNR_HIP(down(out->uidx, P.uidx, (size_t)nt * np_pad * 4));
+    PNR_HIP(down(out->cmap_p, P.cmap, (size_t)nt * np_pad * 4));
+    PNR_HIP(down(out->cnt_p, P.cnt, 8));
+    PNR_HIP(hipStreamSynchronize(st));
     return PNR_OK;
 }
 

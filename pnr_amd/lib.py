@@ -277,6 +277,7 @@ def load():
     L.pnr_set_j8_v.argtypes = [vp] + [vp] * 4
     L.pnr_seed_handover.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
     L.pnr_phased_likelihood.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pnr_phased_decide.argtypes = [vp, i64, C.POINTER(PhdIn), C.POINTER(PhdOut)]
     L.pnr_extract_seeds.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.pnr_extract_seeds_range.argtypes = [vp, i64, i64, C.POINTER(vp), C.POINTER(i64)]
     L.pnr_zncc_batch.argtypes = [vp, vp, i64, vp, vp]
@@ -342,7 +343,7 @@ PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_de
 # test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
 TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
                 "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes", "pnr_render_items", "pnr_test_write_tiff",
-                "pnr_seed_handover", "pnr_phased_likelihood"]
+                "pnr_seed_handover", "pnr_phased_likelihood", "pnr_phased_decide"]
 EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
@@ -371,6 +372,19 @@ def make_params(sigmas=(2, 4, 6), somaradius=0, tolerance=5, znccth=0.3, kappa=3
 # pnr_phased_likelihood (include/pnr_hip_test.h): modes and the flag words it returns
 PHL_FIRST, PHL_REGULAR, PHL_TAIL = 0, 1, 2
 PHL_OX, PHL_OY, PHL_OZ, PHL_Y0, PHL_Y1, PHL_Z0, PHL_Z1, PHL_FAST, PHL_NCH = 5, 6, 7, 8, 9, 10, 11, 12, 13
+# pnr_phased_decide: the flag words it reads and writes besides, and its two argument blocks
+PHL_RES, PHL_STOP, PHL_T, PHL_IT, PHL_DONE, PHL_PAUSE = 0, 1, 2, 3, 4, 14
+PHD_IN = ("flags", "seeds", "part", "prior", "idxres", "xcs", "corr", "cmap", "draws", "den")
+PHD_OUT = ("part_u", "neff", "xcs_u", "oxc", "oT", "ostop", "idxres_u", "prior_u", "flags_u", "cnt_next", "list_next",
+           "part_p", "prior_p", "flags_p", "uidx", "cmap_p", "cnt_p")
+
+
+class PhdIn(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in PHD_IN] + [("lp", C.c_int32), ("mode", C.c_int32)]
+
+
+class PhdOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in PHD_OUT]
 
 
 # what a new Context starts with (tests run every case with both SMC drivers by patching this; the library itself reads no
@@ -825,6 +839,47 @@ class Context:
         check(self.L.pnr_phased_likelihood(self.h, nt, poses.ctypes.data, cen.ctypes.data, modes.ctypes.data, out["corr"].ctypes.data,
                                            out["uidx"].ctypes.data, out["cmap"].ctypes.data, out["flags"].ctypes.data, info.ctypes.data))
         out["info"] = dict(zip(("np_pad", "S", "nsplit", "share", "deep", "cube_copy", "ng", "rounds"), (int(v) for v in info)))
+        return out
+
+    def phased_decide(self, flags, seeds, part, prior, idxres, xcs, corr, cmap, draws=None, den=None, lp=0, predict_only=False):
+        """test tap pnr_phased_decide: ph_update, then the following step's ph_predict, over the given traces in the device's layout --
+        flags (nt, 16), seeds (nt, 6), part (nt, 2, np, 9), prior (nt, np), idxres (nt, np), xcs (nt, 2, 8), corr (nt, S, np_pad), cmap
+        (nt, np_pad), draws (np + 1,) or None, den (l, h, w) or None.  Returns the state after ph_update (part_u, neff, xcs_u, oxc, oT,
+        ostop, idxres_u, prior_u, flags_u, cnt_next, list_next) and after ph_predict (part_p, prior_p, flags_p, uidx, cmap_p, cnt_p);
+        predict_only: ph_predict alone, at the traces' own iterations (iteration 0's draw)"""
+        n_p, S, ni = int(self.p.np), int(self.p.nsig), int(self.p.ni)
+        np_pad = (n_p + 1 + 63) // 64 * 64
+        flags = np.ascontiguousarray(flags, np.int32)
+        nt = len(flags)
+        a = dict(flags=flags, seeds=np.ascontiguousarray(seeds, np.float32), part=np.ascontiguousarray(part, np.float32),
+                 prior=np.ascontiguousarray(prior, np.float32), idxres=np.ascontiguousarray(idxres, np.int32), xcs=np.ascontiguousarray(xcs, np.float32),
+                 corr=np.ascontiguousarray(corr, np.float32), cmap=np.ascontiguousarray(cmap, np.int32))
+        shapes = dict(flags=(nt, 16), seeds=(nt, 6), part=(nt, 2, n_p, 9), prior=(nt, n_p), idxres=(nt, n_p), xcs=(nt, 2, 8), corr=(nt, S, np_pad),
+                      cmap=(nt, np_pad))
+        for k, shp in shapes.items():
+            if a[k].shape != shp:
+                raise PnrError(f"{k} {a[k].shape} for {nt} traces of {n_p} particles: {shp}")
+        if draws is not None:
+            a["draws"] = np.ascontiguousarray(draws, np.uint32)
+            if a["draws"].shape != (n_p + 1,):
+                raise PnrError(f"draws {a['draws'].shape}")
+        if den is not None:
+            a["den"] = np.ascontiguousarray(den, np.uint8)
+            if a["den"].shape != tuple(self.shape):
+                raise PnrError(f"den {a['den'].shape} for a volume {self.shape}")
+        i32, f32 = np.int32, np.float32
+        out = dict(part_u=np.zeros(shapes["part"], f32), neff=np.zeros((nt, ni), f32), xcs_u=np.zeros(shapes["xcs"], f32), oxc=np.zeros((nt, ni, 8), f32),
+                   oT=np.zeros(nt, i32), ostop=np.zeros(nt, i32), idxres_u=np.zeros(shapes["idxres"], i32), prior_u=np.zeros(shapes["prior"], f32),
+                   flags_u=np.zeros(shapes["flags"], i32), cnt_next=np.zeros(1, i32), list_next=np.zeros(nt, i32),
+                   part_p=np.zeros(shapes["part"], f32), prior_p=np.zeros(shapes["prior"], f32), flags_p=np.zeros(shapes["flags"], i32),
+                   uidx=np.zeros((nt, np_pad), i32), cmap_p=np.zeros((nt, np_pad), i32), cnt_p=np.zeros(2, i32))
+        pin, pout = PhdIn(), PhdOut()
+        for k in PHD_IN:
+            setattr(pin, k, a[k].ctypes.data if k in a else None)
+        pin.lp, pin.mode = int(lp), int(bool(predict_only))
+        for k in PHD_OUT:
+            setattr(pout, k, out[k].ctypes.data)
+        check(self.L.pnr_phased_decide(self.h, nt, C.byref(pin), C.byref(pout)))
         return out
 
     def zncc(self, pos_dir):

@@ -64,6 +64,15 @@ def load_oracle():
     L.orc_trace.argtypes = [C.c_void_p, f32p, u8p, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_int), C.c_int,
                             C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_trace.restype = C.c_int
+    L.orc_tracker_set_rng.argtypes = [C.c_void_p, u32p, C.c_int]
+    L.orc_tracker_set_rng.restype = None
+    L.orc_smc_draw.argtypes = [C.c_void_p, C.c_int, f32p, C.c_void_p, C.c_int, C.c_void_p, f32p, f32p, i32p, i32p]
+    L.orc_smc_draw.restype = C.c_int
+    L.orc_smc_decide.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_float), f32p, f32p,
+                                 i32p, C.POINTER(C.c_int), i32p, f32p]
+    L.orc_smc_decide.restype = C.c_int
+    L.orc_smc_pending.argtypes = [C.c_void_p, f32p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.orc_smc_pending.restype = C.c_int
     L.orc_replay.argtypes = [f32p, C.c_int64, i32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.c_void_p, C.c_int64, i32p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.orc_replay.restype = C.c_int64
@@ -182,6 +191,50 @@ class Tracker:
 
     def rng(self):
         return np.ctypeslib.as_array(self.L.orc_tracker_rng(self.h), shape=(self.np + 1,)).copy()
+
+    def set_rng(self, draws):
+        """replace the np + 1 draws of the tracker's rand() stream"""
+        d = np.ascontiguousarray(draws, np.uint32)
+        assert d.shape == (self.np + 1,)
+        self.L.orc_tracker_set_rng(self.h, d, len(d))
+
+    def smc_draw(self, it, seed6, prev=None, resampled_prev=0, idxres_prev=None):
+        """orc_smc_draw: poses (np, 6), prior (np,), dir (np,) the parent's direction index (-1: a NaN direction, no reference value;
+        0 at iteration 0), s (np,) the prediction offset drawn"""
+        poses, prior, nodir, sidx = np.zeros((self.np, 6), np.float32), np.zeros(self.np, np.float32), np.zeros(self.np, np.int32), np.zeros(self.np, np.int32)
+        if it > 0:
+            prev = np.ascontiguousarray(prev, np.float32)
+            assert prev.shape == (self.np, 9)
+            idx = np.ascontiguousarray(idxres_prev if idxres_prev is not None else np.zeros(self.np), np.int32)
+            assert idx.shape == (self.np,) and (not resampled_prev or ((idx >= 0) & (idx < self.np)).all())
+            self.L.orc_smc_draw(self.h, it, np.ascontiguousarray(seed6, np.float32), prev.ctypes.data, int(resampled_prev), idx.ctypes.data, poses, prior, nodir, sidx)
+        else:
+            self.L.orc_smc_draw(self.h, 0, np.ascontiguousarray(seed6, np.float32), None, 0, None, poses, prior, nodir, sidx)
+        return poses, prior, nodir, sidx
+
+    def smc_decide(self, it, poses, prior, prevw, cs, dims):
+        """orc_smc_decide on the per-scale correlations cs (S, np); dims = (w, h, l).  Returns a dict: border, xf (np, 9), neff, csw,
+        xc7, xyz1, resampled, idxres and ui (None unless resampled)"""
+        poses, prior = np.ascontiguousarray(poses, np.float32), np.ascontiguousarray(prior, np.float32)
+        cs = np.ascontiguousarray(cs, np.float32)
+        assert poses.shape == (self.np, 6) and prior.shape == (self.np,) and cs.shape == (len(self.sigs), self.np)
+        pw = None if prevw is None else np.ascontiguousarray(prevw, np.float32)
+        assert pw is None or pw.shape == (self.np,)
+        xf, csw, xc7, xyz1, idx = np.zeros((self.np, 9), np.float32), np.zeros(self.np, np.float32), np.zeros(7, np.float32), np.zeros(3, np.int32), np.zeros(self.np, np.int32)
+        ui = np.zeros(self.np, np.float32)
+        neff, res = C.c_float(), C.c_int()
+        border = self.L.orc_smc_decide(self.h, it, poses, prior, None if pw is None else pw.ctypes.data, cs, dims[0], dims[1], dims[2], xf, C.byref(neff),
+                                       csw, xc7, xyz1, C.byref(res), idx, ui)
+        return dict(border=bool(border), xf=xf, neff=np.float32(neff.value), csw=csw, xc7=xc7, xyz1=xyz1, resampled=bool(res.value),
+                    idxres=idx if res.value else None, ui=ui if res.value else None)
+
+    def smc_pending(self, cs, sig_in):
+        """orc_smc_pending: (best, sig, best < znccth) of a centroid with per-scale correlations cs (S,)"""
+        cs = np.ascontiguousarray(cs, np.float32)
+        assert cs.shape == (len(self.sigs),)
+        best, sig = C.c_float(), C.c_float(float(sig_in))
+        low = self.L.orc_smc_pending(self.h, cs, C.byref(best), C.byref(sig))
+        return np.float32(best.value), np.float32(sig.value), bool(low)
 
     def model(self, s):
         M = self.L.orc_tracker_model_count(self.h, s)

@@ -157,6 +157,32 @@ def test_trace_nan_direction_and_border_seed(oracle):
             assert np.array_equal(mat(xc[j])[:rows], xco[:rows], equal_nan=True)
 
 
+def test_trace_nonfinite_centroid(oracle):
+    """Kc = 1e30: every likelihood is exp(+-huge) = inf or 0, so the normalised weights and with them N_eff and the centroid are NaN
+    at iteration 0.  The reference's build converts the rounded NaN to INT_MIN (x86): the trace leaves the volume, stop 1 at T = 0;
+    the record of that iteration carries the NaN centroid (its own correlation has no reference value: Tracker::interp indexes the
+    image with the converted NaN)"""
+    img = synth.synth(48, 40, 24, seed=1)
+    so = np.array([[24, 12, 11, 0.6, 0.8, 0, 0, 0], [30, 20, 12, 0, 0, 1, 0, 0]], np.float32)
+    To = orc.Tracker(oracle, [2.0, 3.0], 2, 20, 10, 3.0, 0.3, Kc=1e30, zdist=2.0)
+    seeds = np.zeros(len(so), lib.SEED_DT)
+    for i, k in enumerate(lib.SEED_DT.names):
+        seeds[k] = so[:, i]
+    c = pnr_amd.Context(pnr_amd.make_params(sigmas=[2.0, 3.0], np_=20, ni=10, Kc=1e30), 0)
+    c.set_volume(img)
+    T, stop, xc, dbg = c.trace_batch(seeds, dbg_iters=2)
+    c.close()
+    for i, sd in enumerate(so):
+        for d, sgn in enumerate((1, -1)):
+            q = sd[:6].copy(); q[3:] *= sgn
+            Tn, st, xco, xf, idx, neff = To.trace(img, q, max_dbg=2)
+            j = 2 * i + d
+            assert (Tn, st) == (0, 1) and np.isnan(xco[0, :3]).all() and np.isnan(neff[0]) and np.isnan(xf[0, :, 6]).any()
+            assert T[j] == Tn and stop[j] == st, (j, T[j], stop[j])
+            assert np.array_equal(mat(xc[j])[0, :6], xco[0, :6], equal_nan=True)
+            assert np.array_equal(dbg["xfilt"][j, 0], xf[0], equal_nan=True) and np.array_equal(dbg["neff"][j, :1], neff[:1], equal_nan=True)
+
+
 def test_trace_leaving_through_a_border(oracle):
     """bright lines running into the +y, +z and -x faces: the trace leaves the volume there, and the record of the failing
     iteration still carries the ZNCC of the out-of-volume centroid, whose samples are clamped onto the two outermost
