@@ -5,10 +5,12 @@
 //
 // dist_prep turns the segments into two float4 each: (a, r) and (ab, 0), so a segment is two scalar dwordx4 loads per wave and the
 // vector unit only does the ~25 operations of the pair.  Every pair counts, so a point whose minimum stays +inf reports the first
-// segment of the smallest slice.  Above it: tree_sample, the host's sampling of a tree.
+// segment of the smallest slice.  Above it, the host's side of a tree distance: tree_sample, the
+// sampling of a tree; tree_side and direction_metrics, the points and segments of one tree and the metrics of one direction.
 #include "distance.h"
 #include "call.h"
 #include "pairmin.h"
+#include <algorithm>
 #include <cmath>
 
 namespace pnr {
@@ -46,6 +48,46 @@ int tree_sample(const float *xyz, const int32_t *parent, int64_t n, float zscale
     }
     *n_out = k;
     return PNR_OK;
+}
+
+int tree_side(const char *which, const float *xyz, const int32_t *parent, int64_t n, const pnr_distance_opts &o, TreeSide &s)
+{
+    PNR_REQUIRE(n >= 1 && n <= PNR_DISTANCE_MAX_N && xyz && parent, PNR_E_ARG, "pnr_tree_distance: tree %s has %lld nodes (1 to 2^22)", which, (long long)n);
+    int rc = tree_sample(xyz, parent, n, o.zscale, o.step, nullptr, nullptr, 0, &s.np);
+    if (rc) return rc;
+    PNR_REQUIRE(s.np <= PNR_DISTANCE_MAX_N, PNR_E_ARG, "pnr_tree_distance: tree %s has %lld sample points (at most 2^22): raise the step", which, (long long)s.np);
+    s.n = n;
+    s.pts.resize((size_t)s.np * 3);
+    s.owner.resize((size_t)s.np);
+    s.d.resize((size_t)s.np);
+    if ((rc = tree_sample(xyz, parent, n, o.zscale, o.step, s.pts.data(), s.owner.data(), s.np, &s.np))) return rc;
+    s.a.resize((size_t)n * 3);
+    s.b.resize((size_t)n * 3);
+    for (int64_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) s.a[(size_t)(3 * i + k)] = k == 2 ? xyz[3 * i + 2] * o.zscale : xyz[3 * i + k];
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t q = parent[i] < 0 ? i : parent[i];
+        for (int k = 0; k < 3; k++) s.b[(size_t)(3 * i + k)] = s.a[(size_t)(3 * q + k)];
+    }
+    return PNR_OK;
+}
+// the metrics of one direction: sequential f64 sums in point order
+void direction_metrics(const std::vector<float> &d, float thr, pnr_distance_dir &r)
+{
+    double sum = 0, sum_big = 0;
+    float mx = 0.f;
+    int64_t big = 0;
+    for (float v : d) {
+        sum += (double)v;
+        if (v >= thr) sum_big += (double)v, big++;
+        mx = std::max(mx, v);
+    }
+    r.n = (int64_t)d.size();
+    r.n_big = big;
+    r.mean = sum / (double)r.n;
+    r.ssd = big ? sum_big / (double)big : 0.0;
+    r.pct = (double)big / (double)r.n;
+    r.max = (double)mx;
 }
 
 } // namespace pnr

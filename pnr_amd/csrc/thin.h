@@ -1,6 +1,8 @@
-// thin.h -- topological thinning of the traced 8-bit volume to a curve skeleton (thin.hip), behind pnr_skeletonize.
+// thin.h -- topological thinning of the traced 8-bit volume to a curve skeleton (thin.hip), behind pnr_skeletonize, and
+// the skeleton's voxels as a forest, behind pnr_skeleton_forest.
 #pragma once
 #include "ctx.h"
+#include <vector>
 
 namespace pnr {
 
@@ -11,6 +13,11 @@ constexpr int THIN_TY = 8;
 constexpr int THIN_TZ = 8;
 // voxels per work-group of the count and list kernels (one raster-order chunk; a wave owns a contiguous quarter of it)
 constexpr int THIN_CHUNK = 4096;
+
+// The k voxels vox (linear indices of a w x h x l grid, any order; node i = vox[i]) as a forest, behind pnr_skeleton_forest: Kruskal over the
+// 26-adjacent pairs under (len2, lo, hi); every key is distinct, so the forest is unique.  edges: sorted by (lo, hi), d = the step length.
+// Pure host code; k and the grid are checked by the caller.  PNR_E_ARG: a voxel outside the grid or listed twice.
+int skeleton_forest(const char *who, const int64_t *vox, int64_t k, int64_t w, int64_t h, int64_t l, std::vector<pnr_bridge> &edges);
 
 } // namespace pnr
 

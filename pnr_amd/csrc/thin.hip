@@ -20,9 +20,12 @@
 //                written in raster order with their degree (object voxels in N26).
 //   thin_finish  the state becomes 0 / 255.
 // The host reads one word of deletions and the eight list lengths per round.
+// Below the kernels: skeleton_forest, the host's Kruskal over the skeleton's voxels.
 #include "thin.h"
 #include "call.h"
 #include "volume.h"
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -407,3 +410,56 @@ int pnr_thin_run(pnr_ctx *c, const char *who, const pnr_thin_opts &o, pnr_thin_i
     if (deg_out && fill) std::memcpy(deg_out, deg.data(), fill);
     return PNR_OK;
 }
+
+namespace pnr {
+
+int skeleton_forest(const char *who, const int64_t *vox, int64_t k, int64_t w, int64_t h, int64_t l, std::vector<pnr_bridge> &out)
+{
+    const int64_t N = w * h * l;
+    std::vector<std::pair<int64_t, int32_t>> at((size_t)k); // (voxel, node), sorted by voxel
+    for (int64_t i = 0; i < k; i++) {
+        PNR_REQUIRE(vox[i] >= 0 && vox[i] < N, PNR_E_ARG, "%s: voxel %lld of node %lld is outside the grid", who, (long long)vox[i], (long long)i);
+        at[(size_t)i] = {vox[i], (int32_t)i};
+    }
+    std::sort(at.begin(), at.end());
+    for (int64_t i = 1; i < k; i++) PNR_REQUIRE(at[(size_t)i].first != at[(size_t)i - 1].first, PNR_E_ARG, "%s: voxel %lld is listed twice", who, (long long)at[(size_t)i].first);
+    struct Edge {
+        int32_t len2, lo, hi;
+    };
+    std::vector<Edge> edges;
+    for (int64_t i = 0; i < k; i++) {
+        const int64_t v = at[(size_t)i].first, x = v % w, y = v / w % h, z = v / (w * h);
+        for (int dz = 0; dz <= 1; dz++)
+            for (int dy = -1; dy <= 1; dy++)
+                for (int dx = -1; dx <= 1; dx++) {
+                    if (!(dz > 0 || dy > 0 || (dy == 0 && dx > 0))) continue; // the 13 forward neighbours
+                    const int64_t nx = x + dx, ny = y + dy, nz = z + dz;
+                    if (nx < 0 || nx >= w || ny < 0 || ny >= h || nz >= l) continue;
+                    const int64_t u = (nz * h + ny) * w + nx;
+                    const auto it = std::lower_bound(at.begin() + i + 1, at.end(), std::make_pair(u, (int32_t)0));
+                    if (it == at.end() || it->first != u) continue;
+                    const int32_t a = at[(size_t)i].second, b = it->second;
+                    edges.push_back(Edge{dx * dx + dy * dy + dz * dz, std::min(a, b), std::max(a, b)});
+                }
+    }
+    std::sort(edges.begin(), edges.end(), [](const Edge &p, const Edge &q) { return p.len2 != q.len2 ? p.len2 < q.len2 : p.lo != q.lo ? p.lo < q.lo : p.hi < q.hi; });
+    std::vector<int32_t> up((size_t)k);
+    for (int64_t i = 0; i < k; i++) up[(size_t)i] = (int32_t)i;
+    auto find = [&](int32_t a) {
+        while (up[(size_t)a] != a) a = up[(size_t)a] = up[(size_t)up[(size_t)a]];
+        return a;
+    };
+    std::vector<Edge> kept;
+    for (const Edge &e : edges) {
+        const int32_t a = find(e.lo), b = find(e.hi);
+        if (a == b) continue;
+        up[(size_t)std::max(a, b)] = std::min(a, b);
+        kept.push_back(e);
+    }
+    std::sort(kept.begin(), kept.end(), [](const Edge &p, const Edge &q) { return p.lo != q.lo ? p.lo < q.lo : p.hi < q.hi; });
+    out.clear();
+    for (const Edge &e : kept) out.push_back(pnr_bridge{e.lo, e.hi, sqrtf((float)e.len2)});
+    return PNR_OK;
+}
+
+} // namespace pnr

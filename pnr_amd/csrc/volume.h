@@ -13,3 +13,9 @@ int pnr_volume_u16_run(pnr_ctx *c, const uint16_t *d_src, int nchan, int channel
 int pnr_byte_sum_run(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_sum, unsigned long long *sum);
 // The threshold "thr = -1" of the radii, the coverage and the components: *t = the floor of the exact mean of V, at least 1.
 int pnr_mean_threshold(pnr_ctx *c, const char *who, const char *group, const uint8_t *V, int64_t N, unsigned long long *d_word, int *t);
+
+namespace pnr {
+// A tool's finished result becomes the context's volume (pnr_filter_volume, pnr_despeckle_volume; api.cpp): what pnr_set_volume of the same
+// bytes leaves -- owned, the same dimensions, no later pipeline state.
+void replace_volume(pnr_ctx *c, DevBuf<uint8_t> &&v);
+} // namespace pnr

@@ -233,118 +233,11 @@ def load():
         except Exception:
             pass
     L = C.CDLL(LIB_PATH)
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    L.pnr_last_error.restype = C.c_char_p
-    L.pnr_default_params.argtypes = [C.POINTER(Params)]
-    L.pnr_default_params.restype = None
-    L.pnr_create.argtypes = [C.POINTER(Params), i32, C.POINTER(vp)]
-    L.pnr_destroy.argtypes = [vp]
-    L.pnr_destroy.restype = None
-    L.pnr_set_stream.argtypes = [vp, vp]
-    L.pnr_synchronize.argtypes = [vp]
-    L.pnr_set_volume.argtypes = [vp, vp, i64, i64, i64]
-    L.pnr_set_volume_device.argtypes = [vp, vp, i64, i64, i64]
-    L.pnr_set_volume_u16.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.pnr_set_volume_u16_device.argtypes = [vp, vp, i64, i64, i64, i32, i32, C.POINTER(Window), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.pnr_get_volume.argtypes = [vp, vp]
-    L.pnr_measure_radii.argtypes = [vp, vp, i64, C.POINTER(RadiusOpts), vp, C.POINTER(C.c_int32)]
-    L.pnr_filter_volume.argtypes = [vp, C.POINTER(FilterOpts)]
-    L.pnr_point_segment_distance.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
-    L.pnr_tree_sample.argtypes = [vp, vp, i64, C.c_float, C.c_float, vp, vp, i64, C.POINTER(i64)]
-    L.pnr_tree_distance.argtypes = [vp, vp, vp, i64, vp, vp, i64, C.POINTER(DistanceOpts), C.POINTER(DistanceResult), vp, vp, i64, vp, vp, i64]
-    L.pnr_nearest_other.argtypes = [vp, vp, vp, i64, vp, vp]
-    L.pnr_join_trees.argtypes = [vp, vp, vp, i64, C.POINTER(JoinOpts), vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_join_reroot.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
-    L.pnr_render_tree.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), vp, vp]
-    L.pnr_tree_coverage.argtypes = [vp, vp, vp, vp, i64, C.POINTER(RenderOpts), C.POINTER(Coverage), vp, vp, vp, vp, vp]
-    L.pnr_label_components.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo), vp, vp, i64]
-    L.pnr_despeckle_volume.argtypes = [vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]
-    L.pnr_distance_transform.argtypes = [vp, C.POINTER(EdtOpts), C.POINTER(EdtInfo), vp, vp, i64, vp]
-    L.pnr_skeletonize.argtypes = [vp, C.POINTER(ThinOpts), C.POINTER(ThinInfo), vp, vp, vp, i64]
-    L.pnr_skeleton_forest.argtypes = [vp, i64, i64, i64, i64, vp, i64, C.POINTER(i64)]
-    L.pnr_geodesic_distance.argtypes = [vp, vp, vp, i64, C.POINTER(GeoOpts), C.POINTER(GeoInfo), vp, vp, vp, i64, vp, vp, i32, vp, vp]
-    L.pnr_geodesic_bridges.argtypes = [vp, vp, vp, i64, C.POINTER(GeoJoinOpts), C.POINTER(GeoJoinInfo), vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
-    L.pnr_join_expand.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, C.POINTER(i64), vp]
-    L.pnr_render_items.argtypes = [vp, vp, vp, i64, i64, i64, i64, C.POINTER(RenderOpts), i64, i64, vp, i64, C.POINTER(i64)]
-    L.pnr_test_write_tiff.argtypes = [C.c_char_p, vp, i64, i64, i64]
-    L.pnr_radius_offsets.argtypes = [C.c_float, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
-    L.pnr_pair_tiles.argtypes = [i64, i64, i64, i64, vp, i64, C.POINTER(i64)]
-    L.pnr_live_bytes.argtypes = [C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_frangi.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.pnr_get_frangi.argtypes = [vp] + [vp] * 5
-    L.pnr_gaussian.argtypes = [vp, C.c_float, vp]
-    L.pnr_hessian.argtypes = [vp, C.c_float] + [vp] * 6
-    L.pnr_set_j8_v.argtypes = [vp] + [vp] * 4
-    L.pnr_seed_handover.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
-    L.pnr_phased_likelihood.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pnr_phased_decide.argtypes = [vp, i64, C.POINTER(PhdIn), C.POINTER(PhdOut)]
-    L.pnr_extract_seeds.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
-    L.pnr_extract_seeds_range.argtypes = [vp, i64, i64, C.POINTER(vp), C.POINTER(i64)]
-    L.pnr_zncc_batch.argtypes = [vp, vp, i64, vp, vp]
-    L.pnr_score_filter_sort_seeds.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.pnr_score_filter_seeds.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.pnr_sort_seeds.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.pnr_trace_batch.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]
-    L.pnr_replay_traces.argtypes = [C.POINTER(Params), i64, i64, i64, vp, i64, vp, vp, vp, i64, C.POINTER(i64), vp, i64,
-                                    C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_trace_replay.argtypes = [vp, vp, i64, i64, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_reconstruct.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, vp, i64, C.POINTER(i64)]
-    L.pnr_reconstruct_ctx.argtypes = [vp, vp, i64, vp, i64, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, vp, i64, C.POINTER(i64)]
-    L.pnr_reconstruct_stage_ctx.argtypes = [vp, vp, i64, vp, i64, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, i64, C.POINTER(i64),
-                                            vp, i64, C.POINTER(i64)]
-    L.pnr_get_table.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
-    L.pnr_frangi_slab.argtypes = [vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.pnr_quantise_j8.argtypes = [vp, C.c_float, C.c_float]
-    L.pnr_soma.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(i64)]
-    L.pnr_get_soma.argtypes = [vp, vp, i64, C.POINTER(i64), vp, vp, i64, C.POINTER(i64)]
-    L.pnr_replay_traces_ctx.argtypes = [vp, vp, i64, vp, vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_set_profiling.argtypes = [vp, i32]
-    L.pnr_set_smc_driver.argtypes = [vp, i32]
-    L.pnr_get_kernel_ms.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)]
-    L.pnr_reset_kernel_ms.argtypes = [vp]
-    L.pnr_expf_batch.argtypes = [vp, vp, i64, vp]
-    L.pnr_eigen_batch.argtypes = [vp, vp, i64, vp, vp]
-    L.pnr_get_graph.argtypes = [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
-    L.pnr_trace_replay_sharded.argtypes = [vp, vp, i64, i32, i32, ALLGATHER_FN, vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64),
-                                           C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_sched_playback.argtypes = [C.POINTER(Params), i64, i64, i64, vp, i64, i32, i32, ALLGATHER_FN, vp, i64, TRACE_FN, vp, i32, i32, i32, i32, i32,
-                                     vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_sched_playback2.argtypes = [C.POINTER(Params), i64, i64, i64, vp, i64, i32, i32, ALLGATHER_FN, vp, i64, TRACE_FN, vp, i32, i32, i32, i32, i32, i32, i32, i32,
-                                      vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.pnr_get_trace_log.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.pnr_shm_exchange_open.argtypes = [C.c_char_p, i32, i32, i64, C.POINTER(vp)]
-    L.pnr_shm_allgather.argtypes = [vp, vp, vp, i64]
-    L.pnr_shm_exchange_close.argtypes = [vp]
-    L.pnr_shm_exchange_close.restype = None
-    L.pnr_rccl_unique_id.argtypes = [vp]
-    L.pnr_rccl_exchange_open.argtypes = [vp, i32, i32, i32, i64, C.POINTER(vp)]
-    L.pnr_rccl_allgather.argtypes = [vp, vp, vp, i64]
-    L.pnr_rccl_allreduce_minmax.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.pnr_rccl_exchange_close.argtypes = [vp]
-    L.pnr_rccl_exchange_close.restype = None
-    L.pnr_set_option.argtypes = [vp, C.c_char_p, i64]
-    L.pnr_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
-    for name in EXPORTS:
-        if name not in ("pnr_last_error", "pnr_default_params", "pnr_destroy", "pnr_shm_exchange_close", "pnr_rccl_exchange_close"):
-            getattr(L, name).restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
-
-
-# the drop-in boundary (include/pnr_hip.h)
-PRODUCT_EXPORTS = ["pnr_last_error", "pnr_default_params", "pnr_create", "pnr_destroy", "pnr_set_stream", "pnr_synchronize",
-                   "pnr_set_volume", "pnr_set_volume_device", "pnr_set_volume_u16", "pnr_set_volume_u16_device", "pnr_get_volume", "pnr_measure_radii", "pnr_filter_volume", "pnr_point_segment_distance", "pnr_tree_sample", "pnr_tree_distance", "pnr_nearest_other", "pnr_join_trees", "pnr_join_reroot", "pnr_render_tree", "pnr_tree_coverage", "pnr_label_components", "pnr_despeckle_volume", "pnr_distance_transform", "pnr_skeletonize", "pnr_skeleton_forest", "pnr_geodesic_distance", "pnr_geodesic_bridges", "pnr_join_expand", "pnr_frangi", "pnr_get_frangi", "pnr_extract_seeds", "pnr_extract_seeds_range",
-                   "pnr_zncc_batch", "pnr_score_filter_sort_seeds", "pnr_trace_batch", "pnr_replay_traces", "pnr_replay_traces_ctx",
-                   "pnr_frangi_slab", "pnr_quantise_j8", "pnr_soma", "pnr_get_soma", "pnr_trace_replay", "pnr_reconstruct", "pnr_reconstruct_ctx", "pnr_reconstruct_stage", "pnr_set_profiling",
-                   "pnr_set_smc_driver", "pnr_get_kernel_ms", "pnr_reset_kernel_ms", "pnr_get_graph", "pnr_trace_replay_sharded",
-                   "pnr_set_option", "pnr_get_option", "pnr_score_filter_seeds", "pnr_sort_seeds", "pnr_get_trace_log",
-                   "pnr_shm_exchange_open", "pnr_shm_allgather", "pnr_shm_exchange_close",
-                   "pnr_rccl_unique_id", "pnr_rccl_exchange_open", "pnr_rccl_allgather", "pnr_rccl_allreduce_minmax", "pnr_rccl_exchange_close"]
-# test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
-TEST_EXPORTS = ["pnr_gaussian", "pnr_hessian", "pnr_set_j8_v", "pnr_get_table", "pnr_expf_batch", "pnr_eigen_batch",
-                "pnr_sched_playback", "pnr_sched_playback2", "pnr_reconstruct_stage_ctx", "pnr_radius_offsets", "pnr_pair_tiles", "pnr_live_bytes", "pnr_render_items", "pnr_test_write_tiff",
-                "pnr_seed_handover", "pnr_phased_likelihood", "pnr_phased_decide"]
-EXPORTS = PRODUCT_EXPORTS + TEST_EXPORTS
 
 
 def check(rc):
@@ -385,6 +278,106 @@ class PhdIn(C.Structure):
 
 class PhdOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in PHD_OUT]
+
+
+# The C boundary, one entry per function: name -> (restype, argtypes).  load() binds exactly these, and the export lists are their keys.
+_vp, _i64, _i32, _f32, _str, _rc = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_char_p, C.c_int
+_pi64, _pi32, _pf32 = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)
+_volume_u16 = [_vp, _vp, _i64, _i64, _i64, _i32, _i32, C.POINTER(Window), _pi32, _pi32]
+_seed_filter = [_vp, _vp, _i64, _pi64]
+_graph_out = [_vp, _i64, _pi64, _vp, _i64, _pi64]  # nodes, cap_nodes, n_nodes, links, cap_links, n_links
+_recon_in = [_vp, _i64, _vp, _i64, _f32, _f32, _i32, _f32, _f32, _i32]  # nodes, links, the five constants, tree_size_min or stage
+_playback = [C.POINTER(Params), _i64, _i64, _i64, _vp, _i64, _i32, _i32, ALLGATHER_FN, _vp, _i64, TRACE_FN, _vp, _i32, _i32, _i32, _i32, _i32]
+# the drop-in boundary (include/pnr_hip.h)
+PRODUCT_SIGNATURES = {
+    "pnr_last_error": (_str, []),
+    "pnr_default_params": (None, [C.POINTER(Params)]),
+    "pnr_create": (_rc, [C.POINTER(Params), _i32, C.POINTER(_vp)]),
+    "pnr_destroy": (None, [_vp]),
+    "pnr_set_stream": (_rc, [_vp, _vp]),
+    "pnr_synchronize": (_rc, [_vp]),
+    "pnr_set_volume": (_rc, [_vp, _vp, _i64, _i64, _i64]),
+    "pnr_set_volume_device": (_rc, [_vp, _vp, _i64, _i64, _i64]),
+    "pnr_set_volume_u16": (_rc, _volume_u16),
+    "pnr_set_volume_u16_device": (_rc, _volume_u16),
+    "pnr_get_volume": (_rc, [_vp, _vp]),
+    "pnr_measure_radii": (_rc, [_vp, _vp, _i64, C.POINTER(RadiusOpts), _vp, _pi32]),
+    "pnr_filter_volume": (_rc, [_vp, C.POINTER(FilterOpts)]),
+    "pnr_point_segment_distance": (_rc, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "pnr_tree_sample": (_rc, [_vp, _vp, _i64, _f32, _f32, _vp, _vp, _i64, _pi64]),
+    "pnr_tree_distance": (_rc, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(DistanceOpts), C.POINTER(DistanceResult), _vp, _vp, _i64, _vp, _vp, _i64]),
+    "pnr_nearest_other": (_rc, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "pnr_join_trees": (_rc, [_vp, _vp, _vp, _i64, C.POINTER(JoinOpts), _vp, _vp, _vp, _vp, _i64, _pi64, _pi64, _pi64]),
+    "pnr_join_reroot": (_rc, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "pnr_render_tree": (_rc, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, C.POINTER(RenderOpts), _vp, _vp]),
+    "pnr_tree_coverage": (_rc, [_vp, _vp, _vp, _vp, _i64, C.POINTER(RenderOpts), C.POINTER(Coverage), _vp, _vp, _vp, _vp, _vp]),
+    "pnr_label_components": (_rc, [_vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo), _vp, _vp, _i64]),
+    "pnr_despeckle_volume": (_rc, [_vp, C.POINTER(ComponentsOpts), C.POINTER(ComponentsInfo)]),
+    "pnr_distance_transform": (_rc, [_vp, C.POINTER(EdtOpts), C.POINTER(EdtInfo), _vp, _vp, _i64, _vp]),
+    "pnr_skeletonize": (_rc, [_vp, C.POINTER(ThinOpts), C.POINTER(ThinInfo), _vp, _vp, _vp, _i64]),
+    "pnr_skeleton_forest": (_rc, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _pi64]),
+    "pnr_geodesic_distance": (_rc, [_vp, _vp, _vp, _i64, C.POINTER(GeoOpts), C.POINTER(GeoInfo), _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "pnr_geodesic_bridges": (_rc, [_vp, _vp, _vp, _i64, C.POINTER(GeoJoinOpts), C.POINTER(GeoJoinInfo), _vp, _i64, _pi64, _vp, _i64, _pi64]),
+    "pnr_join_expand": (_rc, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _pi64, _vp]),
+    "pnr_frangi": (_rc, [_vp, _pf32, _pf32]),
+    "pnr_frangi_slab": (_rc, [_vp, _i64, _i64, _pf32, _pf32]),
+    "pnr_quantise_j8": (_rc, [_vp, _f32, _f32]),
+    "pnr_get_frangi": (_rc, [_vp] + [_vp] * 5),
+    "pnr_extract_seeds": (_rc, [_vp, C.POINTER(_vp), _pi64]),
+    "pnr_extract_seeds_range": (_rc, [_vp, _i64, _i64, C.POINTER(_vp), _pi64]),
+    "pnr_zncc_batch": (_rc, [_vp, _vp, _i64, _vp, _vp]),
+    "pnr_score_filter_sort_seeds": (_rc, _seed_filter),
+    "pnr_score_filter_seeds": (_rc, _seed_filter),
+    "pnr_sort_seeds": (_rc, _seed_filter),
+    "pnr_trace_batch": (_rc, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "pnr_soma": (_rc, [_vp, _vp, _pi32, _pi64]),
+    "pnr_get_soma": (_rc, [_vp, _vp, _i64, _pi64, _vp, _vp, _i64, _pi64]),
+    "pnr_replay_traces": (_rc, [C.POINTER(Params), _i64, _i64, _i64, _vp, _i64, _vp, _vp] + _graph_out + [_pi64]),
+    "pnr_replay_traces_ctx": (_rc, [_vp, _vp, _i64, _vp, _vp] + _graph_out + [_pi64]),
+    "pnr_trace_replay": (_rc, [_vp, _vp, _i64, _i64] + _graph_out + [_pi64, _pi64]),
+    "pnr_trace_replay_sharded": (_rc, [_vp, _vp, _i64, _i32, _i32, ALLGATHER_FN, _vp] + _graph_out + [_pi64, _pi64]),
+    "pnr_get_graph": (_rc, [_vp] + _graph_out),
+    "pnr_get_trace_log": (_rc, [_vp, _vp, _i64, _pi64]),
+    "pnr_reconstruct": (_rc, _recon_in + [_vp, _vp, _i64, _pi64]),
+    "pnr_reconstruct_ctx": (_rc, [_vp] + _recon_in + [_vp, _vp, _i64, _pi64]),
+    "pnr_reconstruct_stage": (_rc, _recon_in + _graph_out),
+    "pnr_set_profiling": (_rc, [_vp, _i32]),
+    "pnr_set_smc_driver": (_rc, [_vp, _i32]),
+    "pnr_get_kernel_ms": (_rc, [_vp, _str, C.POINTER(C.c_double), _pi64]),
+    "pnr_reset_kernel_ms": (_rc, [_vp]),
+    "pnr_set_option": (_rc, [_vp, _str, _i64]),
+    "pnr_get_option": (_rc, [_vp, _str, _pi64]),
+    "pnr_shm_exchange_open": (_rc, [_str, _i32, _i32, _i64, C.POINTER(_vp)]),
+    "pnr_shm_allgather": (_rc, [_vp, _vp, _vp, _i64]),
+    "pnr_shm_exchange_close": (None, [_vp]),
+    "pnr_rccl_unique_id": (_rc, [_vp]),
+    "pnr_rccl_exchange_open": (_rc, [_vp, _i32, _i32, _i32, _i64, C.POINTER(_vp)]),
+    "pnr_rccl_allgather": (_rc, [_vp, _vp, _vp, _i64]),
+    "pnr_rccl_allreduce_minmax": (_rc, [_vp, _pf32, _pf32]),
+    "pnr_rccl_exchange_close": (None, [_vp]),
+}
+# test taps (include/pnr_hip_test.h): single stages of the device code and the scheduler over a host engine, for tests/ only
+TEST_SIGNATURES = {
+    "pnr_gaussian": (_rc, [_vp, _f32, _vp]),
+    "pnr_hessian": (_rc, [_vp, _f32] + [_vp] * 6),
+    "pnr_set_j8_v": (_rc, [_vp] + [_vp] * 4),
+    "pnr_get_table": (_rc, [_vp, _str, _vp, _i64, _pi64]),
+    "pnr_expf_batch": (_rc, [_vp, _vp, _i64, _vp]),
+    "pnr_eigen_batch": (_rc, [_vp, _vp, _i64, _vp, _vp]),
+    "pnr_sched_playback": (_rc, _playback + _graph_out + [_pi64, _pi64]),
+    "pnr_sched_playback2": (_rc, _playback + [_i32, _i32, _i32] + _graph_out + [_pi64, _pi64]),
+    "pnr_reconstruct_stage_ctx": (_rc, [_vp] + _recon_in + _graph_out),
+    "pnr_radius_offsets": (_rc, [_f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _pi64]),
+    "pnr_pair_tiles": (_rc, [_i64, _i64, _i64, _i64, _vp, _i64, _pi64]),
+    "pnr_live_bytes": (_rc, [_pi64, _pi64]),
+    "pnr_render_items": (_rc, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, C.POINTER(RenderOpts), _i64, _i64, _vp, _i64, _pi64]),
+    "pnr_test_write_tiff": (_rc, [_str, _vp, _i64, _i64, _i64]),
+    "pnr_seed_handover": (_rc, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _vp, _vp]),
+    "pnr_phased_likelihood": (_rc, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pnr_phased_decide": (_rc, [_vp, _i64, C.POINTER(PhdIn), C.POINTER(PhdOut)]),
+}
+SIGNATURES = {**PRODUCT_SIGNATURES, **TEST_SIGNATURES}
+PRODUCT_EXPORTS, TEST_EXPORTS, EXPORTS = list(PRODUCT_SIGNATURES), list(TEST_SIGNATURES), list(SIGNATURES)
 
 
 # what a new Context starts with (tests run every case with both SMC drivers by patching this; the library itself reads no
@@ -1034,31 +1027,11 @@ class Context:
     # ---- reconstruct() with its neighbour stages on this GPU ----
     def reconstruct(self, nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0, tree_size_min=0):
         """pnr_reconstruct_ctx: the output of lib.reconstruct, byte for byte -> tree nodes (index 0 dummy), parents (-1 = root)"""
-        nodes = np.ascontiguousarray(nodes, NODE_DT)
-        links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
-        cap = max(16, 4 * len(nodes))
-        while True:
-            out = np.zeros(cap, NODE_DT)
-            par = np.zeros(cap, np.int32)
-            n = C.c_int64()
-            check(self.L.pnr_reconstruct_ctx(self.h, nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius,
-                                             refine_iter, epsilon2, group_radius, tree_size_min, out.ctypes.data, par.ctypes.data, cap,
-                                             C.byref(n)))
-            if n.value <= cap:
-                return out[:n.value].copy(), par[:n.value].copy()
-            cap = int(n.value)
+        return _reconstruct(self.L.pnr_reconstruct_ctx, (self.h,), nodes, links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, tree_size_min)
 
     def reconstruct_stage(self, nodes, links, stage, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0):
         """test tap pnr_reconstruct_stage_ctx: lib.reconstruct_stage with the device stages -> nodes, link pairs"""
-        nodes = np.ascontiguousarray(nodes, NODE_DT)
-        links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
-        args = (nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, stage)
-        nn, nl = C.c_int64(), C.c_int64()
-        check(self.L.pnr_reconstruct_stage_ctx(self.h, *args, None, 0, C.byref(nn), None, 0, C.byref(nl)))
-        out = np.zeros(nn.value, NODE_DT)
-        lk = np.zeros((nl.value, 2), np.int32)
-        check(self.L.pnr_reconstruct_stage_ctx(self.h, *args, out.ctypes.data, len(out), C.byref(nn), lk.ctypes.data, len(lk), C.byref(nl)))
-        return out, lk
+        return _reconstruct_stage(self.L.pnr_reconstruct_stage_ctx, (self.h,), nodes, links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, stage)
 
     def kernel_ms(self, group):
         ms, n = C.c_double(), C.c_int64()
@@ -1201,7 +1174,11 @@ def sched_playback(params, shape, seeds, trace_fn, rank=0, world=1, exchange=Non
 
 def reconstruct(nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0, tree_size_min=0):
     """reconstruct() chain on the host (pnr_reconstruct): tree nodes (index 0 dummy) and parent indices (-1 = root)."""
-    L = load()
+    return _reconstruct(load().pnr_reconstruct, (), nodes, links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, tree_size_min)
+
+
+def _reconstruct(fn, head, nodes, links, *consts):
+    """pnr_reconstruct[_ctx] (head: nothing, or the context): grow the outputs until the tree fits"""
     nodes = np.ascontiguousarray(nodes, NODE_DT)
     links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
     cap = max(16, 4 * len(nodes))
@@ -1209,11 +1186,23 @@ def reconstruct(nodes, links, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, ep
         out = np.zeros(cap, NODE_DT)
         par = np.zeros(cap, np.int32)
         n = C.c_int64()
-        check(L.pnr_reconstruct(nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius, refine_iter,
-                                epsilon2, group_radius, tree_size_min, out.ctypes.data, par.ctypes.data, cap, C.byref(n)))
+        check(fn(*head, nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), *consts, out.ctypes.data, par.ctypes.data, cap, C.byref(n)))
         if n.value <= cap:
             return out[:n.value].copy(), par[:n.value].copy()
         cap = int(n.value)
+
+
+def _reconstruct_stage(fn, head, nodes, links, *consts):
+    """pnr_reconstruct_stage[_ctx]: count first, then fetch"""
+    nodes = np.ascontiguousarray(nodes, NODE_DT)
+    links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
+    args = (*head, nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), *consts)
+    nn, nl = C.c_int64(), C.c_int64()
+    check(fn(*args, None, 0, C.byref(nn), None, 0, C.byref(nl)))
+    out = np.zeros(nn.value, NODE_DT)
+    lk = np.zeros((nl.value, 2), np.int32)
+    check(fn(*args, out.ctypes.data, len(out), C.byref(nn), lk.ctypes.data, len(lk), C.byref(nl)))
+    return out, lk
 
 
 def tree_sample(xyz, parent, zscale=1, step=1, count_only=False):
@@ -1393,19 +1382,7 @@ def pair_tiles(n, m, split=0, budget=0):
 
 def reconstruct_stage(nodes, links, stage, trace_rsmpl=0.0, sig2radius=0.0, refine_iter=0, epsilon2=0.0, group_radius=0.0):
     """the node list behind a stage of reconstruct() (pnr_reconstruct_stage: 1 _n0res_, 2 _n1_, 3 _n2_, 4 _n2tree_) -> nodes, link pairs"""
-    L = load()
-    nodes = np.ascontiguousarray(nodes, NODE_DT)
-    links = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
-    L.pnr_reconstruct_stage.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int,
-                                        C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    nn, nl = C.c_int64(), C.c_int64()
-    check(L.pnr_reconstruct_stage(nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius, refine_iter, epsilon2,
-                                  group_radius, stage, None, 0, C.byref(nn), None, 0, C.byref(nl)))
-    out = np.zeros(nn.value, NODE_DT)
-    lk = np.zeros((nl.value, 2), np.int32)
-    check(L.pnr_reconstruct_stage(nodes.ctypes.data, len(nodes), links.ctypes.data, len(links), trace_rsmpl, sig2radius, refine_iter, epsilon2,
-                                  group_radius, stage, out.ctypes.data, len(out), C.byref(nn), lk.ctypes.data, len(lk), C.byref(nl)))
-    return out, lk
+    return _reconstruct_stage(load().pnr_reconstruct_stage, (), nodes, links, trace_rsmpl, sig2radius, refine_iter, epsilon2, group_radius, stage)
 
 
 def kernel_source_hash(names=("smc_phased.hip", "smc_device.h", "smc.hip", "ctx.h", "stream_sched.h")):
