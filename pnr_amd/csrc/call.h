@@ -1,5 +1,5 @@
 // call.h -- the staging of one bounded call on the context's stream: its device buffers as typed parts of ONE allocation, and the chain
-// of HIP calls with one sticky error.  Users: the volume and tree tools (volume, radius, filter, distance, join, render, components, edt,
+// of HIP calls with one sticky error; timed() is a launch under a timer group of its own.  Users: the volume and tree tools (volume, radius, filter, distance, join, render, components, edt,
 // geodesic, geojoin), the side stages (recon, soma), the test taps (frangi.hip: eigen, hessian, gaussian, the direction volumes; smc.hip:
 // expf) and the uploads and read-backs of the api*.cpp files.
 #pragma once
@@ -59,12 +59,13 @@ T *Part<T>::get() const { return (T *)(buf->base() + off); }
 
 // The HIP calls of one tool call on c's stream.  After the first failure every further call is a no-op; finish() reports it.
 class Call {
+    pnr_ctx *c_;
     const char *who_;
     hipStream_t st_;
     hipError_t e_ = hipSuccess;
 
 public:
-    Call(pnr_ctx *c, const char *who) : who_(who), st_(c->stream) {}
+    Call(pnr_ctx *c, const char *who) : c_(c), who_(who), st_(c->stream) {}
     hipStream_t stream() const { return st_; }
     bool ok() const { return e_ == hipSuccess; }
     void note(hipError_t e) // the result of a HIP call made elsewhere (pairmin.h pair_sweep)
@@ -94,6 +95,16 @@ public:
     }
     template <typename... P, typename... A>
     void launch(void (*kernel)(P...), dim3 grid, dim3 block, const A &...args) { launch(kernel, grid, block, Lds{0}, args...); }
+    // one launch as one entry of the timer group: tic, launch, toc(group, 1) on the call's context
+    template <typename... P, typename... A>
+    void timed(const char *group, void (*kernel)(P...), dim3 grid, dim3 block, Lds lds, const A &...args)
+    {
+        c_->tic();
+        launch(kernel, grid, block, lds, args...);
+        c_->toc(group, 1);
+    }
+    template <typename... P, typename... A>
+    void timed(const char *group, void (*kernel)(P...), dim3 grid, dim3 block, const A &...args) { timed(group, kernel, grid, block, Lds{0}, args...); }
     // synchronises the stream: PNR_OK, or the first failure through hip_fail
     int finish()
     {

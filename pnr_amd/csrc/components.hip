@@ -19,6 +19,7 @@
 // The host takes the sizes, drops what is below min_size and numbers the rest in the same order.
 #include "components.h"
 #include "call.h"
+#include "grid.h"
 #include "volume.h"
 #include <cstring>
 
@@ -32,7 +33,6 @@ using pnr::CC_TZ;
 constexpr int TPB = CC_TX * CC_TY;  // threads of a work-group: one slice of the tile
 constexpr int TILE = TPB * CC_TZ;   // voxels of a tile
 constexpr int NWAVES = TPB / 64;
-constexpr int MAX_BLOCKS = 2048;
 constexpr unsigned NONE = 0xffffffffu; // the link of a background voxel (N <= 2^32 - 2: never an index)
 // the packing of cc_stats: size (11 bits) | sum << 11; sx | sy << 15; one bit per local x; one bit per local y | local z << 8
 static_assert(TPB == 256 && CC_TX == 32 && CC_TY == 8 && TILE == 1024, "cc_stats packs a tile's partial sums into 32-bit LDS words");
@@ -47,18 +47,9 @@ struct Tiles {
     int conn26; // 0: the 3 backward face neighbours, 1: all 13
 };
 
-struct Origin {
-    int x0, y0, z0;
-};
-
-__device__ __forceinline__ Origin tile_origin(const Tiles &a)
-{
-    const unsigned b = blockIdx.x, per_z = (unsigned)a.tiles_x * (unsigned)a.tiles_y;
-    const unsigned tz = b / per_z, r = b - tz * per_z, ty = r / (unsigned)a.tiles_x, tx = r - ty * (unsigned)a.tiles_x;
-    return Origin{(int)tx * CC_TX, (int)ty * CC_TY, (int)tz * CC_TZ};
-}
-
-__device__ __forceinline__ long long vox(const Tiles &a, int x, int y, int z) { return ((long long)z * a.h + y) * a.w + x; }
+using Origin = pnr::TileAt;
+__device__ __forceinline__ Origin tile_origin(const Tiles &a) { return pnr::tile_origin(blockIdx.x, a.tiles_x, a.tiles_y, CC_TX, CC_TY, CC_TZ); }
+__device__ __forceinline__ long long vox(const Tiles &a, int x, int y, int z) { return pnr::voxel_index(a.w, a.h, x, y, z); }
 
 // is (dx, dy, dz) one of the backward offsets of the connectivity?  (constant after unrolling, up to conn26)
 __device__ __forceinline__ bool backward(int dx, int dy, int dz, int conn26)
@@ -373,25 +364,14 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
     if (o.thr < 0 && (rc = pnr_mean_threshold(c, who, "components_threshold", c->d_img, N, d_sum, &t))) return rc; // the global mean
     pnr::Call call(c, who);
     const Tiles ta{c->d_img, d_link, w, h, l, tiles_x, tiles_y, t, o.connectivity == 26 ? 1 : 0};
-    c->tic();
-    call.launch(cc_local, dim3((unsigned)tiles), dim3(TPB), ta);
-    c->toc("components_local", 1);
-    c->tic();
-    call.launch(cc_merge, dim3((unsigned)tiles), dim3(TPB), ta);
-    c->toc("components_merge", 1);
-    c->tic();
-    call.launch(cc_flatten, dim3((unsigned)chunks), dim3(TPB), d_link, (long long)N, d_cnt);
-    c->toc("components_flatten", 1);
+    call.timed("components_local", cc_local, dim3((unsigned)tiles), dim3(TPB), ta);
+    call.timed("components_merge", cc_merge, dim3((unsigned)tiles), dim3(TPB), ta);
+    call.timed("components_flatten", cc_flatten, dim3((unsigned)chunks), dim3(TPB), d_link, (long long)N, d_cnt);
     // the chunk counts become their exclusive scan
     std::vector<unsigned> cnt((size_t)chunks);
     call.down(cnt.data(), d_cnt);
     if ((rc = call.finish())) return rc;
-    int64_t K = 0; // every component, the small ones included
-    for (auto &v : cnt) {
-        const unsigned n = v;
-        v = (unsigned)K;
-        K += n;
-    }
+    const int64_t K = pnr::exclusive_scan_counts(cnt); // every component, the small ones included
     // the full numbering, the statistics, and what min_size keeps
     pnr::CallBuf sbuf;
     const size_t k = (size_t)K;
@@ -406,12 +386,8 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
         call.up(d_cnt, cnt.data());
         call.fill((char *)s_size.get(), 0, s_mn.off - s_size.off);
         call.fill(s_mn, 0xff);
-        c->tic();
-        call.launch(cc_number, dim3((unsigned)chunks), dim3(TPB), d_link, (long long)N, d_cnt, d_id, s_roots);
-        c->toc("components_number", 1);
-        c->tic();
-        call.launch(cc_stats, dim3((unsigned)tiles), dim3(TPB), ta, d_id, sa);
-        c->toc("components_stats", 1);
+        call.timed("components_number", cc_number, dim3((unsigned)chunks), dim3(TPB), d_link, (long long)N, d_cnt, d_id, s_roots);
+        call.timed("components_stats", cc_stats, dim3((unsigned)tiles), dim3(TPB), ta, d_id, sa);
         size.resize(k);
         call.down(size.data(), s_size);
         if ((rc = call.finish())) return rc;
@@ -458,10 +434,8 @@ int pnr_components_run(pnr_ctx *c, const char *who, const pnr_components_opts &o
         call.up(s_new, newid.data());
     }
     const long long groups = (N + 3) >> 2;
-    c->tic();
-    call.launch(cc_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((groups + TPB - 1) / TPB, MAX_BLOCKS))), dim3(TPB), d_link, d_id, d_new, c->d_img,
-                d_out.get(), label_out ? 1 : 0, (long long)N);
-    c->toc("components_finish", 1);
+    call.timed("components_finish", cc_finish, dim3(pnr::grid_blocks((groups + TPB - 1) / TPB)), dim3(TPB), d_link, d_id, d_new, c->d_img, d_out.get(),
+               label_out ? 1 : 0, (long long)N);
     if (label_out) call.down(label_out, d_link.get(), (size_t)N);
     if ((rc = call.finish())) return rc;
     if (despeckled) *despeckled = std::move(d_out);

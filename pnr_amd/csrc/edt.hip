@@ -26,6 +26,7 @@
 // row carries of the x pass and then gy, the table, four words, and the points.
 #include "edt.h"
 #include "call.h"
+#include "grid.h"
 #include "volume.h"
 #include <cstring>
 
@@ -36,7 +37,6 @@ using pnr::EDT_TPB;
 using pnr::EDT_WX;
 
 constexpr int XTPB = EDT_ROWS * 64; // threads of a work-group of the x pass: one wave per row
-constexpr int MAX_BLOCKS = 2048;    // of the grid-stride statistics kernel
 static_assert(EDT_WX == 64, "a word of the x pass is one ballot of a wave");
 static_assert(EDT_TPB % 64 == 0 && EDT_TPB <= 1024, "whole waves");
 
@@ -162,15 +162,7 @@ __global__ __launch_bounds__(EDT_TPB) void edt_sample(const float *d2, const flo
     const long long i = (long long)blockIdx.x * EDT_TPB + threadIdx.x;
     if (i >= n) return;
     const float px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
-    auto finite = [](float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; };
-    float out = -1.f;
-    if (finite(px) && finite(py) && finite(pz)) {
-        const int cx = (int)fminf(fmaxf(px + 0.5f, 0.f), (float)(w - 1));
-        const int cy = (int)fminf(fmaxf(py + 0.5f, 0.f), (float)(h - 1));
-        const int cz = (int)fminf(fmaxf(pz + 0.5f, 0.f), (float)(l - 1));
-        out = d2[((long long)cz * h + cy) * w + cx];
-    }
-    at[i] = out;
+    at[i] = pnr::finite3(px, py, pz) ? d2[pnr::centre_voxel(w, h, l, px, py, pz)] : -1.f;
 }
 
 } // namespace
@@ -201,29 +193,19 @@ int pnr_edt_run(pnr_ctx *c, const char *who, const pnr_edt_opts &o, pnr_edt_info
     uint16_t *d_gx = (uint16_t *)d_a.get();
     unsigned *d_gy = d_b;
     float *d_d2 = d_a;
-    c->tic();
-    call.launch(edt_x, dim3((unsigned)xblocks), dim3(XTPB), XArgs{c->d_img, d_gx, (int *)d_b.get(), (long long)rows, w, (int)words, t, o.rmax});
-    c->toc("edt_x", 1);
-    c->tic();
-    call.launch(edt_y, dim3((unsigned)vblocks), dim3(EDT_TPB), (const uint16_t *)d_gx, d_gy, w, h, (long long)N);
-    c->toc("edt_y", 1);
-    c->tic();
-    call.launch(edt_z, dim3((unsigned)vblocks), dim3(EDT_TPB), (const unsigned *)d_gy, d_d2, (const float *)d_zt.get(), (long long)w * h, l, o.rmax, (long long)N);
-    c->toc("edt_z", 1);
+    call.timed("edt_x", edt_x, dim3((unsigned)xblocks), dim3(XTPB), XArgs{c->d_img, d_gx, (int *)d_b.get(), (long long)rows, w, (int)words, t, o.rmax});
+    call.timed("edt_y", edt_y, dim3((unsigned)vblocks), dim3(EDT_TPB), (const uint16_t *)d_gx, d_gy, w, h, (long long)N);
+    call.timed("edt_z", edt_z, dim3((unsigned)vblocks), dim3(EDT_TPB), (const unsigned *)d_gy, d_d2, (const float *)d_zt.get(), (long long)w * h, l, o.rmax, (long long)N);
     unsigned long long st[3] = {0, 0, 0};
     if (info) {
         call.fill(d_st, 0);
-        c->tic();
-        call.launch(edt_stats, dim3((unsigned)std::min<int64_t>(vblocks, MAX_BLOCKS)), dim3(EDT_TPB), (const float *)d_d2, (long long)N, cap, d_st.get());
-        c->toc("edt_stats", 1);
+        call.timed("edt_stats", edt_stats, dim3(pnr::grid_blocks(vblocks)), dim3(EDT_TPB), (const float *)d_d2, (long long)N, cap, d_st.get());
         call.down(st, d_st);
     }
     if (n > 0) {
         call.up(d_xyz, xyz);
-        c->tic();
-        call.launch(edt_sample, dim3((unsigned)((n + EDT_TPB - 1) / EDT_TPB)), dim3(EDT_TPB), (const float *)d_d2, (const float *)d_xyz.get(), (long long)n, w, h, l,
-                    d_at.get());
-        c->toc("edt_sample", 1);
+        call.timed("edt_sample", edt_sample, dim3((unsigned)((n + EDT_TPB - 1) / EDT_TPB)), dim3(EDT_TPB), (const float *)d_d2, (const float *)d_xyz.get(), (long long)n, w, h, l,
+                   d_at.get());
         call.down(d2_at, d_at);
     }
     if (d2_out) call.down(d2_out, (const float *)d_d2, (size_t)N);

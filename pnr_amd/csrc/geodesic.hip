@@ -27,6 +27,7 @@
 //                stage itself and may replace the targets of the call (geojoin.hip: the bridges between the sources' trees).
 #include "geodesic.h"
 #include "call.h"
+#include "grid.h"
 #include "volume.h"
 #include <cmath>
 #include <vector>
@@ -42,7 +43,6 @@ typedef unsigned long long u64;
 constexpr u64 NONE = ~0ull;
 constexpr int HX = GEO_TX + 2, HY = GEO_TY + 2, HZ = GEO_TZ + 2, CELLS = HX * HY * HZ;
 constexpr int RTPB = GEO_TX * GEO_TY; // threads of a relaxation work-group
-constexpr int MAX_BLOCKS = 2048;      // of the grid-stride statistics kernel
 constexpr int AUTO_ITERS = 128;       // LDS iterations per tile visit (option geo_iters = 0)
 constexpr int AUTO_TILES = 1 << 20;   // tiles per launch (option geo_tiles_per_launch = 0)
 static_assert(RTPB % 64 == 0 && RTPB <= 1024 && GEO_TPB % 64 == 0, "whole waves");
@@ -51,19 +51,9 @@ static_assert(GEO_TX >= 2 && GEO_TY >= 2 && GEO_TZ >= 2, "a voxel is on at most 
 using Dims = pnr::GeoDims;
 using Lens = pnr::GeoLens;
 
-__device__ inline bool finite3(float x, float y, float z)
-{
-    auto finite = [](float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; };
-    return finite(x) && finite(y) && finite(z);
-}
+using pnr::finite3;
 // the centre voxel of the radius rule
-__device__ inline long long centre(const Dims &d, float px, float py, float pz)
-{
-    const int cx = (int)fminf(fmaxf(px + 0.5f, 0.f), (float)(d.w - 1));
-    const int cy = (int)fminf(fmaxf(py + 0.5f, 0.f), (float)(d.h - 1));
-    const int cz = (int)fminf(fmaxf(pz + 0.5f, 0.f), (float)(d.l - 1));
-    return ((long long)cz * d.h + cy) * d.w + cx;
-}
+__device__ inline long long centre(const Dims &d, float px, float py, float pz) { return pnr::centre_voxel(d.w, d.h, d.l, px, py, pz); }
 __device__ inline u64 load_key(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(GEO_TPB) void geo_sources(const uint8_t *V, u64 *key, const float *xyz, const int *label, long long n, Dims d, int t, int *flag,
@@ -117,15 +107,15 @@ __global__ __launch_bounds__(RTPB) void geo_relax(RelaxArgs a)
     __shared__ unsigned touched;         // bit (az + 1) 9 + (ay + 1) 3 + (ax + 1): a voxel in the halo of the tile at that offset changed
     const Dims d = a.d;
     const int tile = a.list[blockIdx.x];
-    const int tix = tile % d.ntx, tiy = tile / d.ntx % d.nty, tiz = tile / (d.ntx * d.nty);
-    const int x0 = tix * GEO_TX, y0 = tiy * GEO_TY, z0 = tiz * GEO_TZ;
+    const pnr::TileAt o = pnr::tile_origin((unsigned)tile, d.ntx, d.nty, GEO_TX, GEO_TY, GEO_TZ);
+    const int tix = o.tx, tiy = o.ty, tiz = o.tz, x0 = o.x0, y0 = o.y0, z0 = o.z0;
     if (threadIdx.x == 0) touched = 0;
     for (int cell = threadIdx.x; cell < CELLS; cell += RTPB) {
         const int gx = x0 + cell % HX - 1, gy = y0 + cell / HX % HY - 1, gz = z0 + cell / (HX * HY) - 1;
         u64 k = NONE;
         unsigned short cc = 0;
         if (gx >= 0 && gx < d.w && gy >= 0 && gy < d.h && gz >= 0 && gz < d.l) {
-            const long long g = ((long long)gz * d.h + gy) * d.w + gx;
+            const long long g = pnr::voxel_index(d.w, d.h, gx, gy, gz);
             const int v = a.V[g];
             if (v >= a.t) cc = a.ctab[v], k = load_key(&a.key[g]);
         }
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(RTPB) void geo_relax(RelaxArgs a)
 #pragma unroll
     for (int z = 0; z < GEO_TZ; z++)
         if (cur[z] < first[z]) { // (a passable voxel inside the volume: the others stay NONE)
-            const long long g = ((long long)(z0 + z) * d.h + (y0 + ly)) * d.w + (x0 + lx);
+            const long long g = pnr::voxel_index(d.w, d.h, x0 + lx, y0 + ly, z0 + z);
             __hip_atomic_store(&a.key[g], cur[z], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned mz = 2u | (z == 0 ? 1u : 0u) | (z == GEO_TZ - 1 ? 4u : 0u);
 #pragma unroll
@@ -282,7 +272,7 @@ __global__ __launch_bounds__(GEO_TPB) void geo_paths(PathArgs a)
             for (int o = 0; o < 27 && q < 0; o++) { // the offset order
                 const int qx = x + o % 3 - 1, qy = y + o / 3 % 3 - 1, qz = z + o / 9 - 1;
                 if (o == 13 || qx < 0 || qx >= d.w || qy < 0 || qy >= d.h || qz < 0 || qz >= d.l) continue;
-                const long long g = ((long long)qz * d.h + qy) * d.w + qx;
+                const long long g = pnr::voxel_index(d.w, d.h, qx, qy, qz);
                 const u64 k = a.key[g];
                 if (k == NONE) continue; // (impassable or unreached)
                 const unsigned wt = a.step.v[o] * (cp + a.ctab[a.V[g]]);
@@ -316,17 +306,13 @@ int pnr_geo_targets(pnr_ctx *c, const char *who, const pnr_geo_keys &k, const pn
     pnr::Call call(c, who);
     call.up(d_axyz, g.at_xyz);
     if (g.d_at || g.label_at) {
-        c->tic();
-        call.launch(geo_sample, dim3((unsigned)((g.m + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB), k.key, (const float *)d_axyz.get(), (long long)g.m, k.d, d_dat.get(), d_lat.get());
-        c->toc("geodesic_sample", 1);
+        call.timed("geodesic_sample", geo_sample, dim3((unsigned)((g.m + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB), k.key, (const float *)d_axyz.get(), (long long)g.m, k.d, d_dat.get(), d_lat.get());
         if (g.d_at) call.down(g.d_at, d_dat);
         if (g.label_at) call.down(g.label_at, d_lat);
     }
     if (paths) {
-        c->tic();
-        call.launch(geo_paths, dim3((unsigned)((m_path + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB),
-                    PathArgs{k.V, k.key, k.ctab, (const float *)d_axyz.get(), (long long)m_path, k.d, g.path_cap, d_plen.get(), d_pvox.get(), k.len});
-        c->toc("geodesic_paths", 1);
+        call.timed("geodesic_paths", geo_paths, dim3((unsigned)((m_path + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB),
+                   PathArgs{k.V, k.key, k.ctab, (const float *)d_axyz.get(), (long long)m_path, k.d, g.path_cap, d_plen.get(), d_pvox.get(), k.len});
         call.down(g.path_len, d_plen);
         call.down(g.path_vox, d_pvox);
     }
@@ -407,10 +393,8 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
         rounds++, visits += count;
         for (int64_t at = 0; at < count; at += per_launch) {
             const int64_t n = std::min(per_launch, count - at);
-            c->tic();
-            call.launch(geo_relax, dim3((unsigned)n), dim3(RTPB),
-                        RelaxArgs{c->d_img, d_key.get(), (const uint16_t *)d_ctab.get(), (const int *)d_list.get() + at, flag[cur ^ 1], d, t, iters, o.dmax, len});
-            c->toc("geodesic_relax", 1);
+            call.timed("geodesic_relax", geo_relax, dim3((unsigned)n), dim3(RTPB),
+                       RelaxArgs{c->d_img, d_key.get(), (const uint16_t *)d_ctab.get(), (const int *)d_list.get() + at, flag[cur ^ 1], d, t, iters, o.dmax, len});
         }
     }
     if (!call.ok()) return call.finish();
@@ -421,16 +405,12 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
     call.down(&dropped, d_drop);
     if (g.info) {
         call.fill(d_st, 0);
-        c->tic();
-        call.launch(geo_stats, dim3((unsigned)std::min<int64_t>(vblocks, MAX_BLOCKS)), dim3(GEO_TPB), c->d_img, (const u64 *)d_key.get(), (long long)N, t, d_st.get());
-        c->toc("geodesic_stats", 1);
+        call.timed("geodesic_stats", geo_stats, dim3(pnr::grid_blocks(vblocks)), dim3(GEO_TPB), c->d_img, (const u64 *)d_key.get(), (long long)N, t, d_st.get());
         call.down(st, d_st);
     }
     if (split_d || split_l) {
-        c->tic();
-        call.launch(geo_split, dim3((unsigned)vblocks), dim3(GEO_TPB), (const u64 *)d_key.get(), (long long)N, split_d ? d_dv.get() : (unsigned *)nullptr,
-                    split_l ? d_lv.get() : (int *)nullptr);
-        c->toc("geodesic_split", 1);
+        call.timed("geodesic_split", geo_split, dim3((unsigned)vblocks), dim3(GEO_TPB), (const u64 *)d_key.get(), (long long)N, split_d ? d_dv.get() : (unsigned *)nullptr,
+                   split_l ? d_lv.get() : (int *)nullptr);
         if (split_d) call.down(g.d_out, d_dv);
         if (split_l) call.down(g.label_out, d_lv);
     }

@@ -22,6 +22,7 @@
 // and the expansion.
 #include "geojoin.h"
 #include "call.h"
+#include "grid.h"
 #include "distance.h"
 #include "join.h"
 #include <algorithm>
@@ -103,9 +104,8 @@ template <bool EDGE>
 __device__ inline void meet(const MeetArgs &a, Tile &s)
 {
     const Dims d = a.d;
-    const long long tile = a.tile0 + blockIdx.x;
-    const int tix = (int)(tile % d.ntx), tiy = (int)(tile / d.ntx % d.nty), tiz = (int)(tile / ((long long)d.ntx * d.nty));
-    const int x0 = tix * GEO_TX, y0 = tiy * GEO_TY, z0 = tiz * GEO_TZ;
+    const pnr::TileAt o = pnr::tile_origin((unsigned)(a.tile0 + blockIdx.x), d.ntx, d.nty, GEO_TX, GEO_TY, GEO_TZ);
+    const int x0 = o.x0, y0 = o.y0, z0 = o.z0;
     if (threadIdx.x < SLOTS) s.slot_comp[threadIdx.x] = -1, s.slot_val[threadIdx.x] = NONE;
     // (the component of a tree is the same word for most cells of a tile; the cost of a byte is looked up where two components meet, which is rare)
 #pragma unroll
@@ -117,7 +117,7 @@ __device__ inline void meet(const MeetArgs &a, Tile &s)
         int cc = -1;
         unsigned char val = 0;
         if (gx >= 0 && gx < d.w && gy >= 0 && gy < d.h && gz < d.l) {
-            const long long g = ((long long)gz * d.h + gy) * d.w + gx;
+            const long long g = pnr::voxel_index(d.w, d.h, gx, gy, gz);
             const u64 k = a.key[g];
             val = a.V[g];
             if ((int)val >= a.t && k != NONE && (unsigned)k < (unsigned)a.trees) dd = (unsigned)(k >> 32), cc = a.comp[(unsigned)k];
@@ -132,7 +132,7 @@ __device__ inline void meet(const MeetArgs &a, Tile &s)
         const int own = (z * JY + ly + 1) * JX + lx + 1;
         const int cp = s.comp[own];
         if (cp < 0) continue;
-        const long long p = ((long long)(z0 + z) * d.h + (y0 + ly)) * d.w + (x0 + lx);
+        const long long p = pnr::voxel_index(d.w, d.h, x0 + lx, y0 + ly, z0 + z);
         unsigned costp = 0; // (0: not looked up yet; a cost is at least 1)
         u64 wp = 0;
 #pragma unroll
@@ -182,14 +182,8 @@ struct Edge { // the key (W, p, o - 13) as (w, e = 13 p + (o - 13)), and the two
     bool operator==(const Edge &o) const { return w == o.w && e == o.e; }
 };
 
-// the centre voxel of the radius rule, as the device computes it
-inline int64_t centre(const Dims &d, const float *p)
-{
-    const int cx = (int)fminf(fmaxf(p[0] + 0.5f, 0.f), (float)(d.w - 1));
-    const int cy = (int)fminf(fmaxf(p[1] + 0.5f, 0.f), (float)(d.h - 1));
-    const int cz = (int)fminf(fmaxf(p[2] + 0.5f, 0.f), (float)(d.l - 1));
-    return ((int64_t)cz * d.h + cy) * d.w + cx;
-}
+// the centre voxel of the radius rule: the function the device calls
+inline int64_t centre(const Dims &d, const float *p) { return pnr::centre_voxel(d.w, d.h, d.l, p[0], p[1], p[2]); }
 
 // what the hook leaves for the second half of the call
 struct Rounds {

@@ -13,6 +13,7 @@
 // The global mean is the byte sum of volume.hip (pnr_mean_threshold).
 #include "radius.h"
 #include "call.h"
+#include "grid.h"
 #include "volume.h"
 #include <cmath>
 #include <cstring>
@@ -78,14 +79,11 @@ __global__ __launch_bounds__(RTPB) void rad_measure(RadArgs a)
     if (wv >= a.n) return; // (the whole wave)
     const int node = __builtin_amdgcn_readfirstlane(a.order[wv]);
     const float px = a.xyz[3 * (long long)node], py = a.xyz[3 * (long long)node + 1], pz = a.xyz[3 * (long long)node + 2];
-    auto finite = [](float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; };
-    if (!(finite(px) && finite(py) && finite(pz))) {
+    if (!pnr::finite3(px, py, pz)) {
         if (lane == 0) a.k_out[node] = -1;
         return;
     }
-    const int cx = (int)fminf(fmaxf(px + 0.5f, 0.f), (float)(a.w - 1));
-    const int cy = (int)fminf(fmaxf(py + 0.5f, 0.f), (float)(a.h - 1));
-    const int cz = (int)fminf(fmaxf(pz + 0.5f, 0.f), (float)(a.l - 1));
+    const int cx = pnr::centre_axis(px, a.w), cy = pnr::centre_axis(py, a.h), cz = pnr::centre_axis(pz, a.l);
     // offset i of the table around the centre: inside the volume? v = its voxel
     auto probe = [&](int i, bool live, unsigned &v) -> bool {
         v = 0;
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(RTPB) void rad_measure(RadArgs a)
         const unsigned o = a.off[i];
         const int x = cx + (int)(o & 255u) - 64, y = cy + (int)((o >> 8) & 255u) - 64, z = cz + (int)((o >> 16) & 255u) - 64;
         const bool inb = (unsigned)x < (unsigned)a.w && (unsigned)y < (unsigned)a.h && (unsigned)z < (unsigned)a.l;
-        if (inb) v = a.img[((long long)z * a.h + y) * a.w + x];
+        if (inb) v = a.img[pnr::voxel_index(a.w, a.h, x, y, z)];
         return inb;
     };
     int t = a.t_abs;
@@ -170,7 +168,7 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         // the order of the 8^3 cells of the centres (positions that are not measured last); it changes no result
         std::vector<std::pair<uint64_t, int>> cell((size_t)n);
         const uint64_t nx8 = (uint64_t)(c->w + 7) >> 3, ny8 = (uint64_t)(c->h + 7) >> 3;
-        auto centre = [](float v, int64_t ext) { return (uint64_t)(int)fminf(fmaxf(v + 0.5f, 0.f), (float)(ext - 1)); };
+        auto centre = [](float v, int64_t ext) { return (uint64_t)pnr::centre_axis(v, (int)ext); };
         for (int64_t i = 0; i < n; i++) {
             const float *p = xyz + 3 * i;
             uint64_t id = ~0ull;
@@ -184,9 +182,7 @@ int pnr_radius_run(pnr_ctx *c, const float *xyz, int64_t n, const pnr_radius_opt
         call.up(d_xyz, xyz);
         call.up(d_ord, order.data());
         const RadArgs a{c->d_img, (int)c->w, (int)c->h, (int)c->l, c->d_rad_off.get(), c->d_rad_start.get(), d_xyz, d_ord, (int)n, o.rmax, t_abs, o.rel_pct, o.bg_permille, d_k};
-        c->tic();
-        call.launch(rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), a);
-        c->toc("radius", 1);
+        call.timed("radius", rad_measure, dim3((unsigned)((n + RWAVES - 1) / RWAVES)), dim3(RTPB), a);
         call.down(k_out, d_k);
         return call.finish(); // (the host vectors above end here)
     }

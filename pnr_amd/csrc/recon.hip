@@ -503,10 +503,8 @@ int pnr_recon_shift(pnr_ctx *c, const std::vector<P4> &src, float s2r, int maxit
         const auto d_bm = bm.add<unsigned>((size_t)groups * nw);
         if ((rc = bm.alloc(who))) return rc;
         call.fill(d_bm, 0);
-        c->tic();
-        call.launch(k_shift_big, dim3(groups), dim3(BIG), (const float4 *)d_src, G.g, (const int *)G.start, (const float4 *)G.gp, s2r, maxiter, eps2,
-                    d_res.get(), (const int *)d_ovf, (const int *)d_novf, d_bm.get(), nw);
-        c->toc("recon", 1);
+        call.timed("recon", k_shift_big, dim3(groups), dim3(BIG), (const float4 *)d_src, G.g, (const int *)G.start, (const float4 *)G.gp, s2r, maxiter, eps2,
+                   d_res.get(), (const int *)d_ovf, (const int *)d_novf, d_bm.get(), nw);
     }
     call.down(res.data() + 1, d_res.get() + 1, (size_t)n - 1);
     return call.finish();
@@ -544,10 +542,8 @@ int pnr_recon_balls(pnr_ctx *c, const std::vector<P4> &pos, float rad, advantra:
         if ((rc = lists.alloc(who))) return rc;
         call.fill(d_novf, 0);
         call.fill(d_cursor, 0);
-        c->tic();
-        call.launch(k_balls, dim3(n - 1), dim3(64), (const float4 *)d_pos, n, G.g, (const int *)G.start, (const float4 *)G.gp, rad, d_off.get(),
-                    d_cnt.get(), d_list.get(), cap, d_cursor.get(), d_ovf.get(), d_novf.get());
-        c->toc("recon", 1);
+        call.timed("recon", k_balls, dim3(n - 1), dim3(64), (const float4 *)d_pos, n, G.g, (const int *)G.start, (const float4 *)G.gp, rad, d_off.get(),
+                   d_cnt.get(), d_list.get(), cap, d_cursor.get(), d_ovf.get(), d_novf.get());
         int novf = 0;
         call.down(&novf, d_novf);
         if ((rc = call.finish())) return rc;
@@ -557,10 +553,8 @@ int pnr_recon_balls(pnr_ctx *c, const std::vector<P4> &pos, float rad, advantra:
             const auto d_bm = bm.add<unsigned>((size_t)groups * nw);
             if ((rc = bm.alloc(who))) return rc;
             call.fill(d_bm, 0);
-            c->tic();
-            call.launch(k_balls_big, dim3(groups), dim3(BIG), (const float4 *)d_pos, G.g, (const int *)G.start, (const float4 *)G.gp, rad, d_off.get(),
-                        d_cnt.get(), d_list.get(), cap, d_cursor.get(), (const int *)d_ovf, (const int *)d_novf, d_bm.get(), nw);
-            c->toc("recon", 1);
+            call.timed("recon", k_balls_big, dim3(groups), dim3(BIG), (const float4 *)d_pos, G.g, (const int *)G.start, (const float4 *)G.gp, rad, d_off.get(),
+                       d_cnt.get(), d_list.get(), cap, d_cursor.get(), (const int *)d_ovf, (const int *)d_novf, d_bm.get(), nw);
         }
         unsigned long long used = 0;
         call.down(&used, d_cursor);

@@ -12,6 +12,7 @@
 // combined inside a lane.  The exact byte sum behind thr = -1 is volume.hip's (pnr_mean_threshold).
 #include "render.h"
 #include "call.h"
+#include "grid.h"
 #include "volume.h"
 #include <cmath>
 #include <cstring>
@@ -112,7 +113,6 @@ namespace {
 
 constexpr int NTPB = 256;          // threads of a work-group
 constexpr int NWAVES = NTPB / 64;
-constexpr int MAX_BLOCKS = 2048;   // grid-stride loops beyond this many work-groups: 256 CUs eight deep
 constexpr unsigned NONE = 0xffffffffu; // the label of a voxel no segment has reached (one hipMemsetAsync of 0xff)
 
 struct ScatArgs {
@@ -273,9 +273,7 @@ int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_
         const size_t k = stage.size() / 8;
         if (k == 0) return true;
         call.up(d_items.get(), stage.data(), 2 * k);
-        c->tic();
-        call.launch(rn_scatter, dim3((unsigned)k), dim3(NTPB), sa);
-        c->toc("render_scatter", 1);
+        call.timed("render_scatter", rn_scatter, dim3((unsigned)k), dim3(NTPB), sa);
         stage.clear();
         return call.finish() == PNR_OK;
     };
@@ -292,9 +290,7 @@ int pnr_render_run(pnr_ctx *c, const char *who, const pnr::RenderTree &t, int64_
     const FinArgs fa{d_lab, V, (long long)N, t_abs, label_out ? 1 : 0, mask_out ? d_mask.get() : nullptr, residual_out ? d_res.get() : nullptr,
                      d_cnt, per_seg ? d_tri.get() : nullptr, (long long)n};
     const long long groups = (N + 3) >> 2;
-    c->tic();
-    call.launch(rn_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((groups + NTPB - 1) / NTPB, MAX_BLOCKS))), dim3(NTPB), fa);
-    c->toc("render_finish", 1);
+    call.timed("render_finish", rn_finish, dim3(pnr::grid_blocks((groups + NTPB - 1) / NTPB)), dim3(NTPB), fa);
     unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
     std::vector<int64_t> tri(per_seg ? (size_t)n * 3 : 0);
     call.down(cnt, d_cnt);

@@ -23,6 +23,7 @@
 // Below the kernels: skeleton_forest, the host's Kruskal over the skeleton's voxels.
 #include "thin.h"
 #include "call.h"
+#include "grid.h"
 #include "volume.h"
 #include <algorithm>
 #include <cmath>
@@ -104,18 +105,9 @@ struct Grid {
     int tiles_x, tiles_y, tiles_z;
 };
 
-struct Origin {
-    int x0, y0, z0;
-};
-
-__device__ __forceinline__ Origin tile_origin(const Grid &a, unsigned b)
-{
-    const unsigned per_z = (unsigned)a.tiles_x * (unsigned)a.tiles_y;
-    const unsigned tz = b / per_z, r = b - tz * per_z, ty = r / (unsigned)a.tiles_x, tx = r - ty * (unsigned)a.tiles_x;
-    return Origin{(int)tx * THIN_TX, (int)ty * THIN_TY, (int)tz * THIN_TZ};
-}
-
-__device__ __forceinline__ long long vox(const Grid &a, int x, int y, int z) { return ((long long)z * a.h + y) * a.w + x; }
+using Origin = pnr::TileAt;
+__device__ __forceinline__ Origin tile_origin(const Grid &a, unsigned b) { return pnr::tile_origin(b, a.tiles_x, a.tiles_y, THIN_TX, THIN_TY, THIN_TZ); }
+__device__ __forceinline__ long long vox(const Grid &a, int x, int y, int z) { return pnr::voxel_index(a.w, a.h, x, y, z); }
 
 // the tile at o with its halo into sh; outside the volume is background
 __device__ __forceinline__ void load_halo(const Grid &a, const Origin &o, uint8_t *sh)
@@ -151,14 +143,14 @@ __global__ __launch_bounds__(TPB) void thin_plan(const unsigned *stamp, int tile
 {
     const long long tiles = (long long)tiles_x * tiles_y * tiles_z, t = (long long)blockIdx.x * TPB + threadIdx.x;
     if (t >= tiles) return;
-    const int tx = (int)(t % tiles_x), ty = (int)(t / tiles_x % tiles_y), tz = (int)(t / ((long long)tiles_x * tiles_y));
+    const pnr::TileAt at = pnr::tile_origin((unsigned)t, tiles_x, tiles_y, 1, 1, 1);
     unsigned last = 0;
     for (int dz = -1; dz <= 1; dz++)
         for (int dy = -1; dy <= 1; dy++)
             for (int dx = -1; dx <= 1; dx++) {
-                const int x = tx + dx, y = ty + dy, z = tz + dz;
+                const int x = at.tx + dx, y = at.ty + dy, z = at.tz + dz;
                 if (x < 0 || x >= tiles_x || y < 0 || y >= tiles_y || z < 0 || z >= tiles_z) continue;
-                last = max(last, stamp[((long long)z * tiles_y + y) * tiles_x + x]);
+                last = max(last, stamp[pnr::voxel_index(tiles_x, tiles_y, x, y, z)]);
             }
     if (last >= lo) list[atomicAdd(count, 1u)] = (unsigned)t;
 }
@@ -297,10 +289,7 @@ __global__ __launch_bounds__(TPB) void thin_finish(unsigned *S4, long long words
     }
 }
 
-unsigned blocks_for(long long items)
-{
-    return (unsigned)std::max<long long>(1, std::min<long long>(items, MAX_BLOCKS));
-}
+unsigned blocks_for(long long items) { return pnr::grid_blocks(items, MAX_BLOCKS); }
 
 } // namespace
 
@@ -327,9 +316,7 @@ int pnr_thin_run(pnr_ctx *c, const char *who, const pnr_thin_opts &o, pnr_thin_i
     call.fill(d_nfg, 0, 1);
     call.fill(d_stamp, 0);
     call.fill(d_S.get() + N, 0, 16); // (the padding thin_finish reads)
-    c->tic();
-    call.launch(thin_init, dim3(blocks_for((N + TPB - 1) / TPB)), dim3(TPB), c->d_img, d_S.get(), (long long)N, t, d_nfg);
-    c->toc("thin_init", 1);
+    call.timed("thin_init", thin_init, dim3(blocks_for((N + TPB - 1) / TPB)), dim3(TPB), c->d_img, d_S.get(), (long long)N, t, d_nfg);
     unsigned long long n_fg = 0;
     call.down(&n_fg, d_nfg, 1);
     int32_t rounds = 0;
@@ -350,14 +337,10 @@ int pnr_thin_run(pnr_ctx *c, const char *who, const pnr_thin_opts &o, pnr_thin_i
                 c->toc("thin_pass", 1);
             }
             if (s == 0) {
-                c->tic();
-                call.launch(thin_mark, dim3(grid), dim3(TPB), ga, list, (const unsigned *)cnt, nt);
-                c->toc("thin_mark", 1);
+                call.timed("thin_mark", thin_mark, dim3(grid), dim3(TPB), ga, list, (const unsigned *)cnt, nt);
             }
-            c->tic();
-            call.launch(thin_pass, dim3(grid), dim3(TPB), ga, list, (const unsigned *)cnt, nt, s, 8u * (unsigned)(rounds - 1) + (unsigned)s + 1u, d_stamp.get(),
-                        d_ctl.get() + 8);
-            c->toc("thin_pass", 1);
+            call.timed("thin_pass", thin_pass, dim3(grid), dim3(TPB), ga, list, (const unsigned *)cnt, nt, s, 8u * (unsigned)(rounds - 1) + (unsigned)s + 1u, d_stamp.get(),
+                       d_ctl.get() + 8);
         }
         call.down(ctl, d_ctl.get(), 9);
         if ((rc = call.finish())) return rc;
@@ -366,18 +349,11 @@ int pnr_thin_run(pnr_ctx *c, const char *who, const pnr_thin_opts &o, pnr_thin_i
         PNR_REQUIRE(rounds < (1 << 28), PNR_E_ARG, "%s: too many rounds", who);
     }
     // the skeleton in raster order: the chunk counts become their exclusive scan
-    c->tic();
-    call.launch(thin_count, dim3((unsigned)chunks), dim3(TPB), (const uint8_t *)d_S.get(), (long long)N, d_cnt.get());
-    c->toc("thin_list", 1);
+    call.timed("thin_list", thin_count, dim3((unsigned)chunks), dim3(TPB), (const uint8_t *)d_S.get(), (long long)N, d_cnt.get());
     std::vector<unsigned> cnt((size_t)chunks);
     call.down(cnt.data(), d_cnt);
     if ((rc = call.finish())) return rc;
-    int64_t K = 0;
-    for (auto &v : cnt) {
-        const unsigned n = v;
-        v = (unsigned)K;
-        K += n;
-    }
+    const int64_t K = pnr::exclusive_scan_counts(cnt);
     const size_t k = (size_t)K;
     std::vector<unsigned> vox(k);
     std::vector<uint8_t> deg(k);
@@ -387,17 +363,13 @@ int pnr_thin_run(pnr_ctx *c, const char *who, const pnr_thin_opts &o, pnr_thin_i
     if (K > 0) {
         if ((rc = lbuf.alloc(who))) return rc;
         call.up(d_cnt, cnt.data());
-        c->tic();
-        call.launch(thin_list, dim3((unsigned)chunks), dim3(TPB), ga, (long long)N, (const unsigned *)d_cnt.get(), l_vox.get(), l_deg.get());
-        c->toc("thin_list", 1);
+        call.timed("thin_list", thin_list, dim3((unsigned)chunks), dim3(TPB), ga, (long long)N, (const unsigned *)d_cnt.get(), l_vox.get(), l_deg.get());
         call.down(vox.data(), l_vox);
         call.down(deg.data(), l_deg);
     }
     if (skel_out) {
         const long long words = (N + 3) >> 2;
-        c->tic();
-        call.launch(thin_finish, dim3(blocks_for((words + TPB - 1) / TPB)), dim3(TPB), (unsigned *)d_S.get(), words);
-        c->toc("thin_finish", 1);
+        call.timed("thin_finish", thin_finish, dim3(blocks_for((words + TPB - 1) / TPB)), dim3(TPB), (unsigned *)d_S.get(), words);
         call.down(skel_out, (const uint8_t *)d_S.get(), (size_t)N);
     }
     if ((rc = call.finish())) return rc;

@@ -17,13 +17,14 @@
 // rule "thr = -1" of the radii, the coverage and the components that rests on it (pnr_mean_threshold).
 #include "volume.h"
 #include "call.h"
+#include "grid.h"
 
 namespace {
 
 constexpr int TPB = 256;            // threads of the min / max and the map kernels
 constexpr int HTPB = 1024;          // threads of a histogram work-group
 constexpr int HWAVES = HTPB / 64;   // ... one private LDS copy of the bins per wave
-constexpr int MAX_BLOCKS = 2048;    // grid-stride loops beyond this many work-groups
+using pnr::MAX_BLOCKS;
 constexpr int MAX_HBLOCKS = 512;
 
 // device state of one call: the window (win[0] = 65535 - lo, win[1] = hi), the selected bins and the ranks left in them, the bins
@@ -243,11 +244,7 @@ __global__ __launch_bounds__(TPB) void vol_sum(const uint8_t *p, long long n, lo
     }
 }
 
-unsigned blocks_for(long long work, int tpb, int cap)
-{
-    const long long b = (work + tpb - 1) / tpb;
-    return (unsigned)std::max<long long>(1, std::min<long long>(b, cap));
-}
+unsigned blocks_for(long long work, int tpb, int cap) { return pnr::grid_blocks((work + tpb - 1) / tpb, cap); }
 
 } // namespace
 
@@ -301,9 +298,7 @@ int pnr_byte_sum_run(pnr_ctx *c, const char *who, const char *group, const uint8
     const long long head = std::min<long long>(N, (long long)((16 - ((uintptr_t)V & 15)) & 15)), nvec = (N - head) >> 4;
     pnr::Call call(c, who);
     call.fill(d_sum, 0, 1);
-    c->tic();
-    call.launch(vol_sum, dim3(blocks_for(std::max<long long>(nvec, 16), TPB, MAX_BLOCKS)), dim3(TPB), V, (long long)N, head, nvec, d_sum);
-    c->toc(group, 1);
+    call.timed(group, vol_sum, dim3(blocks_for(std::max<long long>(nvec, 16), TPB, MAX_BLOCKS)), dim3(TPB), V, (long long)N, head, nvec, d_sum);
     call.down(sum, d_sum, 1);
     return call.finish();
 }

@@ -118,6 +118,25 @@ def test_labels_components_and_info(ctx, shape, kind):
     assert np.array_equal(ctx.get_volume(), V)  # never written
 
 
+# N = 4095, 4096, 4097, 8192, 8193 and 4095 voxels: the ends of the 4096-voxel chunks of the numbering
+CHUNK_SHAPES = [(1, 3, 1365), (1, 2, 2048), (1, 17, 241), (1, 2, 4096), (1, 3, 2731), (3, 5, 273)]
+
+
+@pytest.mark.parametrize("shape", CHUNK_SHAPES, ids=sid)
+def test_checkerboard_numbering_at_the_chunk_ends(ctx, shape):
+    """every foreground voxel is a 6-component of its own: the numbering is the raster rank, in every wave quarter, lane and k"""
+    z, y, x = np.indices(shape)
+    V = np.where((x + y + z) % 2 == 0, 200, 0).astype(np.uint8)
+    fg = np.flatnonzero(V)
+    ctx.set_volume(V)
+    info, labels, comps = ctx.label_components(1, 6, 1)
+    assert info["n_comp"] == len(comps) == len(fg)
+    assert np.array_equal(comps["first"], fg) and (comps["size"] == 1).all()
+    wlabels = np.zeros(V.size, np.int32)
+    wlabels[fg] = np.arange(1, len(fg) + 1)
+    assert np.array_equal(labels, wlabels.reshape(shape))
+
+
 def test_larger_stack_once(ctx):
     ctx.set_volume(volume(BIG, "rand31"))
     for conn in (6, 26):

@@ -83,6 +83,23 @@ def test_mean_threshold_equals_the_rule(ctx):
             assert got[0]["thr_used"] == max(1, int(V.sum(dtype=np.uint64)) // V.size)
 
 
+# N = 4095, 4096, 4097, 8192, 8193 and 4095 voxels: the ends of the 4096-voxel chunks of the voxel list
+CHUNK_SHAPES = ((1, 3, 1365), (1, 2, 2048), (1, 17, 241), (1, 2, 4096), (1, 3, 2731), (3, 5, 273))
+
+
+@pytest.mark.parametrize("shape", CHUNK_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_lattice_of_isolated_voxels_at_the_chunk_ends(ctx, shape):
+    """every second voxel of every axis: nothing is deleted, and the list meets every wave quarter, lane and k of the compaction"""
+    z, y, x = np.indices(shape)
+    V = np.where((x % 2 == 0) & (y % 2 == 0) & (z % 2 == 0), 200, 0).astype(np.uint8)
+    ctx.set_volume(V)
+    got = ctx.skeletonize(1)
+    same(got, ref.skeletonize(V, 1), shape)
+    info, skel, vox, deg = got
+    assert np.array_equal(vox, np.flatnonzero(skel)) and len(vox) == np.count_nonzero(V)
+    assert not deg.any()
+
+
 def test_a_larger_stack_of_blobs(ctx):
     shape = (33, 65, 129)
     ctx.set_volume(reference(shape, "blobs", THR)[0])
