@@ -815,6 +815,70 @@ int pnr_join_expand(const float *xyz /* n x 3 */, const int32_t *parent /* n */,
                     int64_t n_path, int64_t w, int64_t h, int64_t l, float *xyz_out, int32_t *parent_out, int32_t *bridge_of, int64_t cap_nodes, int64_t *n_nodes,
                     pnr_bridge *join_out /* nb */);
 
+/* Grey-level morphological reconstruction of the traced volume (beyond the reference; Vincent 1993): fill holes, h-maxima, h-domes.  Every
+ * other tool decides "foreground" by a threshold on the traced bytes; this repairs the grey image's shape before that decision.  A soma
+ * with a dark nucleus is a hollow object whose "curve skeleton" is a closed surface: PNR_MORPH_FILL closes it first.  Shallow grey-level
+ * maxima join noise into a sponge at the mean threshold: PNR_MORPH_HMAX removes exactly those, and PNR_MORPH_HDOME keeps bright structure
+ * standing at least h above its surroundings whatever its width.
+ * THE RULE (the contract; tests restate it in numpy).  Everything is exact u8 / integer arithmetic.  V is the context's traced u8 volume
+ * (w x h x l, owned or borrowed, windowed and filtered as traced), N = w * h * l.  params.zdist plays no part.
+ *   Neighbourhoods N_C(p), C in {4, 8, 6, 26}: the offsets (dx, dy, dz) in {-1, 0, 1}^3, not all zero.  C = 26: all of them; C = 6: exactly
+ *     one non-zero component; C = 8: dz = 0; C = 4: dz = 0 and exactly one non-zero component.  A neighbour outside the volume does not
+ *     exist.  C = 4 and C = 8 on a 3-D stack treat every slice independently; with l == 1, 6 equals 4 and 26 equals 8.
+ *   Reconstruction by dilation rho_C(M, V): let M' = min(M, V).  R(p) = the maximum, over all C-paths p0, ..., pk = p with k >= 0, of
+ *     min(M'(p0), V(p1), ..., V(pk)).  Equivalently R is the least volume with R >= M' and
+ *     R(p) = min(V(p), max(R(p), max over q in N_C(p) of R(q))).  M' <= R <= V.
+ *   Reconstruction by erosion: rho*_C(M, V) = 255 - rho_C(255 - M, 255 - V).
+ *   Exact whatever the schedule: start from M'; every update replaces R(p) by min(V(p), max of itself and its neighbours); every value ever
+ *     held is <= the fixed point, so values only rise and a stale neighbour value is still a lower bound; when no voxel can rise the
+ *     recursion holds everywhere, and the least fixed point above M' is unique.  No tiling, round structure or launch cut changes a bit.
+ *   Operations (opts->op):
+ *     1 PNR_MORPH_DILATE  marker required      out = rho_C(marker, V)
+ *     2 PNR_MORPH_ERODE   marker required      out = rho*_C(marker, V)
+ *     3 PNR_MORPH_FILL    marker must be NULL  out = rho*_C(M, V), M = V on B_C and 255 elsewhere: grey fill-holes; out >= V; every regional
+ *                                              minimum that is not connected to the border under C is raised to its pass height
+ *     4 PNR_MORPH_HMAX    marker must be NULL  out = rho_C(max(V - h, 0), V), h in 1..255
+ *     5 PNR_MORPH_HDOME   marker must be NULL  out = V - (the volume of op 4), h in 1..255; 0 <= out <= h
+ *     B_C, the border set of op 3: the voxels with x in {0, w - 1} or y in {0, h - 1}, and for C in {6, 26} and l > 1 also those with z in
+ *     {0, l - 1}.  connectivity = 0 is the default of the op: 6 for FILL (the background connectivity of the thinning rule), 26 for the others.
+ *   Summary pnr_morph_info (exact unless said otherwise): n_vox = N, n_changed (voxels with out != V), n_nonzero (out > 0), sum_in and
+ *     sum_out (the u64 sums of V and of out), max_delta (max |out - V|), connectivity (the one used: the op's default for 0), tiles (of
+ *     MORPH_TX x MORPH_TY x MORPH_TZ voxels); tile_visits and rounds: scheduling, not part of the rule, reported and never compared bit for bit.
+ * pnr_morph_reconstruct: all five ops.  marker: N host bytes for ops 1 and 2.  info and out (N host bytes) are nullable.  It never writes V
+ *   (also not a borrowed one), leaves the pipeline state of the context alone and frees every device buffer of the call before it returns.
+ * pnr_morph_volume: ops 3 to 5 only, with the contract of pnr_filter_volume: afterwards the context is what pnr_set_volume of the result's
+ *   bytes leaves -- the same dimensions and 2-D mode, an owned volume, and no later pipeline state (soma, Frangi, J8, seeds and the graph are
+ *   invalidated); pnr_get_volume returns the result; a second call works on the result of the first; a borrowed device volume
+ *   (pnr_set_volume_device) is never written: the result is an owned buffer and the context stops borrowing; the context's volume changes
+ *   only once everything has succeeded: on any failure the context still holds the old volume.
+ * Arguments (anything else: PNR_E_ARG): opts non-NULL, op in 1..5, connectivity in {0, 4, 8, 6, 26}, h in 1..255 for ops 4 and 5 and 0
+ *   otherwise, marker non-NULL exactly for ops 1 and 2, N at most 2^32 - 2.  No volume in the context: PNR_E_STATE.  PNR_E_NOMEM: an
+ *   allocation failed.  Voxel indices are 64-bit; the work runs on the context's stream (pnr_set_stream).  Device memory of a call: N bytes
+ *   of state (the marker is uploaded into it or built from V; it becomes the result in place, and the context's volume under
+ *   pnr_morph_volume), 12 bytes per tile (two flag arrays and the list); 8 bytes of pinned host memory carry the round's tile count.
+ * Kernel times: pnr_get_kernel_ms group "morph" = the sum of "morph_init" (the state from the op), "morph_compact" (the listed tiles of a
+ *   round), "morph_relax" (the tile relaxation) and "morph_finish" (the result and the statistics).  pnr_get_option "morph_rounds" /
+ *   "morph_visits": the rounds and the tile visits of the last call.  pnr_set_option "morph_iters" (LDS iterations per tile visit; 0 =
+ *   automatic, 1 forces a tile to re-queue itself) and "morph_tiles_per_launch" (0 = automatic; small values force launch cuts) change no
+ *   bit: tests reach the boundaries on small stacks with them. */
+#define PNR_MORPH_DILATE 1
+#define PNR_MORPH_ERODE 2
+#define PNR_MORPH_FILL 3
+#define PNR_MORPH_HMAX 4
+#define PNR_MORPH_HDOME 5
+typedef struct pnr_morph_opts {
+    int32_t op, connectivity, h, pad;
+} pnr_morph_opts;
+typedef struct pnr_morph_info {
+    int64_t n_vox, n_changed, n_nonzero;
+    uint64_t sum_in, sum_out;
+    int64_t tiles, tile_visits;
+    int32_t max_delta, connectivity, rounds, pad;
+} pnr_morph_info;
+int pnr_morph_reconstruct(pnr_ctx *ctx, const pnr_morph_opts *opts, const uint8_t *marker /* N, host; ops 1, 2 only */, pnr_morph_info *info /* nullable */,
+                          uint8_t *out /* N, host, nullable */);
+int pnr_morph_volume(pnr_ctx *ctx, const pnr_morph_opts *opts, pnr_morph_info *info /* nullable */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -843,16 +907,17 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   render_piece (0 = automatic: 16) xy voxels of a segment's axis per work item of pnr_render_tree / pnr_tree_coverage | render_box (0 = automatic: 2^15) voxels per item, larger boxes are cut |
  *   render_items_per_launch (0 = automatic: 2^18) items per launch (the same bits -- tests reach piece, box and launch boundaries with them on small inputs) |
  *   geo_iters, geo_tiles_per_launch (0 = automatic) of pnr_geodesic_distance and geojoin_tiles_per_launch (0 = automatic: 2^20) tiles per launch of a sweep of pnr_geodesic_bridges (the same bits) |
+ *   morph_iters, morph_tiles_per_launch (0 = automatic) of pnr_morph_reconstruct / pnr_morph_volume: the same two for its relaxation (the same bits) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
- *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
+ *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "geo_rounds" / "geo_visits", "geojoin_rounds", "morph_rounds" / "morph_visits" (the last call of that tool), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
  *   re-run Frangi without the frangi_prune shortcut -- one pnr_frangi worth of GPU time each; also printed with trace_timing /
  *   seed_timing).  The kernel timers (pnr_get_kernel_ms) include those re-runs. */
 int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e").  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish").  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

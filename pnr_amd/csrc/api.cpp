@@ -322,12 +322,14 @@ const OptEntry OPTS[] = {
     {"render_items_per_launch", nullptr, &pnr::Options::render_items_per_launch, 0, 1 << 24},
     {"geo_iters", &pnr::Options::geo_iters, nullptr, 0, 1 << 16}, {"geo_tiles_per_launch", &pnr::Options::geo_tiles_per_launch, nullptr, 0, 1 << 24},
     {"geojoin_tiles_per_launch", &pnr::Options::geojoin_tiles_per_launch, nullptr, 0, 1 << 24},
+    {"morph_iters", &pnr::Options::morph_iters, nullptr, 0, 1 << 16}, {"morph_tiles_per_launch", &pnr::Options::morph_tiles_per_launch, nullptr, 0, 1 << 24},
 };
 // what pnr_get_option reads besides: counters the calls leave in the context
 struct Counter { const char *key; int64_t pnr_ctx::*count; };
 const Counter COUNTERS[] = {
     {"join_rounds", &pnr_ctx::join_rounds},       {"geo_rounds", &pnr_ctx::geo_rounds},     {"geo_visits", &pnr_ctx::geo_visits},
     {"geojoin_rounds", &pnr_ctx::geojoin_rounds}, {"render_items", &pnr_ctx::render_items}, {"render_pairs", &pnr_ctx::render_pairs},
+    {"morph_rounds", &pnr_ctx::morph_rounds},     {"morph_visits", &pnr_ctx::morph_visits},
     {"frangi_recomputes", &pnr_ctx::frangi_recomputes}, // exact Frangi re-runs so far (one pnr_frangi of GPU time each)
 };
 } // namespace
@@ -433,6 +435,7 @@ const Umbrella UMBRELLAS[] = {
     {"thin", {"thin_threshold", "thin_init", "thin_mark", "thin_pass", "thin_list", "thin_finish"}},
     {"geodesic", {"geodesic_threshold", "geodesic_init", "geodesic_compact", "geodesic_relax", "geodesic_stats", "geodesic_split", "geodesic_sample", "geodesic_paths"}},
     {"geojoin", {"geojoin_meet_w", "geojoin_meet_e"}}, // the two passes of a Boruvka round
+    {"morph", {"morph_init", "morph_compact", "morph_relax", "morph_finish"}},
 };
 } // namespace
 

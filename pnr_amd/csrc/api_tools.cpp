@@ -1,5 +1,5 @@
 // api_tools.cpp -- the extern "C" boundary of libpnr_hip.so (include/pnr_hip.h), third part: the tools on the volume (filter, components,
-// distance transform, skeleton, geodesic distance, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
+// distance transform, skeleton, geodesic distance, morphological reconstruction, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
 // taps (include/pnr_hip_test.h).  An entry point checks its arguments first, then the state (args.h holds the shared rules), and hands
 // over to the tool's own file; no tool needs or touches the pipeline state of the context (Frangi, seeds, graph).
 #include "args.h"
@@ -15,6 +15,7 @@
 #include "thin.h"
 #include "geodesic.h"
 #include "geojoin.h"
+#include "morph.h"
 #include "../host/stack_io.h"
 
 namespace args = pnr::args;
@@ -128,6 +129,41 @@ int pnr_geodesic_distance(pnr_ctx *c, const float *src_xyz, const int32_t *src_l
     PNR_REQUIRE(m == 0 || path_cap == 0 || (path_len && path_vox), PNR_E_ARG, "%s: path_cap = %d needs path_len and path_vox", who, path_cap);
     PNR_TRY(args::volume_u32(c, who));
     return pnr_geodesic_run(c, who, o, pnr_geo_call{src_xyz, src_label, n_src, info, d_out, label_out, at_xyz, m, d_at, label_at, path_cap, path_len, path_vox});
+}
+
+// pnr_morph_reconstruct / pnr_morph_volume (morph.hip): arguments first, then the state and the device; o has the connectivity resolved
+static int morph_args(pnr_ctx *c, const char *who, const pnr_morph_opts *opts, bool need_marker_rule, const uint8_t *marker, pnr_morph_opts &o)
+{
+    PNR_REQUIRE(c && opts, PNR_E_ARG, "null argument");
+    o = *opts;
+    PNR_REQUIRE(o.op >= (need_marker_rule ? PNR_MORPH_DILATE : PNR_MORPH_FILL) && o.op <= PNR_MORPH_HDOME, PNR_E_ARG, "%s: op = %d outside [%d, %d]", who, o.op,
+                need_marker_rule ? PNR_MORPH_DILATE : PNR_MORPH_FILL, PNR_MORPH_HDOME);
+    PNR_REQUIRE(o.connectivity == 0 || o.connectivity == 4 || o.connectivity == 8 || o.connectivity == 6 || o.connectivity == 26, PNR_E_ARG,
+                "%s: connectivity = %d, not 0, 4, 8, 6 or 26", who, o.connectivity);
+    const bool with_h = o.op == PNR_MORPH_HMAX || o.op == PNR_MORPH_HDOME, with_marker = o.op == PNR_MORPH_DILATE || o.op == PNR_MORPH_ERODE;
+    PNR_REQUIRE(with_h ? o.h >= 1 && o.h <= 255 : o.h == 0, PNR_E_ARG, "%s: h = %d, %s", who, o.h, with_h ? "outside [1, 255]" : "not 0 (only ops 4 and 5 take an h)");
+    if (need_marker_rule) PNR_REQUIRE(with_marker == (marker != nullptr), PNR_E_ARG, "%s: op = %d %s", who, o.op, with_marker ? "needs a marker" : "takes no marker");
+    if (o.connectivity == 0) o.connectivity = o.op == PNR_MORPH_FILL ? 6 : 26;
+    return args::volume_u32(c, who);
+}
+
+int pnr_morph_reconstruct(pnr_ctx *c, const pnr_morph_opts *opts, const uint8_t *marker, pnr_morph_info *info, uint8_t *out)
+{
+    static const char *who = "pnr_morph_reconstruct";
+    pnr_morph_opts o;
+    PNR_TRY(morph_args(c, who, opts, true, marker, o));
+    return pnr_morph_run(c, who, o, marker, info, out, nullptr);
+}
+
+int pnr_morph_volume(pnr_ctx *c, const pnr_morph_opts *opts, pnr_morph_info *info)
+{
+    static const char *who = "pnr_morph_volume";
+    pnr_morph_opts o;
+    PNR_TRY(morph_args(c, who, opts, false, nullptr, o));
+    pnr::DevBuf<uint8_t> out;
+    const int rc = pnr_morph_run(c, who, o, nullptr, info, nullptr, &out);
+    if (!rc) pnr::replace_volume(c, std::move(out));
+    return rc;
 }
 
 // pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched

@@ -55,6 +55,12 @@
 //   fields of pnr_thin_info and "trees"; --skeleton-out writes the 0 / 255 volume, --swc the skeleton as a tree (pnr_skeleton_forest, then
 //   pnr_join_reroot at the thickest voxel; radius = the distance transform at the voxel with zdist = Z; the comment block ends in
 //   #skeleton=thr:T,rounds:R,voxels:K,trees:C): an independent baseline for --distance, and fragments for --join-swc --join-geodesic.
+//   --fill-holes 2d|3d, --hmax H | --hdome H (1..255): the last steps of the volume set-up, after --median / --subtract-background and before
+//   --despeckle, on every rank: grey-level fill-holes (pnr_morph_volume PNR_MORPH_FILL, 4-connected in every slice or 6-connected), then the
+//   h-maxima or the h-domes (26-connected).  Every mode that takes the set-up gets them: a tracing run -- the comment block gains
+//   #morph=fill:<2d|3d|off>,hmax:<H|off>,hdome:<H|off> behind #filter --, --skeleton, --components, --edt, --geodesic, --render-swc and
+//   --join-swc --join-geodesic.  --morph -i stack [those flags] --morph-out OUT.tif|.raw: the resulting stack and one JSON line with the
+//   fields of pnr_morph_info of each stage run.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -150,6 +156,8 @@ int main(int argc, char **argv)
     bool geo = false, geo_flag = false;
     advantra::SkeletonJob skel_job;
     bool skeleton = false, skel_flag = false;
+    bool morph = false;
+    std::string morph_out;
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--geodesic")) { geo = true; continue; }
@@ -395,6 +403,29 @@ int main(int argc, char **argv)
             S0.filter.tophat_r = (int32_t)v;
             continue;
         }
+        if (!strcmp(argv[i], "--fill-holes")) {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m != "2d" && m != "3d") { fprintf(stderr, "--fill-holes 2d|3d: grey-level fill-holes in every slice (4-connected), or in 3-D (6-connected)\n"); return 1; }
+            S0.fill_holes = m == "3d" ? 6 : 4;
+            continue;
+        }
+        if (!strcmp(argv[i], "--hmax") || !strcmp(argv[i], "--hdome")) {
+            const bool dome = !strcmp(argv[i], "--hdome");
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 1, 255, v)) {
+                fprintf(stderr, "%s\n", dome ? "--hdome H: the height kept of what stands above its surroundings, an integer from 1 to 255"
+                                             : "--hmax H: the height every grey-level maximum is cut down by, an integer from 1 to 255");
+                return 1;
+            }
+            (dome ? S0.hdome : S0.hmax) = (int)v;
+            continue;
+        }
+        if (!strcmp(argv[i], "--morph")) { morph = true; continue; }
+        if (!strcmp(argv[i], "--morph-out")) {
+            morph_out = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (morph_out.empty()) { fprintf(stderr, "--morph-out OUT: a .tif or .raw file name\n"); return 1; }
+            continue;
+        }
         if (!strcmp(argv[i], "--measure-radius")) { S0.measure_radius = true; continue; }
         if (!strncmp(argv[i], "--radius-", 9)) {
             const std::string flag = argv[i];
@@ -459,16 +490,29 @@ int main(int argc, char **argv)
     if (skel_flag && !skeleton) { fprintf(stderr, "--skeleton-rounds / --skeleton-out / --swc need --skeleton -i stack\n"); return 1; }
     if (edt_flag && !edt) { fprintf(stderr, "--edt-max / --edt-out / --at need --edt -i stack\n"); return 1; }
     if (geo_flag && !geo) { fprintf(stderr, "--from / --to / --paths / --geo-max / --geo-out need --geodesic -i stack\n"); return 1; }
+    if (S0.hmax && S0.hdome) { fprintf(stderr, "--hmax and --hdome: one of them\n"); return 1; }
+    if (!morph_out.empty() && !morph) { fprintf(stderr, "--morph-out needs --morph -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
     if (skeleton) {
         if (geo || geo_flag || edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic ||
-            per_node_flag || !paras.empty()) {
-            fprintf(stderr, "--skeleton: not with a tracing run (-p), --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius or --per-node\n");
+            per_node_flag || !paras.empty() || morph) {
+            fprintf(stderr, "--skeleton: not with a tracing run (-p), --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node or --morph\n");
             return 1;
         }
         if (infiles.empty()) { fprintf(stderr, "--skeleton needs -i <stack>\n"); return 1; }
         if (zscale_flag && dist_opts.zscale < 1.f) { fprintf(stderr, "--skeleton: --zscale Z: a number, 1 or more\n"); return 1; }
         return advantra::skeleton_file(skel_job, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, device) ? 0 : 1;
+    }
+    if (morph) {
+        if (geo || geo_flag || edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic ||
+            per_node_flag || thr_flag || zscale_flag || !paras.empty()) {
+            fprintf(stderr, "--morph: not with a tracing run (-p), --skeleton, --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node, --threshold or --zscale\n");
+            return 1;
+        }
+        if (infiles.empty()) { fprintf(stderr, "--morph needs -i <stack>\n"); return 1; }
+        if (morph_out.empty()) { fprintf(stderr, "--morph needs --morph-out OUT\n"); return 1; }
+        if (!S0.morph()) { fprintf(stderr, "--morph needs one of --fill-holes, --hmax and --hdome\n"); return 1; }
+        return advantra::morph_file(morph_out, infiles, raw_dims, device) ? 0 : 1;
     }
     if (geo) {
         if (edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic || !paras.empty()) {

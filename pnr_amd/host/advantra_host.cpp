@@ -76,6 +76,14 @@ void print_flags()
     printf("--channel C | --raw-type u8|u16 | --window LO,HI | --saturate LO,HI   the input; 16-bit stacks are windowed to 8 bits\n");
     printf("--median 2d|3d            pre-filter: 3 x 3 median in every slice, or 3 x 3 x 3 (on the GPU, before tracing; default: off)\n");
     printf("--subtract-background R   pre-filter: top-hat with a flat box of half-width R in xy and R / zdist in z, 1..%d (after the median)\n", PNR_TOPHAT_MAX_R);
+    printf("--fill-holes 2d|3d        pre-filter: grey-level fill-holes on the GPU (after the median and the top-hat): every dark region that the brighter\n");
+    printf("                          voxels around it cut off from the stack's border is raised to their level -- in every slice (2d, 4-connected) or in 3-D\n");
+    printf("                          (3d, 6-connected); a hollow soma is closed before it is thinned or measured\n");
+    printf("--hmax H | --hdome H      pre-filter (after --fill-holes): h-maxima -- every grey-level maximum is cut down by H, 1..255, so maxima standing less\n");
+    printf("                          than H above their surroundings vanish --, or h-domes: what that removes, the structure standing above its surroundings\n");
+    printf("--morph -i stack          the stack after the volume set-up of tracing with [--fill-holes 2d|3d] [--hmax H | --hdome H] as one JSON line: per stage\n");
+    printf("                          op, h, n_vox, n_changed, n_nonzero, sum_in, sum_out, max_delta, connectivity, tiles, tile_visits, rounds\n");
+    printf("  --morph-out OUT           write the resulting stack as a multi-page 8-bit TIFF, or bare bytes for a .raw name (needed)\n");
     printf("--despeckle MIN[,THR[,CONN]]  pre-filter: foreground components (voxels >= THR, default -1: the stack's mean; CONN 6 or 26, default 26) of\n");
     printf("                          fewer than MIN voxels are set to 0 on the GPU (after the median and the top-hat, before tracing)\n");
     printf("--components -i stack     the connected components of the stack's foreground on the GPU (the same volume setup as tracing) as one JSON\n");
@@ -190,6 +198,11 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         c << "\n#filter=median:" << (fo.median == 3 ? "3d" : fo.median == 2 ? "2d" : "off") << ",tophat:";
         if (fo.tophat_r) c << fo.tophat_r;
         else c << "off";
+    }
+    if (settings().morph()) {
+        const Settings &s = settings();
+        auto level = [&](int v) { return v ? std::to_string(v) : std::string("off"); };
+        c << "\n#morph=fill:" << (s.fill_holes == 6 ? "3d" : s.fill_holes == 4 ? "2d" : "off") << ",hmax:" << level(s.hmax) << ",hdome:" << level(s.hdome);
     }
     if (settings().despeckle && cover)
         c << "\n#despeckle=min:" << settings().despeckle_opts.min_size << ",thr:" << cover->despeckle_thr << ",conn:" << settings().despeckle_opts.connectivity
@@ -336,7 +349,7 @@ struct Pipeline {
     void *const X = RX ? (void *)RX : (void *)S.exchange;
     const bool sharded = world > 1 || S.force_shard;
     const pnr_filter_opts &fo = S.filter;
-    const bool filtered = fo.median || fo.tophat_r || S.despeckle;
+    const bool filtered = fo.median || fo.tophat_r || S.morph() || S.despeckle;
     Ctx ctx;
     Result R;
     bool ok = true;
@@ -370,10 +383,30 @@ struct Pipeline {
         if (S.timing) fprintf(stderr, "[pnr host] despeckle: %.3f s\n", R.t_despeckle);
     }
 
-    void filter() // --median / --subtract-background (/ --despeckle): the context's volume is replaced by its filtered bytes
+    void morph() // --fill-holes / --hmax / --hdome: the (filtered) volume is replaced by its reconstruction, then despeckled
+    {
+        if (S.morph() && ok) {
+            const auto tf = clk::now();
+            Profile prof(ctx, "morph", S.timing || S.verbose);
+            std::vector<MorphStage> stages;
+            ok = morph_stages(ctx, &stages);
+            R.t_morph = secs(tf, clk::now());
+            prof.end();
+            auto level = [](int v) { return v ? std::to_string(v) : std::string("off"); };
+            long long changed = 0;
+            for (const MorphStage &st : stages) changed += st.info.n_changed;
+            printf("morphology... fill holes %s, h-maxima %s, h-dome %s, %lld voxels changed, %g sec.\n", S.fill_holes == 6 ? "3d" : S.fill_holes == 4 ? "2d" : "off",
+                   level(S.hmax).c_str(), level(S.hdome).c_str(), changed, R.t_morph);
+            if (S.verbose) printf("morphology kernels %.3f ms in %lld launches\n", prof.ms, (long long)prof.launches);
+            if (S.timing) fprintf(stderr, "[pnr host] morph: %.3f s, kernels %.3f ms in %lld launches\n", R.t_morph, prof.ms, (long long)prof.launches);
+        }
+        despeckle();
+    }
+
+    void filter() // --median / --subtract-background (/ --fill-holes / --hmax / --hdome / --despeckle): the context's volume is replaced by its filtered bytes
     {
         if (!filtered || !ok) return;
-        if (!fo.median && !fo.tophat_r) return despeckle();
+        if (!fo.median && !fo.tophat_r) return morph();
         const auto tf = clk::now();
         Profile prof(ctx, "filter", S.timing || S.verbose);
         ok = pnr_filter_volume(ctx, &fo) == PNR_OK;
@@ -382,7 +415,7 @@ struct Pipeline {
         printf("pre-filter... median %s, top-hat %d, %g sec.\n", fo.median == 3 ? "3d" : fo.median == 2 ? "2d" : "off", (int)fo.tophat_r, R.t_filter);
         if (S.verbose) printf("pre-filter kernels %.3f ms in %lld launches\n", prof.ms, (long long)prof.launches);
         if (S.timing) fprintf(stderr, "[pnr host] filter: %.3f s, kernels %.3f ms in %lld launches\n", R.t_filter, prof.ms, (long long)prof.launches);
-        despeckle();
+        morph();
     }
 
     void seeds_one_gpu() // volume, pre-filter, soma, Frangi, and the scored and sorted seeds

@@ -52,6 +52,7 @@ struct Result {
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
     double t_filter = 0;           // --median / --subtract-background: the pre-filter (part of t_setup)
+    double t_morph = 0;            // --fill-holes / --hmax / --hdome: the morphological reconstructions (part of t_setup)
     double t_radius = 0;           // --measure-radius: the measurement (kernels, transfers, the first call's shell table)
     double t_load = 0, t_setup = 0, t_write = 0, t_total = 0; // stack file -> memory; context + upload (+ soma); SWC file; advantra_func as a whole
 };
@@ -114,6 +115,13 @@ struct Settings {
     // of --ranks N.  The SWC comment then has a #despeckle= line behind #filter.  The reference has no counterpart.
     bool despeckle = false;
     pnr_components_opts despeckle_opts = {-1, 26, 1};
+    // --fill-holes 2d|3d, --hmax H | --hdome H (1..255): the grey image's shape is repaired on the GPU (pnr_morph_volume) after the
+    // pre-filters -- for 16-bit input after windowing -- and before --despeckle; the fill (PNR_MORPH_FILL with C = 4 in every slice, or
+    // C = 6) runs first, then the h transform (C = 26); on every rank of --ranks N, and in every tool mode that takes the volume set-up.
+    // The SWC comment then has a #morph= line behind #filter.  The reference has no counterpart.
+    int fill_holes = 0; // 0: off, 4: 2d, 6: 3d (the connectivity)
+    int hmax = 0, hdome = 0;
+    bool morph() const { return fill_holes || hmax || hdome; }
 };
 Settings &settings();
 
@@ -213,6 +221,10 @@ struct SkeletonJob {
     std::string out, swc;
 };
 bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
+// advantra_cli --morph -i stack [--fill-holes 2d|3d] [--hmax H | --hdome H] --morph-out OUT: the stack after the volume set-up of tracing,
+// whose last steps are these flags (pnr_morph_volume on `device`), written as a TIFF, or as bare bytes for a .raw name.  One JSON line
+// {"w", "h", "l", "stages": [{"op": "fill" | "hmax" | "hdome", "h", then the fields of pnr_morph_info}, ...]}, a stage per flag in the order run.
+bool morph_file(const std::string &out, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

@@ -53,6 +53,15 @@ struct GeoJoined {
 bool geodesic_join(pnr_ctx *ctx, const float *xyz, const int32_t *parent, int64_t n, const pnr_geojoin_opts &opts, int64_t root, long long w, long long h, long long l,
                    GeoJoined &out);
 
+// tools.cpp: the last steps of the volume set-up -- --fill-holes, then --hmax or --hdome of settings(), each a pnr_morph_volume on ctx's
+// volume; stages (nullable) receives what ran, in order; false when a call failed (pnr_last_error has the reason)
+struct MorphStage {
+    const char *op; // "fill", "hmax", "hdome"
+    int h;
+    pnr_morph_info info;
+};
+bool morph_stages(pnr_ctx *ctx, std::vector<MorphStage> *stages);
+
 // swc_io.cpp: load_swc with its message on stderr; the shortest decimal text without an exponent (nine digits at the most) that reads
 // back as the same f32
 bool read_swc(const std::string &path, SwcTree &out);

@@ -1,5 +1,5 @@
 // tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc (by gap, or --join-geodesic), --render-swc,
-// --components, --edt, --skeleton and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+// --components, --edt, --skeleton, --morph and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
 #include "host_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -24,13 +24,30 @@ static bool write_file(const std::string &name, const char *mode, const std::fun
     return true;
 }
 
-// the volume as it would be traced: windowed to 8 bits, then pre-filtered (never despeckled)
-static bool set_traced_volume(pnr_ctx *ctx, const Stack &st)
+bool morph_stages(pnr_ctx *ctx, std::vector<MorphStage> *stages)
+{
+    const Settings &S = settings();
+    auto run = [&](int op, int conn, int h, const char *name) {
+        const pnr_morph_opts o = {op, conn, h, 0};
+        pnr_morph_info mi = {};
+        if (pnr_morph_volume(ctx, &o, &mi) != PNR_OK) return false;
+        if (stages) stages->push_back(MorphStage{name, h, mi});
+        return true;
+    };
+    if (S.fill_holes && !run(PNR_MORPH_FILL, S.fill_holes, 0, "fill")) return false;
+    if (S.hmax && !run(PNR_MORPH_HMAX, 26, S.hmax, "hmax")) return false;
+    if (S.hdome && !run(PNR_MORPH_HDOME, 26, S.hdome, "hdome")) return false;
+    return true;
+}
+
+// the volume as it would be traced: windowed to 8 bits, pre-filtered, then --fill-holes / --hmax / --hdome (never despeckled)
+static bool set_traced_volume(pnr_ctx *ctx, const Stack &st, std::vector<MorphStage> *stages = nullptr)
 {
     const Settings &S = settings();
     bool ok = (st.bits == 16 ? pnr_set_volume_u16(ctx, st.samples16(), st.w, st.h, st.l, 1, 0, S.windowed ? &S.window : nullptr, nullptr, nullptr)
                              : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
     if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
+    if (ok && S.morph()) ok = morph_stages(ctx, stages);
     return ok || lib_fail("volume");
 }
 
@@ -388,6 +405,30 @@ bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, c
            "\"rounds\": %d, \"thr_used\": %d, \"trees\": %lld}\n",
            (long long)ti.n_vox, (long long)ti.n_fg, (long long)ti.n_skel, (long long)ti.n_end, (long long)ti.n_branch, (long long)ti.n_isolated, (long long)ti.tiles,
            (long long)ti.tile_visits, (int)ti.rounds, (int)ti.thr_used, (long long)trees);
+    return true;
+}
+
+bool morph_file(const std::string &out, const std::vector<char *> &infiles, const std::string &raw_dims, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    Ctx ctx;
+    std::vector<MorphStage> stages;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st, &stages)) return false;
+    std::vector<unsigned char> vol((size_t)(st.w * st.h * st.l));
+    if (pnr_get_volume(ctx, vol.data()) != PNR_OK) return lib_fail("pnr_get_volume");
+    if (!write_stack(out, vol.data(), st.w, st.h, st.l)) return false;
+    printf("{\"w\": %lld, \"h\": %lld, \"l\": %lld, \"stages\": [", st.w, st.h, st.l);
+    for (size_t k = 0; k < stages.size(); k++) {
+        const pnr_morph_info &mi = stages[k].info;
+        printf("%s{\"op\": \"%s\", \"h\": %d, \"n_vox\": %lld, \"n_changed\": %lld, \"n_nonzero\": %lld, \"sum_in\": %llu, \"sum_out\": %llu, \"max_delta\": %d, "
+               "\"connectivity\": %d, \"tiles\": %lld, \"tile_visits\": %lld, \"rounds\": %d}",
+               k ? ", " : "", stages[k].op, stages[k].h, (long long)mi.n_vox, (long long)mi.n_changed, (long long)mi.n_nonzero, (unsigned long long)mi.sum_in,
+               (unsigned long long)mi.sum_out, (int)mi.max_delta, (int)mi.connectivity, (long long)mi.tiles, (long long)mi.tile_visits, (int)mi.rounds);
+    }
+    printf("]}\n");
     return true;
 }
 

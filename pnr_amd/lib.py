@@ -175,6 +175,31 @@ class GeoJoinInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class MorphOpts(C.Structure):
+    """pnr_morph_opts (include/pnr_hip.h): op 1..5 (MORPH_OPS), connectivity 0 (the op's default: 6 for fill, 26 for the others), 4, 8, 6
+    or 26, h 1..255 for hmax / hdome and 0 otherwise"""
+    _fields_ = [("op", C.c_int32), ("connectivity", C.c_int32), ("h", C.c_int32), ("pad", C.c_int32)]
+
+
+class MorphInfo(C.Structure):
+    """pnr_morph_info: the exact summary of a morphological reconstruction (tile_visits and rounds: scheduling, a property of the implementation)"""
+    _fields_ = [("n_vox", C.c_int64), ("n_changed", C.c_int64), ("n_nonzero", C.c_int64), ("sum_in", C.c_uint64), ("sum_out", C.c_uint64), ("tiles", C.c_int64),
+                ("tile_visits", C.c_int64), ("max_delta", C.c_int32), ("connectivity", C.c_int32), ("rounds", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+MORPH_OPS = {"dilate": 1, "erode": 2, "fill": 3, "hmax": 4, "hdome": 5}
+
+
+def _morph_op(op):
+    """a name of MORPH_OPS, or the number itself (the library checks its range)"""
+    if isinstance(op, str) and op not in MORPH_OPS:
+        raise ValueError("morph: op %r, not one of %s" % (op, ", ".join(MORPH_OPS)))
+    return MORPH_OPS[op] if isinstance(op, str) else int(op)
+
+
 # pnr_geo_bridge: the attachment nodes, the meet voxel p and offset o (13..25 of the offset order), the weight W and the bridge's voxel chain
 GEO_BRIDGE = np.dtype([("a", np.int32), ("b", np.int32), ("p", np.int64), ("o", np.int32), ("path_len", np.int32), ("w", np.uint64), ("path_off", np.int64)])
 
@@ -319,6 +344,8 @@ PRODUCT_SIGNATURES = {
     "pnr_geodesic_distance": (_rc, [_vp, _vp, _vp, _i64, C.POINTER(GeoOpts), C.POINTER(GeoInfo), _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
     "pnr_geodesic_bridges": (_rc, [_vp, _vp, _vp, _i64, C.POINTER(GeoJoinOpts), C.POINTER(GeoJoinInfo), _vp, _i64, _pi64, _vp, _i64, _pi64]),
     "pnr_join_expand": (_rc, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _pi64, _vp]),
+    "pnr_morph_reconstruct": (_rc, [_vp, C.POINTER(MorphOpts), _vp, C.POINTER(MorphInfo), _vp]),
+    "pnr_morph_volume": (_rc, [_vp, C.POINTER(MorphOpts), C.POINTER(MorphInfo)]),
     "pnr_frangi": (_rc, [_vp, _pf32, _pf32]),
     "pnr_frangi_slab": (_rc, [_vp, _i64, _i64, _pf32, _pf32]),
     "pnr_quantise_j8": (_rc, [_vp, _f32, _f32]),
@@ -705,6 +732,32 @@ class Context:
                 at["path_len"] = plen
                 at["paths"] = [pvox[k, :abs(int(n))].copy() for k, n in enumerate(plen)]
         return out, D, Lv, at
+
+    def morph_reconstruct(self, marker=None, op="dilate", h=0, connectivity=0, volume=True):
+        """pnr_morph_reconstruct: the grey-level morphological reconstruction of the context's volume V under the rule of include/pnr_hip.h
+        -> (info dict {n_vox, n_changed, n_nonzero, sum_in, sum_out, tiles, tile_visits, max_delta, connectivity, rounds}, out uint8[l, h, w]
+        or None).  op: "dilate" / "erode" (the reconstruction of `marker`, uint8 of V's size, by dilation / by erosion under V), "fill"
+        (grey fill-holes), "hmax" (maxima of height below h removed), "hdome" (V minus the hmax volume); connectivity 0 (6 for fill, 26
+        for the others), 4, 8, 6 or 26.  The context and its volume stay as they are."""
+        m = None
+        if marker is not None:
+            m = np.ascontiguousarray(marker, np.uint8)
+            if m.size != int(np.prod(self.shape)):
+                raise ValueError("morph_reconstruct: a marker of %d voxels for a volume of %d" % (m.size, int(np.prod(self.shape))))
+        o = MorphOpts(_morph_op(op), int(connectivity), int(h), 0)
+        info = MorphInfo()
+        out = np.empty(self.shape, np.uint8) if volume else None
+        check(self.L.pnr_morph_reconstruct(self.h, C.byref(o), m.ctypes.data if m is not None else None, C.byref(info), out.ctypes.data if volume else None))
+        return info.as_dict(), out
+
+    def morph_volume(self, op, h=0, connectivity=0):
+        """pnr_morph_volume: the traced volume is replaced by its "fill", "hmax" or "hdome" (see morph_reconstruct) -> the info dict.  The
+        result is an owned volume (a borrowed one is left as it was and released) and the later pipeline state is invalidated."""
+        o = MorphOpts(_morph_op(op), int(connectivity), int(h), 0)
+        info = MorphInfo()
+        check(self.L.pnr_morph_volume(self.h, C.byref(o), C.byref(info)))
+        self._keep = None
+        return info.as_dict()
 
     def join_trees_geodesic(self, xyz, parent, limit=0, thr=0, step=1, cost=None):
         """pnr_geodesic_bridges of a forest (n x 3 voxel positions, parent indices with a negative value for none) through the context's
