@@ -879,6 +879,66 @@ int pnr_morph_reconstruct(pnr_ctx *ctx, const pnr_morph_opts *opts, const uint8_
                           uint8_t *out /* N, host, nullable */);
 int pnr_morph_volume(pnr_ctx *ctx, const pnr_morph_opts *opts, pnr_morph_info *info /* nullable */);
 
+/* Marker-controlled watershed of the traced volume (beyond the reference; Meyer 1991): the last step of "separate what touches".  Two somas
+ * that touch are one component for pnr_label_components and one tree for pnr_skeletonize, and no threshold parts them: the neck is as
+ * bright as the cells.  pnr_geodesic_distance labels by additive cost, so the nearer source wins even across a dark gap.  The watershed
+ * floods a relief from markers and puts the border on the lowest pass between them (the minimax rule): with the relief 255 - V on the
+ * darkest gap, with a relief made from pnr_distance_transform on the neck.
+ * THE RULE (the contract; tests restate it in numpy).  Everything is exact integer arithmetic.  V is the context's traced u8 volume,
+ * N = w * h * l.  params.zdist plays no part.
+ *   Mask.  V >= t, t = opts->thr, or for thr == -1 the mean rule of pnr_label_components (max(1, floor(sum / N))); thr = 0: every voxel.
+ *   Relief R (u8).  `relief`: N host bytes; NULL: R = 255 - V, bright signal is low ground and floods first.
+ *   Neighbourhoods N_C, C in {4, 8, 6, 26}, exactly as the morphological reconstruction above defines them; connectivity = 0 means 26.
+ *   Markers, in exactly one of two forms (both, or neither: PNR_E_ARG).  marker_vol: N host int32, a value > 0 is a label, 0 none, a
+ *     negative one PNR_E_ARG.  Or n_src > 0 points src_xyz (n x 3 f32, voxel positions) with labels src_label (>= 1; NULL: 1 .. n in
+ *     order), each placed on its centre voxel (the radius rule above).  A point that is not finite and a marker (point or voxel) outside the
+ *     mask are dropped and counted in n_dropped.  Where several points share a voxel the smallest label wins.
+ *   Key.  Every mask voxel carries a key K = (M, D), compared lexicographically.  A marker voxel p has K = (R(p), 0), for good.  Stepping
+ *     from s to a mask neighbour t that is no marker: g(K(s), t) = (R(t), 1) if R(t) > M(s), else (M(s), D(s) + 1).  K(t) is the minimum,
+ *     over all C-paths inside the mask from any marker to t, of g applied along the path.  M is the lowest pass height to a marker -- the
+ *     minimax altitude, the reconstruction by erosion of the marker function under R --, D the steps since the flood last had to rise:
+ *     the order in which Meyer's hierarchical queues reach the voxels.  A mask voxel that no marker reaches has no key.
+ *   Exact whatever the schedule: g is monotone (K <= K' gives g(K, t) <= g(K', t)) and strictly increasing (g(K, t) > K).  Start with the
+ *     markers at their keys and everything else at +inf; every update replaces K(t) by the minimum of itself and g(K(q), t) over its
+ *     neighbours q.  Every value ever held is that of a real path, so keys only fall and a stale neighbour key is still an upper bound;
+ *     the only fixed point is the path minimum.  No tiling, round structure or launch cut changes a bit.
+ *   Label, from the final keys only.  A neighbour s of t is tight when g(K(s), t) == K(t).  L(marker voxel) = its label; L(t) = the
+ *     smallest L(s) over the tight neighbours s of t.  Tight edges rise strictly in K: a recursion over a DAG with one solution, relaxed as
+ *     a falling minimum in any order.  Every region is C-connected and holds its marker.  Unreached voxels and those outside the mask: 0.
+ *   Two passes, necessarily: the triple (M, D, L) carried as one key is NOT monotone -- across a rise both candidates become
+ *     (R(t), 1, .), and a label taken from a key that was not yet final can stick.  The labels are relaxed only once the keys have settled.
+ *   Representation.  The key is the u32 M << 24 | D; D saturates at 2^24 - 1 (saturating addition keeps g monotone), and a call in which
+ *     the D of any voxel ends saturated fails with PNR_E_ARG (the text names the plateau depth and the level).
+ *   Outputs.  label_out (N host int32) and level_out (N host bytes: M of the reached voxels -- the height at which a voxel joined its
+ *     region --, 0 elsewhere), both nullable.  pnr_watershed_info, exact: n_vox = N, n_mask, n_marker_vox (mask voxels that hold a
+ *     marker), n_dropped, n_reached (markers included), n_unreached (= n_mask - n_reached), n_regions (distinct labels in the result),
+ *     m_max, d_max (the largest M and D of a reached voxel; 0 without one), thr_used, connectivity (the one used), tiles (of
+ *     WS_TX x WS_TY x WS_TZ voxels); flood_visits / flood_rounds (pass 1) and label_visits / label_rounds (pass 2): scheduling, not part
+ *     of the rule, reported and never compared bit for bit.
+ * Arguments, checked in this order (PNR_E_ARG unless said otherwise): ctx and opts non-NULL; thr in -1..255; connectivity in {0, 4, 8, 6,
+ *   26}; n_src in 0..2^31 - 2; exactly one marker form (marker_vol, or n_src > 0; src_label only with points); src_xyz with n_src > 0;
+ *   every src_label >= 1; a volume in the context (else PNR_E_STATE) of at most 2^32 - 2 voxels; no negative entry in marker_vol.
+ *   PNR_E_NOMEM: an allocation failed.  The call never writes V (also not a borrowed one), leaves the pipeline state of the context alone,
+ *   runs on the context's stream (pnr_set_stream), uses 64-bit voxel indices and frees every device buffer before it returns.  Device
+ *   memory of a call: 9 bytes per voxel (key, label, relief; the levels replace the relief in place), 12 bytes per tile, 4 bytes per
+ *   marker (the labels for n_regions; 16 per point in the point form); 8 bytes of pinned host memory carry a round's tile count.
+ * Kernel times: pnr_get_kernel_ms group "watershed" = the sum of "watershed_init" (mean threshold, point scatter, first keys),
+ *   "watershed_compact", "watershed_flood" (pass 1), "watershed_label" (pass 2) and "watershed_finish".  pnr_get_option "ws_rounds" /
+ *   "ws_visits": rounds and tile visits of the last call, both passes together.  pnr_set_option "ws_iters" (LDS iterations per tile
+ *   visit; 0 = automatic, 1 forces a tile to re-queue itself) and "ws_tiles_per_launch" (0 = automatic; small values force launch cuts)
+ *   change no bit: tests reach the boundaries on small stacks with them. */
+typedef struct pnr_watershed_opts {
+    int32_t thr, connectivity;
+} pnr_watershed_opts;
+typedef struct pnr_watershed_info {
+    int64_t n_vox, n_mask, n_marker_vox, n_dropped, n_reached, n_unreached, n_regions;
+    int64_t tiles, flood_visits, label_visits;
+    int32_t m_max, d_max, thr_used, connectivity, flood_rounds, label_rounds;
+} pnr_watershed_info;
+int pnr_watershed(pnr_ctx *ctx, const pnr_watershed_opts *opts, const uint8_t *relief /* N, host, nullable */, const int32_t *marker_vol /* N, host, or NULL */,
+                  const float *src_xyz /* n_src x 3, or NULL */, const int32_t *src_label /* n_src, nullable */, int64_t n_src,
+                  pnr_watershed_info *info /* nullable */, int32_t *label_out /* N, host, nullable */, uint8_t *level_out /* N, host, nullable */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -908,16 +968,17 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   render_items_per_launch (0 = automatic: 2^18) items per launch (the same bits -- tests reach piece, box and launch boundaries with them on small inputs) |
  *   geo_iters, geo_tiles_per_launch (0 = automatic) of pnr_geodesic_distance and geojoin_tiles_per_launch (0 = automatic: 2^20) tiles per launch of a sweep of pnr_geodesic_bridges (the same bits) |
  *   morph_iters, morph_tiles_per_launch (0 = automatic) of pnr_morph_reconstruct / pnr_morph_volume: the same two for its relaxation (the same bits) |
+ *   ws_iters, ws_tiles_per_launch (0 = automatic) of pnr_watershed: the same two for both of its passes (the same bits) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
- *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "geo_rounds" / "geo_visits", "geojoin_rounds", "morph_rounds" / "morph_visits" (the last call of that tool), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
+ *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "geo_rounds" / "geo_visits", "geojoin_rounds", "morph_rounds" / "morph_visits", "ws_rounds" / "ws_visits" (the last call of that tool), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
  *   re-run Frangi without the frangi_prune shortcut -- one pnr_frangi worth of GPU time each; also printed with trace_timing /
  *   seed_timing).  The kernel timers (pnr_get_kernel_ms) include those re-runs. */
 int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish").  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish"),"watershed" (pnr_watershed: the sum of "watershed_init", "watershed_compact", "watershed_flood", "watershed_label" and "watershed_finish").  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -323,6 +323,7 @@ const OptEntry OPTS[] = {
     {"geo_iters", &pnr::Options::geo_iters, nullptr, 0, 1 << 16}, {"geo_tiles_per_launch", &pnr::Options::geo_tiles_per_launch, nullptr, 0, 1 << 24},
     {"geojoin_tiles_per_launch", &pnr::Options::geojoin_tiles_per_launch, nullptr, 0, 1 << 24},
     {"morph_iters", &pnr::Options::morph_iters, nullptr, 0, 1 << 16}, {"morph_tiles_per_launch", &pnr::Options::morph_tiles_per_launch, nullptr, 0, 1 << 24},
+    {"ws_iters", &pnr::Options::ws_iters, nullptr, 0, 1 << 16}, {"ws_tiles_per_launch", &pnr::Options::ws_tiles_per_launch, nullptr, 0, 1 << 24},
 };
 // what pnr_get_option reads besides: counters the calls leave in the context
 struct Counter { const char *key; int64_t pnr_ctx::*count; };
@@ -330,6 +331,7 @@ const Counter COUNTERS[] = {
     {"join_rounds", &pnr_ctx::join_rounds},       {"geo_rounds", &pnr_ctx::geo_rounds},     {"geo_visits", &pnr_ctx::geo_visits},
     {"geojoin_rounds", &pnr_ctx::geojoin_rounds}, {"render_items", &pnr_ctx::render_items}, {"render_pairs", &pnr_ctx::render_pairs},
     {"morph_rounds", &pnr_ctx::morph_rounds},     {"morph_visits", &pnr_ctx::morph_visits},
+    {"ws_rounds", &pnr_ctx::ws_rounds},           {"ws_visits", &pnr_ctx::ws_visits},
     {"frangi_recomputes", &pnr_ctx::frangi_recomputes}, // exact Frangi re-runs so far (one pnr_frangi of GPU time each)
 };
 } // namespace
@@ -436,6 +438,7 @@ const Umbrella UMBRELLAS[] = {
     {"geodesic", {"geodesic_threshold", "geodesic_init", "geodesic_compact", "geodesic_relax", "geodesic_stats", "geodesic_split", "geodesic_sample", "geodesic_paths"}},
     {"geojoin", {"geojoin_meet_w", "geojoin_meet_e"}}, // the two passes of a Boruvka round
     {"morph", {"morph_init", "morph_compact", "morph_relax", "morph_finish"}},
+    {"watershed", {"watershed_init", "watershed_compact", "watershed_flood", "watershed_label", "watershed_finish"}},
 };
 } // namespace
 

@@ -1,5 +1,5 @@
 // api_tools.cpp -- the extern "C" boundary of libpnr_hip.so (include/pnr_hip.h), third part: the tools on the volume (filter, components,
-// distance transform, skeleton, geodesic distance, morphological reconstruction, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
+// distance transform, skeleton, geodesic distance, morphological reconstruction, watershed, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
 // taps (include/pnr_hip_test.h).  An entry point checks its arguments first, then the state (args.h holds the shared rules), and hands
 // over to the tool's own file; no tool needs or touches the pipeline state of the context (Frangi, seeds, graph).
 #include "args.h"
@@ -16,6 +16,7 @@
 #include "geodesic.h"
 #include "geojoin.h"
 #include "morph.h"
+#include "watershed.h"
 #include "../host/stack_io.h"
 
 namespace args = pnr::args;
@@ -164,6 +165,32 @@ int pnr_morph_volume(pnr_ctx *c, const pnr_morph_opts *opts, pnr_morph_info *inf
     const int rc = pnr_morph_run(c, who, o, nullptr, info, nullptr, &out);
     if (!rc) pnr::replace_volume(c, std::move(out));
     return rc;
+}
+
+// pnr_watershed (watershed.hip): arguments in the order of the header, then the state and the device, then the marker volume's entries
+int pnr_watershed(pnr_ctx *c, const pnr_watershed_opts *opts, const uint8_t *relief, const int32_t *marker_vol, const float *src_xyz, const int32_t *src_label, int64_t n_src,
+                  pnr_watershed_info *info, int32_t *label_out, uint8_t *level_out)
+{
+    static const char *who = "pnr_watershed";
+    PNR_REQUIRE(c && opts, PNR_E_ARG, "null argument");
+    pnr_watershed_opts o = *opts;
+    PNR_TRY(args::thr_range(who, o.thr));
+    PNR_REQUIRE(o.connectivity == 0 || o.connectivity == 4 || o.connectivity == 8 || o.connectivity == 6 || o.connectivity == 26, PNR_E_ARG,
+                "%s: connectivity = %d, not 0, 4, 8, 6 or 26", who, o.connectivity);
+    PNR_REQUIRE(n_src >= 0 && n_src <= 0x7ffffffeLL, PNR_E_ARG, "%s: n_src = %lld outside [0, 2^31 - 2]", who, (long long)n_src);
+    PNR_REQUIRE(!(marker_vol && (n_src > 0 || src_xyz || src_label)), PNR_E_ARG, "%s: markers as a volume and as points, exactly one of the two forms", who);
+    PNR_REQUIRE(marker_vol || n_src > 0, PNR_E_ARG, "%s: no markers, neither marker_vol nor n_src > 0", who);
+    PNR_REQUIRE(marker_vol || src_xyz, PNR_E_ARG, "%s: n_src = %lld needs src_xyz", who, (long long)n_src);
+    for (int64_t i = 0; src_label && i < n_src; i++)
+        PNR_REQUIRE(src_label[i] >= 1, PNR_E_ARG, "%s: src_label[%lld] = %d, labels are at least 1", who, (long long)i, src_label[i]);
+    if (o.connectivity == 0) o.connectivity = 26;
+    PNR_TRY(args::volume_u32(c, who));
+    int64_t n_pos = 0;
+    for (int64_t i = 0; marker_vol && i < c->N; i++) {
+        PNR_REQUIRE(marker_vol[i] >= 0, PNR_E_ARG, "%s: marker_vol[%lld] = %d is negative", who, (long long)i, marker_vol[i]);
+        n_pos += marker_vol[i] > 0;
+    }
+    return pnr_watershed_run(c, who, o, relief, pnr_ws_markers{marker_vol, n_pos, src_xyz, src_label, n_src}, info, label_out, level_out);
 }
 
 // pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched

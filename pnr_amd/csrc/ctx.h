@@ -114,6 +114,8 @@ struct Options {
     int geojoin_tiles_per_launch = 0; // pnr_geodesic_bridges (geojoin.hip): tiles per launch of a meet pass (0: automatic, 2^20); changes no result: tests reach launch cuts with it
     int morph_iters = 0;        // pnr_morph_reconstruct / pnr_morph_volume (morph.hip): LDS iterations per tile visit (0: automatic, 64; 1: a tile that changed re-queues itself), and
     int morph_tiles_per_launch = 0; // tiles per morph_relax launch (0: automatic, 2^20); neither changes a result: tests reach the re-queue path and launch cuts with them
+    int ws_iters = 0;           // pnr_watershed (watershed.hip): LDS iterations per tile visit of both passes (0: automatic, 64; 1: a tile that changed re-queues itself), and
+    int ws_tiles_per_launch = 0; // tiles per ws_flood / ws_label launch (0: automatic, 2^20); neither changes a result: tests reach the re-queue path and launch cuts with them
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host
@@ -202,6 +204,7 @@ struct pnr_ctx {
     int64_t render_items = 0, render_pairs = 0; // work items and (voxel, segment) tests of the last render (pnr_get_option "render_items" / "render_pairs")
     int64_t geo_rounds = 0, geo_visits = 0; // relaxation rounds and tile visits of the last pnr_geodesic_distance (pnr_get_option "geo_rounds" / "geo_visits")
     int64_t morph_rounds = 0, morph_visits = 0; // relaxation rounds and tile visits of the last morphological reconstruction (pnr_get_option "morph_rounds" / "morph_visits")
+    int64_t ws_rounds = 0, ws_visits = 0; // relaxation rounds and tile visits of the last pnr_watershed, both passes together (pnr_get_option "ws_rounds" / "ws_visits")
     int64_t geojoin_rounds = 0; // Boruvka rounds of the last pnr_geodesic_bridges (pnr_get_option "geojoin_rounds")
     std::vector<int32_t> graph_log; // 5 ints per replayed trace (option "trace_log")
 

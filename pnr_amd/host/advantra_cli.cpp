@@ -61,6 +61,10 @@
 //   #morph=fill:<2d|3d|off>,hmax:<H|off>,hdome:<H|off> behind #filter --, --skeleton, --components, --edt, --geodesic, --render-swc and
 //   --join-swc --join-geodesic.  --morph -i stack [those flags] --morph-out OUT.tif|.raw: the resulting stack and one JSON line with the
 //   fields of pnr_morph_info of each stage run.
+//   --watershed -i stack (--markers-swc tree.swc [--markers-by tree|node] | --markers FILE.raw) [--relief FILE.raw] [--threshold T]
+//   [--connectivity 4|8|6|26] --labels OUT.raw [--levels OUT.raw]: the marker-controlled watershed of the stack after the same volume set-up
+//   (pnr_watershed): the label volume, with --markers-by tree the voxels per traced neuron, and one JSON line with the fields of
+//   pnr_watershed_info.
 // Exit code: 0 = dofunc returned true, 1 = dofunc returned false (usage error).
 #include "advantra_host.h"
 #include <cctype>
@@ -158,6 +162,8 @@ int main(int argc, char **argv)
     bool skeleton = false, skel_flag = false;
     bool morph = false;
     std::string morph_out;
+    advantra::WatershedJob ws_job;
+    bool ws = false, ws_flag = false, ws_by_flag = false, conn_planar = false, comp_only_flag = false; // (--min-size, --per-component: of --components alone)
     advantra::Settings &S0 = advantra::settings();
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--geodesic")) { geo = true; continue; }
@@ -177,6 +183,27 @@ int main(int argc, char **argv)
             }
             (flag == "--from" ? geo_job.from : flag == "--to" ? geo_job.to : flag == "--paths" ? geo_job.paths : geo_job.out) = name;
             geo_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--watershed")) { ws = true; continue; }
+        if (!strcmp(argv[i], "--markers-swc") || !strcmp(argv[i], "--markers") || !strcmp(argv[i], "--relief") || !strcmp(argv[i], "--levels")) {
+            const std::string flag = argv[i];
+            const std::string name = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (name.empty() || (flag != "--markers-swc" && (name.size() <= 4 || name.substr(name.size() - 4) != ".raw"))) {
+                fprintf(stderr, "%s\n", flag == "--markers-swc" ? "--markers-swc FILE.swc" : flag == "--markers" ? "--markers FILE.raw: a .raw file name (bare little-endian int32)"
+                                        : flag == "--relief"    ? "--relief FILE.raw: a .raw file name (bare bytes)"
+                                                                : "--levels OUT.raw: a .raw file name (bare bytes)");
+                return 1;
+            }
+            (flag == "--markers-swc" ? ws_job.markers_swc : flag == "--markers" ? ws_job.markers_raw : flag == "--relief" ? ws_job.relief : ws_job.levels) = name;
+            ws_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--markers-by")) {
+            const std::string by = i + 1 < argc ? argv[++i] : "";
+            if (by != "tree" && by != "node") { fprintf(stderr, "--markers-by tree|node\n"); return 1; }
+            ws_job.by_node = by == "node";
+            ws_flag = ws_by_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--skeleton")) { skeleton = true; continue; }
@@ -218,14 +245,15 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "--threshold")) {
             long v = 0;
             if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
-            comp.opts.thr = edt_job.opts.thr = geo_job.opts.thr = skel_job.opts.thr = (int32_t)v;
+            comp.opts.thr = edt_job.opts.thr = geo_job.opts.thr = skel_job.opts.thr = ws_job.opts.thr = (int32_t)v;
             thr_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--connectivity")) {
             long v = 0;
-            if (!parse_int(i + 1 < argc ? argv[++i] : "", 6, 26, v) || (v != 6 && v != 26)) { fprintf(stderr, "--connectivity 6|26\n"); return 1; }
-            comp.opts.connectivity = (int32_t)v;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 4, 26, v) || (v != 4 && v != 8 && v != 6 && v != 26)) { fprintf(stderr, "--connectivity 6|26 (--watershed: 4|8|6|26)\n"); return 1; }
+            comp.opts.connectivity = ws_job.opts.connectivity = (int32_t)v;
+            conn_planar = v == 4 || v == 8;
             comp_flag = true;
             continue;
         }
@@ -233,7 +261,7 @@ int main(int argc, char **argv)
             long v = 0;
             if (!parse_int(i + 1 < argc ? argv[++i] : "", 1, 0x7fffffffffffffffL, v)) { fprintf(stderr, "--min-size M: an integer from 1\n"); return 1; }
             comp.opts.min_size = v;
-            comp_flag = true;
+            comp_flag = comp_only_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--labels") || !strcmp(argv[i], "--per-component")) {
@@ -245,6 +273,7 @@ int main(int argc, char **argv)
             }
             (lab ? comp.labels : comp.per_component) = name;
             comp_flag = true;
+            if (!lab) comp_only_flag = true;
             continue;
         }
         if (!strcmp(argv[i], "--despeckle")) {
@@ -486,7 +515,9 @@ int main(int argc, char **argv)
     if (join_thr_flag && !join_geodesic) { fprintf(stderr, "--join-threshold needs --join-geodesic D\n"); return 1; }
     if (join_flag && !join_given && !join_geodesic && join_in.empty()) { fprintf(stderr, "--join-root / --join-keep-largest need --join GAP, --join-geodesic D or --join-swc IN.swc OUT.swc\n"); return 1; }
     if (!join_in.empty() && join_root_soma) { fprintf(stderr, "--join-swc: --join-root takes a node id of IN.swc\n"); return 1; }
-    if ((comp_flag && !components) || (thr_flag && !components && !edt && !geo && !skeleton)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt, --geodesic or --skeleton)\n"); return 1; }
+    if (conn_planar && !ws) { fprintf(stderr, "--connectivity 6|26 (--watershed: 4|8|6|26)\n"); return 1; }
+    if (ws_flag && !ws) { fprintf(stderr, "--markers-swc / --markers / --markers-by / --relief / --levels need --watershed -i stack\n"); return 1; }
+    if ((comp_flag && !components && !ws) || (thr_flag && !components && !edt && !geo && !skeleton && !ws)) { fprintf(stderr, "--threshold / --connectivity / --min-size / --labels / --per-component need --components -i stack (--threshold: or --edt, --geodesic or --skeleton)\n"); return 1; }
     if (skel_flag && !skeleton) { fprintf(stderr, "--skeleton-rounds / --skeleton-out / --swc need --skeleton -i stack\n"); return 1; }
     if (edt_flag && !edt) { fprintf(stderr, "--edt-max / --edt-out / --at need --edt -i stack\n"); return 1; }
     if (geo_flag && !geo) { fprintf(stderr, "--from / --to / --paths / --geo-max / --geo-out need --geodesic -i stack\n"); return 1; }
@@ -495,8 +526,8 @@ int main(int argc, char **argv)
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
     if (skeleton) {
         if (geo || geo_flag || edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic ||
-            per_node_flag || !paras.empty() || morph) {
-            fprintf(stderr, "--skeleton: not with a tracing run (-p), --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node or --morph\n");
+            per_node_flag || !paras.empty() || morph || ws || ws_flag) {
+            fprintf(stderr, "--skeleton: not with a tracing run (-p), --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node, --morph or --watershed\n");
             return 1;
         }
         if (infiles.empty()) { fprintf(stderr, "--skeleton needs -i <stack>\n"); return 1; }
@@ -505,14 +536,28 @@ int main(int argc, char **argv)
     }
     if (morph) {
         if (geo || geo_flag || edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic ||
-            per_node_flag || thr_flag || zscale_flag || !paras.empty()) {
-            fprintf(stderr, "--morph: not with a tracing run (-p), --skeleton, --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node, --threshold or --zscale\n");
+            per_node_flag || thr_flag || zscale_flag || !paras.empty() || ws || ws_flag) {
+            fprintf(stderr, "--morph: not with a tracing run (-p), --skeleton, --geodesic, --edt, --components, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node, --threshold, --zscale or --watershed\n");
             return 1;
         }
         if (infiles.empty()) { fprintf(stderr, "--morph needs -i <stack>\n"); return 1; }
         if (morph_out.empty()) { fprintf(stderr, "--morph needs --morph-out OUT\n"); return 1; }
         if (!S0.morph()) { fprintf(stderr, "--morph needs one of --fill-holes, --hmax and --hdome\n"); return 1; }
         return advantra::morph_file(morph_out, infiles, raw_dims, device) ? 0 : 1;
+    }
+    if (ws) {
+        if (geo || geo_flag || edt || edt_flag || components || comp_only_flag || rendering || distance || !join_in.empty() || info || S0.despeckle ||
+            S0.measure_radius || join_given || join_geodesic || per_node_flag || zscale_flag || !paras.empty()) {
+            fprintf(stderr, "--watershed: not with a tracing run (-p), --skeleton, --morph, --geodesic, --edt, --components, --min-size, --per-component, --render-swc, --distance, --join-swc, --join, --info, --despeckle, --measure-radius, --per-node or --zscale\n");
+            return 1;
+        }
+        if (infiles.empty()) { fprintf(stderr, "--watershed needs -i <stack>\n"); return 1; }
+        if (!ws_job.markers_swc.empty() && !ws_job.markers_raw.empty()) { fprintf(stderr, "--markers-swc and --markers: one of them\n"); return 1; }
+        if (ws_job.markers_swc.empty() && ws_job.markers_raw.empty()) { fprintf(stderr, "--watershed needs one of --markers-swc and --markers\n"); return 1; }
+        if (ws_by_flag && ws_job.markers_swc.empty()) { fprintf(stderr, "--markers-by needs --markers-swc\n"); return 1; }
+        if (comp.labels.empty()) { fprintf(stderr, "--watershed needs --labels OUT.raw\n"); return 1; }
+        ws_job.labels = comp.labels;
+        return advantra::watershed_file(ws_job, infiles, raw_dims, device) ? 0 : 1;
     }
     if (geo) {
         if (edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic || !paras.empty()) {

@@ -84,6 +84,16 @@ void print_flags()
     printf("--morph -i stack          the stack after the volume set-up of tracing with [--fill-holes 2d|3d] [--hmax H | --hdome H] as one JSON line: per stage\n");
     printf("                          op, h, n_vox, n_changed, n_nonzero, sum_in, sum_out, max_delta, connectivity, tiles, tile_visits, rounds\n");
     printf("  --morph-out OUT           write the resulting stack as a multi-page 8-bit TIFF, or bare bytes for a .raw name (needed)\n");
+    printf("--watershed -i stack      the marker-controlled watershed of the stack (after the volume set-up of tracing) on the GPU: every voxel from --threshold T\n");
+    printf("                          on (default -1: the stack's mean) gets the label of the marker whose flood over the relief reaches it first; the borders\n");
+    printf("                          lie on the lowest passes.  One JSON line: w, h, l, markers_by, n_markers, then the fields of pnr_watershed_info\n");
+    printf("  --markers-swc FILE.swc    the markers are the nodes of the tree file ...\n");
+    printf("  --markers-by tree|node    ... each labelled with the number of its tree, 1.. by descending node count (default: the voxels per neuron), or with its id\n");
+    printf("  --markers FILE.raw        ... or a marker volume: little-endian int32, > 0 = a label, 0 = none\n");
+    printf("  --relief FILE.raw         the relief to flood as bare bytes (default: 255 - the stack, bright signal floods first)\n");
+    printf("  --connectivity 4|8|6|26   the neighbourhood (default 26; 4 and 8: every slice on its own)\n");
+    printf("  --labels OUT.raw          write the label volume: little-endian int32, 0 = not reached or below the threshold (needed)\n");
+    printf("  --levels OUT.raw          write the pass height at which each voxel joined its region, as bare bytes\n");
     printf("--despeckle MIN[,THR[,CONN]]  pre-filter: foreground components (voxels >= THR, default -1: the stack's mean; CONN 6 or 26, default 26) of\n");
     printf("                          fewer than MIN voxels are set to 0 on the GPU (after the median and the top-hat, before tracing)\n");
     printf("--components -i stack     the connected components of the stack's foreground on the GPU (the same volume setup as tracing) as one JSON\n");

@@ -225,6 +225,18 @@ bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, c
 // whose last steps are these flags (pnr_morph_volume on `device`), written as a TIFF, or as bare bytes for a .raw name.  One JSON line
 // {"w", "h", "l", "stages": [{"op": "fill" | "hmax" | "hdome", "h", then the fields of pnr_morph_info}, ...]}, a stage per flag in the order run.
 bool morph_file(const std::string &out, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
+// advantra_cli --watershed -i stack (--markers-swc tree.swc [--markers-by tree|node] | --markers FILE.raw) [--relief FILE.raw] --labels OUT.raw
+// [--levels OUT.raw]: the marker-controlled watershed of the stack after the volume set-up of tracing (pnr_watershed on `device`).  The
+// markers are the nodes of the SWC file, each labelled with 1 + the number of its tree in the order of pnr_join_reroot (by_node: with its
+// SWC id, 1 .. 2^31 - 1) -- the voxels per neuron --, or a file of w h l little-endian int32.  relief: w h l bytes (empty: 255 - the
+// volume).  labels: every voxel's label as bare little-endian int32; levels (not empty): the pass heights as bare bytes.  One JSON line
+// {"w", "h", "l", "markers_by": "tree" | "node" | "volume", "n_markers", then the fields of pnr_watershed_info}.
+struct WatershedJob {
+    pnr_watershed_opts opts = {-1, 26};
+    std::string markers_swc, markers_raw, relief, labels, levels;
+    bool by_node = false;
+};
+bool watershed_file(const WatershedJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

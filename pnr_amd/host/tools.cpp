@@ -1,5 +1,5 @@
 // tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc (by gap, or --join-geodesic), --render-swc,
-// --components, --edt, --skeleton, --morph and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+// --components, --edt, --skeleton, --morph, --watershed and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
 #include "host_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -429,6 +429,79 @@ bool morph_file(const std::string &out, const std::vector<char *> &infiles, cons
                (unsigned long long)mi.sum_out, (int)mi.max_delta, (int)mi.connectivity, (long long)mi.tiles, (long long)mi.tile_visits, (int)mi.rounds);
     }
     printf("]}\n");
+    return true;
+}
+
+// `count` elements of T from the file `name`, which holds exactly those: false after a message on stderr
+template <typename T>
+static bool read_volume_file(const std::string &name, size_t count, std::vector<T> &out, const char *what)
+{
+    FILE *f = fopen(name.c_str(), "rb");
+    if (!f) {
+        fprintf(stderr, "%s: cannot read the file\n", name.c_str());
+        return false;
+    }
+    out.resize(count + 1);
+    const size_t got = fread(out.data(), sizeof(T), count + 1, f);
+    const bool bad = ferror(f) != 0 || got != count || !feof(f);
+    fclose(f);
+    out.resize(count);
+    if (bad) fprintf(stderr, "%s: not %s of this stack (%zu values of %zu bytes)\n", name.c_str(), what, count, sizeof(T));
+    return !bad;
+}
+
+bool watershed_file(const WatershedJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    const size_t N = (size_t)(st.w * st.h * st.l);
+    SwcTree T;
+    std::vector<int32_t> label, mvol;
+    std::vector<uint8_t> relief;
+    if (!job.markers_swc.empty()) {
+        if (!read_swc(job.markers_swc, T)) return false;
+        const int64_t n = T.n();
+        if (n == 0) {
+            fprintf(stderr, "%s: no nodes\n", job.markers_swc.c_str());
+            return false;
+        }
+        label.resize((size_t)n);
+        if (job.by_node) {
+            for (int64_t i = 0; i < n; i++) {
+                if (T.id[(size_t)i] < 1 || T.id[(size_t)i] > 0x7fffffffLL) {
+                    fprintf(stderr, "%s: node id %lld is no label (1 .. 2147483647)\n", job.markers_swc.c_str(), T.id[(size_t)i]);
+                    return false;
+                }
+                label[(size_t)i] = (int32_t)T.id[(size_t)i];
+            }
+        } else { // the trees as pnr_join_reroot numbers them: by descending node count, ties by ascending root index
+            if (pnr_join_reroot(T.parent.data(), n, nullptr, 0, -1, nullptr, nullptr, label.data()) != PNR_OK) return lib_fail(job.markers_swc.c_str());
+            for (int32_t &v : label) v += 1;
+        }
+    } else if (!read_volume_file(job.markers_raw, N, mvol, "the int32 marker volume"))
+        return false;
+    if (!job.relief.empty() && !read_volume_file(job.relief, N, relief, "the relief")) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    std::vector<int32_t> L(N);
+    std::vector<uint8_t> M(job.levels.empty() ? 0 : N);
+    pnr_watershed_info wi = {};
+    const bool points = mvol.empty();
+    if (pnr_watershed(ctx, &job.opts, relief.empty() ? nullptr : relief.data(), points ? nullptr : mvol.data(), points ? T.xyz.data() : nullptr,
+                      points ? label.data() : nullptr, points ? T.n() : 0, &wi, L.data(), M.empty() ? nullptr : M.data()) != PNR_OK)
+        return lib_fail("pnr_watershed");
+    // (the hosts this builds for are little-endian)
+    if (!write_file(job.labels, "wb", [&](FILE *f) { fwrite(L.data(), 4, N, f); })) return false;
+    if (!job.levels.empty() && !write_file(job.levels, "wb", [&](FILE *f) { fwrite(M.data(), 1, N, f); })) return false;
+    printf("{\"w\": %lld, \"h\": %lld, \"l\": %lld, \"markers_by\": \"%s\", \"n_markers\": %lld, \"n_vox\": %lld, \"n_mask\": %lld, \"n_marker_vox\": %lld, "
+           "\"n_dropped\": %lld, \"n_reached\": %lld, \"n_unreached\": %lld, \"n_regions\": %lld, \"m_max\": %d, \"d_max\": %d, \"thr_used\": %d, "
+           "\"connectivity\": %d, \"tiles\": %lld, \"flood_visits\": %lld, \"label_visits\": %lld, \"flood_rounds\": %d, \"label_rounds\": %d}\n",
+           (long long)st.w, (long long)st.h, (long long)st.l, !points ? "volume" : job.by_node ? "node" : "tree", points ? (long long)T.n() : (long long)wi.n_marker_vox + wi.n_dropped,
+           (long long)wi.n_vox, (long long)wi.n_mask, (long long)wi.n_marker_vox, (long long)wi.n_dropped, (long long)wi.n_reached, (long long)wi.n_unreached,
+           (long long)wi.n_regions, (int)wi.m_max, (int)wi.d_max, (int)wi.thr_used, (int)wi.connectivity, (long long)wi.tiles, (long long)wi.flood_visits,
+           (long long)wi.label_visits, (int)wi.flood_rounds, (int)wi.label_rounds);
     return true;
 }
 

@@ -190,6 +190,20 @@ class MorphInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
+class WatershedOpts(C.Structure):
+    """pnr_watershed_opts (include/pnr_hip.h): thr -1..255 (-1: the global mean; 0: every voxel is in the mask), connectivity 0 (26), 4, 8, 6 or 26"""
+    _fields_ = [("thr", C.c_int32), ("connectivity", C.c_int32)]
+
+
+class WatershedInfo(C.Structure):
+    """pnr_watershed_info: the exact summary of a watershed (the visits and rounds of the two passes: scheduling, a property of the implementation)"""
+    _fields_ = [(k, C.c_int64) for k in ("n_vox", "n_mask", "n_marker_vox", "n_dropped", "n_reached", "n_unreached", "n_regions", "tiles", "flood_visits", "label_visits")] + [
+        (k, C.c_int32) for k in ("m_max", "d_max", "thr_used", "connectivity", "flood_rounds", "label_rounds")]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 MORPH_OPS = {"dilate": 1, "erode": 2, "fill": 3, "hmax": 4, "hdome": 5}
 
 
@@ -346,6 +360,7 @@ PRODUCT_SIGNATURES = {
     "pnr_join_expand": (_rc, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _pi64, _vp]),
     "pnr_morph_reconstruct": (_rc, [_vp, C.POINTER(MorphOpts), _vp, C.POINTER(MorphInfo), _vp]),
     "pnr_morph_volume": (_rc, [_vp, C.POINTER(MorphOpts), C.POINTER(MorphInfo)]),
+    "pnr_watershed": (_rc, [_vp, C.POINTER(WatershedOpts), _vp, _vp, _vp, _vp, _i64, C.POINTER(WatershedInfo), _vp, _vp]),
     "pnr_frangi": (_rc, [_vp, _pf32, _pf32]),
     "pnr_frangi_slab": (_rc, [_vp, _i64, _i64, _pf32, _pf32]),
     "pnr_quantise_j8": (_rc, [_vp, _f32, _f32]),
@@ -421,6 +436,7 @@ class Context:
         h = C.c_void_p()
         check(self.L.pnr_create(C.byref(params), device, C.byref(h)))
         self.h = h
+        self.device = device
         self.shape = None
         self.window = None  # (lo, hi) of the last 16-bit set_volume
         self._keep = None
@@ -758,6 +774,63 @@ class Context:
         check(self.L.pnr_morph_volume(self.h, C.byref(o), C.byref(info)))
         self._keep = None
         return info.as_dict()
+
+    def watershed(self, markers=None, points=None, labels=None, relief=None, thr=-1, connectivity=26, volume=True, levels=False):
+        """pnr_watershed: the marker-controlled watershed of the context's volume under the rule of include/pnr_hip.h -> (info dict {n_vox,
+        n_mask, n_marker_vox, n_dropped, n_reached, n_unreached, n_regions, tiles, flood_visits, label_visits, m_max, d_max, thr_used,
+        connectivity, flood_rounds, label_rounds}, L int32[l, h, w] or None, M uint8[l, h, w] or None).  The mask is V >= thr (-1: the
+        global mean), the relief `relief` (uint8 of V's size; None: 255 - V).  The markers come in exactly one form: `markers`, an int32
+        volume (> 0: a label, 0: none), or `points`, n x 3 positions (x, y, z) with `labels` (>= 1; None: 1 .. n).  L: the label of every
+        reached voxel, 0 elsewhere; M (levels=True): the pass height at which a voxel joined its region, 0 where none did.  The context
+        and its volume stay as they are."""
+        n = int(np.prod(self.shape))
+        mv = xyz = lab = rel = None
+        if markers is not None:
+            mv = np.ascontiguousarray(markers, np.int32)
+            if mv.size != n:
+                raise ValueError("watershed: a marker volume of %d voxels for a volume of %d" % (mv.size, n))
+        if points is not None:
+            xyz = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+            if xyz is None or len(lab) != len(xyz):
+                raise ValueError("watershed: %d labels for %d points" % (len(lab), len(xyz) if xyz is not None else 0))
+        if relief is not None:
+            rel = np.ascontiguousarray(relief, np.uint8)
+            if rel.size != n:
+                raise ValueError("watershed: a relief of %d voxels for a volume of %d" % (rel.size, n))
+        o = WatershedOpts(int(thr), int(connectivity))
+        info = WatershedInfo()
+        Lv = np.empty(self.shape, np.int32) if volume else None
+        Mv = np.empty(self.shape, np.uint8) if levels else None
+        check(self.L.pnr_watershed(self.h, C.byref(o), rel.ctypes.data if rel is not None else None, mv.ctypes.data if mv is not None else None,
+                                   xyz.ctypes.data if xyz is not None and len(xyz) else None, lab.ctypes.data if lab is not None and len(lab) else None,
+                                   len(xyz) if xyz is not None else 0, C.byref(info), Lv.ctypes.data if volume else None, Mv.ctypes.data if levels else None))
+        return info.as_dict(), Lv, Mv
+
+    def split_touching(self, h, thr=-1, rmax=64, scale=4, connectivity=26):
+        """Touching cells of {V >= thr} parted along their necks: the classical chain distance transform -> extended maxima -> markers ->
+        watershed, each stage one call of this library, the volumes passing through the host between them (four downloads and three
+        uploads of N voxels; a device-resident chain does not exist):
+          1. D2 = distance_transform(thr, rmax);  2. the thickness map Q = min(255, floor(scale * sqrt(D2))) in f32 single operations;
+          3. on a second context of the same device that holds Q: morph_volume("hmax", h), then morph_reconstruct(op="hdome", h=1) -- its
+             voxels > 0 are the extended maxima of Q, the cores that stand at least h above their necks;
+          4. label_components(thr=1, connectivity=26) of those cores: the markers;
+          5. watershed(relief=255 - Q, markers, thr, connectivity) on this context.
+        -> (info dict of the watershed, labels int32[l, h, w], n_cells = the number of markers).  h in 1..255 is in units of Q."""
+        _, d2, _ = self.distance_transform(thr=thr, rmax=rmax)
+        q = np.minimum(np.float32(255), np.floor(np.float32(scale) * np.sqrt(d2, dtype=np.float32), dtype=np.float32)).astype(np.uint8)
+        other = Context(self.p, self.device)
+        try:
+            other.set_volume(q)
+            other.morph_volume("hmax", h=int(h), connectivity=26)
+            _, dome = other.morph_reconstruct(op="hdome", h=1, connectivity=26)
+            other.set_volume(dome)  # (0 or 1)
+            cinfo, markers, _ = other.label_components(thr=1, connectivity=26)
+        finally:
+            other.close()
+        info, lab, _ = self.watershed(markers=markers, relief=(255 - q).astype(np.uint8), thr=thr, connectivity=connectivity)
+        return info, lab, int(cinfo["n_comp"])
 
     def join_trees_geodesic(self, xyz, parent, limit=0, thr=0, step=1, cost=None):
         """pnr_geodesic_bridges of a forest (n x 3 voxel positions, parent indices with a negative value for none) through the context's

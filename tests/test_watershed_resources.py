@@ -1,0 +1,31 @@
+"""CPU (hipcc cross-compiles gfx950 without a GPU): the budgets of the watershed kernels (pnr_amd/csrc/watershed.hip), read from the
+compiler's own resource report with the mechanism of test_kernel_resources.py: every kernel is there exactly once, none uses scratch, and
+the flood -- an LDS-latency-bound relaxation, hidden only by resident waves -- leaves room for at least four waves per SIMD (its 21 KB of
+LDS per 256 threads allow seven).  The occupancy of ws_label is recorded in DESIGN.md, not asserted."""
+import pytest
+from test_kernel_resources import compile_isa
+
+KERNELS = ("ws_init", "ws_compact", "ws_flood", "ws_label", "ws_finish")
+
+
+@pytest.fixture(scope="module")
+def usage(tmp_path_factory):
+    return compile_isa(tmp_path_factory, "watershed.hip")[0]
+
+
+def test_every_watershed_kernel_is_in_the_report(usage):
+    for frag in KERNELS:
+        hit = [k for k in usage if frag in k]
+        assert len(hit) == 1, (frag, sorted(usage))
+    assert len(usage) == len(KERNELS), sorted(usage)
+
+
+def test_no_scratch(usage):
+    assert usage
+    for name, u in usage.items():
+        assert u["ScratchSize"] == 0, (name, u)
+
+
+def test_the_flood_leaves_four_waves_per_simd(usage):
+    hit = [u for name, u in usage.items() if "ws_flood" in name]
+    assert len(hit) == 1 and hit[0]["Occupancy"] >= 4, hit
