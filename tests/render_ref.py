@@ -10,12 +10,14 @@ def radii(radius, rscale=1, radd=0):
     return np.maximum(np.asarray(radius, F).reshape(-1) * F(rscale) + F(radd), F(0))
 
 
-def inside(shape, a, b, ra, rb, zscale=1):
-    """bool[l, h, w]: the voxels of the grid inside the segment (a, b) with the radii (ra, rb); a, b scaled float32[3]"""
+def inside(shape, a, b, ra, rb, zscale=1, origin=(0, 0, 0)):
+    """bool[l, h, w]: the voxels of the grid inside the segment (a, b) with the radii (ra, rb); a, b scaled float32[3].  origin = (z0, y0, x0):
+    the grid is the part of a larger one that starts at this voxel (the voxel coordinates, not the array indices, enter the f32 arithmetic)"""
     l, h, w = shape
-    px = np.arange(w, dtype=F)[None, None, :]
-    py = np.arange(h, dtype=F)[None, :, None]
-    pz = (np.arange(l, dtype=F) * F(zscale))[:, None, None]
+    z0, y0, x0 = origin
+    px = np.arange(x0, x0 + w, dtype=F)[None, None, :]
+    py = np.arange(y0, y0 + h, dtype=F)[None, :, None]
+    pz = (np.arange(z0, z0 + l, dtype=F) * F(zscale))[:, None, None]
     a, b = np.asarray(a, F), np.asarray(b, F)
     ab = b - a
     den = (ab[0] * ab[0] + ab[1] * ab[1]) + ab[2] * ab[2]
@@ -31,15 +33,15 @@ def inside(shape, a, b, ra, rb, zscale=1):
     return d2 <= rt * rt
 
 
-def render(xyz, radius, parent, shape, zscale=1, rscale=1, radd=0):
-    """-> L int32[l, h, w]: 1 + the smallest segment that holds the voxel, 0 for none"""
+def render(xyz, radius, parent, shape, zscale=1, rscale=1, radd=0, origin=(0, 0, 0)):
+    """-> L int32[l, h, w]: 1 + the smallest segment that holds the voxel, 0 for none (origin: see inside())"""
     x = scaled(xyz, zscale)
     rr = radii(radius, rscale, radd)
     parent = np.asarray(parent).reshape(-1)
     L = np.zeros(shape, np.int32)
     for i in range(len(x) - 1, -1, -1):  # descending: the smallest index is written last
         q = i if parent[i] < 0 else int(parent[i])
-        L[inside(shape, x[i], x[q], rr[i], rr[q], zscale)] = i + 1
+        L[inside(shape, x[i], x[q], rr[i], rr[q], zscale, origin)] = i + 1
     return L
 
 

@@ -512,3 +512,53 @@ def test_cli_json_csv_paths_and_raw(tmp_path):
             for j, (f, g) in enumerate(zip(ch, wk)):
                 assert [int(v) for v in f] == [nid + j, 2, g % w, g // w % h, g // (w * h), 1, nid + j + 1 if j + 1 < len(wk) else -1]
             nid += len(wk)
+
+
+# ---- voxel indices above 2^31 ----
+def _two_blocks(shape):
+    """two blocks of passable and impassable voxels in a stack that is background elsewhere (bigvol.geo_case), borrowed from the device, with
+    sources in both (on tile faces, two on one voxel, labels just below 2^31, one on background: dropped), every voxel of both blocks
+    as a target and the walks of five targets per block -> (the smallest index of the far block, the expected result).  A step needs both
+    of its voxels passable and the threshold is 100, so no path leaves a block: D, L, the walks and the counts are those of
+    geodesic_ref.sweeps on the crop around each block, translated; d_max is the larger, max_at its first voxel.  Under the automatic
+    options and with one iteration per visit and one tile per launch."""
+    import bigvol
+    case = bigvol.geo_case(shape)
+    first = bigvol.check_placement(case["blocks"], shape, (TZ, TY, TX))
+    want = bigvol.geo_want(case)
+    reached = want["d"] != ref.UNREACHED
+    t, c = bigvol.open_stack(case["blocks"], shape)
+    try:
+        for iters, per in ((0, 0), (1, 1)):
+            c.set_option("geo_iters", iters)
+            c.set_option("geo_tiles_per_launch", per)
+            info, D, L, at = c.geodesic(case["sources"], case["labels"], thr=case["thr"], volume=False, targets=case["targets"], path_cap=case["path_cap"])
+            assert D is None and L is None
+            assert {k: info[k] for k in bigvol.GEO_INFO} == want["info"], (iters, info, want["info"])
+            assert at["d"].dtype == np.uint32 and np.array_equal(at["d"], want["d"]), (iters, int((at["d"] != want["d"]).sum()))
+            assert at["label"].dtype == np.int32 and np.array_equal(at["label"], want["label"]), (iters, int((at["label"] != want["label"]).sum()))
+            assert np.array_equal(at["path_len"] > 0, reached) and (at["path_len"] >= 0).all()  # every walk is complete: the cap is enough
+            for k, wk in want["paths"].items():
+                assert at["path_len"][k] == want["path_len"][k] and at["paths"][k].dtype == np.int64 and np.array_equal(at["paths"][k], wk), (iters, k)
+    finally:
+        c.set_option("geo_iters", 0)
+        c.set_option("geo_tiles_per_launch", 0)
+        c.close()
+    assert bigvol.untouched(t, case["blocks"])
+    return first, want
+
+
+def test_two_blocks_on_a_small_stack():
+    """the placement of the case below at 96 x 64 x 41, where test_bigvol_host.py restates the whole stack"""
+    import bigvol
+    _two_blocks(bigvol.SMALL)
+
+
+def test_indices_beyond_2_to_31():
+    """2048 x 2048 x 513 voxels (N > 2^31): the u64 key volume, geo_sources' tile flags, the ~index word of geo_stats, geo_sample, int64
+    voxels from geo_paths; the far block is the last plane, in the one-plane partial tile, and holds the stack's last voxel (a source)"""
+    import bigvol
+    first, want = _two_blocks(bigvol.SHAPE)
+    far = [k for k, p in want["paths"].items() if len(p) and p[0] > 2**31]
+    assert first > 2**31 and len(far) >= 3 and all((want["paths"][k] > 2**31).all() for k in far) and max(want["path_len"][k] for k in far) > 3
+    assert want["info"]["n_vox"] == int(np.prod(bigvol.SHAPE, dtype=np.int64)) and want["info"]["n_src_dropped"] == 1 and want["info"]["d_max"] > 0

@@ -459,3 +459,46 @@ def test_cli_tracing_run_with_and_without_the_flag(tmp_path):
     assert [ln for ln in c2 if ln not in c0] == ["#join=geodesic:1,thr:%d,bridges:0,trees:%d->%d,inserted:0" % (thr, winfo["n_trees_in"], winfo["n_trees_in"])] and len(rows2) == n
     # usage: one join or the other
     assert _cli("--join", "0", "--join-geodesic", "0", "-f", "advantra_func", "-i", str(tmp_path / "plain.tif"), "-p", *PARAS).returncode == 1
+
+
+# ---- voxel indices above 2^31 ----
+def _two_blocks(shape):
+    """seven fragments, three in the near and four in the far block of a stack that is background elsewhere (bigvol.join_case), borrowed from the
+    device -> (the bridges of the far block, the expected info).  The threshold is 100 and the background 0, so there is no passable route
+    between the blocks and no meet edge joins them: Kruskal's algorithm over two edge sets that share no tree is the merge by key of
+    its runs on the crops (geojoin_ref.solve), their voxels and nodes translated.  The raster order of a crop's voxels is that of their
+    absolute indices (both lexicographic in z, y, x), so the tie-break (W, p, o) carries over; the far block is uniform and its fragments
+    F1, F2, F3 lie equally far apart, so ties on W decide there.  The fragments of the two blocks alternate in the node order: the tree
+    numbers are those of the whole forest."""
+    import bigvol
+    case = bigvol.join_case(shape)
+    bigvol.check_placement(case["blocks"], shape, (TZ, TY, TX))
+    wb, wvox, winfo, per_block = bigvol.join_want(case)
+    t, c = bigvol.open_stack(case["blocks"], shape)
+    try:
+        bridges, paths, info = c.join_trees_geodesic(case["xyz"], case["parent"], case["limit"], thr=case["thr"])
+    finally:
+        c.close()
+    assert bridges.dtype == lib.GEO_BRIDGE and bridges.tobytes() == wb.astype(lib.GEO_BRIDGE).tobytes(), (bridges, wb)
+    assert paths["vox"].dtype == np.int64 and np.array_equal(paths["vox"], wvox) and paths["shape"] == tuple(shape)
+    assert {k: info[k] for k in bigvol.JOIN_INFO} == winfo, (info, winfo)
+    assert all(i["n_bridges"] >= 1 for i in per_block) and info["n_trees_in"] == 7 and info["n_trees_out"] == 7 - info["n_bridges"] >= 2
+    far = bridges[bridges["p"] >= int(bigvol.index_of(0, 0, shape[0] - 1, shape))]
+    assert len(far) >= 2 and len(set(far["w"].tolist())) < len(far), "a tie on W in the far block"
+    assert bigvol.untouched(t, case["blocks"])
+    return far, winfo
+
+
+def test_two_blocks_on_a_small_stack():
+    """the placement of the case below at 96 x 64 x 41, where test_bigvol_host.py restates the whole stack"""
+    import bigvol
+    _two_blocks(bigvol.SMALL)
+
+
+def test_indices_beyond_2_to_31():
+    """2048 x 2048 x 513 voxels (N > 2^31): the edge key (13 p + (o - 13)) << 22 with 13 p above 2^32, unpacked by the host with e / 13, on top
+    of the geodesic flood's u64 keys; the far block is the last plane, in the one-plane partial tile"""
+    import bigvol
+    far, winfo = _two_blocks(bigvol.SHAPE)
+    assert all(13 * int(p) > 2**32 and int(p) > 2**31 for p in far["p"])
+    assert bigvol.check_placement(bigvol.join_case(bigvol.SHAPE)["blocks"], bigvol.SHAPE, (TZ, TY, TX)) > 2**31

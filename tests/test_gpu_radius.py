@@ -433,3 +433,44 @@ def test_cli_measure_radius(tmp_path, case):
         d_one, d_one_plain = _parse(one)[1], _parse(one_plain)[1]
         assert len(d_one) == len(t1) - 1 and [r[5] for r in d_one] == _column(t1, ctx.measure_radii(xyz1)[0], d_one_plain)
     ctx.close()
+
+
+# ---- voxel indices above 2^31 ----
+def _two_blocks(shape):
+    """balls, slabs and discs in both blocks of a stack that is background elsewhere (bigvol.radius_case), borrowed from the device; positions at
+    their centres and off them, on the far faces and beyond them, and one that is not finite; absolute and relative mode -> the radii.
+    A shell voxel outside the volume is not counted and one inside counts by its value, so the radii are those of radius_ref.measure
+    on crops that reach rmax = 12 beyond every centre, or to the stack's face where that comes first: the far faces of the far crop are the stack's."""
+    import bigvol
+    case = bigvol.radius_case(shape)
+    bigvol.check_placement(case["blocks"], shape, (1, 1, 1))  # (no tiles in this tool: the other placement rules)
+    t, c = bigvol.open_stack(case["blocks"], shape)
+    out = []
+    try:
+        for rel_pct in (0, 50):
+            want = bigvol.radius_want(case, rel_pct)
+            k, thr_used = c.measure_radii(case["xyz"], thr=case["thr"], rel_pct=rel_pct, rmax=bigvol.RAD_RMAX)
+            assert k.dtype == np.int32 and np.array_equal(k, want), (rel_pct, k, want)
+            assert thr_used == (0 if rel_pct else case["thr"]) and (k == -1).sum() == 1 and len(set(k.tolist())) >= 4
+            out.append(k)
+    finally:
+        c.close()
+    assert bigvol.untouched(t, case["blocks"])
+    return case, out
+
+
+def test_two_blocks_on_a_small_stack():
+    """the placement of the case below at 96 x 64 x 41, where test_bigvol_host.py restates the whole stack"""
+    import bigvol
+    _two_blocks(bigvol.SMALL)
+
+
+def test_indices_beyond_2_to_31():
+    """2048 x 2048 x 513 voxels (N > 2^31): rad_measure gathers through voxel_index at the last plane, the shells cut at the three far faces;
+    the far block is the last plane and holds the stack's last voxel, which is one of the positions"""
+    import bigvol
+    l, h, w = bigvol.SHAPE
+    case, (k_abs, k_rel) = _two_blocks(bigvol.SHAPE)
+    assert bigvol.check_placement(case["blocks"], bigvol.SHAPE, (1, 1, 1)) > 2**31
+    far = np.flatnonzero(case["xyz"][:, 2] >= l - 1)
+    assert len(far) >= 5 and (k_abs[far] > 0).sum() >= 2 and (case["xyz"][far] == (w - 1, h - 1, l - 1)).all(1).any()

@@ -354,3 +354,44 @@ def test_cli_mask_and_coverage_while_tracing(tmp_path):
     inside = ((vox >= 0) & (vox < np.array(img.shape[::-1]))).all(1) & (np.abs(xyz - vox).max(1) < 0.25) & (radius >= 1)
     assert inside.sum() > 0 and (mask[vox[inside, 2], vox[inside, 1], vox[inside, 0]] == 255).all()
     assert float(fields["thr"]) == max(1, int(img.astype(np.int64).sum()) // img.size)
+
+
+# ---- voxel indices above 2^31 ----
+def _two_blocks(shape):
+    """a six-node tree with mixed radii (one of 12) in each block of a stack that is background elsewhere (bigvol.render_case), borrowed from the
+    device -> the coverage.  A voxel's label depends on its absolute coordinates and the segments alone (render_ref takes the crop's
+    origin), so the per-node triples and the counts are the sums over two crops that hold every voxel a segment can reach and every
+    foreground voxel: the box of a tree's nodes widened by the largest radius + 2 and the tree's block, cut where the stack cuts them."""
+    import bigvol
+    case = bigvol.render_case(shape)
+    bigvol.check_placement(case["blocks"], shape, (1, 1, 1))  # (no tiles in this tool: the other placement rules)
+    wcov, wvox, wfg, wsum = bigvol.render_want(case)
+    t, c = bigvol.open_stack(case["blocks"], shape)
+    try:
+        cov = c.tree_coverage(case["xyz"], case["radius"], case["parent"], zscale=bigvol.REN_ZS, thr=case["thr"], per_node=True)
+    finally:
+        c.close()
+    assert {k: cov[k] for k in wcov} == wcov, (cov, wcov)
+    for k, v in (("seg_vox", wvox), ("seg_fg", wfg), ("seg_sum", wsum)):
+        assert cov[k].dtype == np.int64 and np.array_equal(cov[k], v), (k, cov[k], v)
+    assert (wvox > 0).sum() >= 8 and wcov["n_both"] > 100 and wcov["n_vox"] == int(np.prod(shape, dtype=np.int64))
+    assert bigvol.untouched(t, case["blocks"])
+    return case, cov
+
+
+def test_two_blocks_on_a_small_stack():
+    """the placement of the case below at 96 x 64 x 41, where test_bigvol_host.py restates the whole stack"""
+    import bigvol
+    _two_blocks(bigvol.SMALL)
+
+
+def test_indices_beyond_2_to_31():
+    """2048 x 2048 x 513 voxels (N > 2^31): rn_scatter's atomics at lab + ((z h + y) w + x), rn_finish over (N + 3) >> 2 groups; the far tree ends
+    beside the stack's last voxel with a radius of 12: its capsule is cut by z = l - 1, y = h - 1 and x = w - 1"""
+    import bigvol
+    l, h, w = bigvol.SHAPE
+    case, cov = _two_blocks(bigvol.SHAPE)
+    assert bigvol.check_placement(case["blocks"], bigvol.SHAPE, (1, 1, 1)) > 2**31 and cov["n_vox"] == l * h * w
+    thick = len(case["xyz"]) - 2
+    (x, y, z), r = case["xyz"][thick], case["radius"][thick]
+    assert x + r > w - 1 and y + r > h - 1 and z * bigvol.REN_ZS + r > (l - 1) * bigvol.REN_ZS and cov["seg_vox"][thick] > 100

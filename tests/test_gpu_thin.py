@@ -239,3 +239,44 @@ def test_cli_skeleton_swc(ctx, tmp_path):
     assert np.array_equal(np.array([f[5] for f in rows], np.float32), np.array([b for _, b in radii], np.float32))
     at = np.array([f[5] for f in rows], np.float32)
     assert par[0] == -1 and at[0] == at.max()  # the first root is the thickest skeleton voxel
+
+
+# ---- voxel indices above 2^31 ----
+def _two_blocks(shape):
+    """two thick objects in a stack that is background elsewhere (bigvol.thin_case), borrowed from the device -> (the smallest index of the far
+    block, info, vox).  Outside the volume is background under the rule, so each block thins like the crop around it on its own, and
+    the crops start at even coordinates, so their voxels keep their subfields: vox and deg are the crops' lists translated and merged
+    in ascending order, the counts their sums, the rounds those of the slowest block."""
+    import bigvol
+    case = bigvol.thin_case(shape)
+    first = bigvol.check_placement(case["blocks"], shape, (TZ, TY, TX))
+    winfo, wvox, wdeg = bigvol.thin_want(case)
+    t, c = bigvol.open_stack(case["blocks"], shape)
+    try:
+        info, skel, vox, deg = c.skeletonize(case["thr"], volume=False, voxels=True)
+    finally:
+        c.close()
+    assert skel is None
+    for k, v in winfo.items():
+        assert info[k] == v, (k, info, winfo)
+    assert vox.dtype == np.int64 and np.array_equal(vox, wvox), (len(vox), len(wvox), vox[:4], wvox[:4])
+    assert deg.dtype == np.uint8 and np.array_equal(deg, wdeg)
+    assert info["tiles"] == tiles_of(shape) and info["rounds"] >= 3 and info["tile_visits"] >= 8 * info["tiles"]
+    assert bigvol.untouched(t, case["blocks"])
+    return first, info, vox
+
+
+def test_two_blocks_on_a_small_stack():
+    """the placement of the case below at 96 x 64 x 41, where test_bigvol_host.py restates the whole stack"""
+    import bigvol
+    _two_blocks(bigvol.SMALL)
+
+
+def test_indices_beyond_2_to_31():
+    """2048 x 2048 x 513 voxels (N > 2^31): 64-bit voxel arithmetic in thin_mark and thin_pass, voxel indices above the sign bit in thin_list,
+    x, y, z recovered from them; the far block is the last plane, in the one-plane partial tile, and holds the stack's last voxel"""
+    import bigvol
+    l, h, w = bigvol.SHAPE
+    first, info, vox = _two_blocks(bigvol.SHAPE)
+    assert first > 2**31 and vox.max() > 2**31 and info["n_vox"] == l * h * w and (vox > 2**31).sum() > 5
+    assert info["tile_visits"] < 9 * info["tiles"]  # after round 1 only the tiles around the blocks are visited

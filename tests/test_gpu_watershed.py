@@ -339,3 +339,53 @@ def test_cli_labels_equal_the_python_call(ctx, tmp_path):
         js = json.loads(r.stdout.strip().splitlines()[-1])
         assert {k: js[k] for k in ref.EXACT} == {k: info[k] for k in ref.EXACT} and (js["w"], js["h"], js["l"]) == (w, h, l) and js["markers_by"] == by
         assert js["n_regions"] == len(set(labels))
+
+
+# ---- voxel indices above 2^31 ----
+def _two_blocks(shape):
+    """the "rand3" content (holes in the mask, three levels of relief, ties everywhere, labels 1..5) and the "adjacent" pair (two markers on
+    either side of a tile face) in both blocks of a stack that is background elsewhere (bigvol.ws_case), borrowed from the device; the
+    markers are points, the relief is 255 - V, for 26 and 6 neighbours -> (the smallest index of the far block, the infos).  The mask is
+    V >= 1 and a key passes between mask voxels only, so no region leaves its block: L and M on the crop around each block are those of
+    ws_ref.run on the crop, L is 0 everywhere else (counted over the whole array), the counts are the sums and the maxima."""
+    import bigvol
+    case = bigvol.ws_case(shape)
+    first = bigvol.check_placement(case["blocks"], shape, (TZ, TY, TX))
+    t, c = bigvol.open_stack(case["blocks"], shape)
+    infos = []
+    try:
+        for conn in (26, 6):
+            winfo, parts = bigvol.ws_want(case, conn)
+            info, L, M = c.watershed(points=case["points"], labels=case["labels"], relief=None, thr=case["thr"], connectivity=conn, volume=True, levels=True)
+            assert {k: info[k] for k in ref.EXACT} == winfo, (conn, info, winfo)
+            assert L.dtype == np.int32 and M.dtype == np.uint8 and L.shape == M.shape == tuple(shape)
+            for (z0, y0, x0), wl, wm in parts:
+                at = (slice(z0, z0 + wl.shape[0]), slice(y0, y0 + wl.shape[1]), slice(x0, x0 + wl.shape[2]))
+                assert np.array_equal(L[at], wl), (conn, (z0, y0, x0), int((L[at] != wl).sum()), np.argwhere(L[at] != wl)[:4].tolist())
+                assert np.array_equal(M[at], wm), (conn, (z0, y0, x0), int((M[at] != wm).sum()), np.argwhere(M[at] != wm)[:4].tolist())
+            assert np.count_nonzero(L) == winfo["n_reached"] and np.count_nonzero(M) == sum(np.count_nonzero(wm) for _, _, wm in parts)  # no stray store
+            assert info["flood_rounds"] >= 1 and info["label_rounds"] >= 1 and min(info["flood_visits"], info["label_visits"]) >= info["tiles"]
+            infos.append(info)
+            del L, M
+    finally:
+        c.close()
+    assert bigvol.untouched(t, case["blocks"])
+    return first, infos
+
+
+def test_two_blocks_on_a_small_stack():
+    """the placement of the case below at 96 x 64 x 41, where test_bigvol_host.py restates the whole stack"""
+    import bigvol
+    _two_blocks(bigvol.SMALL)
+
+
+def test_indices_beyond_2_to_31():
+    """2048 x 2048 x 513 voxels (N > 2^31): ws_init's indices and marker list, the stores of both relaxations, ws_finish's statistics; the far
+    block is the last plane, in the one-plane partial tile, and holds the stack's last voxel.  Round 1 of either pass lists every tile,
+    more than the 2^20 of an automatic launch, so the cut launches run.  The one test here that downloads whole volumes (L and M)."""
+    import bigvol
+    l, h, w = bigvol.SHAPE
+    first, infos = _two_blocks(bigvol.SHAPE)
+    assert first > 2**31
+    for info in infos:
+        assert info["tiles"] == -(-l // TZ) * -(-h // TY) * -(-w // TX) and info["flood_visits"] >= info["tiles"] > 2**20 and info["n_vox"] == l * h * w
