@@ -939,6 +939,74 @@ int pnr_watershed(pnr_ctx *ctx, const pnr_watershed_opts *opts, const uint8_t *r
                   const float *src_xyz /* n_src x 3, or NULL */, const int32_t *src_label /* n_src, nullable */, int64_t n_src,
                   pnr_watershed_info *info /* nullable */, int32_t *label_out /* N, host, nullable */, uint8_t *level_out /* N, host, nullable */);
 
+/* Automatic thresholds from the histogram of the context's u8 volume V (threshold.hip), and a local threshold.
+ *
+ * The rule (restated in numpy by tests/threshold_ref.py; every value below is exact):
+ *   H[v], v = 0..255: the number of voxels with value v, in u64.  lo in 0..255 picks the counted bins [lo, 255] (lo = 1 ignores the
+ *   zeros a top-hat, a despeckle or a residual leave).  n = sum H[v], S = sum v H[v] over the counted bins.  Every method yields `raw`;
+ *   thr = min(255, max(raw, lo, 1)), so zero is never foreground.  n == 0: thr = 255, n_counted = 0, PNR_OK.
+ *   PNR_THR_MEAN: raw = S div n (lo = 0: the rule "thr = -1" of the tools).
+ *   PNR_THR_OTSU: for t = lo + 1 .. 255 class 0 is the bins [lo, t), class 1 the bins [t, 255], with counts n0, n1 and sums S0, S1; t is
+ *     valid when n0 > 0 and n1 > 0.  In IEEE double, in this order, no contraction: w0 = (double)n0, w1 = (double)n1,
+ *     d = (double)S1 / w1 - (double)S0 / w0, score = ((w0 * w1) * d) * d (the conversions are exact: fewer than 2^45 voxels).  raw = the
+ *     smallest valid t with the largest score; no valid t (one non-empty bin b): raw = b.
+ *   PNR_THR_TRIANGLE (the bright side: bright on dark): p = the smallest counted v with the largest H, e = the largest counted v with
+ *     H > 0.  e - p < 2: raw = e.  Else, for b = p + 1 .. e - 1 in signed 64-bit, g(b) = (H[p] - H[e]) (e - b) + (H[e] - H[b]) (e - p)
+ *     ((e - p) times the height of the chord from the peak to the end above the histogram at b); raw = b* + 1 for the smallest b* with
+ *     the largest g.
+ *   PNR_THR_TOP (the brightest share), top_ppm in 1..999999: k = floor(n top_ppm / 10^6); raw = the smallest t in [lo, 255] with
+ *     sum_{v >= t} H[v] <= k; none: raw = 255.
+ *   PNR_THR_MAXENTROPY: the reference's maxentropy_th (toolbox.cpp:657-737) on H, the function pnr_soma thresholds with; it needs lo == 0
+ *     and every bin below 2^31 (the reference's int hist[]), else PNR_E_ARG.  Parity as for the soma path: pinned on the oracle's
+ *     restatement.
+ *
+ * pnr_threshold_from_hist: the rule and nothing else; pure host, no context.  Arguments (anything else: PNR_E_ARG): hist, opts and info
+ *   non-NULL, method in 0..4, lo in 0..255, top_ppm in 1..999999 for PNR_THR_TOP and 0 otherwise, fewer than 2^45 voxels in all.
+ *   info: thr, method, lo; n_vox (all bins), n_counted = n, sum_counted = S; v_min, v_max (the smallest and largest counted v with
+ *   H > 0) and peak (p above), -1 each when n == 0; n_fg = the voxels >= thr over all bins.
+ * pnr_auto_threshold: the histogram of the context's volume on its stream (one read of N bytes; kernel time group "threshold"), then the
+ *   function above.  hist_out (nullable): the 256 counts.  No volume in the context: PNR_E_STATE.  The context is left as it is; V is
+ *   never written; the 2 KiB of device bins are freed before the call returns.
+ *
+ * The local threshold, pnr_local_opts {r, offset, scale_256, floor, binary}:
+ *   the box is the top-hat's: rx = ry = r, rz = (int)((float)r / zd) with one f32 division, zd = params.zdist (only dz = 0 when l == 1).
+ *   B(p) = the box around p cut to the volume, n(p) = |B(p)|, S(p) = the sum of V over B(p).  keep(p) iff V(p) >= floor and
+ *   256 n(p) V(p) >= scale_256 S(p) + 256 offset n(p) in signed 64-bit; out(p) = keep ? (binary ? 255 : V(p)) : 0.  A box larger than
+ *   the stack is legal.  Arguments (anything else: PNR_E_ARG): opts non-NULL, r in 1..PNR_LOCAL_MAX_R, offset in -255..255, scale_256 in
+ *   0..4096, floor in 1..255, binary in {0, 1}.  No volume in the context: PNR_E_STATE.
+ * pnr_local_threshold: out (N host bytes, nullable) receives the result; the context and its volume stay as they are.
+ * pnr_local_threshold_volume: the result becomes the context's volume under the contract of pnr_filter_volume: an owned buffer, a
+ *   borrowed device volume is never written (it is released), the later pipeline state is invalidated, and on any failure the context
+ *   still holds the old volume.
+ *   info (nullable) of both: n_vox = N, n_kept (voxels with keep), sum_in and sum_out (the sums of V and of out), rx, ry, rz.  All
+ *   indices are 64-bit.  Device memory of a call beyond the N bytes of the result: (6 s + 10 rz + 8) w h bytes for slabs of
+ *   s = max(1, min(l, 2^24 / (w h))) planes (threshold.h), freed before the call returns (PNR_E_NOMEM: an allocation failed).  Kernel
+ *   time group "local_threshold".  pnr_set_option "lt_slab_vox" (0 = automatic: 2^24) changes no bit: tests reach slab boundaries on
+ *   small stacks with it. */
+enum { PNR_THR_MEAN = 0, PNR_THR_OTSU = 1, PNR_THR_TRIANGLE = 2, PNR_THR_TOP = 3, PNR_THR_MAXENTROPY = 4 };
+typedef struct pnr_threshold_opts {
+    int32_t method, lo, top_ppm, pad;
+} pnr_threshold_opts;
+typedef struct pnr_threshold_info {
+    int64_t n_vox, n_counted;
+    uint64_t sum_counted;
+    int64_t n_fg;
+    int32_t thr, method, lo, v_min, v_max, peak;
+} pnr_threshold_info;
+int pnr_threshold_from_hist(const uint64_t hist[256], const pnr_threshold_opts *opts, pnr_threshold_info *info);
+int pnr_auto_threshold(pnr_ctx *ctx, const pnr_threshold_opts *opts, pnr_threshold_info *info, uint64_t *hist_out /* 256, nullable */);
+#define PNR_LOCAL_MAX_R 64
+typedef struct pnr_local_opts {
+    int32_t r, offset, scale_256, floor, binary, pad;
+} pnr_local_opts;
+typedef struct pnr_local_info {
+    int64_t n_vox, n_kept;
+    uint64_t sum_in, sum_out;
+    int32_t rx, ry, rz, pad;
+} pnr_local_info;
+int pnr_local_threshold(pnr_ctx *ctx, const pnr_local_opts *opts, pnr_local_info *info /* nullable */, uint8_t *out /* N, host, nullable */);
+int pnr_local_threshold_volume(pnr_ctx *ctx, const pnr_local_opts *opts, pnr_local_info *info /* nullable */);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -969,6 +1037,7 @@ int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
  *   geo_iters, geo_tiles_per_launch (0 = automatic) of pnr_geodesic_distance and geojoin_tiles_per_launch (0 = automatic: 2^20) tiles per launch of a sweep of pnr_geodesic_bridges (the same bits) |
  *   morph_iters, morph_tiles_per_launch (0 = automatic) of pnr_morph_reconstruct / pnr_morph_volume: the same two for its relaxation (the same bits) |
  *   ws_iters, ws_tiles_per_launch (0 = automatic) of pnr_watershed: the same two for both of its passes (the same bits) |
+ *   lt_slab_vox (0 = automatic: 2^24) voxels per slab of whole planes of pnr_local_threshold / pnr_local_threshold_volume (the same bits -- tests reach slab boundaries with it on small stacks) |
  *   tentative (1) the streaming scheduler pauses traces that a tentative replay of everything recorded so far cuts, and ends them
  *   itself once that verdict is final (fewer wasted SMC iterations; same graph).
  *   pnr_get_option also knows "join_rounds" (the nearest-other passes of the last pnr_join_trees), "render_items" / "render_pairs" (the last render), "geo_rounds" / "geo_visits", "geojoin_rounds", "morph_rounds" / "morph_visits", "ws_rounds" / "ws_visits" (the last call of that tool), "host_threads_effective" and "frangi_recomputes" (how often pnr_get_frangi / pnr_quantise_j8 had to
@@ -978,7 +1047,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish"),"watershed" (pnr_watershed: the sum of "watershed_init", "watershed_compact", "watershed_flood", "watershed_label" and "watershed_finish").  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish"),"watershed" (pnr_watershed: the sum of "watershed_init", "watershed_compact", "watershed_flood", "watershed_label" and "watershed_finish"),"threshold" (pnr_auto_threshold: the histogram),"local_threshold" (pnr_local_threshold / pnr_local_threshold_volume: the three passes of every slab).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

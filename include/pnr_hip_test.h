@@ -157,6 +157,15 @@ int pnr_render_items(const float *xyz, const float *radius, const int32_t *paren
  * pass classic TIFF's 4 GiB is refused from the dimensions alone (PNR_E_ARG, nothing is written; img may then be NULL). */
 int pnr_test_write_tiff(const char *path, const uint8_t *img, int64_t w, int64_t h, int64_t l);
 
+/* The kernels behind pnr_auto_threshold and pnr_local_threshold on bytes of any size, also below the 2 x 2 x 1 a context takes as its
+ * volume (threshold.hip).  pnr_test_histogram: hist[256] = the histogram of the n host bytes (1 to 2^32), copied to device memory `offset`
+ * (0..15) bytes past a 16-byte boundary.  pnr_test_local_threshold: the rule of pnr_local_threshold on the host volume vol (w x h x l, sides
+ * from 1, x fastest; zdist is the context's) into out (w h l host bytes); opts as there.  The context's own volume is neither needed nor
+ * touched. */
+int pnr_test_histogram(pnr_ctx *ctx, const uint8_t *bytes, int64_t n, int32_t offset, uint64_t *hist);
+int pnr_test_local_threshold(pnr_ctx *ctx, const uint8_t *vol, int64_t w, int64_t h, int64_t l, const pnr_local_opts *opts, pnr_local_info *info /* nullable */,
+                             uint8_t *out);
+
 /* Bytes of device and of pinned host memory the library holds at this moment, over all contexts and exchanges of the process
  * (every allocation goes through one owner type that counts them); either pointer may be NULL. */
 int pnr_live_bytes(int64_t *device, int64_t *pinned);

@@ -324,6 +324,7 @@ const OptEntry OPTS[] = {
     {"geojoin_tiles_per_launch", &pnr::Options::geojoin_tiles_per_launch, nullptr, 0, 1 << 24},
     {"morph_iters", &pnr::Options::morph_iters, nullptr, 0, 1 << 16}, {"morph_tiles_per_launch", &pnr::Options::morph_tiles_per_launch, nullptr, 0, 1 << 24},
     {"ws_iters", &pnr::Options::ws_iters, nullptr, 0, 1 << 16}, {"ws_tiles_per_launch", &pnr::Options::ws_tiles_per_launch, nullptr, 0, 1 << 24},
+    {"lt_slab_vox", nullptr, &pnr::Options::lt_slab_vox, 0, 1ll << 40},
 };
 // what pnr_get_option reads besides: counters the calls leave in the context
 struct Counter { const char *key; int64_t pnr_ctx::*count; };

@@ -1,5 +1,5 @@
 // api_tools.cpp -- the extern "C" boundary of libpnr_hip.so (include/pnr_hip.h), third part: the tools on the volume (filter, components,
-// distance transform, skeleton, geodesic distance, morphological reconstruction, watershed, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
+// distance transform, skeleton, geodesic distance, morphological reconstruction, watershed, thresholds, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
 // taps (include/pnr_hip_test.h).  An entry point checks its arguments first, then the state (args.h holds the shared rules), and hands
 // over to the tool's own file; no tool needs or touches the pipeline state of the context (Frangi, seeds, graph).
 #include "args.h"
@@ -17,6 +17,7 @@
 #include "geojoin.h"
 #include "morph.h"
 #include "watershed.h"
+#include "threshold.h"
 #include "../host/stack_io.h"
 
 namespace args = pnr::args;
@@ -191,6 +192,84 @@ int pnr_watershed(pnr_ctx *c, const pnr_watershed_opts *opts, const uint8_t *rel
         n_pos += marker_vol[i] > 0;
     }
     return pnr_watershed_run(c, who, o, relief, pnr_ws_markers{marker_vol, n_pos, src_xyz, src_label, n_src}, info, label_out, level_out);
+}
+
+// ---- thresholds (threshold_rule.cpp, threshold.hip): the rule checks its own arguments; then the state and the device ----
+int pnr_threshold_from_hist(const uint64_t *hist, const pnr_threshold_opts *opts, pnr_threshold_info *info)
+{
+    return pnr::threshold_rule("pnr_threshold_from_hist", hist, opts, info);
+}
+
+int pnr_auto_threshold(pnr_ctx *c, const pnr_threshold_opts *opts, pnr_threshold_info *info, uint64_t *hist_out)
+{
+    static const char *who = "pnr_auto_threshold";
+    PNR_REQUIRE(c && opts && info, PNR_E_ARG, "null argument");
+    uint64_t hist[256] = {0};
+    pnr_threshold_info dry;
+    PNR_TRY(pnr::threshold_rule(who, hist, opts, &dry)); // (the arguments, before any work)
+    PNR_TRY(args::volume_set(c, who));
+    PNR_HIP(hipSetDevice(c->device));
+    PNR_TRY(pnr_hist_run(c, who, "threshold", c->d_img, c->N, hist));
+    PNR_TRY(pnr::threshold_rule(who, hist, opts, info));
+    if (hist_out) std::copy(hist, hist + 256, hist_out);
+    return PNR_OK;
+}
+
+static int local_args(pnr_ctx *c, const char *who, const pnr_local_opts *opts, bool need_volume = true)
+{
+    PNR_REQUIRE(c && opts, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(opts->r >= 1 && opts->r <= PNR_LOCAL_MAX_R, PNR_E_ARG, "%s: r = %d outside [1, %d]", who, opts->r, PNR_LOCAL_MAX_R);
+    PNR_REQUIRE(opts->offset >= -255 && opts->offset <= 255, PNR_E_ARG, "%s: offset = %d outside [-255, 255]", who, opts->offset);
+    PNR_REQUIRE(opts->scale_256 >= 0 && opts->scale_256 <= 4096, PNR_E_ARG, "%s: scale_256 = %d outside [0, 4096]", who, opts->scale_256);
+    PNR_REQUIRE(opts->floor >= 1 && opts->floor <= 255, PNR_E_ARG, "%s: floor = %d outside [1, 255]", who, opts->floor);
+    PNR_REQUIRE(opts->binary == 0 || opts->binary == 1, PNR_E_ARG, "%s: binary = %d, not 0 or 1", who, opts->binary);
+    if (need_volume) PNR_TRY(args::volume_set(c, who));
+    PNR_HIP(hipSetDevice(c->device));
+    return PNR_OK;
+}
+
+int pnr_local_threshold(pnr_ctx *c, const pnr_local_opts *opts, pnr_local_info *info, uint8_t *out)
+{
+    static const char *who = "pnr_local_threshold";
+    PNR_TRY(local_args(c, who, opts));
+    return pnr_local_run(c, who, pnr_local_vol_of(c), *opts, info, out, nullptr);
+}
+
+int pnr_local_threshold_volume(pnr_ctx *c, const pnr_local_opts *opts, pnr_local_info *info)
+{
+    static const char *who = "pnr_local_threshold_volume";
+    PNR_TRY(local_args(c, who, opts));
+    pnr::DevBuf<uint8_t> out;
+    const int rc = pnr_local_run(c, who, pnr_local_vol_of(c), *opts, info, nullptr, &out);
+    if (!rc) pnr::replace_volume(c, std::move(out));
+    return rc;
+}
+
+// test taps (pnr_hip_test.h): the two kernels' entry points on bytes of any size, also below the 2 x 2 x 1 a context takes as its volume
+int pnr_test_histogram(pnr_ctx *c, const uint8_t *bytes, int64_t n, int32_t offset, uint64_t *hist)
+{
+    static const char *who = "pnr_test_histogram";
+    PNR_REQUIRE(c && bytes && hist, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(n >= 1 && n <= (1LL << 32) && offset >= 0 && offset <= 15, PNR_E_ARG, "%s: n = %lld bytes (1 to 2^32) at offset %d (0 to 15)", who, (long long)n, offset);
+    PNR_HIP(hipSetDevice(c->device));
+    pnr::DevBuf<uint8_t> buf;
+    PNR_TRY(pnr::dev_alloc(buf, (size_t)n + 16, who));
+    uint8_t *V = buf.get() + ((16 - ((uintptr_t)buf.get() & 15)) & 15) + offset; // `offset` bytes past a 16-byte boundary
+    PNR_HIP(hipMemcpy(V, bytes, (size_t)n, hipMemcpyHostToDevice));
+    return pnr_hist_run(c, who, "threshold", V, n, hist);
+}
+
+int pnr_test_local_threshold(pnr_ctx *c, const uint8_t *vol, int64_t w, int64_t h, int64_t l, const pnr_local_opts *opts, pnr_local_info *info, uint8_t *out)
+{
+    static const char *who = "pnr_test_local_threshold";
+    PNR_REQUIRE(vol && out, PNR_E_ARG, "null argument");
+    PNR_REQUIRE(w >= 1 && h >= 1 && l >= 1 && w <= 1 << 20 && h <= 1 << 20 && l <= 1 << 20 && w * h * l <= (1LL << 32), PNR_E_ARG, "%s: volume %lld x %lld x %lld", who, (long long)w,
+                (long long)h, (long long)l);
+    PNR_TRY(local_args(c, who, opts, false));
+    pnr::DevBuf<uint8_t> buf;
+    PNR_TRY(pnr::dev_alloc(buf, (size_t)(w * h * l), who));
+    PNR_HIP(hipMemcpy(buf.get(), vol, (size_t)(w * h * l), hipMemcpyHostToDevice));
+    return pnr_local_run(c, who, pnr_local_vol{buf.get(), w, h, l}, *opts, info, out, nullptr);
 }
 
 // pnr_measure_radii: arguments first, then the state; the pipeline state of the context (Frangi, seeds, graph) is neither needed nor touched

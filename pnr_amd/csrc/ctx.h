@@ -116,6 +116,7 @@ struct Options {
     int morph_tiles_per_launch = 0; // tiles per morph_relax launch (0: automatic, 2^20); neither changes a result: tests reach the re-queue path and launch cuts with them
     int ws_iters = 0;           // pnr_watershed (watershed.hip): LDS iterations per tile visit of both passes (0: automatic, 64; 1: a tile that changed re-queues itself), and
     int ws_tiles_per_launch = 0; // tiles per ws_flood / ws_label launch (0: automatic, 2^20); neither changes a result: tests reach the re-queue path and launch cuts with them
+    int64_t lt_slab_vox = 0;    // pnr_local_threshold[_volume] (threshold.hip): voxels per slab of whole planes (0: automatic, 2^24); changes no result: tests reach slab boundaries with it
     int64_t exchange_block = 0; // bytes per rank and exchange of the sharded tracer; 0 = automatic (256 KB / world, at least 32 KB)
 };
 int host_threads(const Options &o); // worker threads to use on this host

@@ -1,6 +1,6 @@
 // grid.h -- the rules the volume tools share, each written once: the centre voxel of a position (the radius rule of include/pnr_hip.h),
 // a tile's place and a voxel's linear index, the host scan of the chunk counts of a raster-order compaction, and the size of a
-// grid-stride launch.  Users: radius, edt, geodesic, geojoin, components, thin, render, volume.  Small inline functions.
+// grid-stride launch.  Users: radius, edt, geodesic, geojoin, components, thin, render, volume, threshold.  Small inline functions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>

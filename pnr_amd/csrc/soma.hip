@@ -14,6 +14,7 @@
 // as "saturated" into the GPU density map -- by the trace kernels' early stop.
 #include "call.h"
 #include "replay.h"
+#include "threshold.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -126,44 +127,6 @@ __global__ __launch_bounds__(64) void row_compact(const unsigned char *__restric
         if (f) vox[o + __popcll(m & ((1ull << threadIdx.x) - 1ull))] = row * w + x;
         o += __popcll(m);
     }
-}
-
-// toolbox.cpp:657-737 on the histogram
-unsigned char maxentropy_from_hist(const unsigned long long *h)
-{
-    float sum = 0;
-    for (int i = 0; i < 256; i++) sum += (float)(int)h[i]; // `int hist[]` added into a float
-    float nh[256], pT[256], hB[256], hW[256];
-    for (int i = 0; i < 256; i++) nh[i] = (float)(int)h[i] / sum;
-    pT[0] = nh[0];
-    for (int i = 1; i < 256; i++) pT[i] = pT[i - 1] + nh[i];
-    const float eps = FLT_MIN;
-    for (int t = 0; t < 256; t++) {
-        if (pT[t] > eps) {
-            float hh = 0;
-            for (int i = 0; i <= t; i++)
-                if (nh[i] > eps) hh -= nh[i] / pT[t] * std::log(nh[i] / pT[t]); // float overload
-            hB[t] = hh;
-        } else {
-            hB[t] = 0;
-        }
-        const double pTW = 1 - pT[t];
-        if (pTW > eps) {
-            float hh = 0;
-            for (int i = t + 1; i < 256; i++)
-                if (nh[i] > eps) hh = (float)((double)hh - nh[i] / pTW * std::log(nh[i] / pTW));
-            hW[t] = hh;
-        } else {
-            hW[t] = 0;
-        }
-    }
-    float jMax = hB[0] + hW[0];
-    unsigned char tMax = 0;
-    for (int t = 1; t < 256; t++) {
-        const double j = hB[t] + hW[t];
-        if (j > jMax) { jMax = (float)j; tMax = (unsigned char)t; }
-    }
-    return tMax;
 }
 
 // conn3d (toolbox.cpp:245-509) with diagonal = true, valuesOverDouble = 0, minRegSize = 1 on the binarised stack: every
@@ -285,7 +248,7 @@ int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold)
     call.down(hist, d_hist);
     if (E8_out) call.down(E8_out, d_E, (size_t)n);
     if ((rc = call.finish())) return rc;
-    const int th = maxentropy_from_hist(hist);
+    const int th = pnr::maxentropy_from_hist(hist); // (threshold_rule.cpp: shared with PNR_THR_MAXENTROPY)
     if (threshold) *threshold = th;
     call.launch(row_count, dim3((unsigned)rows), dim3(64), (const unsigned char *)d_E, w, th, d_cnt.get());
     std::vector<int> cnt((size_t)rows);

@@ -18,12 +18,12 @@
 #include "volume.h"
 #include "call.h"
 #include "grid.h"
+#include "hist.h"
 
 namespace {
 
 constexpr int TPB = 256;            // threads of the min / max and the map kernels
-constexpr int HTPB = 1024;          // threads of a histogram work-group
-constexpr int HWAVES = HTPB / 64;   // ... one private LDS copy of the bins per wave
+constexpr int HTPB = pnr::HIST_TPB;  // threads of a histogram work-group (hist.h)
 using pnr::MAX_BLOCKS;
 constexpr int MAX_HBLOCKS = 512;
 
@@ -77,12 +77,6 @@ __device__ __forceinline__ unsigned wave_max(unsigned x)
     return x;
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned x)
-{
-    for (int d = 32; d >= 1; d >>= 1) x += (unsigned)__shfl_xor((int)x, d, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(TPB) void vol_minmax(Src s, VolState *st)
 {
     __shared__ unsigned part[2][TPB / 64];
@@ -100,30 +94,11 @@ __global__ __launch_bounds__(TPB) void vol_minmax(Src s, VolState *st)
     }
 }
 
-// key(v) -> bin in [0, NB) or -1 (not counted); hot: the bin counted in registers
+// the histogram of hist.h over the channel's samples
 template <int NB, class K>
 __device__ __forceinline__ void histogram(const Src &s, K &&key, int hot, unsigned long long *out)
 {
-    __shared__ unsigned h[HWAVES][NB];
-    for (int k = threadIdx.x; k < HWAVES * NB; k += HTPB) (&h[0][0])[k] = 0;
-    __syncthreads();
-    const int w = threadIdx.x >> 6;
-    unsigned nhot = 0;
-    visit(s, [&](unsigned v) {
-        const int b = key(v);
-        if (b == hot) nhot++;
-        else if (b >= 0) atomicAdd(&h[w][b], 1u);
-    });
-    if (hot >= 0) {
-        nhot = wave_sum(nhot);
-        if ((threadIdx.x & 63) == 0) atomicAdd(&h[w][hot], nhot);
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < NB; b += HTPB) {
-        unsigned long long t = 0;
-        for (int k = 0; k < HWAVES; k++) t += h[k][b];
-        if (t) atomicAdd(&out[b], t);
-    }
+    pnr::histogram<NB>([&](auto &&f) { visit(s, f); }, key, hot, out);
 }
 
 __global__ __launch_bounds__(HTPB) void vol_hist_coarse(Src s, VolState *st)

@@ -61,6 +61,13 @@
 //   #morph=fill:<2d|3d|off>,hmax:<H|off>,hdome:<H|off> behind #filter --, --skeleton, --components, --edt, --geodesic, --render-swc and
 //   --join-swc --join-geodesic.  --morph -i stack [those flags] --morph-out OUT.tif|.raw: the resulting stack and one JSON line with the
 //   fields of pnr_morph_info of each stage run.
+//   --local-threshold R[,OFFSET[,SCALE_256]] [--local-binary]: the next step of the volume set-up, after --fill-holes / --hmax / --hdome and before
+//   --despeckle, on every rank and in every tool mode that takes the set-up: the local threshold of pnr_local_threshold_volume (floor 1); the
+//   comment block gains #local=r:R,offset:C,scale:K,kept:N behind #morph.
+//   --auto-threshold -i stack [--threshold-lo LO] [--histogram FILE.csv]: one JSON line with thr and n_fg of mean, otsu, triangle, maxentropy
+//   and top1 from one histogram pass on the GPU (pnr_auto_threshold); --histogram writes `v,count`.
+//   Every flag that takes "T or -1" (--threshold, --coverage-threshold, --radius-threshold, --join-threshold, the THR of --despeckle) also
+//   takes mean|otsu|triangle|maxentropy|topP[:LO]; the tool's JSON line or SWC comment then gains thr_method.
 //   --watershed -i stack (--markers-swc tree.swc [--markers-by tree|node] | --markers FILE.raw) [--relief FILE.raw] [--threshold T]
 //   [--connectivity 4|8|6|26] --labels OUT.raw [--levels OUT.raw]: the marker-controlled watershed of the stack after the same volume set-up
 //   (pnr_watershed): the label volume, with --markers-by tree the voxels per traced neuron, and one JSON line with the fields of
@@ -129,6 +136,15 @@ static bool parse_int(const char *txt, long lo, long hi, long &out)
     return true;
 }
 
+// "T or -1", or a threshold word (advantra_host.h ThrWord): the word leaves -1 in `out` until it is resolved on the volume
+static bool parse_thr(const char *txt, long &out, advantra::ThrWord &word)
+{
+    if (parse_int(txt, -1, 255, out)) return true;
+    if (!advantra::parse_threshold_word(txt, word)) return false;
+    out = -1;
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     std::vector<char *> infiles, paras;
@@ -162,6 +178,9 @@ int main(int argc, char **argv)
     bool skeleton = false, skel_flag = false;
     bool morph = false;
     std::string morph_out;
+    bool auto_thr = false, auto_flag = false;
+    int auto_lo = 0;
+    std::string auto_hist;
     advantra::WatershedJob ws_job;
     bool ws = false, ws_flag = false, ws_by_flag = false, conn_planar = false, comp_only_flag = false; // (--min-size, --per-component: of --components alone)
     advantra::Settings &S0 = advantra::settings();
@@ -244,7 +263,7 @@ int main(int argc, char **argv)
         }
         if (!strcmp(argv[i], "--threshold")) {
             long v = 0;
-            if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+            if (!parse_thr(i + 1 < argc ? argv[++i] : "", v, S0.thr_word)) { fprintf(stderr, "--threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
             comp.opts.thr = edt_job.opts.thr = geo_job.opts.thr = skel_job.opts.thr = ws_job.opts.thr = (int32_t)v;
             thr_flag = true;
             continue;
@@ -284,7 +303,7 @@ int main(int argc, char **argv)
                 else part.back() += ch;
             }
             long m = 0, t = -1, cn = 26;
-            if (part.size() > 3 || !parse_int(part[0].c_str(), 1, 0x7fffffffffffffffL, m) || (part.size() > 1 && !parse_int(part[1].c_str(), -1, 255, t)) ||
+            if (part.size() > 3 || !parse_int(part[0].c_str(), 1, 0x7fffffffffffffffL, m) || (part.size() > 1 && !parse_thr(part[1].c_str(), t, S0.despeckle_word)) ||
                 (part.size() > 2 && (!parse_int(part[2].c_str(), 6, 26, cn) || (cn != 6 && cn != 26)))) {
                 fprintf(stderr, "--despeckle MIN[,THR[,CONN]]: MIN an integer from 1, THR 0..255 or -1 for the stack's mean, CONN 6 or 26\n");
                 return 1;
@@ -366,7 +385,7 @@ int main(int argc, char **argv)
         }
         if (!strcmp(argv[i], "--join-threshold")) {
             long v = 0;
-            if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--join-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+            if (!parse_thr(i + 1 < argc ? argv[++i] : "", v, S0.join_word)) { fprintf(stderr, "--join-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
             join_thr = (int)v;
             join_thr_flag = true;
             continue;
@@ -415,7 +434,7 @@ int main(int argc, char **argv)
         }
         if (!strcmp(argv[i], "--coverage-threshold")) {
             long v = 0;
-            if (!parse_int(i + 1 < argc ? argv[++i] : "", -1, 255, v)) { fprintf(stderr, "--coverage-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+            if (!parse_thr(i + 1 < argc ? argv[++i] : "", v, S0.coverage_word)) { fprintf(stderr, "--coverage-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
             render.opts.thr = (int32_t)v;
             render_flag = true;
             continue;
@@ -449,6 +468,37 @@ int main(int argc, char **argv)
             (dome ? S0.hdome : S0.hmax) = (int)v;
             continue;
         }
+        if (!strcmp(argv[i], "--local-threshold")) {
+            const std::string txt = i + 1 < argc ? argv[++i] : "";
+            std::vector<std::string> part(1);
+            for (char ch : txt) {
+                if (ch == ',') part.emplace_back();
+                else part.back() += ch;
+            }
+            long r = 0, off = 0, sc = 256;
+            if (part.size() > 3 || !parse_int(part[0].c_str(), 1, PNR_LOCAL_MAX_R, r) || (part.size() > 1 && !parse_int(part[1].c_str(), -255, 255, off)) ||
+                (part.size() > 2 && !parse_int(part[2].c_str(), 0, 4096, sc))) {
+                fprintf(stderr, "--local-threshold R[,OFFSET[,SCALE_256]]: R an integer from 1 to %d, OFFSET -255..255, SCALE_256 0..4096\n", PNR_LOCAL_MAX_R);
+                return 1;
+            }
+            S0.local.r = (int32_t)r, S0.local.offset = (int32_t)off, S0.local.scale_256 = (int32_t)sc;
+            continue;
+        }
+        if (!strcmp(argv[i], "--local-binary")) { S0.local.binary = 1; continue; }
+        if (!strcmp(argv[i], "--auto-threshold")) { auto_thr = true; continue; }
+        if (!strcmp(argv[i], "--threshold-lo")) {
+            long v = 0;
+            if (!parse_int(i + 1 < argc ? argv[++i] : "", 0, 255, v)) { fprintf(stderr, "--threshold-lo LO: an integer from 0 to 255\n"); return 1; }
+            auto_lo = (int)v;
+            auto_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--histogram")) {
+            auto_hist = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
+            if (auto_hist.empty()) { fprintf(stderr, "--histogram FILE.csv\n"); return 1; }
+            auto_flag = true;
+            continue;
+        }
         if (!strcmp(argv[i], "--morph")) { morph = true; continue; }
         if (!strcmp(argv[i], "--morph-out")) {
             morph_out = i + 1 < argc && argv[i + 1][0] != '-' ? argv[++i] : "";
@@ -461,7 +511,7 @@ int main(int argc, char **argv)
             long v = 0;
             const char *txt = i + 1 < argc ? argv[++i] : "";
             if (flag == "--radius-threshold") {
-                if (!parse_int(txt, -1, 255, v)) { fprintf(stderr, "--radius-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
+                if (!parse_thr(txt, v, S0.radius_word)) { fprintf(stderr, "--radius-threshold T: an integer from 0 to 255, or -1 for the stack's mean\n"); return 1; }
                 S0.radius.thr = (int32_t)v;
                 S0.radius.rel_pct = 0;
                 radius_abs = true;
@@ -523,7 +573,18 @@ int main(int argc, char **argv)
     if (geo_flag && !geo) { fprintf(stderr, "--from / --to / --paths / --geo-max / --geo-out need --geodesic -i stack\n"); return 1; }
     if (S0.hmax && S0.hdome) { fprintf(stderr, "--hmax and --hdome: one of them\n"); return 1; }
     if (!morph_out.empty() && !morph) { fprintf(stderr, "--morph-out needs --morph -i stack\n"); return 1; }
+    if (S0.local.binary && !S0.local.r) { fprintf(stderr, "--local-binary needs --local-threshold R\n"); return 1; }
+    if (auto_flag && !auto_thr) { fprintf(stderr, "--threshold-lo / --histogram need --auto-threshold -i stack\n"); return 1; }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
+    if (auto_thr) {
+        if (skeleton || skel_flag || geo || geo_flag || edt || edt_flag || components || comp_flag || thr_flag || rendering || distance || !join_in.empty() || info || S0.despeckle ||
+            S0.measure_radius || join_given || join_geodesic || per_node_flag || zscale_flag || !paras.empty() || morph || ws || ws_flag) {
+            fprintf(stderr, "--auto-threshold: not with a tracing run (-p), another tool mode, --threshold, --despeckle, --measure-radius, --join, --per-node or --zscale\n");
+            return 1;
+        }
+        if (infiles.empty()) { fprintf(stderr, "--auto-threshold needs -i <stack>\n"); return 1; }
+        return advantra::auto_threshold_file(auto_lo, auto_hist, infiles, raw_dims, device) ? 0 : 1;
+    }
     if (skeleton) {
         if (geo || geo_flag || edt || edt_flag || components || comp_flag || rendering || distance || !join_in.empty() || info || S0.despeckle || S0.measure_radius || join_given || join_geodesic ||
             per_node_flag || !paras.empty() || morph || ws || ws_flag) {
@@ -591,7 +652,7 @@ int main(int argc, char **argv)
     if (S0.despeckle && (rendering || distance || !join_in.empty() || info)) { fprintf(stderr, "--despeckle needs a tracing run\n"); return 1; }
     if (rendering) {
         if (distance || !join_in.empty() || coverage) { fprintf(stderr, "--render-swc: not with --distance, --join-swc or --coverage (the JSON line has the coverage)\n"); return 1; }
-        if (infiles.empty() && (mask_out.empty() || !residual_out.empty() || !per_node.empty() || render.opts.thr != -1)) {
+        if (infiles.empty() && (mask_out.empty() || !residual_out.empty() || !per_node.empty() || render.opts.thr != -1 || S0.coverage_word.given)) {
             fprintf(stderr, "--render-swc without -i: -d w,h,l gives the grid and only --mask OUT is allowed (and needed)\n");
             return 1;
         }

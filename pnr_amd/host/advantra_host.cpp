@@ -94,6 +94,17 @@ void print_flags()
     printf("  --connectivity 4|8|6|26   the neighbourhood (default 26; 4 and 8: every slice on its own)\n");
     printf("  --labels OUT.raw          write the label volume: little-endian int32, 0 = not reached or below the threshold (needed)\n");
     printf("  --levels OUT.raw          write the pass height at which each voxel joined its region, as bare bytes\n");
+    printf("--local-threshold R[,OFFSET[,SCALE_256]]   pre-filter (after --fill-holes / --hmax / --hdome, before --despeckle): a voxel is kept where it is at least\n");
+    printf("                          SCALE_256 / 256 times the mean of the box of half-width R in xy and R / zdist in z around it, plus OFFSET; the others are set\n");
+    printf("                          to 0 (R 1..%d, OFFSET -255..255, default 0, SCALE_256 0..4096, default 256); the comment block gains #local=r:R,offset:C,scale:K,kept:N\n", PNR_LOCAL_MAX_R);
+    printf("  --local-binary            kept voxels become 255\n");
+    printf("--auto-threshold -i stack every threshold rule on the stack (after the volume set-up of tracing) from one histogram pass on the GPU, as one JSON line:\n");
+    printf("                          w, h, l, n_vox, lo, and thr and n_fg (the voxels from thr on) of mean, otsu, triangle, maxentropy and top1 (the brightest 1 %%)\n");
+    printf("  --threshold-lo LO         only the values from LO on are counted, 0..255 (default 0; 1 ignores the zeros a top-hat leaves)\n");
+    printf("  --histogram FILE.csv      write the 256 counts as `v,count`\n");
+    printf("threshold words           --threshold, --coverage-threshold, --radius-threshold, --join-threshold and the THR of --despeckle also take, in the place of\n");
+    printf("                          T or -1, mean|otsu|triangle|maxentropy|topP, each with an optional :LO (topP: the brightest P per cent; LO as --threshold-lo);\n");
+    printf("                          the tool's JSON line or SWC comment then names the word as thr_method\n");
     printf("--despeckle MIN[,THR[,CONN]]  pre-filter: foreground components (voxels >= THR, default -1: the stack's mean; CONN 6 or 26, default 26) of\n");
     printf("                          fewer than MIN voxels are set to 0 on the GPU (after the median and the top-hat, before tracing)\n");
     printf("--components -i stack     the connected components of the stack's foreground on the GPU (the same volume setup as tracing) as one JSON\n");
@@ -214,12 +225,14 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         auto level = [&](int v) { return v ? std::to_string(v) : std::string("off"); };
         c << "\n#morph=fill:" << (s.fill_holes == 6 ? "3d" : s.fill_holes == 4 ? "2d" : "off") << ",hmax:" << level(s.hmax) << ",hdome:" << level(s.hdome);
     }
+    if (settings().local.r && cover)
+        c << "\n#local=r:" << settings().local.r << ",offset:" << settings().local.offset << ",scale:" << settings().local.scale_256 << ",kept:" << cover->local_kept;
     if (settings().despeckle && cover)
         c << "\n#despeckle=min:" << settings().despeckle_opts.min_size << ",thr:" << cover->despeckle_thr << ",conn:" << settings().despeckle_opts.connectivity
-          << ",removed:" << cover->despeckle_removed << ",voxels:" << cover->despeckle_voxels;
+          << ",removed:" << cover->despeckle_removed << ",voxels:" << cover->despeckle_voxels << thr_method_swc(settings().despeckle_word);
     if (join && settings().join_geodesic)
         c << "\n#join=geodesic:" << settings().join_limit << ",thr:" << join->join_thr_used << ",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->"
-          << join->join_trees_out << ",inserted:" << join->join_inserted;
+          << join->join_trees_out << ",inserted:" << join->join_inserted << thr_method_swc(settings().join_word);
     else if (join) c << "\n#join=gap:" << f32_text(settings().join_gap) <<",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->" << join->join_trees_out;
     if (radius_thr) {
         const pnr_radius_opts &ro = settings().radius;
@@ -227,6 +240,7 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         if (ro.rel_pct > 0) c << "rel:" << ro.rel_pct;
         else c << *radius_thr;
         c << ",rmax=" << ro.rmax << ",bg=" << ro.bg_permille;
+        if (ro.rel_pct == 0) c << thr_method_swc(settings().radius_word);
     }
     if (cover && cover->have_coverage) {
         char buf[200];
@@ -359,7 +373,7 @@ struct Pipeline {
     void *const X = RX ? (void *)RX : (void *)S.exchange;
     const bool sharded = world > 1 || S.force_shard;
     const pnr_filter_opts &fo = S.filter;
-    const bool filtered = fo.median || fo.tophat_r || S.morph() || S.despeckle;
+    const bool filtered = fo.median || fo.tophat_r || S.morph() || S.local.r || S.despeckle;
     Ctx ctx;
     Result R;
     bool ok = true;
@@ -385,7 +399,8 @@ struct Pipeline {
         if (!S.despeckle || !ok) return;
         const auto tf = clk::now();
         pnr_components_info ci = {};
-        ok = pnr_despeckle_volume(ctx, &S.despeckle_opts, &ci) == PNR_OK;
+        pnr_components_opts co = S.despeckle_opts;
+        ok = resolve_threshold(ctx, S.despeckle_word, co.thr) && pnr_despeckle_volume(ctx, &co, &ci) == PNR_OK;
         R.t_despeckle = secs(tf, clk::now());
         R.despeckle_removed = ci.n_small, R.despeckle_voxels = ci.vox_small, R.despeckle_thr = ci.thr_used;
         printf("despeckle... %lld components of fewer than %lld voxels (%lld voxels) removed, threshold %d, %g sec.\n", (long long)ci.n_small,
@@ -393,7 +408,23 @@ struct Pipeline {
         if (S.timing) fprintf(stderr, "[pnr host] despeckle: %.3f s\n", R.t_despeckle);
     }
 
-    void morph() // --fill-holes / --hmax / --hdome: the (filtered) volume is replaced by its reconstruction, then despeckled
+    void local_threshold() // --local-threshold: the volume is replaced by its local threshold
+    {
+        if (!S.local.r || !ok) return;
+        const auto tf = clk::now();
+        Profile prof(ctx, "local_threshold", S.timing || S.verbose);
+        pnr_local_info li = {};
+        ok = local_stage(ctx, &li);
+        R.t_local = secs(tf, clk::now());
+        prof.end();
+        R.local_kept = li.n_kept;
+        printf("local threshold... box %d x %d x %d, offset %d, scale %d/256, %lld of %lld voxels kept, %g sec.\n", (int)li.rx, (int)li.ry, (int)li.rz, (int)S.local.offset,
+               (int)S.local.scale_256, (long long)li.n_kept, (long long)li.n_vox, R.t_local);
+        if (S.verbose) printf("local threshold kernels %.3f ms in %lld launches\n", prof.ms, (long long)prof.launches);
+        if (S.timing) fprintf(stderr, "[pnr host] local threshold: %.3f s, kernels %.3f ms in %lld launches\n", R.t_local, prof.ms, (long long)prof.launches);
+    }
+
+    void morph() // --fill-holes / --hmax / --hdome: the (filtered) volume is replaced by its reconstruction, then thresholded locally and despeckled
     {
         if (S.morph() && ok) {
             const auto tf = clk::now();
@@ -410,6 +441,7 @@ struct Pipeline {
             if (S.verbose) printf("morphology kernels %.3f ms in %lld launches\n", prof.ms, (long long)prof.launches);
             if (S.timing) fprintf(stderr, "[pnr host] morph: %.3f s, kernels %.3f ms in %lld launches\n", R.t_morph, prof.ms, (long long)prof.launches);
         }
+        local_threshold();
         despeckle();
     }
 
@@ -652,7 +684,8 @@ struct Pipeline {
     // list is rewritten in tree order
     bool join_geodesic(clk::time_point tj, const TreeArrays &T, int64_t n, int64_t root)
     {
-        const pnr_geojoin_opts go = {S.join_thr, S.join_limit, 1.f, nullptr};
+        pnr_geojoin_opts go = {S.join_thr, S.join_limit, 1.f, nullptr};
+        if (!resolve_threshold(ctx, S.join_word, go.thr)) return false;
         GeoJoined J;
         Profile prof(ctx, "geojoin", S.timing);
         if (!geodesic_join(ctx, T.xyz.data() + 3, T.par.data() + 1, n, go, root, w, h, l, J)) return false;
@@ -694,7 +727,9 @@ struct Pipeline {
         const TreeArrays T = tree_arrays(R.tree, R.parent, nullptr);
         R.radius_k.assign(nt, -1);
         Profile prof(ctx, "radius", S.timing);
-        if (pnr_measure_radii(ctx, T.xyz.data(), (int64_t)nt, &S.radius, R.radius_k.data(), &R.radius_thr) != PNR_OK) return lib_fail(nullptr);
+        pnr_radius_opts ro = S.radius;
+        if (ro.rel_pct == 0 && !resolve_threshold(ctx, S.radius_word, ro.thr)) return false;
+        if (pnr_measure_radii(ctx, T.xyz.data(), (int64_t)nt, &ro, R.radius_k.data(), &R.radius_thr) != PNR_OK) return lib_fail(nullptr);
         if (nt) R.radius_k[0] = -1; // the dummy
         radius = measured_radius_column(R.tree, R.radius_k);
         t5 = clk::now();

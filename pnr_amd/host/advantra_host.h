@@ -52,10 +52,22 @@ struct Result {
     std::string swc_path;
     double t_frangi = 0, t_seeds = 0, t_select = 0, t_trace = 0, t_recon = 0;
     double t_filter = 0;           // --median / --subtract-background: the pre-filter (part of t_setup)
+    long long local_kept = 0;      // --local-threshold: the voxels pnr_local_threshold_volume kept
+    double t_local = 0;            // ... and its time (part of t_setup)
     double t_morph = 0;            // --fill-holes / --hmax / --hdome: the morphological reconstructions (part of t_setup)
     double t_radius = 0;           // --measure-radius: the measurement (kernels, transfers, the first call's shell table)
     double t_load = 0, t_setup = 0, t_write = 0, t_total = 0; // stack file -> memory; context + upload (+ soma); SWC file; advantra_func as a whole
 };
+
+// a threshold given as a word where a flag takes "T or -1": mean|otsu|triangle|maxentropy|topP, each with an optional :LO (P: the
+// brightest P per cent, up to 4 decimals; LO: the counted bins are [LO, 255]).  The word is resolved by pnr_auto_threshold on the bytes
+// on which the -1 rule would have taken its mean and passed on as a number; the tool's JSON line or SWC comment then names it (thr_method).
+struct ThrWord {
+    bool given = false;
+    pnr_threshold_opts opts = {0, 0, 0, 0};
+    std::string text;
+};
+bool parse_threshold_word(const char *txt, ThrWord &out); // false: no such word (out is left as it was)
 
 // switches of the head-less driver (advantra_cli flags; the plugin's compile-time TRACING_VERBOSE / saveMidres taps)
 struct Settings {
@@ -122,6 +134,12 @@ struct Settings {
     int fill_holes = 0; // 0: off, 4: 2d, 6: 3d (the connectivity)
     int hmax = 0, hdome = 0;
     bool morph() const { return fill_holes || hmax || hdome; }
+    // --local-threshold R[,OFFSET[,SCALE_256]] [--local-binary]: the local threshold (pnr_local_threshold_volume, floor 1) is the next step of
+    // the volume set-up, after --fill-holes / --hmax / --hdome and before --despeckle, on every rank and in every tool mode that takes the
+    // set-up.  The SWC comment then has a #local= line behind #morph.  The reference has no counterpart.
+    pnr_local_opts local = {0, 0, 256, 1, 0, 0}; // r = 0: off
+    // the words given to --threshold (the tool modes), --coverage-threshold, --radius-threshold, --join-threshold and the THR of --despeckle
+    ThrWord thr_word, coverage_word, radius_word, join_word, despeckle_word;
 };
 Settings &settings();
 
@@ -237,6 +255,11 @@ struct WatershedJob {
     bool by_node = false;
 };
 bool watershed_file(const WatershedJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
+// advantra_cli --auto-threshold -i stack [--threshold-lo LO] [--histogram FILE.csv]: every threshold rule on the stack after the volume
+// set-up of tracing, from one histogram pass (pnr_auto_threshold on `device`, then pnr_threshold_from_hist on its counts).  One JSON line
+// {"w", "h", "l", "n_vox", "lo", "mean": {"thr", "n_fg"}, "otsu": ..., "triangle": ..., "maxentropy": ..., "top1": ...} (maxentropy with
+// lo = 0 whatever LO is; null where the reference's int histogram cannot hold a bin); histogram (not empty): a CSV `v,count` under a header line.
+bool auto_threshold_file(int lo, const std::string &histogram, const std::vector<char *> &infiles, const std::string &raw_dims, int device);
 // save_nodelist (Advantra_plugin.cpp:480-523).  radius (optional, one entry per node): a node whose entry is >= 0 writes it as its
 // radius instead of sig2r * sig
 bool save_nodelist(const std::vector<pnr_node> &nodes, const std::vector<int32_t> &links, const std::string &swcname,

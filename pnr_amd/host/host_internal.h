@@ -62,6 +62,15 @@ struct MorphStage {
 };
 bool morph_stages(pnr_ctx *ctx, std::vector<MorphStage> *stages);
 
+// tools.cpp: --local-threshold of settings() on ctx's volume (pnr_local_threshold_volume); nothing to do without the flag; false when the
+// call failed (pnr_last_error has the reason)
+bool local_stage(pnr_ctx *ctx, pnr_local_info *info);
+// tools.cpp: thr = the word's threshold on ctx's current volume (pnr_auto_threshold); a word that was not given leaves thr; false after lib_fail
+bool resolve_threshold(pnr_ctx *ctx, const ThrWord &word, int32_t &thr);
+// `, "thr_method": "<word>"` for a JSON line, `,thr_method:<word>` for an SWC comment; empty without a word
+std::string thr_method_json(const ThrWord &word);
+std::string thr_method_swc(const ThrWord &word);
+
 // swc_io.cpp: load_swc with its message on stderr; the shortest decimal text without an exponent (nine digits at the most) that reads
 // back as the same f32
 bool read_swc(const std::string &path, SwcTree &out);

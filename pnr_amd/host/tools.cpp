@@ -1,5 +1,5 @@
 // tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc (by gap, or --join-geodesic), --render-swc,
-// --components, --edt, --skeleton, --morph, --watershed and --geodesic.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+// --components, --edt, --skeleton, --morph, --watershed, --geodesic and --auto-threshold.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
 #include "host_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -40,7 +40,55 @@ bool morph_stages(pnr_ctx *ctx, std::vector<MorphStage> *stages)
     return true;
 }
 
-// the volume as it would be traced: windowed to 8 bits, pre-filtered, then --fill-holes / --hmax / --hdome (never despeckled)
+bool local_stage(pnr_ctx *ctx, pnr_local_info *info)
+{
+    const Settings &S = settings();
+    return !S.local.r || pnr_local_threshold_volume(ctx, &S.local, info) == PNR_OK;
+}
+
+bool parse_threshold_word(const char *txt, ThrWord &out)
+{
+    std::string name = txt;
+    long lo = 0;
+    const size_t colon = name.find(':');
+    if (colon != std::string::npos) {
+        char *end = nullptr;
+        const char *t = txt + colon + 1;
+        lo = strtol(t, &end, 10);
+        if (!*t || *end || lo < 0 || lo > 255) return false;
+        name.resize(colon);
+    }
+    pnr_threshold_opts o = {0, (int32_t)lo, 0, 0};
+    if (name == "mean") o.method = PNR_THR_MEAN;
+    else if (name == "otsu") o.method = PNR_THR_OTSU;
+    else if (name == "triangle") o.method = PNR_THR_TRIANGLE;
+    else if (name == "maxentropy") o.method = PNR_THR_MAXENTROPY;
+    else if (name.size() > 3 && name.compare(0, 3, "top") == 0 && (isdigit((unsigned char)name[3]) || name[3] == '.')) {
+        char *end = nullptr;
+        const double pct = strtod(name.c_str() + 3, &end);
+        if (*end || !(pct > 0.0 && pct < 100.0)) return false;
+        o.method = PNR_THR_TOP;
+        o.top_ppm = (int32_t)std::lround(pct * 1e4);
+        if (o.top_ppm < 1 || o.top_ppm > 999999) return false;
+    } else
+        return false;
+    out.given = true, out.opts = o, out.text = txt;
+    return true;
+}
+
+bool resolve_threshold(pnr_ctx *ctx, const ThrWord &word, int32_t &thr)
+{
+    if (!word.given) return true;
+    pnr_threshold_info ti = {};
+    if (pnr_auto_threshold(ctx, &word.opts, &ti, nullptr) != PNR_OK) return lib_fail("pnr_auto_threshold");
+    thr = ti.thr;
+    return true;
+}
+
+std::string thr_method_json(const ThrWord &word) { return word.given ? ", \"thr_method\": \"" + word.text + "\"" : std::string(); }
+std::string thr_method_swc(const ThrWord &word) { return word.given ? ",thr_method:" + word.text : std::string(); }
+
+// the volume as it would be traced: windowed to 8 bits, pre-filtered, then --fill-holes / --hmax / --hdome and --local-threshold (never despeckled)
 static bool set_traced_volume(pnr_ctx *ctx, const Stack &st, std::vector<MorphStage> *stages = nullptr)
 {
     const Settings &S = settings();
@@ -48,6 +96,7 @@ static bool set_traced_volume(pnr_ctx *ctx, const Stack &st, std::vector<MorphSt
                              : pnr_set_volume(ctx, st.bytes(), st.w, st.h, st.l)) == PNR_OK;
     if (ok && (S.filter.median || S.filter.tophat_r)) ok = pnr_filter_volume(ctx, &S.filter) == PNR_OK;
     if (ok && S.morph()) ok = morph_stages(ctx, stages);
+    if (ok) ok = local_stage(ctx, nullptr);
     return ok || lib_fail("volume");
 }
 
@@ -196,13 +245,16 @@ bool join_swc_geodesic_file(const std::string &in, const std::string &out, const
     p.zdist = zscale; // (also the z half-width of --subtract-background)
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().join_word;
+    pnr_geojoin_opts jo = opts;
+    if (!resolve_threshold(ctx, word, jo.thr)) return false;
     GeoJoined J;
-    if (!geodesic_join(ctx, T.xyz.data(), T.parent.data(), n, opts, root, st.w, st.h, st.l, J)) return false;
+    if (!geodesic_join(ctx, T.xyz.data(), T.parent.data(), n, jo, root, st.w, st.h, st.l, J)) return false;
     const pnr_geojoin_info &gi = J.info;
     int64_t written = 0;
     if (!write_file(out, "w", [&](FILE *f) {
-            fprintf(f, "#join=geodesic:%llu,thr:%d,bridges:%lld,trees:%lld->%lld,inserted:%lld\n##n,type,x,y,z,radius,parent\n", (unsigned long long)opts.limit, (int)gi.thr_used,
-                    (long long)gi.n_bridges, (long long)gi.n_trees_in, (long long)gi.n_trees_out, (long long)gi.n_inserted);
+            fprintf(f, "#join=geodesic:%llu,thr:%d,bridges:%lld,trees:%lld->%lld,inserted:%lld%s\n##n,type,x,y,z,radius,parent\n", (unsigned long long)opts.limit, (int)gi.thr_used,
+                    (long long)gi.n_bridges, (long long)gi.n_trees_in, (long long)gi.n_trees_out, (long long)gi.n_inserted, thr_method_swc(word).c_str());
             std::vector<int64_t> pos((size_t)J.n2(), -1);
             for (int64_t k = 0; k < J.n2(); k++) {
                 const size_t v = (size_t)J.order[(size_t)k];
@@ -218,9 +270,9 @@ bool join_swc_geodesic_file(const std::string &in, const std::string &out, const
         }))
         return false;
     printf("{\"nodes\": %lld, \"n_trees_in\": %lld, \"n_trees_lost\": %lld, \"n_trees_out\": %lld, \"n_bridges\": %lld, \"n_inserted\": %lld, \"w_max\": %llu, \"thr_used\": %d, "
-           "\"n_src\": %lld, \"n_src_dropped\": %lld, \"limit\": %llu, \"zdist\": %.17g, \"rounds\": %d}\n",
+           "\"n_src\": %lld, \"n_src_dropped\": %lld, \"limit\": %llu, \"zdist\": %.17g, \"rounds\": %d%s}\n",
            (long long)written, (long long)gi.n_trees_in, (long long)gi.n_trees_lost, (long long)gi.n_trees_out, (long long)gi.n_bridges, (long long)gi.n_inserted,
-           (unsigned long long)gi.w_max, (int)gi.thr_used, (long long)gi.n_src, (long long)gi.n_src_dropped, (unsigned long long)opts.limit, (double)zscale, (int)gi.rounds);
+           (unsigned long long)gi.w_max, (int)gi.thr_used, (long long)gi.n_src, (long long)gi.n_src_dropped, (unsigned long long)opts.limit, (double)zscale, (int)gi.rounds, thr_method_json(word).c_str());
     return true;
 }
 
@@ -264,13 +316,16 @@ bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, c
     if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().coverage_word;
+    pnr_render_opts ro = job.opts;
+    if (!resolve_threshold(ctx, word, ro.thr)) return false;
     const size_t N = (size_t)(st.w * st.h * st.l);
     std::vector<unsigned char> mask(job.mask.empty() ? 0 : N), residual(job.residual.empty() ? 0 : N);
     std::vector<int64_t> vox, fg, sum;
     if (!job.per_node.empty()) vox.assign((size_t)n, 0), fg.assign((size_t)n, 0), sum.assign((size_t)n, 0);
     pnr_coverage c;
     int64_t items = 0;
-    const int rc = pnr_tree_coverage(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), n, &job.opts, &c, job.per_node.empty() ? nullptr : vox.data(),
+    const int rc = pnr_tree_coverage(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), n, &ro, &c, job.per_node.empty() ? nullptr : vox.data(),
                                      job.per_node.empty() ? nullptr : fg.data(), job.per_node.empty() ? nullptr : sum.data(),
                                      job.mask.empty() ? nullptr : mask.data(), job.residual.empty() ? nullptr : residual.data());
     pnr_get_option(ctx, "render_items", &items);
@@ -283,9 +338,9 @@ bool render_swc_file(const RenderJob &job, const std::vector<char *> &infiles, c
         }))
         return false;
     printf("{\"n_vox\": %lld, \"n_tree\": %lld, \"n_fg\": %lld, \"n_both\": %lld, \"sum_fg\": %lld, \"sum_both\": %lld, \"thr_used\": %d, \"covered\": %.17g, "
-           "\"on_signal\": %.17g, \"covered_intensity\": %.17g, \"nodes\": %lld, \"items\": %lld}\n",
+           "\"on_signal\": %.17g, \"covered_intensity\": %.17g, \"nodes\": %lld, \"items\": %lld%s}\n",
            (long long)c.n_vox, (long long)c.n_tree, (long long)c.n_fg, (long long)c.n_both, (long long)c.sum_fg, (long long)c.sum_both, (int)c.thr_used, c.covered,
-           c.on_signal, c.covered_intensity, (long long)n, (long long)items);
+           c.on_signal, c.covered_intensity, (long long)n, (long long)items, thr_method_json(word).c_str());
     return true;
 }
 
@@ -298,14 +353,17 @@ bool components_file(const ComponentsJob &job, const std::vector<char *> &infile
     if (zscale >= 1.f) p.zdist = zscale; // (the z half-width of --subtract-background)
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().thr_word;
+    pnr_components_opts co = job.opts;
+    if (!resolve_threshold(ctx, word, co.thr)) return false;
     const size_t N = (size_t)(st.w * st.h * st.l);
     std::vector<int32_t> labels(job.labels.empty() ? 0 : N);
     std::vector<pnr_component> comps;
     pnr_components_info ci = {};
-    int rc = pnr_label_components(ctx, &job.opts, &ci, job.labels.empty() ? nullptr : labels.data(), nullptr, 0);
+    int rc = pnr_label_components(ctx, &co, &ci, job.labels.empty() ? nullptr : labels.data(), nullptr, 0);
     if (rc == PNR_OK && !job.per_component.empty() && ci.n_comp > 0) { // "n_comp > cap: call again"
         comps.resize((size_t)ci.n_comp);
-        rc = pnr_label_components(ctx, &job.opts, &ci, nullptr, comps.data(), (int64_t)comps.size());
+        rc = pnr_label_components(ctx, &co, &ci, nullptr, comps.data(), (int64_t)comps.size());
     }
     if (rc != PNR_OK) return lib_fail("pnr_label_components");
     if (!job.labels.empty() && !write_file(job.labels, "wb", [&](FILE *f) { fwrite(labels.data(), 4, N, f); })) return false; // (the hosts this builds for are little-endian)
@@ -318,8 +376,8 @@ bool components_file(const ComponentsJob &job, const std::vector<char *> &infile
             }
         }))
         return false;
-    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_comp\": %lld, \"n_small\": %lld, \"vox_small\": %lld, \"largest\": %lld, \"thr_used\": %d}\n", (long long)ci.n_vox,
-           (long long)ci.n_fg, (long long)ci.n_comp, (long long)ci.n_small, (long long)ci.vox_small, (long long)ci.largest, (int)ci.thr_used);
+    printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_comp\": %lld, \"n_small\": %lld, \"vox_small\": %lld, \"largest\": %lld, \"thr_used\": %d%s}\n", (long long)ci.n_vox,
+           (long long)ci.n_fg, (long long)ci.n_comp, (long long)ci.n_small, (long long)ci.vox_small, (long long)ci.largest, (int)ci.thr_used, thr_method_json(word).c_str());
     return true;
 }
 
@@ -334,10 +392,13 @@ bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::
     p.zdist = zscale; // (also the z half-width of --subtract-background)
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().thr_word;
+    pnr_edt_opts eo = job.opts;
+    if (!resolve_threshold(ctx, word, eo.thr)) return false;
     const size_t N = (size_t)(st.w * st.h * st.l);
     std::vector<float> d(job.out.empty() ? 0 : N), at((size_t)T.n());
     pnr_edt_info ei = {};
-    if (pnr_distance_transform(ctx, &job.opts, &ei, job.out.empty() ? nullptr : d.data(), T.n() ? T.xyz.data() : nullptr, T.n(), T.n() ? at.data() : nullptr) != PNR_OK)
+    if (pnr_distance_transform(ctx, &eo, &ei, job.out.empty() ? nullptr : d.data(), T.n() ? T.xyz.data() : nullptr, T.n(), T.n() ? at.data() : nullptr) != PNR_OK)
         return lib_fail("pnr_distance_transform");
     for (float &v : d) v = sqrtf(v);
     if (!job.out.empty() && !write_file(job.out, "wb", [&](FILE *f) { fwrite(d.data(), 4, N, f); })) return false; // (the hosts this builds for are little-endian)
@@ -349,7 +410,7 @@ bool edt_file(const EdtJob &job, const std::vector<char *> &infiles, const std::
     printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_capped\": %lld, \"thr_used\": %d, \"rmax\": %d, \"zdist\": %.17g, \"d_max\": %.17g, \"max_at\": ", (long long)ei.n_vox,
            (long long)ei.n_fg, (long long)ei.n_capped, (int)ei.thr_used, (int)job.opts.rmax, (double)zscale, (double)sqrtf(ei.d2_max));
     print_max_at(ei.first_max, st.w, st.h);
-    printf("}\n");
+    printf("%s}\n", thr_method_json(word).c_str());
     return true;
 }
 
@@ -362,14 +423,17 @@ bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, c
     p.zdist = zscale; // (the radii of --swc; also the z half-width of --subtract-background)
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().thr_word;
+    pnr_thin_opts to = job.opts;
+    if (!resolve_threshold(ctx, word, to.thr)) return false;
     const size_t N = (size_t)(st.w * st.h * st.l);
     std::vector<unsigned char> skel(job.out.empty() ? 0 : N);
     pnr_thin_info ti = {};
-    if (pnr_skeletonize(ctx, &job.opts, &ti, nullptr, nullptr, nullptr, 0) != PNR_OK) return lib_fail("pnr_skeletonize"); // "n_skel > cap: call again"
+    if (pnr_skeletonize(ctx, &to, &ti, nullptr, nullptr, nullptr, 0) != PNR_OK) return lib_fail("pnr_skeletonize"); // "n_skel > cap: call again"
     const int64_t n = ti.n_skel;
     std::vector<int64_t> vox((size_t)n);
     std::vector<uint8_t> deg((size_t)n);
-    if ((n > 0 || !job.out.empty()) && pnr_skeletonize(ctx, &job.opts, &ti, job.out.empty() ? nullptr : skel.data(), vox.data(), deg.data(), n) != PNR_OK)
+    if ((n > 0 || !job.out.empty()) && pnr_skeletonize(ctx, &to, &ti, job.out.empty() ? nullptr : skel.data(), vox.data(), deg.data(), n) != PNR_OK)
         return lib_fail("pnr_skeletonize");
     std::vector<pnr_bridge> edges((size_t)std::max<int64_t>(n - 1, 0));
     int64_t ne = 0;
@@ -389,7 +453,8 @@ bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, c
             if (pnr_join_reroot(par.data(), n, edges.data(), ne, root, par_out.data(), order.data(), comp.data()) != PNR_OK) return lib_fail("pnr_join_reroot");
         }
         if (!write_file(job.swc, "w", [&](FILE *f) {
-                fprintf(f, "##n,type,x,y,z,radius,parent\n#skeleton=thr:%d,rounds:%d,voxels:%lld,trees:%lld\n", (int)ti.thr_used, (int)ti.rounds, (long long)n, (long long)trees);
+                fprintf(f, "##n,type,x,y,z,radius,parent\n#skeleton=thr:%d,rounds:%d,voxels:%lld,trees:%lld%s\n", (int)ti.thr_used, (int)ti.rounds, (long long)n, (long long)trees,
+                        thr_method_swc(word).c_str());
                 std::vector<int64_t> pos((size_t)n, -1);
                 for (int64_t k = 0; k < n; k++) {
                     const size_t v = (size_t)order[(size_t)k];
@@ -402,9 +467,9 @@ bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, c
     }
     if (!job.out.empty() && !write_stack(job.out, skel.data(), st.w, st.h, st.l)) return false;
     printf("{\"n_vox\": %lld, \"n_fg\": %lld, \"n_skel\": %lld, \"n_end\": %lld, \"n_branch\": %lld, \"n_isolated\": %lld, \"tiles\": %lld, \"tile_visits\": %lld, "
-           "\"rounds\": %d, \"thr_used\": %d, \"trees\": %lld}\n",
+           "\"rounds\": %d, \"thr_used\": %d, \"trees\": %lld%s}\n",
            (long long)ti.n_vox, (long long)ti.n_fg, (long long)ti.n_skel, (long long)ti.n_end, (long long)ti.n_branch, (long long)ti.n_isolated, (long long)ti.tiles,
-           (long long)ti.tile_visits, (int)ti.rounds, (int)ti.thr_used, (long long)trees);
+           (long long)ti.tile_visits, (int)ti.rounds, (int)ti.thr_used, (long long)trees, thr_method_json(word).c_str());
     return true;
 }
 
@@ -485,11 +550,14 @@ bool watershed_file(const WatershedJob &job, const std::vector<char *> &infiles,
     pnr_default_params(&p);
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().thr_word;
+    pnr_watershed_opts wo = job.opts;
+    if (!resolve_threshold(ctx, word, wo.thr)) return false;
     std::vector<int32_t> L(N);
     std::vector<uint8_t> M(job.levels.empty() ? 0 : N);
     pnr_watershed_info wi = {};
     const bool points = mvol.empty();
-    if (pnr_watershed(ctx, &job.opts, relief.empty() ? nullptr : relief.data(), points ? nullptr : mvol.data(), points ? T.xyz.data() : nullptr,
+    if (pnr_watershed(ctx, &wo, relief.empty() ? nullptr : relief.data(), points ? nullptr : mvol.data(), points ? T.xyz.data() : nullptr,
                       points ? label.data() : nullptr, points ? T.n() : 0, &wi, L.data(), M.empty() ? nullptr : M.data()) != PNR_OK)
         return lib_fail("pnr_watershed");
     // (the hosts this builds for are little-endian)
@@ -497,11 +565,11 @@ bool watershed_file(const WatershedJob &job, const std::vector<char *> &infiles,
     if (!job.levels.empty() && !write_file(job.levels, "wb", [&](FILE *f) { fwrite(M.data(), 1, N, f); })) return false;
     printf("{\"w\": %lld, \"h\": %lld, \"l\": %lld, \"markers_by\": \"%s\", \"n_markers\": %lld, \"n_vox\": %lld, \"n_mask\": %lld, \"n_marker_vox\": %lld, "
            "\"n_dropped\": %lld, \"n_reached\": %lld, \"n_unreached\": %lld, \"n_regions\": %lld, \"m_max\": %d, \"d_max\": %d, \"thr_used\": %d, "
-           "\"connectivity\": %d, \"tiles\": %lld, \"flood_visits\": %lld, \"label_visits\": %lld, \"flood_rounds\": %d, \"label_rounds\": %d}\n",
+           "\"connectivity\": %d, \"tiles\": %lld, \"flood_visits\": %lld, \"label_visits\": %lld, \"flood_rounds\": %d, \"label_rounds\": %d%s}\n",
            (long long)st.w, (long long)st.h, (long long)st.l, !points ? "volume" : job.by_node ? "node" : "tree", points ? (long long)T.n() : (long long)wi.n_marker_vox + wi.n_dropped,
            (long long)wi.n_vox, (long long)wi.n_mask, (long long)wi.n_marker_vox, (long long)wi.n_dropped, (long long)wi.n_reached, (long long)wi.n_unreached,
            (long long)wi.n_regions, (int)wi.m_max, (int)wi.d_max, (int)wi.thr_used, (int)wi.connectivity, (long long)wi.tiles, (long long)wi.flood_visits,
-           (long long)wi.label_visits, (int)wi.flood_rounds, (int)wi.label_rounds);
+           (long long)wi.label_visits, (int)wi.flood_rounds, (int)wi.label_rounds, thr_method_json(word).c_str());
     return true;
 }
 
@@ -557,6 +625,9 @@ bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, c
     p.zdist = zscale; // (also the z half-width of --subtract-background)
     Ctx ctx;
     if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    const ThrWord &word = settings().thr_word;
+    pnr_geo_opts go = job.opts;
+    if (!resolve_threshold(ctx, word, go.thr)) return false;
     const size_t N = (size_t)(st.w * st.h * st.l);
     const int64_t m = B.n();
     std::vector<uint32_t> D(job.out.empty() ? 0 : N), d_at((size_t)m);
@@ -570,7 +641,7 @@ bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, c
         cap = (int32_t)std::min<size_t>({(size_t)PNR_GEO_MAX_PATH, N, std::max<size_t>(64, ((size_t)1 << 26) / (size_t)m)});
         plen.resize((size_t)m), pvox.resize((size_t)m * (size_t)cap);
     }
-    if (pnr_geodesic_distance(ctx, src.data(), label.data(), (int64_t)label.size(), &job.opts, &gi, job.out.empty() ? nullptr : D.data(), job.out.empty() ? nullptr : L.data(),
+    if (pnr_geodesic_distance(ctx, src.data(), label.data(), (int64_t)label.size(), &go, &gi, job.out.empty() ? nullptr : D.data(), job.out.empty() ? nullptr : L.data(),
                               m ? B.xyz.data() : nullptr, m, m ? d_at.data() : nullptr, m ? l_at.data() : nullptr, cap, cap ? plen.data() : nullptr,
                               cap ? pvox.data() : nullptr) != PNR_OK)
         return lib_fail("pnr_geodesic_distance");
@@ -592,7 +663,36 @@ bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, c
            (long long)gi.n_vox, (long long)gi.n_pass, (long long)gi.n_reached, (long long)gi.n_src, (long long)gi.n_src_dropped, (int)gi.thr_used, (unsigned)job.opts.dmax,
            (double)zscale, (unsigned)gi.d_max, (double)gi.d_max / 64.0);
     print_max_at(gi.first_max, st.w, st.h);
-    printf(", \"rounds\": %d}\n", (int)gi.rounds);
+    printf(", \"rounds\": %d%s}\n", (int)gi.rounds, thr_method_json(word).c_str());
+    return true;
+}
+
+bool auto_threshold_file(int lo, const std::string &histogram, const std::vector<char *> &infiles, const std::string &raw_dims, int device)
+{
+    Stack st;
+    if (load_input_stack(infiles[0], raw_dims, st) != Loaded::ok) return false;
+    pnr_params p;
+    pnr_default_params(&p);
+    Ctx ctx;
+    if (!ctx.create(p, device) || !set_traced_volume(ctx, st)) return false;
+    uint64_t H[256];
+    const pnr_threshold_opts mean = {PNR_THR_MEAN, lo, 0, 0};
+    pnr_threshold_info ti = {};
+    if (pnr_auto_threshold(ctx, &mean, &ti, H) != PNR_OK) return lib_fail("pnr_auto_threshold"); // the one histogram pass
+    if (!histogram.empty() && !write_file(histogram, "w", [&](FILE *f) {
+            fprintf(f, "v,count\n");
+            for (int v = 0; v < 256; v++) fprintf(f, "%d,%llu\n", v, (unsigned long long)H[v]);
+        }))
+        return false;
+    printf("{\"w\": %lld, \"h\": %lld, \"l\": %lld, \"n_vox\": %lld, \"lo\": %d", st.w, st.h, st.l, (long long)ti.n_vox, lo);
+    const struct { const char *name; pnr_threshold_opts o; } rules[] = {{"mean", mean}, {"otsu", {PNR_THR_OTSU, lo, 0, 0}}, {"triangle", {PNR_THR_TRIANGLE, lo, 0, 0}},
+                                                                        {"maxentropy", {PNR_THR_MAXENTROPY, 0, 0, 0}}, {"top1", {PNR_THR_TOP, lo, 10000, 0}}};
+    for (const auto &r : rules) {
+        if (pnr_threshold_from_hist(H, &r.o, &ti) == PNR_OK) printf(", \"%s\": {\"thr\": %d, \"n_fg\": %lld}", r.name, (int)ti.thr, (long long)ti.n_fg);
+        else if (r.o.method == PNR_THR_MAXENTROPY) printf(", \"%s\": null", r.name); // (a bin of 2^31 voxels or more)
+        else return lib_fail("pnr_threshold_from_hist");
+    }
+    printf("}\n");
     return true;
 }
 

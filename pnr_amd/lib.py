@@ -204,6 +204,78 @@ class WatershedInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class ThresholdOpts(C.Structure):
+    """pnr_threshold_opts (include/pnr_hip.h): method 0..4 (THRESHOLD_METHODS), lo 0..255 (the counted bins are [lo, 255]), top_ppm 1..999999 for "top" and 0 otherwise"""
+    _fields_ = [("method", C.c_int32), ("lo", C.c_int32), ("top_ppm", C.c_int32), ("pad", C.c_int32)]
+
+
+class ThresholdInfo(C.Structure):
+    """pnr_threshold_info: the threshold and the exact counts it was read from (v_min, v_max, peak: over the counted bins, -1 when they are empty)"""
+    _fields_ = [("n_vox", C.c_int64), ("n_counted", C.c_int64), ("sum_counted", C.c_uint64), ("n_fg", C.c_int64)] + [
+        (k, C.c_int32) for k in ("thr", "method", "lo", "v_min", "v_max", "peak")]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["method"] = THRESHOLD_NAMES[self.method]
+        return d
+
+
+THRESHOLD_METHODS = {"mean": 0, "otsu": 1, "triangle": 2, "top": 3, "maxentropy": 4}
+THRESHOLD_NAMES = {v: k for k, v in THRESHOLD_METHODS.items()}
+
+
+def parse_threshold(word):
+    """a threshold word -> (method name, lo, top_ppm or None): "mean", "otsu", "triangle", "maxentropy" or "topP" (the brightest P per cent,
+    up to 4 decimals), each with an optional ":LO" (the counted bins are [LO, 255])"""
+    name, sep, lo = str(word).partition(":")
+    try:
+        lo = int(lo) if sep else 0
+        if name.startswith("top") and name != "top":
+            ppm = int(round(float(name[3:]) * 1e4))
+            return "top", lo, ppm
+    except ValueError:
+        name = None
+    if name not in THRESHOLD_METHODS or name == "top":
+        raise ValueError("threshold %r: a number, or mean, otsu, triangle, maxentropy or topP (P per cent), each with an optional :LO" % (word,))
+    return name, lo, None
+
+
+def _threshold_opts(method, lo, top_ppm):
+    if isinstance(method, str) and method not in THRESHOLD_METHODS:
+        raise ValueError("threshold: method %r, not one of %s" % (method, ", ".join(THRESHOLD_METHODS)))
+    m = THRESHOLD_METHODS[method] if isinstance(method, str) else int(method)
+    return ThresholdOpts(m, int(lo), int(top_ppm) if top_ppm is not None else 0, 0)
+
+
+def threshold_from_hist(H, method, lo=0, top_ppm=None):
+    """pnr_threshold_from_hist: the threshold rule of include/pnr_hip.h on 256 counts -> the info dict {n_vox, n_counted, sum_counted, n_fg,
+    thr, method, lo, v_min, v_max, peak}.  method: "mean", "otsu", "triangle", "top" (with top_ppm, the brightest share in parts per
+    million) or "maxentropy".  Pure host: needs no GPU."""
+    H = np.ascontiguousarray(H, np.uint64).reshape(-1)
+    if len(H) != 256:
+        raise ValueError("threshold_from_hist: %d counts, not 256" % len(H))
+    o = _threshold_opts(method, lo, top_ppm)
+    info = ThresholdInfo()
+    check(load().pnr_threshold_from_hist(H.ctypes.data, C.byref(o), C.byref(info)))
+    return info.as_dict()
+
+
+class LocalOpts(C.Structure):
+    """pnr_local_opts (include/pnr_hip.h): r 1..64, offset -255..255, scale_256 0..4096, floor 1..255, binary 0 / 1"""
+    _fields_ = [(k, C.c_int32) for k in ("r", "offset", "scale_256", "floor", "binary", "pad")]
+
+
+class LocalInfo(C.Structure):
+    """pnr_local_info: the exact counts of a local threshold and the half-widths of its box"""
+    _fields_ = [("n_vox", C.c_int64), ("n_kept", C.c_int64), ("sum_in", C.c_uint64), ("sum_out", C.c_uint64)] + [(k, C.c_int32) for k in ("rx", "ry", "rz", "pad")]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+PNR_LOCAL_MAX_R = 64
+
+
 MORPH_OPS = {"dilate": 1, "erode": 2, "fill": 3, "hmax": 4, "hdome": 5}
 
 
@@ -361,6 +433,10 @@ PRODUCT_SIGNATURES = {
     "pnr_morph_reconstruct": (_rc, [_vp, C.POINTER(MorphOpts), _vp, C.POINTER(MorphInfo), _vp]),
     "pnr_morph_volume": (_rc, [_vp, C.POINTER(MorphOpts), C.POINTER(MorphInfo)]),
     "pnr_watershed": (_rc, [_vp, C.POINTER(WatershedOpts), _vp, _vp, _vp, _vp, _i64, C.POINTER(WatershedInfo), _vp, _vp]),
+    "pnr_threshold_from_hist": (_rc, [_vp, C.POINTER(ThresholdOpts), C.POINTER(ThresholdInfo)]),
+    "pnr_auto_threshold": (_rc, [_vp, C.POINTER(ThresholdOpts), C.POINTER(ThresholdInfo), _vp]),
+    "pnr_local_threshold": (_rc, [_vp, C.POINTER(LocalOpts), C.POINTER(LocalInfo), _vp]),
+    "pnr_local_threshold_volume": (_rc, [_vp, C.POINTER(LocalOpts), C.POINTER(LocalInfo)]),
     "pnr_frangi": (_rc, [_vp, _pf32, _pf32]),
     "pnr_frangi_slab": (_rc, [_vp, _i64, _i64, _pf32, _pf32]),
     "pnr_quantise_j8": (_rc, [_vp, _f32, _f32]),
@@ -414,6 +490,8 @@ TEST_SIGNATURES = {
     "pnr_live_bytes": (_rc, [_pi64, _pi64]),
     "pnr_render_items": (_rc, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, C.POINTER(RenderOpts), _i64, _i64, _vp, _i64, _pi64]),
     "pnr_test_write_tiff": (_rc, [_str, _vp, _i64, _i64, _i64]),
+    "pnr_test_histogram": (_rc, [_vp, _vp, _i64, _i32, _vp]),
+    "pnr_test_local_threshold": (_rc, [_vp, _vp, _i64, _i64, _i64, C.POINTER(LocalOpts), C.POINTER(LocalInfo), _vp]),
     "pnr_seed_handover": (_rc, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _vp, _vp]),
     "pnr_phased_likelihood": (_rc, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pnr_phased_decide": (_rc, [_vp, _i64, C.POINTER(PhdIn), C.POINTER(PhdOut)]),
@@ -520,7 +598,7 @@ class Context:
         (rel_pct = 0; thr = -1: the global mean), 0 in the relative mode"""
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         k = np.empty(len(xyz), np.int32)
-        o = RadiusOpts(int(thr), int(rel_pct), int(rmax), int(bg_permille))
+        o = RadiusOpts(self._thr(thr), int(rel_pct), int(rmax), int(bg_permille))
         t = C.c_int32()
         check(self.L.pnr_measure_radii(self.h, xyz.ctypes.data, len(xyz), C.byref(o), k.ctypes.data, C.byref(t)))
         return k, t.value
@@ -614,7 +692,7 @@ class Context:
         "seg_sum" (int64[n]: the voxels labelled with the node, the foreground among them, the sum of V over them), mask adds "mask"
         (uint8, 255 under the tree), residual adds "residual" (V where the tree is not, else 0)"""
         xyz, radius, parent = _tree_arrays("tree_coverage", xyz, radius, parent)
-        o = RenderOpts(float(zscale), float(rscale), float(radd), int(thr))
+        o = RenderOpts(float(zscale), float(rscale), float(radd), self._thr(thr))
         cov = Coverage()
         out = {}
         if per_node:
@@ -633,7 +711,7 @@ class Context:
         26-connectivity -> (info dict {n_vox, n_fg, n_comp, n_small, vox_small, largest, thr_used}, labels int32[l, h, w] or None,
         comps COMPONENT_DT[n_comp]).  The components of at least min_size voxels are numbered 1.. by their first voxel in raster order;
         label 0 is background and the dropped components.  cap: at most this many entries of comps (info["n_comp"] stays the full count)."""
-        o = ComponentsOpts(int(thr), int(connectivity), int(min_size))
+        o = ComponentsOpts(self._thr(thr), int(connectivity), int(min_size))
         info = ComponentsInfo()
         lab = np.empty(self.shape, np.int32) if labels else None
         lp = lab.ctypes.data if labels else None
@@ -652,7 +730,7 @@ class Context:
         """pnr_despeckle_volume: the foreground components ({V >= thr}, thr = -1: the global mean) of fewer than min_size voxels are set
         to 0 in the traced volume -> the info dict of label_components (n_small / vox_small: what was removed).  The result is an owned
         volume (a borrowed one is left as it was and released) and the later pipeline state is invalidated; min_size = 1 changes nothing."""
-        o = ComponentsOpts(int(thr), int(connectivity), int(min_size))
+        o = ComponentsOpts(self._thr(thr), int(connectivity), int(min_size))
         info = ComponentsInfo()
         check(self.L.pnr_despeckle_volume(self.h, C.byref(o), C.byref(info)))
         if o.min_size > 1:
@@ -665,7 +743,7 @@ class Context:
         first_max, d2_max, thr_used, d_max, max_at}, d2 float32[l, h, w] or None, at float32[n] or None).  points: n x 3 positions
         (x, y, z) -> D2 at their centre voxels (-1: a position that is not finite).  squared=False: the f32 square roots of both (and -1
         stays -1).  d_max = sqrt(d2_max); max_at = (x, y, z) of first_max, None without foreground."""
-        o = EdtOpts(int(thr), int(rmax))
+        o = EdtOpts(self._thr(thr), int(rmax))
         info = EdtInfo()
         d2 = np.empty(self.shape, np.float32) if volume else None
         xyz = np.ascontiguousarray(points, np.float32).reshape(-1, 3) if points is not None else None
@@ -690,7 +768,7 @@ class Context:
         thr_used}, skel uint8[l, h, w] of 0 / 255 or None, vox int64[n_skel] ascending linear indices or None, deg uint8[n_skel] the
         skeleton voxels in N26 or None).  max_rounds: stop after this many rounds (0: when nothing is deleted).  cap: at most this many
         entries of vox and deg (info["n_skel"] stays the full count)."""
-        o = ThinOpts(int(thr), int(max_rounds))
+        o = ThinOpts(self._thr(thr), int(max_rounds))
         info = ThinInfo()
         skel = np.empty(self.shape, np.uint8) if volume else None
         sp = skel.ctypes.data if volume else None
@@ -721,7 +799,7 @@ class Context:
         tab = np.ascontiguousarray(cost, np.uint16).reshape(-1) if cost is not None else None
         if tab is not None and len(tab) != 256:
             raise ValueError("geodesic: the cost table has 256 entries")
-        o = GeoOpts(int(thr), int(dmax), tab.ctypes.data_as(C.POINTER(C.c_uint16)) if tab is not None else None)
+        o = GeoOpts(self._thr(thr), int(dmax), tab.ctypes.data_as(C.POINTER(C.c_uint16)) if tab is not None else None)
         info = GeoInfo()
         D = np.empty(self.shape, np.uint32) if volume else None
         Lv = np.empty(self.shape, np.int32) if volume else None
@@ -799,7 +877,7 @@ class Context:
             rel = np.ascontiguousarray(relief, np.uint8)
             if rel.size != n:
                 raise ValueError("watershed: a relief of %d voxels for a volume of %d" % (rel.size, n))
-        o = WatershedOpts(int(thr), int(connectivity))
+        o = WatershedOpts(self._thr(thr), int(connectivity))
         info = WatershedInfo()
         Lv = np.empty(self.shape, np.int32) if volume else None
         Mv = np.empty(self.shape, np.uint8) if levels else None
@@ -818,6 +896,7 @@ class Context:
           4. label_components(thr=1, connectivity=26) of those cores: the markers;
           5. watershed(relief=255 - Q, markers, thr, connectivity) on this context.
         -> (info dict of the watershed, labels int32[l, h, w], n_cells = the number of markers).  h in 1..255 is in units of Q."""
+        thr = self._thr(thr)
         _, d2, _ = self.distance_transform(thr=thr, rmax=rmax)
         q = np.minimum(np.float32(255), np.floor(np.float32(scale) * np.sqrt(d2, dtype=np.float32), dtype=np.float32)).astype(np.uint8)
         other = Context(self.p, self.device)
@@ -846,7 +925,7 @@ class Context:
         tab = np.ascontiguousarray(cost, np.uint16).reshape(-1) if cost is not None else None
         if tab is not None and len(tab) != 256:
             raise ValueError("join_trees_geodesic: the cost table has 256 entries")
-        o = GeoJoinOpts(int(thr), int(limit), float(step), tab.ctypes.data_as(C.POINTER(C.c_uint16)) if tab is not None else None)
+        o = GeoJoinOpts(self._thr(thr), int(limit), float(step), tab.ctypes.data_as(C.POINTER(C.c_uint16)) if tab is not None else None)
         info = GeoJoinInfo()
         nb, npath = C.c_int64(), C.c_int64()
         cap_b, cap_p = 64, 4096
@@ -859,6 +938,59 @@ class Context:
                 break
             cap_b, cap_p = max(cap_b, nb.value), max(cap_p, npath.value)
         return bridges[:nb.value].copy(), {"vox": vox[:npath.value].copy(), "shape": tuple(int(v) for v in self.shape)}, info.as_dict()
+
+    def auto_threshold(self, method="otsu", lo=0, top_ppm=None, hist=False):
+        """pnr_auto_threshold: the threshold of the context's volume under the rule of include/pnr_hip.h, from one histogram pass on the GPU
+        -> the info dict of threshold_from_hist, or (info, H uint64[256]) with hist=True.  The context stays as it is."""
+        o = _threshold_opts(method, lo, top_ppm)
+        info = ThresholdInfo()
+        H = np.zeros(256, np.uint64) if hist else None
+        check(self.L.pnr_auto_threshold(self.h, C.byref(o), C.byref(info), H.ctypes.data if hist else None))
+        return (info.as_dict(), H) if hist else info.as_dict()
+
+    def _thr(self, thr):
+        """the thr of a tool: a number as it is (-1: the tool's own mean rule), or a threshold word (parse_threshold) resolved by
+        auto_threshold on the context's current volume"""
+        if not isinstance(thr, str):
+            return int(thr)
+        method, lo, ppm = parse_threshold(thr)
+        return self.auto_threshold(method, lo, ppm)["thr"]
+
+    def local_threshold(self, r, offset=0, scale_256=256, floor=1, binary=False, volume=True):
+        """pnr_local_threshold: a voxel is kept where V >= floor and 256 n V >= scale_256 S + 256 offset n, with n and S the size and the
+        sum of the box (r, r, int(r / zdist)) around it cut to the volume; out = V (255 with binary) where kept, else 0 -> (info dict
+        {n_vox, n_kept, sum_in, sum_out, rx, ry, rz}, out uint8[l, h, w] or None).  The context and its volume stay as they are."""
+        o = LocalOpts(int(r), int(offset), int(scale_256), int(floor), int(bool(binary)), 0)
+        info = LocalInfo()
+        out = np.empty(self.shape, np.uint8) if volume else None
+        check(self.L.pnr_local_threshold(self.h, C.byref(o), C.byref(info), out.ctypes.data if volume else None))
+        return info.as_dict(), out
+
+    def local_threshold_volume(self, r, offset=0, scale_256=256, floor=1, binary=False):
+        """pnr_local_threshold_volume: the traced volume is replaced by its local threshold (see local_threshold) -> the info dict.  The
+        result is an owned volume (a borrowed one is left as it was and released) and the later pipeline state is invalidated."""
+        o = LocalOpts(int(r), int(offset), int(scale_256), int(floor), int(bool(binary)), 0)
+        info = LocalInfo()
+        check(self.L.pnr_local_threshold_volume(self.h, C.byref(o), C.byref(info)))
+        self._keep = None
+        return info.as_dict()
+
+    def tap_histogram(self, data, offset=0):
+        """pnr_test_histogram (test tap): the histogram kernel on the bytes `data`, `offset` bytes past a 16-byte boundary -> uint64[256]"""
+        data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        H = np.zeros(256, np.uint64)
+        check(self.L.pnr_test_histogram(self.h, data.ctypes.data, len(data), int(offset), H.ctypes.data))
+        return H
+
+    def tap_local_threshold(self, V, r, offset=0, scale_256=256, floor=1, binary=False):
+        """pnr_test_local_threshold (test tap): local_threshold on the volume V (l, h, w) of any size -> (info dict, out)"""
+        V = np.ascontiguousarray(V, np.uint8)
+        l, h, w = V.shape
+        o = LocalOpts(int(r), int(offset), int(scale_256), int(floor), int(bool(binary)), 0)
+        info = LocalInfo()
+        out = np.empty(V.shape, np.uint8)
+        check(self.L.pnr_test_local_threshold(self.h, V.ctypes.data, w, h, l, C.byref(o), C.byref(info), out.ctypes.data))
+        return info.as_dict(), out
 
     def set_stream(self, stream_ptr):
         check(self.L.pnr_set_stream(self.h, stream_ptr))
