@@ -1007,6 +1007,58 @@ typedef struct pnr_local_info {
 int pnr_local_threshold(pnr_ctx *ctx, const pnr_local_opts *opts, pnr_local_info *info /* nullable */, uint8_t *out /* N, host, nullable */);
 int pnr_local_threshold_volume(pnr_ctx *ctx, const pnr_local_opts *opts, pnr_local_info *info /* nullable */);
 
+/* Pruning a tree's short side branches, and the per-node morphometry a tree-order file is followed by (beyond the reference; the step
+ * Vaa3D does by rounds of "delete the short terminal branches, recount, delete again").  The rule is decided in ONE pass from one
+ * quantity per node, its height, and does not depend on the order of the nodes except through one stated tie rule; the tests restate
+ * it in numpy (tests/prune_ref.py).  Every value below is exact.
+ *   Input.  A forest: xyz (n x 3 f32), radius (n f32, NULL = all 0), parent[i] in [-1, n), any negative value = root, no cycle: the
+ *     layout of pnr_join_trees.  Options {zscale, min_length, radius_factor, min_tree}; opts = NULL = {1, 0, 0, 0}.
+ *   Units.  Every length is an integer in units of 1/256 xy voxel: Q(x) = floor(256 x + 0.5), evaluated in double.
+ *   1 Edge.  For a non-root i with parent p: q[i] = Q(sqrt(dx*dx + dy*dy + dz*dz)), the differences taken in double from the f32
+ *     inputs, dz times (double)zscale, the sum from the left, no contraction, sqrt correctly rounded.  q[root] = 0.
+ *   2 Height.  H[i] = 0 for a leaf, else the maximum over the children c of q[c] + H[c].
+ *   3 Continuing child.  Of a node with children: the child with the largest q[c] + H[c]; at a tie the smallest index.
+ *   4 Segment heads.  Every root is a head, and so is every node that is not its parent's continuing child.  seg[i] = the nearest head on
+ *     the path from i to its root, i included.  S[c] = q[c] + H[c] for a non-root head, S = H for a root.
+ *   5 Removal.  A non-root head c with parent p is removed iff S[c] < max(Q(min_length), Q((double)radius_factor * radius[p])); a root
+ *     is removed iff H[root] < Q(min_tree); a node is removed iff some head on its path to the root, itself included, is removed.  With
+ *     all three options 0 nothing is removed: the call is the morphometry alone.
+ *   6 Per-node outputs (n entries each, all nullable): keep (u8, 1 = stays), height (u32, H), path (u32, the sum of q from the root),
+ *     order (i32, the number of non-root heads on the path from the root, i included: the centrifugal branch order), seg (i32).
+ *   7 Range.  If any q[c] + H[c] or any path reaches 2^32 units (2^24 xy voxels of path) the call fails with PNR_E_ARG; nothing wraps.
+ *     1 <= n < 2^31.
+ *   Consequences: a continuing child is never removed on account of its own segment; the heights of the kept nodes do not change, so
+ *     pruning the pruned tree removes nothing; keep is monotone in min_length.
+ *   pnr_prune_info: n, n_roots, n_leaves (no child), n_branch (2 or more children), n_segments (heads); n_removed (nodes),
+ *     n_removed_segments (heads among them), n_removed_trees (roots among them); length_in, length_out (the sums of q over all and over
+ *     the kept nodes); h_max, order_max (over all nodes); rounds_up, rounds_down (the launches of the two jumping loops; 0 on the host).
+ *   PNR_E_ARG: n outside the range or xyz / parent missing, zscale <= 0, a negative (or not finite) option, a coordinate or radius that
+ *     is not finite, a parent >= n, a cycle, the range of 7.
+ * pnr_prune_tree: the rule on ctx's GPU (prune.hip) by pointer jumping: ceil(log2(depth)) + 1 launches up (heights, paths) and as many
+ *   down (order, segment, removal), depth = the most edges between a node and its root; no kernel walks a chain.  It needs no volume and
+ *   leaves the pipeline state alone; every device buffer (about 100 bytes per node) is freed before it returns (PNR_E_NOMEM: an
+ *   allocation failed).  Kernel time group "prune".
+ * pnr_prune_tree_host: the same rule as one sequential pass in topological order (prune_rule.cpp); pure host, no context.
+ * pnr_prune_apply: pure host.  The kept nodes in input order: new_index_out[i] (n entries, nullable) = the new index of node i or -1,
+ *   parent_out (n entries, nullable; the first *m are written) = the remapped parent of every kept node, *m = their number.  A file in
+ *   tree order stays in tree order.  PNR_E_ARG: a parent >= n, a kept node whose parent is removed. */
+typedef struct pnr_prune_opts {
+    float zscale, min_length, radius_factor, min_tree;
+} pnr_prune_opts; /* NULL = {1, 0, 0, 0} */
+typedef struct pnr_prune_info {
+    int64_t n, n_roots, n_leaves, n_branch, n_segments, n_removed, n_removed_segments, n_removed_trees;
+    uint64_t length_in, length_out;
+    uint32_t h_max;
+    int32_t order_max, rounds_up, rounds_down;
+} pnr_prune_info;
+int pnr_prune_tree(pnr_ctx *ctx, const float *xyz /* n x 3 */, const float *radius /* n, nullable */, const int32_t *parent /* n */, int64_t n,
+                   const pnr_prune_opts *opts /* NULL = defaults */, pnr_prune_info *info /* nullable */, uint8_t *keep, uint32_t *height, uint32_t *path,
+                   int32_t *order, int32_t *seg);
+int pnr_prune_tree_host(const float *xyz /* n x 3 */, const float *radius /* n, nullable */, const int32_t *parent /* n */, int64_t n,
+                        const pnr_prune_opts *opts /* NULL = defaults */, pnr_prune_info *info /* nullable */, uint8_t *keep, uint32_t *height, uint32_t *path,
+                        int32_t *order, int32_t *seg);
+int pnr_prune_apply(const int32_t *parent /* n */, const uint8_t *keep /* n */, int64_t n, int32_t *new_index_out, int32_t *parent_out, int64_t *m);
+
 /* How pnr_trace_batch / pnr_trace_replay schedule the particle filter on the GPU (results are bit-identical):
  * 0 = one launch per SMC phase over all active traces of a batch (default), 1 = one persistent work-group per trace. */
 int pnr_set_smc_driver(pnr_ctx *ctx, int driver);
@@ -1047,7 +1099,7 @@ int pnr_set_option(pnr_ctx *ctx, const char *key, int64_t value);
 int pnr_get_option(pnr_ctx *ctx, const char *key, int64_t *value);
 
 /* Per-kernel-group device time (HIP events on the ctx stream) accumulated since the last reset:
- * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish"),"watershed" (pnr_watershed: the sum of "watershed_init", "watershed_compact", "watershed_flood", "watershed_label" and "watershed_finish"),"threshold" (pnr_auto_threshold: the histogram),"local_threshold" (pnr_local_threshold / pnr_local_threshold_volume: the three passes of every slab).  Enabled by set_profiling. */
+ * groups: "gauss","hessian_eigen","j8","seed_maxima","soma","zncc","smc" (sampling kernel; the whole trace kernel of the persistent driver),"smc_sums","smc_predict","smc_update","smc_cube" (the traces' cubes fetched once per step),"recon" (pnr_reconstruct_ctx),"volume" (pnr_set_volume_u16: windowing to 8 bits),"radius" (pnr_measure_radii),"filter" (pnr_filter_volume: median and top-hat),"distance" (pnr_point_segment_distance / pnr_tree_distance),"join" (pnr_nearest_other / pnr_join_trees),"render" (pnr_render_tree / pnr_tree_coverage: the sum of "render_scatter" and "render_finish"),"components" (pnr_label_components / pnr_despeckle_volume: the sum of its "components_*" phases),"edt" (pnr_distance_transform: the sum of "edt_threshold", "edt_x", "edt_y", "edt_z", "edt_stats", "edt_sample"),"geodesic" (pnr_geodesic_distance: the sum of its "geodesic_*" phases),"geojoin" (pnr_geodesic_bridges: the sum of "geojoin_meet_w" and "geojoin_meet_e"),"morph" (pnr_morph_reconstruct / pnr_morph_volume: the sum of "morph_init", "morph_compact", "morph_relax" and "morph_finish"),"watershed" (pnr_watershed: the sum of "watershed_init", "watershed_compact", "watershed_flood", "watershed_label" and "watershed_finish"),"threshold" (pnr_auto_threshold: the histogram),"local_threshold" (pnr_local_threshold / pnr_local_threshold_volume: the three passes of every slab),"prune" (pnr_prune_tree: every launch of the call).  Enabled by set_profiling. */
 int pnr_set_profiling(pnr_ctx *ctx, int enable);
 int pnr_get_kernel_ms(pnr_ctx *ctx, const char *group, double *ms, int64_t *launches);
 int pnr_reset_kernel_ms(pnr_ctx *ctx);

@@ -1,5 +1,5 @@
 // api_tools.cpp -- the extern "C" boundary of libpnr_hip.so (include/pnr_hip.h), third part: the tools on the volume (filter, components,
-// distance transform, skeleton, geodesic distance, morphological reconstruction, watershed, thresholds, radii) and on trees (distance, join, geodesic join, render), with their pure-host test
+// distance transform, skeleton, geodesic distance, morphological reconstruction, watershed, thresholds, radii) and on trees (distance, join, geodesic join, render, prune), with their pure-host test
 // taps (include/pnr_hip_test.h).  An entry point checks its arguments first, then the state (args.h holds the shared rules), and hands
 // over to the tool's own file; no tool needs or touches the pipeline state of the context (Frangi, seeds, graph).
 #include "args.h"
@@ -18,6 +18,7 @@
 #include "morph.h"
 #include "watershed.h"
 #include "threshold.h"
+#include "prune.h"
 #include "../host/stack_io.h"
 
 namespace args = pnr::args;
@@ -416,6 +417,32 @@ int pnr_join_expand(const float *xyz, const int32_t *parent, int64_t n, const pn
                 (long long)w, (long long)h, (long long)l);
     for (int64_t i = 0; i < n; i++) PNR_REQUIRE(parent[i] < n, PNR_E_ARG, "%s: parent[%lld] = %d outside [-1, %lld)", who, (long long)i, parent[i], (long long)n);
     return pnr_geojoin_expand(xyz, parent, n, bridges, nb, path_vox, n_path, w, h, l, xyz_out, parent_out, bridge_of, cap_nodes, n_nodes, join_out);
+}
+
+// ---- pruning the tree (prune_rule.cpp, prune.hip): the shared arguments first; neither a volume nor any pipeline state is needed or touched ----
+int pnr_prune_tree(pnr_ctx *c, const float *xyz, const float *radius, const int32_t *parent, int64_t n, const pnr_prune_opts *opts, pnr_prune_info *info, uint8_t *keep,
+                   uint32_t *height, uint32_t *path, int32_t *order, int32_t *seg)
+{
+    static const char *who = "pnr_prune_tree";
+    PNR_REQUIRE(c, PNR_E_ARG, "null ctx");
+    pnr_prune_opts o;
+    PNR_TRY(pnr::prune_args(who, xyz, radius, parent, n, opts, o));
+    PNR_HIP(hipSetDevice(c->device));
+    return pnr_prune_run(c, who, xyz, radius, parent, n, o, info, keep, height, path, order, seg);
+}
+
+int pnr_prune_tree_host(const float *xyz, const float *radius, const int32_t *parent, int64_t n, const pnr_prune_opts *opts, pnr_prune_info *info, uint8_t *keep,
+                        uint32_t *height, uint32_t *path, int32_t *order, int32_t *seg)
+{
+    static const char *who = "pnr_prune_tree_host";
+    pnr_prune_opts o;
+    PNR_TRY(pnr::prune_args(who, xyz, radius, parent, n, opts, o));
+    return pnr::prune_rule(who, xyz, radius, parent, n, o, info, keep, height, path, order, seg);
+}
+
+int pnr_prune_apply(const int32_t *parent, const uint8_t *keep, int64_t n, int32_t *new_index_out, int32_t *parent_out, int64_t *m)
+{
+    return pnr::prune_apply(parent, keep, n, new_index_out, parent_out, m);
 }
 
 // ---- rendering the tree (render.hip): arguments first; pnr_render_tree needs no volume, neither call touches the pipeline state ----

@@ -44,6 +44,17 @@ struct UnionFind {
     }
 };
 
+// the parent links as a union-find; a link inside one set closes a cycle (every node has at most one link of its own)
+inline int link_trees(const int32_t *parent, int64_t n, UnionFind &uf, const char *who)
+{
+    for (int64_t i = 0; i < n; i++) {
+        PNR_REQUIRE(parent[i] < n, PNR_E_ARG, "%s: parent[%lld] = %d outside [-1, %lld)", who, (long long)i, parent[i], (long long)n);
+        if (parent[i] < 0) continue;
+        PNR_REQUIRE(uf.unite((int32_t)i, parent[i]), PNR_E_ARG, "%s: the parent chain of node %lld does not end (a cycle)", who, (long long)i);
+    }
+    return PNR_OK;
+}
+
 // parent[i] in [-1, n) (any negative value = none) without a cycle, or PNR_E_ARG; comp_out[i] (nullable) = the smallest node index of
 // i's input tree -- a label >= 0 per tree
 int join_input_trees(const int32_t *parent, int64_t n, int32_t *comp_out, const char *who);

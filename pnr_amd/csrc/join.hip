@@ -78,16 +78,6 @@ int JoinSearch::run(const int32_t *label, bool root, float *d_out, int32_t *j_ou
 
 // ---- the host side ----
 namespace {
-// the parent links as a union-find; a link inside one set closes a cycle (every node has at most one link of its own)
-int link_trees(const int32_t *parent, int64_t n, UnionFind &uf, const char *who)
-{
-    for (int64_t i = 0; i < n; i++) {
-        PNR_REQUIRE(parent[i] < n, PNR_E_ARG, "%s: parent[%lld] = %d outside [-1, %lld)", who, (long long)i, parent[i], (long long)n);
-        if (parent[i] < 0) continue;
-        PNR_REQUIRE(uf.unite((int32_t)i, parent[i]), PNR_E_ARG, "%s: the parent chain of node %lld does not end (a cycle)", who, (long long)i);
-    }
-    return PNR_OK;
-}
 struct Key { // (bits(d2), lo, hi), compared lexicographically
     uint32_t bits;
     int32_t lo, hi;

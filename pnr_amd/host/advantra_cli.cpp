@@ -29,6 +29,12 @@
 //   --join-swc IN.swc OUT.swc --join-geodesic D -i stack [--zscale Z] [--join-threshold T]: the same on a file and a stack; one JSON line.
 //   --join-swc IN.swc OUT.swc [--join GAP] [--zscale Z] [--join-root ID] [--join-keep-largest]: the same on a file (device -g); one JSON
 //   line {"nodes","trees_in","trees_out","bridges","longest_bridge","rounds"}.
+//   --prune-swc IN.swc [OUT.swc] [--prune-length L] [--prune-radius K] [--prune-min-tree M] [--zscale Z] [--per-node FILE.csv]: the file's side
+//   branches shorter than max(L, K x the radius of the node they leave) and its trees lower than M (xy voxels) removed on the GPU
+//   (pnr_prune_tree on device -g); OUT.swc has the kept nodes in the input's order with ids 1..m under a comment block that ends in
+//   #prune=length:L,radius:K,min_tree:M,removed:N,segments:S; one JSON line with the fields of pnr_prune_info, lengths in voxels; the CSV is
+//   `id,keep,height,path,order,seg_id` per input node.  --prune L[,K[,M]]: the same while tracing (after --join / --join-geodesic, before
+//   --measure-radius, zscale = zdist; #prune= behind #join) and with --skeleton --swc (before the file is written; #prune= behind #skeleton=).
 //   --render-swc IN.swc -i stack [--mask OUT] [--residual OUT] [--per-node FILE.csv] [--zscale Z] [--radius-scale S] [--radius-add A]
 //   [--coverage-threshold T]: the file rendered into the stack on the GPU (pnr_tree_coverage on device -g; the stack goes through the
 //   same volume setup as tracing: --channel, --window / --saturate, --median, --subtract-background); one JSON line with the fields of
@@ -165,6 +171,9 @@ int main(int argc, char **argv)
     unsigned long long join_limit = 0;
     int join_thr = 0;
     std::string join_in, join_out;
+    std::string prune_in, prune_out;
+    bool prune_flag = false, prune_given = false;
+    pnr_prune_opts prune_opts = {1.f, 0.f, 0.f, 0.f};
     advantra::RenderJob render;
     std::string mask_out, residual_out;
     bool coverage = false, render_flag = false, per_node_flag = false;
@@ -406,6 +415,40 @@ int main(int argc, char **argv)
             join_out = argv[++i];
             continue;
         }
+        if (!strcmp(argv[i], "--prune-swc")) {
+            if (i + 1 >= argc || argv[i + 1][0] == '-') { fprintf(stderr, "--prune-swc IN.swc [OUT.swc]\n"); return 1; }
+            prune_in = argv[++i];
+            if (i + 1 < argc && argv[i + 1][0] != '-') prune_out = argv[++i];
+            continue;
+        }
+        if (!strcmp(argv[i], "--prune-length") || !strcmp(argv[i], "--prune-radius") || !strcmp(argv[i], "--prune-min-tree")) {
+            const std::string flag = argv[i];
+            float v = 0;
+            if (!parse_float(i + 1 < argc ? argv[++i] : "", v) || v < 0) {
+                fprintf(stderr, "%s\n", flag == "--prune-length" ? "--prune-length L: the shortest side branch kept, in xy voxels, a number, 0 or more"
+                                        : flag == "--prune-radius" ? "--prune-radius K: a side branch is kept from K times its parent's radius on, a number, 0 or more"
+                                                                   : "--prune-min-tree M: the lowest tree kept, in xy voxels, a number, 0 or more");
+                return 1;
+            }
+            (flag == "--prune-length" ? prune_opts.min_length : flag == "--prune-radius" ? prune_opts.radius_factor : prune_opts.min_tree) = v;
+            prune_flag = true;
+            continue;
+        }
+        if (!strcmp(argv[i], "--prune")) {
+            const std::string txt = i + 1 < argc ? argv[++i] : "";
+            std::vector<std::string> part(1);
+            for (char ch : txt) {
+                if (ch == ',') part.emplace_back();
+                else part.back() += ch;
+            }
+            float v[3] = {0.f, 0.f, 0.f};
+            bool ok = part.size() <= 3;
+            for (size_t k = 0; ok && k < part.size(); k++) ok = parse_float(part[k].c_str(), v[k]) && v[k] >= 0;
+            if (!ok) { fprintf(stderr, "--prune L[,K[,M]]: numbers, 0 or more: the shortest side branch kept, times its parent's radius, the lowest tree kept (xy voxels)\n"); return 1; }
+            S0.prune = prune_given = true;
+            S0.prune_opts = pnr_prune_opts{1.f, v[0], v[1], v[2]};
+            continue;
+        }
         if (!strcmp(argv[i], "--per-node")) {
             if (i + 1 >= argc) { fprintf(stderr, "--per-node PREFIX (--distance) or FILE.csv (--render-swc)\n"); return 1; }
             per_node = argv[++i];
@@ -556,7 +599,7 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool rendering = !render.swc.empty();
-    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt && !geo) || (zscale_flag && !distance && join_in.empty() && !rendering && !components && !edt && !geo && !skeleton)) {
+    if ((dist_flag && !distance) || (per_node_flag && !distance && !rendering && !edt && !geo && prune_in.empty()) || (zscale_flag && !distance && join_in.empty() && prune_in.empty() && !rendering && !components && !edt && !geo && !skeleton)) {
         fprintf(stderr, "--distance-step / --distance-threshold / --zscale / --per-node need --distance A.swc B.swc (--zscale: or --join-swc or --skeleton; --zscale, --per-node: or --render-swc, --edt or --geodesic)\n");
         return 1;
     }
@@ -575,6 +618,21 @@ int main(int argc, char **argv)
     if (!morph_out.empty() && !morph) { fprintf(stderr, "--morph-out needs --morph -i stack\n"); return 1; }
     if (S0.local.binary && !S0.local.r) { fprintf(stderr, "--local-binary needs --local-threshold R\n"); return 1; }
     if (auto_flag && !auto_thr) { fprintf(stderr, "--threshold-lo / --histogram need --auto-threshold -i stack\n"); return 1; }
+    if (prune_flag && prune_in.empty()) { fprintf(stderr, "--prune-length / --prune-radius / --prune-min-tree need --prune-swc IN.swc [OUT.swc]\n"); return 1; }
+    if (prune_given && !prune_in.empty()) { fprintf(stderr, "--prune L[,K[,M]] and --prune-swc: one or the other (--prune-swc takes --prune-length, --prune-radius, --prune-min-tree)\n"); return 1; }
+    if (prune_given && (geo || edt || components || rendering || distance || !join_in.empty() || info || morph || ws || auto_thr || !swc_info.empty() || (skeleton && skel_job.swc.empty()))) {
+        fprintf(stderr, "--prune L[,K[,M]] needs a tracing run or --skeleton --swc OUT.swc\n");
+        return 1;
+    }
+    if (!prune_in.empty()) {
+        if (skeleton || skel_flag || geo || geo_flag || edt || edt_flag || components || comp_flag || thr_flag || rendering || distance || !join_in.empty() || info || S0.despeckle ||
+            S0.measure_radius || join_given || join_geodesic || join_flag || !paras.empty() || morph || ws || ws_flag || auto_thr || !swc_info.empty()) {
+            fprintf(stderr, "--prune-swc: not with a tracing run (-p), another tool mode, --threshold, --despeckle, --measure-radius or --join\n");
+            return 1;
+        }
+        prune_opts.zscale = dist_opts.zscale;
+        return advantra::prune_swc_file(prune_in, prune_out, prune_opts, per_node, device) ? 0 : 1;
+    }
     if (!swc_info.empty()) return advantra::print_swc_info(swc_info) ? 0 : 1;
     if (auto_thr) {
         if (skeleton || skel_flag || geo || geo_flag || edt || edt_flag || components || comp_flag || thr_flag || rendering || distance || !join_in.empty() || info || S0.despeckle ||
@@ -593,6 +651,7 @@ int main(int argc, char **argv)
         }
         if (infiles.empty()) { fprintf(stderr, "--skeleton needs -i <stack>\n"); return 1; }
         if (zscale_flag && dist_opts.zscale < 1.f) { fprintf(stderr, "--skeleton: --zscale Z: a number, 1 or more\n"); return 1; }
+        skel_job.prune = prune_given, skel_job.prune_opts = S0.prune_opts;
         return advantra::skeleton_file(skel_job, infiles, raw_dims, zscale_flag ? dist_opts.zscale : 1.f, device) ? 0 : 1;
     }
     if (morph) {

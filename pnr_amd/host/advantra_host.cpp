@@ -63,6 +63,16 @@ void print_flags()
     printf("  --join-threshold T        voxels below T are impassable, 0..255, -1: the stack's mean (default 0: every voxel is passable)\n");
     printf("--join-swc IN.swc OUT.swc --join-geodesic D -i stack   the same on an SWC file and a stack (the volume setup of --geodesic; [--zscale Z]\n");
     printf("                          [--join-threshold T] [--join-root ID] [--join-keep-largest]); one JSON line with the summary\n");
+    printf("--prune L[,K[,M]]         while tracing (after --join / --join-geodesic, before --measure-radius), and with --skeleton --swc: side branches shorter than\n");
+    printf("                          max(L, K x the radius of the node they leave) and trees lower than M, in xy voxels, are removed on the GPU in one pass (a\n");
+    printf("                          branch = what hangs on a node beside its longest continuation); the comment block gains\n");
+    printf("                          #prune=length:L,radius:K,min_tree:M,removed:N,segments:S\n");
+    printf("--prune-swc IN.swc [OUT.swc]   the same on an SWC file: OUT.swc has the kept nodes in the input's order with ids 1..m; one JSON line with the counts,\n");
+    printf("                          lengths in xy voxels; without a threshold it is the morphometry of the file\n");
+    printf("  --prune-length L | --prune-radius K | --prune-min-tree M   the three thresholds, numbers, 0 or more (default 0: off)\n");
+    printf("  --zscale Z                z counts Z-fold (default 1)\n");
+    printf("  --per-node FILE.csv       `id,keep,height,path,order,seg_id` per input node: its longest way down, its way from the root (xy voxels), its\n");
+    printf("                            branch order and the first node of its segment\n");
     printf("--render-swc IN.swc       render an SWC file into the stack given with -i (the same volume setup as tracing) on the GPU; one JSON line with\n");
     printf("                          the coverage counts: how much of the foreground the tree covers, how much of the tree lies on signal\n");
     printf("  --mask OUT                write the mask (255 under the tree) as a multi-page 8-bit TIFF, or bare bytes for a .raw name\n");
@@ -234,6 +244,7 @@ static std::string swc_comment(const std::vector<std::string> &paras, const pnr_
         c << "\n#join=geodesic:" << settings().join_limit << ",thr:" << join->join_thr_used << ",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->"
           << join->join_trees_out << ",inserted:" << join->join_inserted << thr_method_swc(settings().join_word);
     else if (join) c << "\n#join=gap:" << f32_text(settings().join_gap) <<",bridges:" << join->join_bridges << ",trees:" << join->join_trees_in << "->" << join->join_trees_out;
+    if (cover && cover->have_prune) c << "\n" << prune_comment(settings().prune_opts, cover->prune);
     if (radius_thr) {
         const pnr_radius_opts &ro = settings().radius;
         c << "\n#radius=measured,thr=";
@@ -720,6 +731,37 @@ struct Pipeline {
         return true;
     }
 
+    bool prune() // --prune: short side branches and low trees go (pnr_prune_tree); the kept nodes stay in their order
+    {
+        if (!S.prune || R.tree.size() <= 1) return true;
+        const int64_t n = (int64_t)R.tree.size() - 1; // without the dummy
+        const TreeArrays T = tree_arrays(R.tree, R.parent, nullptr);
+        pnr_prune_opts po = S.prune_opts;
+        po.zscale = p.zdist;
+        std::vector<uint8_t> keep((size_t)n);
+        std::vector<int32_t> idx((size_t)n), par((size_t)n);
+        int64_t m = 0;
+        Profile prof(ctx, "prune", S.timing);
+        if (pnr_prune_tree(ctx, T.xyz.data() + 3, T.rad.data() + 1, T.par.data() + 1, n, &po, &R.prune, keep.data(), nullptr, nullptr, nullptr, nullptr) != PNR_OK ||
+            pnr_prune_apply(T.par.data() + 1, keep.data(), n, idx.data(), par.data(), &m) != PNR_OK)
+            return lib_fail(nullptr);
+        R.have_prune = true;
+        std::vector<pnr_node> tree(1, R.tree[0]);
+        std::vector<int32_t> parent(1, R.parent[0]);
+        for (int64_t v = 0; v < n; v++) {
+            if (!keep[(size_t)v]) continue;
+            tree.push_back(R.tree[(size_t)v + 1]);
+            parent.push_back(par[(size_t)idx[(size_t)v]] < 0 ? -1 : par[(size_t)idx[(size_t)v]] + 1);
+        }
+        R.tree.swap(tree);
+        R.parent.swap(parent);
+        printf("prune... %lld of %lld nodes in %lld segments removed, %zu nodes written\n", (long long)R.prune.n_removed, (long long)n, (long long)R.prune.n_removed_segments,
+               R.tree.size() - 1);
+        prof.end();
+        if (S.timing) fprintf(stderr, "[pnr host] prune: %d + %d rounds, kernels %.3f ms in %lld launches\n", (int)R.prune.rounds_up, (int)R.prune.rounds_down, prof.ms, (long long)prof.launches);
+        return true;
+    }
+
     bool measure_radius() // --measure-radius: the radius column, measured on the volume this context traced
     {
         if (!S.measure_radius) return true;
@@ -831,7 +873,7 @@ bool reconstruction_func(const unsigned char *data1d, long long w, long long h, 
     R.t_frangi = secs(P.t0, P.t1); R.t_seeds = secs(P.t1, P.t2); R.t_select = secs(P.t2, P.t3); R.t_trace = secs(P.t3, P.t4);
     R.t_setup = secs(P.t_begin, P.t0); // context, upload of the stack, soma path
     printf("\n-----\n%g%% seeds used \n", P.nseeds ? 100.0 * P.used / P.nseeds : 0.0);
-    if (!P.reconstruct() || !P.join()) return false;
+    if (!P.reconstruct() || !P.join() || !P.prune()) return false;
     P.t5 = clk::now();
     R.t_recon = secs(P.t4, P.t5);
     if (!P.measure_radius() || !P.render()) return false;

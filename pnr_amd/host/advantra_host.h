@@ -43,6 +43,8 @@ struct Result {
     long long join_inserted = 0;   // --join-geodesic: the nodes pnr_join_expand inserted
     int join_thr_used = 0;         // ... and the threshold pnr_geodesic_bridges used
     double t_join = 0;
+    bool have_prune = false;       // --prune: what pnr_prune_tree reported
+    pnr_prune_info prune = {};
     bool have_coverage = false;    // --mask / --residual / --coverage: the final tree rendered on the traced volume (pnr_tree_coverage)
     pnr_coverage coverage = {};
     double t_render = 0;
@@ -116,6 +118,13 @@ struct Settings {
     unsigned long long join_limit = 0;
     int join_thr = 0;
     long long join_root_id = 0; // 0: the first soma node, if any
+    // --prune L[,K[,M]]: the forest -- after --join / --join-geodesic, before --measure-radius -- loses its side branches shorter than
+    // max(L, K x the radius of the node they leave) and its trees lower than M xy voxels on the GPU (pnr_prune_tree, zscale = zdist, the
+    // radii the file would be written with); the kept nodes stay in their order and the comment block gains
+    // #prune=length:L,radius:K,min_tree:M,removed:N,segments:S behind #join.  Without --join soma nodes are roots and go only under M.
+    // With --skeleton --swc the same is applied to the skeleton before the file is written (radius = the distance transform).
+    bool prune = false;
+    pnr_prune_opts prune_opts = {1.f, 0.f, 0.f, 0.f}; // (zscale is filled in where it runs)
     // --mask OUT, --residual OUT, --coverage: the final tree -- after --join and --measure-radius, with the f32 radius each SWC line is
     // written from and zscale = zdist -- is rendered on the traced volume (pnr_tree_coverage): OUT receives the mask (255 under the
     // tree) / the residual (the volume where the tree is not) as a stack (save_stack_u8), and the comment block gains a #coverage= line.
@@ -188,6 +197,14 @@ bool join_swc_geodesic_file(const std::string &in, const std::string &out, const
 // (not empty) are written with save_stack_u8, `per_node` is a CSV `id,vox,fg,sum` per node under a header line, and one JSON line has
 // the fields of pnr_coverage, then "nodes" and "items".  Without a stack, raw_dims = "w,h,l" gives the grid and only the mask is
 // written (pnr_render_tree); the JSON line is {"n_vox", "n_tree", "nodes", "items"}.
+// advantra_cli --prune-swc IN.swc [OUT.swc]: pnr_prune_tree of the file on `device` (opts: zscale and the three thresholds in xy voxels).
+// OUT.swc (not empty): the kept nodes in the input's order with ids 1..m, type and radius carried over, under a comment block that ends in
+// #prune=length:L,radius:K,min_tree:M,removed:N,segments:S.  per_node (not empty): a CSV `id,keep,height,path,order,seg_id` per input node
+// under a header line, the lengths in xy voxels (units / 256, exact in %.17g).  Prints one JSON line with the fields of pnr_prune_info, the
+// lengths in voxels.
+bool prune_swc_file(const std::string &in, const std::string &out, const pnr_prune_opts &opts, const std::string &per_node, int device);
+// the #prune= line of an SWC comment block (no newline)
+std::string prune_comment(const pnr_prune_opts &opts, const pnr_prune_info &info);
 struct RenderJob {
     std::string swc, mask, residual, per_node;
     pnr_render_opts opts = {1.f, 1.f, 0.f, -1};
@@ -233,10 +250,12 @@ bool geodesic_file(const GeodesicJob &job, const std::vector<char *> &infiles, c
 // name.  `swc` (not empty): the skeleton as a tree -- pnr_skeleton_forest, then pnr_join_reroot at the voxel with the largest D2 (the
 // smallest index on ties); coordinates = the voxel's x, y, z, radius = sqrtf(D2) of pnr_distance_transform at those points (thr = thr_used,
 // rmax = 64), type 2, ids 1..n in tree order with every parent before its children; the comment block ends in
-// #skeleton=thr:T,rounds:R,voxels:K,trees:C.
+// #skeleton=thr:T,rounds:R,voxels:K,trees:C, followed by #prune= (as --prune-swc writes it) when the job prunes.
 struct SkeletonJob {
     pnr_thin_opts opts = {-1, 0};
     std::string out, swc;
+    bool prune = false; // --prune L[,K[,M]]: the tree of `swc` is pruned before it is written (pnr_prune_tree, zscale = the context's zdist)
+    pnr_prune_opts prune_opts = {1.f, 0.f, 0.f, 0.f};
 };
 bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, const std::string &raw_dims, float zscale, int device);
 // advantra_cli --morph -i stack [--fill-holes 2d|3d] [--hmax H | --hdome H] --morph-out OUT: the stack after the volume set-up of tracing,

@@ -1,5 +1,5 @@
 // tools.cpp -- the tool modes of advantra_cli (see advantra_host.h): --distance, --join-swc (by gap, or --join-geodesic), --render-swc,
-// --components, --edt, --skeleton, --morph, --watershed, --geodesic and --auto-threshold.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
+// --prune-swc, --components, --edt, --skeleton, --morph, --watershed, --geodesic and --auto-threshold.  Each loads its files, opens one context, makes one call through the C ABI and prints one JSON line.
 #include "host_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -192,6 +192,56 @@ bool join_swc_file(const std::string &in, const std::string &out, float gap, flo
         return false;
     printf("{\"nodes\": %lld, \"trees_in\": %lld, \"trees_out\": %lld, \"bridges\": %lld, \"longest_bridge\": %.9g, \"rounds\": %lld}\n", (long long)written,
            (long long)t_in, (long long)t_out, (long long)nb, nb ? (double)bridges[(size_t)nb - 1].d : 0.0, (long long)rounds);
+    return true;
+}
+
+std::string prune_comment(const pnr_prune_opts &opts, const pnr_prune_info &info)
+{
+    return "#prune=length:" + f32_text(opts.min_length) + ",radius:" + f32_text(opts.radius_factor) + ",min_tree:" + f32_text(opts.min_tree) + ",removed:" +
+           std::to_string((long long)info.n_removed) + ",segments:" + std::to_string((long long)info.n_removed_segments);
+}
+
+bool prune_swc_file(const std::string &in, const std::string &out, const pnr_prune_opts &opts, const std::string &per_node, int device)
+{
+    SwcTree T;
+    if (!read_swc(in, T)) return false;
+    const int64_t n = T.n();
+    if (n == 0) {
+        fprintf(stderr, "%s: no nodes\n", in.c_str());
+        return false;
+    }
+    pnr_params p;
+    pnr_default_params(&p);
+    Ctx ctx;
+    if (!ctx.create(p, device)) return false;
+    std::vector<uint8_t> keep((size_t)n);
+    std::vector<uint32_t> height((size_t)n), path((size_t)n);
+    std::vector<int32_t> order((size_t)n), seg((size_t)n), idx((size_t)n), par((size_t)n);
+    pnr_prune_info pi = {};
+    int64_t m = 0;
+    if (pnr_prune_tree(ctx, T.xyz.data(), T.radius.data(), T.parent.data(), n, &opts, &pi, keep.data(), height.data(), path.data(), order.data(), seg.data()) != PNR_OK)
+        return lib_fail("pnr_prune_tree");
+    if (pnr_prune_apply(T.parent.data(), keep.data(), n, idx.data(), par.data(), &m) != PNR_OK) return lib_fail("pnr_prune_apply");
+    if (!out.empty() && !write_file(out, "w", [&](FILE *f) {
+            fprintf(f, "##n,type,x,y,z,radius,parent\n%s\n", prune_comment(opts, pi).c_str());
+            for (size_t v = 0; v < (size_t)n; v++)
+                if (keep[v])
+                    fprintf(f, "%lld %d %s %s %s %s %lld\n", (long long)idx[v] + 1, T.type[v], f32_text(T.xyz[3 * v]).c_str(), f32_text(T.xyz[3 * v + 1]).c_str(),
+                            f32_text(T.xyz[3 * v + 2]).c_str(), f32_text(T.radius[v]).c_str(), par[(size_t)idx[v]] < 0 ? -1LL : (long long)par[(size_t)idx[v]] + 1);
+        }))
+        return false;
+    if (!per_node.empty() && !write_file(per_node, "w", [&](FILE *f) {
+            fprintf(f, "id,keep,height,path,order,seg_id\n");
+            for (size_t v = 0; v < (size_t)n; v++)
+                fprintf(f, "%lld,%d,%.17g,%.17g,%d,%lld\n", T.id[v], (int)keep[v], height[v] / 256.0, path[v] / 256.0, (int)order[v], T.id[(size_t)seg[v]]);
+        }))
+        return false;
+    printf("{\"nodes\": %lld, \"nodes_out\": %lld, \"zscale\": %.9g, \"min_length\": %.9g, \"radius_factor\": %.9g, \"min_tree\": %.9g, \"n_roots\": %lld, \"n_leaves\": %lld, "
+           "\"n_branch\": %lld, \"n_segments\": %lld, \"n_removed\": %lld, \"n_removed_segments\": %lld, \"n_removed_trees\": %lld, \"length_in\": %.17g, \"length_out\": %.17g, "
+           "\"h_max\": %.17g, \"order_max\": %d, \"rounds_up\": %d, \"rounds_down\": %d}\n",
+           (long long)pi.n, (long long)m, (double)opts.zscale, (double)opts.min_length, (double)opts.radius_factor, (double)opts.min_tree, (long long)pi.n_roots, (long long)pi.n_leaves,
+           (long long)pi.n_branch, (long long)pi.n_segments, (long long)pi.n_removed, (long long)pi.n_removed_segments, (long long)pi.n_removed_trees, (double)pi.length_in / 256.0,
+           (double)pi.length_out / 256.0, pi.h_max / 256.0, (int)pi.order_max, (int)pi.rounds_up, (int)pi.rounds_down);
     return true;
 }
 
@@ -452,14 +502,27 @@ bool skeleton_file(const SkeletonJob &job, const std::vector<char *> &infiles, c
             const int64_t root = std::max_element(d2.begin(), d2.end()) - d2.begin(); // (the first of the largest: the soma guess of --edt)
             if (pnr_join_reroot(par.data(), n, edges.data(), ne, root, par_out.data(), order.data(), comp.data()) != PNR_OK) return lib_fail("pnr_join_reroot");
         }
+        // --prune: the radius column as it is written, then the rule on the nodes in voxel order; a removed node is not written
+        std::vector<uint8_t> keep((size_t)n, 1);
+        pnr_prune_opts po = job.prune_opts;
+        po.zscale = zscale;
+        pnr_prune_info pi = {};
+        if (job.prune && n > 0) {
+            std::vector<float> rad((size_t)n);
+            for (int64_t i = 0; i < n; i++) rad[(size_t)i] = sqrtf(d2[(size_t)i]);
+            if (pnr_prune_tree(ctx, xyz.data(), rad.data(), par_out.data(), n, &po, &pi, keep.data(), nullptr, nullptr, nullptr, nullptr) != PNR_OK) return lib_fail("pnr_prune_tree");
+        }
         if (!write_file(job.swc, "w", [&](FILE *f) {
                 fprintf(f, "##n,type,x,y,z,radius,parent\n#skeleton=thr:%d,rounds:%d,voxels:%lld,trees:%lld%s\n", (int)ti.thr_used, (int)ti.rounds, (long long)n, (long long)trees,
                         thr_method_swc(word).c_str());
+                if (job.prune) fprintf(f, "%s\n", prune_comment(po, pi).c_str());
                 std::vector<int64_t> pos((size_t)n, -1);
+                int64_t written = 0;
                 for (int64_t k = 0; k < n; k++) {
                     const size_t v = (size_t)order[(size_t)k];
-                    pos[v] = k + 1;
-                    fprintf(f, "%lld 2 %s %s %s %s %lld\n", (long long)(k + 1), f32_text(xyz[3 * v]).c_str(), f32_text(xyz[3 * v + 1]).c_str(), f32_text(xyz[3 * v + 2]).c_str(),
+                    if (!keep[v]) continue;
+                    pos[v] = ++written;
+                    fprintf(f, "%lld 2 %s %s %s %s %lld\n", (long long)written, f32_text(xyz[3 * v]).c_str(), f32_text(xyz[3 * v + 1]).c_str(), f32_text(xyz[3 * v + 2]).c_str(),
                             f32_text(sqrtf(d2[v])).c_str(), par_out[v] < 0 ? -1LL : (long long)pos[(size_t)par_out[v]]);
                 }
             }))

@@ -273,6 +273,21 @@ class LocalInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
+class PruneOpts(C.Structure):
+    """pnr_prune_opts (include/pnr_hip.h): zscale > 0, min_length, radius_factor and min_tree >= 0 (xy voxels; all 0: nothing is removed)"""
+    _fields_ = [(k, C.c_float) for k in ("zscale", "min_length", "radius_factor", "min_tree")]
+
+
+class PruneInfo(C.Structure):
+    """pnr_prune_info: the exact summary of a pruning (lengths in units of 1/256 xy voxel; rounds_up / rounds_down: launches of the two
+    jumping loops on the GPU, 0 on the host)"""
+    _fields_ = ([(k, C.c_int64) for k in ("n", "n_roots", "n_leaves", "n_branch", "n_segments", "n_removed", "n_removed_segments", "n_removed_trees")] +
+                [("length_in", C.c_uint64), ("length_out", C.c_uint64), ("h_max", C.c_uint32)] + [(k, C.c_int32) for k in ("order_max", "rounds_up", "rounds_down")])
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 PNR_LOCAL_MAX_R = 64
 
 
@@ -437,6 +452,9 @@ PRODUCT_SIGNATURES = {
     "pnr_auto_threshold": (_rc, [_vp, C.POINTER(ThresholdOpts), C.POINTER(ThresholdInfo), _vp]),
     "pnr_local_threshold": (_rc, [_vp, C.POINTER(LocalOpts), C.POINTER(LocalInfo), _vp]),
     "pnr_local_threshold_volume": (_rc, [_vp, C.POINTER(LocalOpts), C.POINTER(LocalInfo)]),
+    "pnr_prune_tree": (_rc, [_vp, _vp, _vp, _vp, _i64, C.POINTER(PruneOpts), C.POINTER(PruneInfo), _vp, _vp, _vp, _vp, _vp]),
+    "pnr_prune_tree_host": (_rc, [_vp, _vp, _vp, _i64, C.POINTER(PruneOpts), C.POINTER(PruneInfo), _vp, _vp, _vp, _vp, _vp]),
+    "pnr_prune_apply": (_rc, [_vp, _vp, _i64, _vp, _vp, _pi64]),
     "pnr_frangi": (_rc, [_vp, _pf32, _pf32]),
     "pnr_frangi_slab": (_rc, [_vp, _i64, _i64, _pf32, _pf32]),
     "pnr_quantise_j8": (_rc, [_vp, _f32, _f32]),
@@ -672,6 +690,13 @@ class Context:
             cap = nb.value
         res = (out[0], out[1], out[2], bridges[:nb.value].copy())
         return res + ({"trees_in": t0.value, "trees_out": t1.value, "rounds": self.get_option("join_rounds")},) if counts else res
+
+    def prune_tree(self, xyz, radius, parent, zscale=1, min_length=0, radius_factor=0, min_tree=0):
+        """pnr_prune_tree of a forest (n x 3 positions, n radii in xy voxels or None, parent indices with a negative value for a root):
+        a side branch shorter than max(min_length, radius_factor x its parent's radius) and a tree lower than min_tree (xy voxels) are
+        removed by the rule of include/pnr_hip.h -> (info dict, keep uint8[n], height uint32[n], path uint32[n], order int32[n], seg
+        int32[n]); the lengths in units of 1/256 xy voxel.  All three at 0: the morphometry alone.  Needs no volume."""
+        return _prune_call(lambda *a: self.L.pnr_prune_tree(self.h, *a), "prune_tree", xyz, radius, parent, zscale, min_length, radius_factor, min_tree)
 
     def render_tree(self, xyz, radius, parent, shape, zscale=1, rscale=1, radd=0, labels=True, mask=False):
         """pnr_render_tree of a tree (n x 3 positions, n radii in xy voxels, parent indices with a negative value for none) on the grid
@@ -1530,6 +1555,40 @@ def join_expand(xyz, parent, bridges, paths):
     xyz2, parent2, of = np.empty((n2.value, 3), np.float32), np.empty(n2.value, np.int32), np.empty(n2.value - n, np.int32)
     check(L.pnr_join_expand(*args, xyz2.ctypes.data, parent2.ctypes.data, of.ctypes.data if len(of) else None, n2.value, C.byref(n2), join.ctypes.data if nb else None))
     return xyz2, parent2, of, join
+
+
+def _prune_call(fn, who, xyz, radius, parent, zscale, min_length, radius_factor, min_tree):
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    if radius is not None:
+        radius = np.ascontiguousarray(radius, np.float32).reshape(-1)
+    if len(parent) != len(xyz) or (radius is not None and len(radius) != len(xyz)):
+        raise PnrError(f"{who}: one radius and one parent per node")
+    n = len(xyz)
+    o, info = PruneOpts(float(zscale), float(min_length), float(radius_factor), float(min_tree)), PruneInfo()
+    out = [np.zeros(n, t) for t in (np.uint8, np.uint32, np.uint32, np.int32, np.int32)]
+    check(fn(xyz.ctypes.data if n else None, radius.ctypes.data if radius is not None and n else None, parent.ctypes.data if n else None, n, C.byref(o), C.byref(info),
+             *(a.ctypes.data if n else None for a in out)))
+    return (info.as_dict(), *out)
+
+
+def prune_tree_host(xyz, radius, parent, zscale=1, min_length=0, radius_factor=0, min_tree=0):
+    """pnr_prune_tree_host (pure host; no GPU needed): Context.prune_tree as one sequential pass, the same outputs (rounds_up =
+    rounds_down = 0)"""
+    return _prune_call(load().pnr_prune_tree_host, "prune_tree_host", xyz, radius, parent, zscale, min_length, radius_factor, min_tree)
+
+
+def prune_apply(parent, keep):
+    """pnr_prune_apply (pure host; no GPU needed): the kept nodes in input order -> (new_index int32[n] (-1: removed), parent int32[m]
+    remapped); a keep that holds a child of a removed node is refused"""
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+    if len(parent) != len(keep):
+        raise PnrError("prune_apply: one keep per node")
+    n, m = len(parent), C.c_int64()
+    idx, par = np.empty(n, np.int32), np.empty(n, np.int32)
+    check(load().pnr_prune_apply(parent.ctypes.data if n else None, keep.ctypes.data if n else None, n, idx.ctypes.data if n else None, par.ctypes.data if n else None, C.byref(m)))
+    return idx, par[:m.value].copy()
 
 
 def _tree_arrays(who, xyz, radius, parent):
