@@ -19,6 +19,11 @@ int pnr_hessian(pnr_ctx *ctx, float sig, float *Dzz, float *Dyy, float *Dyz, flo
 /* Feed externally produced J8/V (host, N each) instead of pnr_frangi's: lets extractSeeds be
  * tested in isolation exactly like SeedExtractor::extractSeeds(tolerance,J8,...,Vx,Vy,Vz). */
 int pnr_set_j8_v(pnr_ctx *ctx, const uint8_t *J8, const uint8_t *Vx, const uint8_t *Vy, const uint8_t *Vz);
+/* pnr_get_frangi of the box lo <= (z, y, x) < hi alone (lo, hi: three values each, z first): the same volumes in HBM, with the same
+ * exact re-run first where J or a direction volume is asked for after a pruned run, but only the box is copied, into dense host arrays
+ * of (hi[0] - lo[0]) x (hi[1] - lo[1]) x (hi[2] - lo[2]) elements (any may be NULL).  For stacks whose whole f32 J a test cannot
+ * afford to download (above 2^31 voxels: 9 GB). */
+int pnr_get_frangi_box(pnr_ctx *ctx, const int64_t *lo, const int64_t *hi, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, uint8_t *Vz);
 
 /* What the GPU half of pnr_extract_seeds_range hands to the host's flood fill for the layers [z0, z1) of the context's J8 (same
  * argument rules), nl = z1 - z0 layers: the stage runs as it does there (extremes, bitmap and row counts, row prefix, keys and

@@ -46,11 +46,12 @@ int pnr_quantise_j8(pnr_ctx *c, float Jmin, float Jmax)
     return pnr_j8_run(c, Jmin, Jmax);
 }
 
-int pnr_get_frangi(pnr_ctx *c, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, uint8_t *Vz)
+// what a read-back of the Frangi outputs needs in HBM first: the exact J (`exact`: J or a direction volume is asked for) and the
+// direction volumes (`dirs`)
+static int frangi_for_readback(pnr_ctx *c, bool exact, bool dirs)
 {
     PNR_REQUIRE(c && c->have_j8 && c->d_J.get(), PNR_E_STATE, "pnr_get_frangi: run pnr_frangi first");
-    const size_t n = (size_t)c->N;
-    if ((J || Vx || Vy || Vz) && c->frangi_pruned) {
+    if (exact && c->frangi_pruned) {
         // the last run skipped the solver where the response could not reach J8 = 1 (option frangi_prune): J8, the extremes and the
         // seeds are exact, the f32 J and the winning scale of J8 = 0 voxels are not -- recompute without the shortcut, same extremes
         const float jmin = c->Jmin, jmax = c->Jmax;
@@ -60,13 +61,45 @@ int pnr_get_frangi(pnr_ctx *c, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, 
         PNR_TRY(pnr_frangi_run_range(c, c->fr_zs0, c->fr_zs1, false, nullptr, nullptr));
         PNR_TRY(pnr_j8_run(c, jmin, jmax));
     }
-    if (Vx || Vy || Vz) PNR_TRY(pnr_frangi_materialise_v(c)); // the pipeline itself only needs the directions at the seeds
+    if (dirs) PNR_TRY(pnr_frangi_materialise_v(c)); // the pipeline itself only needs the directions at the seeds
+    return PNR_OK;
+}
+
+int pnr_get_frangi(pnr_ctx *c, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, uint8_t *Vz)
+{
+    PNR_TRY(frangi_for_readback(c, J || Vx || Vy || Vz, Vx || Vy || Vz));
+    const size_t n = (size_t)c->N;
     pnr::Call call(c, "pnr_get_frangi");
     if (J) call.down(J, c->d_J.get(), n);
     if (J8) call.down(J8, c->d_J8.get(), n);
     if (Vx) call.down(Vx, c->d_Vx.get(), n);
     if (Vy) call.down(Vy, c->d_Vy.get(), n);
     if (Vz) call.down(Vz, c->d_Vz.get(), n);
+    return call.finish();
+}
+
+// test tap (pnr_hip_test.h): pnr_get_frangi of the box [lo, hi) alone, plane by plane as 2-D copies
+int pnr_get_frangi_box(pnr_ctx *c, const int64_t *lo, const int64_t *hi, float *J, uint8_t *J8, uint8_t *Vx, uint8_t *Vy, uint8_t *Vz)
+{
+    PNR_REQUIRE(c && lo && hi, PNR_E_ARG, "null argument");
+    const int64_t ext[3] = {c->l, c->h, c->w};
+    for (int a = 0; a < 3; a++)
+        PNR_REQUIRE(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= ext[a], PNR_E_ARG, "pnr_get_frangi_box: [%lld, %lld) outside [0, %lld) on axis %d", (long long)lo[a],
+                    (long long)hi[a], (long long)ext[a], a);
+    PNR_TRY(frangi_for_readback(c, J || Vx || Vy || Vz, Vx || Vy || Vz));
+    const size_t bh = (size_t)(hi[1] - lo[1]), bw = (size_t)(hi[2] - lo[2]), w = (size_t)c->w, h = (size_t)c->h;
+    pnr::Call call(c, "pnr_get_frangi_box");
+    const auto box = [&](void *dst, const void *src, size_t es) {
+        if (!dst) return;
+        for (int64_t z = lo[0]; z < hi[0] && call.ok(); z++)
+            call.note(hipMemcpy2DAsync((char *)dst + (size_t)(z - lo[0]) * bh * bw * es, bw * es, (const char *)src + (((size_t)z * h + (size_t)lo[1]) * w + (size_t)lo[2]) * es, w * es,
+                                       bw * es, bh, hipMemcpyDeviceToHost, call.stream()));
+    };
+    box(J, c->d_J.get(), 4);
+    box(J8, c->d_J8.get(), 1);
+    box(Vx, c->d_Vx.get(), 1);
+    box(Vy, c->d_Vy.get(), 1);
+    box(Vz, c->d_Vz.get(), 1);
     return call.finish();
 }
 

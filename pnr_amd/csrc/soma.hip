@@ -248,6 +248,7 @@ int pnr_soma_run(pnr_ctx *c, uint8_t *E8_out, int32_t *threshold)
     call.down(hist, d_hist);
     if (E8_out) call.down(E8_out, d_E, (size_t)n);
     if ((rc = call.finish())) return rc;
+    if ((rc = pnr::maxentropy_bins_fit(who, hist))) return rc; // (a mostly dark stack above 2^31 voxels: have_soma stays false)
     const int th = pnr::maxentropy_from_hist(hist); // (threshold_rule.cpp: shared with PNR_THR_MAXENTROPY)
     if (threshold) *threshold = th;
     call.launch(row_count, dim3((unsigned)rows), dim3(64), (const unsigned char *)d_E, w, th, d_cnt.get());

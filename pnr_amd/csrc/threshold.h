@@ -14,8 +14,10 @@ namespace pnr {
 
 // The rule of include/pnr_hip.h on the 256 counts: arguments (texts as `who`'s), then *info.  Pure host.
 int threshold_rule(const char *who, const uint64_t *hist, const pnr_threshold_opts *opts, pnr_threshold_info *info);
-// the reference's maxentropy_th (toolbox.cpp:657-737) on the histogram; every count below 2^31 (pnr_soma, PNR_THR_MAXENTROPY)
+// the reference's maxentropy_th (toolbox.cpp:657-737) on the histogram; every count below 2^31 (pnr_soma, PNR_THR_MAXENTROPY).  Both
+// callers ask maxentropy_bins_fit first: PNR_OK, or PNR_E_ARG and "<who>: maxentropy needs every bin below 2^31, bin B holds N".
 unsigned char maxentropy_from_hist(const unsigned long long *h);
+int maxentropy_bins_fit(const char *who, const unsigned long long *h);
 
 } // namespace pnr
 

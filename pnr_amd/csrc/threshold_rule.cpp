@@ -8,6 +8,13 @@
 
 namespace pnr {
 
+// what maxentropy_from_hist asks of its counts: the rule reads a bin as the reference's `int`
+int maxentropy_bins_fit(const char *who, const unsigned long long *h)
+{
+    for (int v = 0; v < 256; v++) PNR_REQUIRE(h[v] < (1ull << 31), PNR_E_ARG, "%s: maxentropy needs every bin below 2^31, bin %d holds %llu", who, v, h[v]);
+    return PNR_OK;
+}
+
 // toolbox.cpp:657-737 on the histogram
 unsigned char maxentropy_from_hist(const unsigned long long *h)
 {
@@ -114,14 +121,15 @@ int threshold_rule(const char *who, const uint64_t *hist, const pnr_threshold_op
         PNR_REQUIRE(o.top_ppm >= 1 && o.top_ppm <= 999999, PNR_E_ARG, "%s: top_ppm = %d outside [1, 999999]", who, o.top_ppm);
     else
         PNR_REQUIRE(o.top_ppm == 0, PNR_E_ARG, "%s: top_ppm = %d, not 0 (only method 3 takes a share)", who, o.top_ppm);
-    u64 n_vox = 0;
+    u64 n_vox = 0, me[256]; // me: the counts as maxentropy_from_hist takes them
     for (int v = 0; v < 256; v++) {
         PNR_REQUIRE(hist[v] < MAX_VOX && n_vox + hist[v] < MAX_VOX, PNR_E_ARG, "%s: more than 2^45 - 1 voxels (bin %d holds %llu)", who, v, (u64)hist[v]);
         n_vox += hist[v];
     }
     if (o.method == PNR_THR_MAXENTROPY) {
         PNR_REQUIRE(o.lo == 0, PNR_E_ARG, "%s: maxentropy needs lo = 0, not %d", who, o.lo);
-        for (int v = 0; v < 256; v++) PNR_REQUIRE(hist[v] < (1ull << 31), PNR_E_ARG, "%s: maxentropy needs every bin below 2^31, bin %d holds %llu", who, v, (u64)hist[v]);
+        for (int v = 0; v < 256; v++) me[v] = hist[v];
+        if (const int rc = maxentropy_bins_fit(who, me)) return rc;
     }
     u64 n = 0, S = 0;
     int v_min = -1, v_max = -1, peak = -1;
@@ -141,11 +149,7 @@ int threshold_rule(const char *who, const uint64_t *hist, const pnr_threshold_op
         case PNR_THR_OTSU: raw = otsu_raw(hist, o.lo, n, S); break;
         case PNR_THR_TRIANGLE: raw = triangle_raw(hist, peak, v_max); break;
         case PNR_THR_TOP: raw = top_raw(hist, o.lo, n, o.top_ppm); break;
-        default: {
-            u64 h[256];
-            for (int v = 0; v < 256; v++) h[v] = hist[v];
-            raw = maxentropy_from_hist(h);
-        }
+        default: raw = maxentropy_from_hist(me);
         }
         thr = std::min(255, std::max(raw, std::max(o.lo, 1)));
     }

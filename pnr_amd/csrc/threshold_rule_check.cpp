@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 namespace pnr {
 static char last[512];
@@ -69,6 +70,21 @@ int main()
     EXPECT(pnr::threshold_rule("check", H, &o, &info) == PNR_E_ARG);
     H[0] = ~0ull;
     EXPECT(pnr::threshold_rule("check", H, &o, &info) == PNR_E_ARG);
+    { // the boundary of maximum entropy: a bin of 2^31 - 1 is read whole as the reference's `int`, one of 2^31 is refused -- by the
+      // rule and by the check pnr_soma shares with it
+        uint64_t B[256] = {0};
+        unsigned long long b[256] = {0};
+        B[0] = b[0] = (1ull << 31) - 1, B[40] = b[40] = 1000, B[200] = b[200] = 10;
+        const pnr_threshold_opts me{PNR_THR_MAXENTROPY, 0, 0, 0};
+        EXPECT(pnr::threshold_rule("check", B, &me, &info) == PNR_OK && info.thr >= 1 && info.thr <= 255 && info.n_vox == (int64_t)((1ull << 31) + 1009));
+        EXPECT(pnr::maxentropy_bins_fit("check", b) == PNR_OK);
+        B[0] = b[0] = 1ull << 31;
+        EXPECT(pnr::threshold_rule("check", B, &me, &info) == PNR_E_ARG);
+        EXPECT(pnr::maxentropy_bins_fit("check", b) == PNR_E_ARG);
+        EXPECT(std::string(pnr::last) == "check: maxentropy needs every bin below 2^31, bin 0 holds 2147483648");
+        b[0] = 5, b[255] = ~0ull;
+        EXPECT(pnr::maxentropy_bins_fit("check", b) == PNR_E_ARG);
+    }
     H[0] = 1;
     for (const pnr_threshold_opts bad : {pnr_threshold_opts{-1, 0, 0, 0}, pnr_threshold_opts{5, 0, 0, 0}, pnr_threshold_opts{1, -1, 0, 0}, pnr_threshold_opts{1, 256, 0, 0},
                                          pnr_threshold_opts{3, 0, 0, 0}, pnr_threshold_opts{3, 0, 1000000, 0}, pnr_threshold_opts{1, 0, 5, 0}})

@@ -497,6 +497,7 @@ TEST_SIGNATURES = {
     "pnr_gaussian": (_rc, [_vp, _f32, _vp]),
     "pnr_hessian": (_rc, [_vp, _f32] + [_vp] * 6),
     "pnr_set_j8_v": (_rc, [_vp] + [_vp] * 4),
+    "pnr_get_frangi_box": (_rc, [_vp, _vp, _vp] + [_vp] * 5),
     "pnr_get_table": (_rc, [_vp, _str, _vp, _i64, _pi64]),
     "pnr_expf_batch": (_rc, [_vp, _vp, _i64, _vp]),
     "pnr_eigen_batch": (_rc, [_vp, _vp, _i64, _vp, _vp]),
@@ -1049,6 +1050,22 @@ class Context:
                 out[k] = np.empty(self.shape, np.uint8)
         ptr = lambda k: out[k].ctypes.data if k in out else None
         check(self.L.pnr_get_frangi(self.h, ptr("J"), ptr("J8"), ptr("Vx"), ptr("Vy"), ptr("Vz")))
+        return out
+
+    def get_frangi_box(self, lo, hi, J=True, J8=True, V=True):
+        """test tap pnr_get_frangi_box: get_frangi of the box lo <= (z, y, x) < hi alone"""
+        lo, hi = np.array(lo, np.int64), np.array(hi, np.int64)
+        shape = tuple(int(b - a) for a, b in zip(lo, hi))
+        out = {}
+        if J:
+            out["J"] = np.empty(shape, np.float32)
+        if J8:
+            out["J8"] = np.empty(shape, np.uint8)
+        if V:
+            for k in ("Vx", "Vy", "Vz"):
+                out[k] = np.empty(shape, np.uint8)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        check(self.L.pnr_get_frangi_box(self.h, lo.ctypes.data, hi.ctypes.data, ptr("J"), ptr("J8"), ptr("Vx"), ptr("Vy"), ptr("Vz")))
         return out
 
     def gaussian(self, sig):

@@ -205,3 +205,76 @@ def test_soma_filters_vs_golden(name):
     c.set_volume(g["img"])
     s = c.soma(want_e8=True)
     assert np.array_equal(s["E8"], g["blurred"])
+
+
+# ---- the sparse stack above 2^31 voxels (tests/bigtrace.py) and its sibling ----
+def _sparse_soma_context(shape):
+    import bigtrace
+    return bigtrace.open_stack(shape, dict(bigtrace.PARAMS, somaradius=3))
+
+
+@pytest.fixture(scope="module")
+def dark_stack():
+    """2048 x 2048 x 536, zero but for two blocks of tubes, borrowed by a context with somaradius 3; the two tests below share it, so
+    that the second runs on the context that refused the call"""
+    import torch
+    import bigtrace
+    t, c = _sparse_soma_context(bigtrace.SHAPE)
+    S = dict(c=c, error=None)
+    yield S
+    c.close()
+    del t
+    torch.cuda.empty_cache()
+
+
+def _refused(S):
+    if S["error"] is None:
+        with pytest.raises(lib.PnrError) as e:
+            S["c"].soma()
+        S["error"] = str(e.value)
+    return S["error"]
+
+
+def test_soma_refuses_a_histogram_bin_of_2_31(dark_stack):
+    """bin 0 of the eroded + blurred stack's histogram holds more than 2^31 voxels, which the maximum-entropy rule would read as a
+    negative `int` (threshold_rule.cpp; the reference's `int hist[]`): pnr_soma refuses it by name and leaves no soma map behind"""
+    import re
+    import bigtrace
+    shape = bigtrace.SHAPE
+    n_vox = int(np.prod(shape, dtype=np.int64))
+    text = _refused(dark_stack)
+    m = re.search(r"pnr_soma: maxentropy needs every bin below 2\^31, bin 0 holds (\d+)", text)
+    assert m and "error -1" in text, text
+    assert max(2**31, n_vox - sum(B.size for _, B in bigtrace.blocks(shape))) <= int(m.group(1)) < n_vox, "all but some voxels of the blocks"
+    assert not dark_stack["c"].have_soma()
+
+
+def test_context_goes_on_after_the_refused_soma(dark_stack, oracle):
+    """the context that refused pnr_soma stays usable: its Frangi gives the bytes that test_gpu_bigtrace.py holds against the oracle"""
+    import bigtrace
+    c = dark_stack["c"]
+    _refused(dark_stack)
+    fw = bigtrace.frangi_reference(oracle, bigtrace.SHAPE)
+    assert not c.have_soma() and c.frangi() == (fw["jmin"], fw["jmax"])
+    bigtrace.check_frangi(c, fw, whole_j8=False)
+
+
+def test_soma_of_the_sparse_sibling_vs_oracle(oracle):
+    """the same blocks on 160 x 96 x 72, the same call: every bin fits, and the soma path equals the oracle's"""
+    import torch
+    import bigtrace
+    shape = bigtrace.SMALL
+    img = bigtrace.host_stack(shape)
+    E8o, tho, smapo, n4o = orc.soma_extract(oracle, img, 3)
+    t, c = _sparse_soma_context(shape)
+    s = c.soma(want_e8=True)
+    assert c.have_soma() and np.array_equal(s["E8"], E8o) and s["threshold"] == tho
+    hist = np.bincount(E8o.reshape(-1), minlength=256).astype(np.int64)
+    assert hist[0] > 0.9 * img.size and oracle.orc_maxentropy_hist(hist) == tho
+    fg = np.flatnonzero(smapo.reshape(-1) > 0)
+    assert np.array_equal(s["vox"], fg) and np.array_equal(s["lab"], smapo.reshape(-1)[fg]) and len(s["nodes"]) == len(n4o)
+    if len(n4o):
+        assert np.array_equal(np.stack([s["nodes"][k] for k in ("x", "y", "z", "sig")], -1), n4o)
+    c.close()
+    del t
+    torch.cuda.empty_cache()

@@ -99,6 +99,25 @@ def test_maxentropy_is_the_oracles(oracle):
     assert pnr_amd.threshold_from_hist(H, "maxentropy")["thr"] == max(1, int(fn(H.astype(np.int64))))
 
 
+def test_maxentropy_at_the_width_of_the_references_int(oracle):
+    """the rule reads a bin as `int`: 2^31 - 1 is the largest count it reads whole -- accepted, and the oracle's threshold -- and 2^31
+    is refused, in bin 0 (a dark stack above 2^31 voxels) as anywhere else.  pnr_soma asks the same function (test_gpu_soma.py)"""
+    fn = oracle.orc_maxentropy_hist
+    rng = np.random.default_rng(7)
+    tubes = np.zeros(256, np.uint64)
+    tubes[1:220] = rng.integers(0, 4000, 219)
+    for b in (0, 100):
+        H = tubes.copy()
+        H[b] = 2**31 - 1
+        got = pnr_amd.threshold_from_hist(H, "maxentropy")
+        assert got == ref.from_hist(H, "maxentropy", maxentropy=fn) and got["thr"] == max(1, int(fn(H.astype(np.int64)))) and got["n_vox"] == int(H.sum()), b
+        H[b] = 2**31
+        _fails("pnr_threshold_from_hist: maxentropy needs every bin below 2^31, bin %d holds 2147483648" % b, H, "maxentropy")
+    H = tubes.copy()
+    H[0] = 2248146944 - int(tubes.sum())  # the bin 0 of a sparse 2048 x 2048 x 536 stack
+    _fails("pnr_threshold_from_hist: maxentropy needs every bin below 2^31, bin 0 holds %d" % int(H[0]), H, "maxentropy")
+
+
 def _fails(text, *args):
     with pytest.raises(pnr_amd.PnrError) as e:
         pnr_amd.threshold_from_hist(*args)
