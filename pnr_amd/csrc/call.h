@@ -1,6 +1,6 @@
 // call.h -- the staging of one bounded call on the context's stream: its device buffers as typed parts of ONE allocation, and the chain
 // of HIP calls with one sticky error; timed() is a launch under a timer group of its own.  Users: the volume and tree tools (volume, radius, filter, distance, join, render, components, edt,
-// geodesic, geojoin, threshold, prune), the side stages (recon, soma), the test taps (frangi.hip: eigen, hessian, gaussian, the direction volumes; smc.hip:
+// geodesic, geojoin, morph, watershed and the rounds they share in tilework, threshold, prune), the side stages (recon, soma), the test taps (frangi.hip: eigen, hessian, gaussian, the direction volumes; smc.hip:
 // expf) and the uploads and read-backs of the api*.cpp files.
 #pragma once
 #include "ctx.h"

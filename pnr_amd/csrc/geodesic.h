@@ -1,6 +1,7 @@
 // geodesic.h -- the gray-weighted geodesic distance through the traced 8-bit volume (geodesic.hip), behind pnr_geodesic_distance.
 #pragma once
 #include "ctx.h"
+#include "grid.h"
 
 namespace pnr {
 
@@ -9,13 +10,10 @@ namespace pnr {
 constexpr int GEO_TX = 32;
 constexpr int GEO_TY = 8;
 constexpr int GEO_TZ = 4;
-// voxels (threads) per work-group of the source, compaction, statistics, split, sample and path kernels
+// voxels (threads) per work-group of the source, statistics, split, sample and path kernels (= TILE_TPB: the extent check of tilework.h)
 constexpr int GEO_TPB = 256;
 
-// the volume's extents and its tiles along every axis
-struct GeoDims {
-    int w, h, l, ntx, nty, ntz;
-};
+using GeoDims = TileDims; // in tiles of GEO_TX x GEO_TY x GEO_TZ
 // the 26 step lengths by (dz + 1) 9 + (dy + 1) 3 + (dx + 1): the offset order with the centre (0) in the middle
 struct GeoLens {
     unsigned v[27];

@@ -8,16 +8,13 @@
 //
 //   geo_sources  a thread per source: the centre voxel; a passable one takes the label with a 64-bit atomic minimum (D = 0) and marks its
 //                tile and the tiles of its 26 neighbours; the others are counted as dropped.  The keys were filled with ones before.
-//   geo_compact  the marked tiles of the current flag array into a list (cleared as they are listed), and their count.
 //   geo_relax    a work-group per listed tile.  It loads the keys and costs of the tile and its halo of 1 into LDS (impassable and
 //                non-existent cells: NONE, cost 0; keys with relaxed agent-scope atomic loads, another tile may be writing them), then
 //                iterates in LDS: a thread owns the GEO_TZ voxels of a z column and gathers, for each of the 9 neighbouring columns, the 6
 //                keys once for the 3 dz of all its voxels.  Reads and writes of an iteration are separated by barriers.  It stops when an
-//                iteration changed nothing, or after `iters` iterations -- then the tile marks itself for the next round.  Changed keys
-//                are stored (atomic, so that a reader never sees half a key; only the owner tile ever writes a voxel), and every
-//                neighbouring tile whose halo holds a changed voxel is marked in the NEXT flag array.  No work-group waits for another.
-//   host loop    compact -> the count through 8 bytes of pinned memory -> relax over the list in launches of at most tiles_per_launch
-//                -> swap the flag arrays; until the count is 0.  Rounds ~ tiles along the longest path, not voxels along it.
+//                iteration changed nothing, or after `iters` iterations.  Changed keys are stored (atomic, so that a reader never sees
+//                half a key).  The rounds, the flags and who marks whom: tilework.h; round 1 lists the tiles geo_sources marked.  Rounds ~
+//                tiles along the longest path, not voxels along it.
 //   geo_stats    n_pass, n_reached and the maximum of (D << 32) | ~index over the reached voxels (one 64-bit atomic maximum per
 //                work-group): the largest D and the smallest index that attains it.
 //   geo_split    D and L from the keys where the caller asks for the volumes.
@@ -28,6 +25,7 @@
 #include "geodesic.h"
 #include "call.h"
 #include "grid.h"
+#include "tilework.h"
 #include "volume.h"
 #include <cmath>
 #include <vector>
@@ -44,9 +42,7 @@ constexpr u64 NONE = ~0ull;
 constexpr int HX = GEO_TX + 2, HY = GEO_TY + 2, HZ = GEO_TZ + 2, CELLS = HX * HY * HZ;
 constexpr int RTPB = GEO_TX * GEO_TY; // threads of a relaxation work-group
 constexpr int AUTO_ITERS = 128;       // LDS iterations per tile visit (option geo_iters = 0)
-constexpr int AUTO_TILES = 1 << 20;   // tiles per launch (option geo_tiles_per_launch = 0)
-static_assert(RTPB % 64 == 0 && RTPB <= 1024 && GEO_TPB % 64 == 0, "whole waves");
-static_assert(GEO_TX >= 2 && GEO_TY >= 2 && GEO_TZ >= 2, "a voxel is on at most one of the two faces of an axis");
+static_assert(pnr::tile_shape_ok<GEO_TX, GEO_TY, GEO_TZ, GEO_TPB>());
 
 using Dims = pnr::GeoDims;
 using Lens = pnr::GeoLens;
@@ -80,14 +76,6 @@ __global__ __launch_bounds__(GEO_TPB) void geo_sources(const uint8_t *V, u64 *ke
             for (int qx = max(x - 1, 0); qx <= min(x + 1, d.w - 1); qx++) flag[((long long)(qz / GEO_TZ) * d.nty + qy / GEO_TY) * d.ntx + qx / GEO_TX] = 1;
 }
 
-__global__ __launch_bounds__(GEO_TPB) void geo_compact(int *flag, int tiles, int *list, u64 *count)
-{
-    const int i = blockIdx.x * GEO_TPB + threadIdx.x;
-    if (i >= tiles || !flag[i]) return;
-    flag[i] = 0;
-    list[atomicAdd(count, 1ull)] = i; // (at most `tiles` entries: every tile is listed once)
-}
-
 struct RelaxArgs {
     const uint8_t *V;
     u64 *key;
@@ -104,23 +92,21 @@ __global__ __launch_bounds__(RTPB) void geo_relax(RelaxArgs a)
 {
     __shared__ u64 sk[CELLS];
     __shared__ unsigned short sc[CELLS]; // 0: impassable or outside the volume
-    __shared__ unsigned touched;         // bit (az + 1) 9 + (ay + 1) 3 + (ax + 1): a voxel in the halo of the tile at that offset changed
+    __shared__ unsigned touched;         // the halo_bits of the voxels that changed
     const Dims d = a.d;
     const int tile = a.list[blockIdx.x];
     const pnr::TileAt o = pnr::tile_origin((unsigned)tile, d.ntx, d.nty, GEO_TX, GEO_TY, GEO_TZ);
-    const int tix = o.tx, tiy = o.ty, tiz = o.tz, x0 = o.x0, y0 = o.y0, z0 = o.z0;
     if (threadIdx.x == 0) touched = 0;
-    for (int cell = threadIdx.x; cell < CELLS; cell += RTPB) {
-        const int gx = x0 + cell % HX - 1, gy = y0 + cell / HX % HY - 1, gz = z0 + cell / (HX * HY) - 1;
+    pnr::stage_cells<GEO_TX, GEO_TY, GEO_TZ>(d, o, [&](int cx, int cy, int cz, bool inside, long long g, bool) {
         u64 k = NONE;
         unsigned short cc = 0;
-        if (gx >= 0 && gx < d.w && gy >= 0 && gy < d.h && gz >= 0 && gz < d.l) {
-            const long long g = pnr::voxel_index(d.w, d.h, gx, gy, gz);
+        if (inside) {
             const int v = a.V[g];
             if (v >= a.t) cc = a.ctab[v], k = load_key(&a.key[g]);
         }
+        const int cell = (cz * HY + cy) * HX + cx;
         sk[cell] = k, sc[cell] = cc;
-    }
+    });
     __syncthreads();
     const int lx = threadIdx.x % GEO_TX, ly = threadIdx.x / GEO_TX;
     const int own = (HY + ly + 1) * HX + lx + 1; // the cell of the thread's voxel z = 0; z + 1 is HX * HY further
@@ -164,30 +150,14 @@ __global__ __launch_bounds__(RTPB) void geo_relax(RelaxArgs a)
         if (!again) break;
     }
     unsigned mine = 0;
-    const unsigned mx = 2u | (lx == 0 ? 1u : 0u) | (lx == GEO_TX - 1 ? 4u : 0u), my = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
 #pragma unroll
     for (int z = 0; z < GEO_TZ; z++)
         if (cur[z] < first[z]) { // (a passable voxel inside the volume: the others stay NONE)
-            const long long g = pnr::voxel_index(d.w, d.h, x0 + lx, y0 + ly, z0 + z);
+            const long long g = pnr::voxel_index(d.w, d.h, o.x0 + lx, o.y0 + ly, o.z0 + z);
             __hip_atomic_store(&a.key[g], cur[z], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned mz = 2u | (z == 0 ? 1u : 0u) | (z == GEO_TZ - 1 ? 4u : 0u);
-#pragma unroll
-            for (int az = 0; az < 3; az++)
-#pragma unroll
-                for (int ay = 0; ay < 3; ay++)
-                    if ((mz >> az & 1u) && (my >> ay & 1u)) mine |= mx << (az * 9 + ay * 3);
+            mine |= pnr::halo_bits<GEO_TX, GEO_TY, GEO_TZ>(lx, ly, z);
         }
-    if (mine) atomicOr(&touched, mine);
-    __syncthreads();
-    if (threadIdx.x < 27) {
-        const int ax = (int)threadIdx.x % 3 - 1, ay = (int)threadIdx.x / 3 % 3 - 1, az = (int)threadIdx.x / 9 - 1;
-        if (threadIdx.x == 13) {
-            if (again) a.flag_next[tile] = 1; // the iteration bound cut the tile's own convergence short
-        } else if (touched >> threadIdx.x & 1u) {
-            const int nx = tix + ax, ny = tiy + ay, nz = tiz + az;
-            if (nx >= 0 && nx < d.ntx && ny >= 0 && ny < d.nty && nz >= 0 && nz < d.ntz) a.flag_next[(nz * d.nty + ny) * d.ntx + nx] = 1;
-        }
-    }
+    pnr::mark_tiles(a.flag_next, d, o, tile, touched, mine, again);
 }
 
 // out: n_pass | n_reached | the maximum of (D << 32) | ~index over the reached voxels (zeroed by the host)
@@ -323,9 +293,10 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
 {
     pnr_geo_call g = g_in; // (the hook may replace the targets)
     const int64_t N = c->N;
-    const Dims d{(int)c->w, (int)c->h, (int)c->l, (int)((c->w + GEO_TX - 1) / GEO_TX), (int)((c->h + GEO_TY - 1) / GEO_TY), (int)((c->l + GEO_TZ - 1) / GEO_TZ)};
-    const int64_t tiles = (int64_t)d.ntx * d.nty * d.ntz, vblocks = (N + GEO_TPB - 1) / GEO_TPB;
-    PNR_REQUIRE(tiles < (1LL << 31) - GEO_TPB && vblocks < (1LL << 31), PNR_E_ARG, "%s: volume extent too large", who);
+    Dims d;
+    int rc = pnr::tile_dims<GEO_TX, GEO_TY, GEO_TZ>(c, who, d);
+    if (rc) return rc;
+    const int64_t tiles = d.tiles(), vblocks = (N + GEO_TPB - 1) / GEO_TPB;
     // the cost table and the step lengths (f32, single operations: this file is built with -ffp-contract=off)
     uint16_t ctab[256];
     unsigned cmax = 0, lmax = 0;
@@ -344,61 +315,38 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
     const bool split_d = g.d_out != nullptr, split_l = g.label_out != nullptr;
     pnr::CallBuf buf; // (freed when the call returns)
     const auto d_key = buf.add<u64>((size_t)N);
-    const auto d_flag = buf.add<int>((size_t)tiles * 2), d_list = buf.add<int>((size_t)tiles);
+    pnr::TileRounds rounds(c, who, buf, d);
     const auto d_ctab = buf.add<uint16_t>(256);
-    const auto d_word = buf.add<u64>(1), d_count = buf.add<u64>(1), d_drop = buf.add<u64>(1), d_st = buf.add<u64>(3);
+    const auto d_word = buf.add<u64>(1), d_drop = buf.add<u64>(1), d_st = buf.add<u64>(3);
     const auto d_sxyz = buf.add<float>((size_t)g.n_src * 3);
     const auto d_slab = buf.add<int>(g.src_label ? (size_t)g.n_src : 0);
     const auto d_dv = buf.add<unsigned>(split_d ? (size_t)N : 0);
     const auto d_lv = buf.add<int>(split_l ? (size_t)N : 0);
-    int rc = buf.alloc(who);
-    if (rc) return rc;
-    pnr::PinBuf<u64> h_count;
-    if (h_count.alloc(1) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("%s: pinned allocation of 8 B failed", who);
-        return PNR_E_NOMEM;
-    }
+    if ((rc = buf.alloc(who)) || (rc = rounds.pin())) return rc;
     int t = o.thr;
     if (o.thr < 0 && (rc = pnr_mean_threshold(c, who, "geodesic_threshold", c->d_img, N, d_word, &t))) return rc; // the global mean
     pnr::Call call(c, who);
-    int *flag[2] = {d_flag.get(), d_flag.get() + tiles};
     call.up(d_ctab, ctab);
     c->tic();
     call.fill(d_key, 0xff);
-    call.fill(d_flag, 0);
+    rounds.seed_none(call);
     call.fill(d_drop, 0);
     if (g.n_src > 0) {
         call.up(d_sxyz, g.src_xyz);
         if (g.src_label) call.up(d_slab, g.src_label);
         call.launch(geo_sources, dim3((unsigned)((g.n_src + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB), c->d_img, d_key.get(), (const float *)d_sxyz.get(),
-                    g.src_label ? (const int *)d_slab.get() : (const int *)nullptr, (long long)g.n_src, d, t, flag[0], d_drop.get());
+                    g.src_label ? (const int *)d_slab.get() : (const int *)nullptr, (long long)g.n_src, d, t, rounds.flag0(), d_drop.get());
     }
     c->toc("geodesic_init", 1);
     const int iters = c->opt.geo_iters > 0 ? c->opt.geo_iters : AUTO_ITERS;
-    const int64_t per_launch = c->opt.geo_tiles_per_launch > 0 ? c->opt.geo_tiles_per_launch : AUTO_TILES;
-    int64_t rounds = 0, visits = 0;
+    pnr::TileRounds::Tally done;
     c->geo_rounds = c->geo_visits = 0;
-    for (int cur = 0; call.ok(); cur ^= 1) {
-        c->tic();
-        call.fill(d_count, 0);
-        call.launch(geo_compact, dim3((unsigned)((tiles + GEO_TPB - 1) / GEO_TPB)), dim3(GEO_TPB), flag[cur], (int)tiles, d_list.get(), d_count.get());
-        c->toc("geodesic_compact", 1);
-        call.down(h_count.get(), d_count);
-        if ((rc = call.finish())) return rc;
-        const int64_t count = (int64_t)*h_count.get();
-        if (count == 0) break;
-        PNR_REQUIRE(count <= tiles && rounds < N + tiles + 16, PNR_E_HIP, "%s: the relaxation did not settle (round %lld, %lld tiles listed)", who, (long long)rounds,
-                    (long long)count);
-        rounds++, visits += count;
-        for (int64_t at = 0; at < count; at += per_launch) {
-            const int64_t n = std::min(per_launch, count - at);
-            call.timed("geodesic_relax", geo_relax, dim3((unsigned)n), dim3(RTPB),
-                       RelaxArgs{c->d_img, d_key.get(), (const uint16_t *)d_ctab.get(), (const int *)d_list.get() + at, flag[cur ^ 1], d, t, iters, o.dmax, len});
-        }
-    }
-    if (!call.ok()) return call.finish();
-    c->geo_rounds = rounds, c->geo_visits = visits;
+    rc = rounds.run(call, "geodesic_compact", pnr::tiles_per_launch(c->opt.geo_tiles_per_launch), N + tiles + 16, 0, [&](const int *list, int64_t n, int *flag_next) {
+        call.timed("geodesic_relax", geo_relax, dim3((unsigned)n), dim3(RTPB),
+                   RelaxArgs{c->d_img, d_key.get(), (const uint16_t *)d_ctab.get(), list, flag_next, d, t, iters, o.dmax, len});
+    }, done);
+    if (rc) return rc;
+    c->geo_rounds = done.rounds, c->geo_visits = done.visits;
     const pnr_geo_keys keys{c->d_img, d_key.get(), d_ctab.get(), t, d, len};
     if (g.hook && (rc = g.hook(g.hook_user, c, who, keys, g))) return rc;
     u64 st[3] = {0, 0, 0}, dropped = 0;
@@ -422,7 +370,7 @@ int pnr_geodesic_run(pnr_ctx *c, const char *who, const pnr_geo_opts &o, const p
     if (g.info) {
         const int64_t reached = (int64_t)st[1];
         *g.info = pnr_geo_info{N, (int64_t)st[0], reached, g.n_src - (int64_t)dropped, (int64_t)dropped, reached ? (int64_t)(uint32_t)~(uint32_t)st[2] : -1,
-                               reached ? (uint32_t)(st[2] >> 32) : 0u, t, (int32_t)std::min<int64_t>(rounds, INT32_MAX), 0};
+                               reached ? (uint32_t)(st[2] >> 32) : 0u, t, (int32_t)std::min<int64_t>(done.rounds, INT32_MAX), 0};
     }
     return PNR_OK;
 }

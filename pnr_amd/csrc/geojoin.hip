@@ -23,6 +23,7 @@
 #include "geojoin.h"
 #include "call.h"
 #include "grid.h"
+#include "tilework.h"
 #include "distance.h"
 #include "join.h"
 #include <algorithm>
@@ -45,7 +46,6 @@ constexpr int JTPB = GEO_TX * GEO_TY; // threads of a work-group
 constexpr int SLOTS = 64;             // of the LDS table (a power of two)
 constexpr int PROBES = 4;
 constexpr int OTHER_BITS = 22;        // the other side's component in best_e (trees < 2^22 = PNR_JOIN_MAX_N)
-constexpr int64_t AUTO_TILES = 1 << 20; // tiles per launch (option geojoin_tiles_per_launch = 0)
 constexpr int32_t FIRST_CAP = 256;      // voxels of a bridge's walk in the first target stage; only a longer one is walked again with the full cap
 static_assert(JTPB % 64 == 0 && JTPB <= 1024 && JTPB >= SLOTS, "whole waves, and a thread per slot");
 static_assert(PNR_JOIN_MAX_N <= 1 << OTHER_BITS, "a tree number fits the low bits of best_e");
@@ -212,8 +212,8 @@ struct Rounds {
 int meet_rounds(pnr_ctx *c, const char *who, const pnr_geo_keys &k, Rounds &r)
 {
     const Dims d = k.d;
-    const int64_t tiles = (int64_t)d.ntx * d.nty * d.ntz, T = r.trees;
-    const int64_t per_launch = c->opt.geojoin_tiles_per_launch > 0 ? c->opt.geojoin_tiles_per_launch : AUTO_TILES;
+    const int64_t tiles = d.tiles(), T = r.trees;
+    const int64_t per_launch = pnr::tiles_per_launch(c->opt.geojoin_tiles_per_launch);
     const int launches = (int)((tiles + per_launch - 1) / per_launch);
     pnr::CallBuf buf; // (freed when the rounds are over)
     const auto d_comp = buf.add<int>((size_t)T);

@@ -1,6 +1,6 @@
 // grid.h -- the rules the volume tools share, each written once: the centre voxel of a position (the radius rule of include/pnr_hip.h),
 // a tile's place and a voxel's linear index, the host scan of the chunk counts of a raster-order compaction, and the size of a
-// grid-stride launch.  Users: radius, edt, geodesic, geojoin, components, thin, render, volume, threshold.  Small inline functions.
+// grid-stride launch.  Users: radius, edt, tilework (morph, watershed, geodesic), geojoin, components, thin, render, volume, threshold.  Small inline functions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -21,6 +21,12 @@ __host__ __device__ inline long long centre_voxel(int w, int h, int l, float px,
 {
     return voxel_index(w, h, centre_axis(px, w), centre_axis(py, h), centre_axis(pz, l));
 }
+
+// ---- a volume's extents and its tiles along every axis (built and checked by tile_dims, tilework.h) ----
+struct TileDims {
+    int w, h, l, ntx, nty, ntz;
+    int64_t tiles() const { return (int64_t)ntx * nty * ntz; }
+};
 
 // ---- tile number (x fastest) -> its place in the tile grid and its first voxel; fewer than 2^31 tiles ----
 struct TileAt {

@@ -10,7 +10,7 @@ namespace pnr {
 constexpr int MORPH_TX = 32;
 constexpr int MORPH_TY = 8;
 constexpr int MORPH_TZ = 8;
-// voxels (threads) per work-group of the init, compaction and finish kernels
+// voxels (threads) per work-group of the init and finish kernels (= TILE_TPB: the extent check of tilework.h)
 constexpr int MORPH_TPB = 256;
 
 } // namespace pnr

@@ -8,24 +8,20 @@
 //
 //   morph_init     a thread per voxel: the state from the op -- min(M, V) of the uploaded marker (DILATE), min(255 - M, 255 - V) (ERODE),
 //                  255 - V on the border set and 0 elsewhere (FILL), max(V - h, 0) (HMAX, HDOME).
-//   morph_compact  the marked tiles of the current flag array into a list (cleared as they are listed), and their count.
 //   morph_relax    a work-group per listed tile.  It loads the state of the tile and its halo of 1 and the mask bytes of the tile into LDS
 //                  (non-existent cells: 0), then iterates in LDS: a thread owns a line and runs a forward and a backward running
 //                  min(V, max(R, previous)) along it -- the x rows, then the y columns, then (C = 6, 26) the z columns, the halo cell in
 //                  front of a line as its first `previous` --, which carries a value any distance along an axis in one pass; with C = 8 or
 //                  26 one step over the full 3 x 3 (x 3) neighbourhood follows, reads and writes separated by a barrier.  It stops when an
 //                  iteration changed nothing -- every voxel was then compared with each of its neighbours while nothing was written --
-//                  or after `iters` iterations: then the tile marks itself for the next round.  Changed bytes are stored (only the owner
-//                  tile ever writes a voxel), and every neighbouring tile whose halo holds a changed voxel is marked in the NEXT flag
-//                  array.  A reader may see a stale halo byte inside a launch: a lower bound, and its writer has marked the reader.  No
-//                  work-group waits for another, no atomic touches a voxel.
-//   host loop      compact -> the count through 8 bytes of pinned memory -> relax over the list in launches of at most tiles_per_launch
-//                  -> swap the flag arrays; until the count is 0.  In round 1 every tile is listed.
+//                  or after `iters` iterations.  Changed bytes are stored; a stale halo byte is a lower bound.  No atomic touches a
+//                  voxel.  The rounds, the flags and who marks whom: tilework.h; in round 1 every tile is listed.
 //   morph_finish   the state becomes the result in place (255 - R for the erosion forms, V - R for HDOME), four bytes at a time where
 //                  the alignment of V allows, with the statistics as block partials and one set of atomics per work-group.
 #include "morph.h"
 #include "call.h"
 #include "grid.h"
+#include "tilework.h"
 #include <vector>
 
 namespace {
@@ -39,13 +35,8 @@ typedef unsigned long long u64;
 constexpr int HX = MORPH_TX + 2, HY = MORPH_TY + 2, HZ = MORPH_TZ + 2, SXY = HX * HY, CELLS = SXY * HZ;
 constexpr int RTPB = MORPH_TX * MORPH_TY; // threads of a relaxation work-group
 constexpr int AUTO_ITERS = 64;            // LDS iterations per tile visit (option morph_iters = 0)
-constexpr int AUTO_TILES = 1 << 20;       // tiles per launch (option morph_tiles_per_launch = 0)
-static_assert(RTPB % 64 == 0 && RTPB <= 1024 && MORPH_TPB % 64 == 0, "whole waves");
-static_assert(MORPH_TX >= 2 && MORPH_TY >= 2 && MORPH_TZ >= 2, "a voxel is on at most one of the two faces of an axis");
-
-struct Dims {
-    int w, h, l, ntx, nty, ntz;
-};
+static_assert(pnr::tile_shape_ok<MORPH_TX, MORPH_TY, MORPH_TZ, MORPH_TPB>());
+using Dims = pnr::TileDims;
 
 struct InitArgs {
     const uint8_t *V;
@@ -69,14 +60,6 @@ __global__ __launch_bounds__(MORPH_TPB) void morph_init(InitArgs a)
         r = border ? 255u - v : 0u;
     } else r = v > (unsigned)a.hh ? v - (unsigned)a.hh : 0u;
     a.R[i] = (uint8_t)r;
-}
-
-__global__ __launch_bounds__(MORPH_TPB) void morph_compact(int *flag, int tiles, int *list, u64 *count)
-{
-    const int i = blockIdx.x * MORPH_TPB + threadIdx.x;
-    if (i >= tiles || !flag[i]) return;
-    flag[i] = 0;
-    list[atomicAdd(count, 1ull)] = i; // (at most `tiles` entries: every tile is listed once)
 }
 
 struct RelaxArgs {
@@ -117,23 +100,20 @@ __global__ __launch_bounds__(RTPB) void morph_relax(RelaxArgs a)
 {
     __shared__ uint8_t sr[CELLS]; // the state; 0: outside the volume
     __shared__ uint8_t sv[CELLS]; // the mask of the tile's own cells; 0: outside the volume (such a cell stays 0) and in the halo (never read)
-    __shared__ unsigned touched;  // bit (az + 1) 9 + (ay + 1) 3 + (ax + 1): a voxel in the halo of the tile at that offset changed
+    __shared__ unsigned touched;  // the halo_bits of the voxels that changed
     const Dims d = a.d;
     const int tile = a.list[blockIdx.x];
     const pnr::TileAt o = pnr::tile_origin((unsigned)tile, d.ntx, d.nty, MORPH_TX, MORPH_TY, MORPH_TZ);
-    const int tix = o.tx, tiy = o.ty, tiz = o.tz, x0 = o.x0, y0 = o.y0, z0 = o.z0;
     if (threadIdx.x == 0) touched = 0;
-    for (int cell = threadIdx.x; cell < CELLS; cell += RTPB) {
-        const int cx = cell % HX, cy = cell / HX % HY, cz = cell / SXY;
-        const int gx = x0 + cx - 1, gy = y0 + cy - 1, gz = z0 + cz - 1;
+    pnr::stage_cells<MORPH_TX, MORPH_TY, MORPH_TZ>(d, o, [&](int cx, int cy, int cz, bool inside, long long g, bool own_cell) {
         unsigned r = 0, v = 0;
-        if (gx >= 0 && gx < d.w && gy >= 0 && gy < d.h && gz >= 0 && gz < d.l) {
-            const long long g = pnr::voxel_index(d.w, d.h, gx, gy, gz);
+        if (inside) {
             r = __hip_atomic_load(&a.R[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (another tile may be writing its bytes)
-            if (cx >= 1 && cx <= MORPH_TX && cy >= 1 && cy <= MORPH_TY && cz >= 1 && cz <= MORPH_TZ) v = a.V[g] ^ a.cmpl;
+            if (own_cell) v = a.V[g] ^ a.cmpl;
         }
+        const int cell = (cz * HY + cy) * HX + cx;
         sr[cell] = (uint8_t)r, sv[cell] = (uint8_t)v;
-    }
+    });
     __syncthreads();
     const int lx = threadIdx.x % MORPH_TX, ly = threadIdx.x / MORPH_TX;
     const int own = (HY + ly + 1) * HX + lx + 1; // the cell of the thread's voxel z = 0; z + 1 is SXY further
@@ -181,32 +161,16 @@ __global__ __launch_bounds__(RTPB) void morph_relax(RelaxArgs a)
         if (!again) break;
     }
     unsigned mine = 0;
-    const unsigned mx = 2u | (lx == 0 ? 1u : 0u) | (lx == MORPH_TX - 1 ? 4u : 0u), my = 2u | (ly == 0 ? 1u : 0u) | (ly == MORPH_TY - 1 ? 4u : 0u);
 #pragma unroll
     for (int z = 0; z < MORPH_TZ; z++) {
         const unsigned cur = sr[own + z * SXY];
         if (cur != first[z]) { // (a voxel inside the volume: the others stay 0)
-            const long long g = pnr::voxel_index(d.w, d.h, x0 + lx, y0 + ly, z0 + z);
+            const long long g = pnr::voxel_index(d.w, d.h, o.x0 + lx, o.y0 + ly, o.z0 + z);
             __hip_atomic_store(&a.R[g], (uint8_t)cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned mz = 2u | (z == 0 ? 1u : 0u) | (z == MORPH_TZ - 1 ? 4u : 0u);
-#pragma unroll
-            for (int az = 0; az < 3; az++)
-#pragma unroll
-                for (int ay = 0; ay < 3; ay++)
-                    if ((mz >> az & 1u) && (my >> ay & 1u)) mine |= mx << (az * 9 + ay * 3);
+            mine |= pnr::halo_bits<MORPH_TX, MORPH_TY, MORPH_TZ>(lx, ly, z);
         }
     }
-    if (mine) atomicOr(&touched, mine);
-    __syncthreads();
-    if (threadIdx.x < 27) {
-        const int ax = (int)threadIdx.x % 3 - 1, ay = (int)threadIdx.x / 3 % 3 - 1, az = (int)threadIdx.x / 9 - 1;
-        if (threadIdx.x == 13) {
-            if (again) a.flag_next[tile] = 1; // the iteration bound cut the tile's own convergence short
-        } else if (touched >> threadIdx.x & 1u) {
-            const int nx = tix + ax, ny = tiy + ay, nz = tiz + az;
-            if (nx >= 0 && nx < d.ntx && ny >= 0 && ny < d.nty && nz >= 0 && nz < d.ntz) a.flag_next[(nz * d.nty + ny) * d.ntx + nx] = 1;
-        }
-    }
+    pnr::mark_tiles(a.flag_next, d, o, tile, touched, mine, again);
 }
 
 // st (zeroed by the host): n_changed | n_nonzero | sum_in | sum_out | max_delta
@@ -268,57 +232,33 @@ __global__ __launch_bounds__(MORPH_TPB) void morph_finish(const uint8_t *V, uint
 int pnr_morph_run(pnr_ctx *c, const char *who, const pnr_morph_opts &o, const uint8_t *marker, pnr_morph_info *info, uint8_t *out, pnr::DevBuf<uint8_t> *keep)
 {
     const int64_t N = c->N;
-    const Dims d{(int)c->w, (int)c->h, (int)c->l, (int)((c->w + MORPH_TX - 1) / MORPH_TX), (int)((c->h + MORPH_TY - 1) / MORPH_TY), (int)((c->l + MORPH_TZ - 1) / MORPH_TZ)};
-    const int64_t tiles = (int64_t)d.ntx * d.nty * d.ntz, vblocks = (N + MORPH_TPB - 1) / MORPH_TPB;
-    PNR_REQUIRE(tiles < (1LL << 31) - MORPH_TPB && vblocks < (1LL << 31), PNR_E_ARG, "%s: volume extent too large", who);
+    Dims d;
+    int rc = pnr::tile_dims<MORPH_TX, MORPH_TY, MORPH_TZ>(c, who, d);
+    if (rc) return rc;
+    const int64_t tiles = d.tiles(), vblocks = (N + MORPH_TPB - 1) / MORPH_TPB;
     const bool erosion = o.op == PNR_MORPH_ERODE || o.op == PNR_MORPH_FILL;
     const unsigned cmpl = erosion ? 255u : 0u;
     pnr::DevBuf<uint8_t> state; // (freed when the call returns, or handed to the caller)
-    int rc = pnr::dev_alloc(state, (size_t)N, who, "for the state volume");
-    if (rc) return rc;
+    if ((rc = pnr::dev_alloc(state, (size_t)N, who, "for the state volume"))) return rc;
     pnr::CallBuf buf; // (freed when the call returns)
-    const auto d_flag = buf.add<int>((size_t)tiles * 2), d_list = buf.add<int>((size_t)tiles);
-    const auto d_count = buf.add<u64>(1), d_st = buf.add<u64>(5);
-    if ((rc = buf.alloc(who))) return rc;
-    pnr::PinBuf<u64> h_count;
-    if (h_count.alloc(1) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("%s: pinned allocation of 8 B failed", who);
-        return PNR_E_NOMEM;
-    }
+    pnr::TileRounds rounds(c, who, buf, d);
+    const auto d_st = buf.add<u64>(5);
+    if ((rc = buf.alloc(who)) || (rc = rounds.pin())) return rc;
     pnr::Call call(c, who);
     uint8_t *const R = state.get();
-    int *flag[2] = {d_flag.get(), d_flag.get() + tiles};
     if (marker) call.up(R, marker, (size_t)N);
     call.timed("morph_init", morph_init, dim3((unsigned)vblocks), dim3(MORPH_TPB),
                InitArgs{c->d_img, R, (long long)N, d.w, d.h, d.l, o.op, o.h, (o.connectivity == 6 || o.connectivity == 26) && d.l > 1 ? 1 : 0});
-    call.fill(flag[0], 1, (size_t)tiles); // round 1: every tile
-    call.fill(flag[1], 0, (size_t)tiles);
+    rounds.seed_all(call);
     const int iters = c->opt.morph_iters > 0 ? c->opt.morph_iters : AUTO_ITERS;
-    const int64_t per_launch = c->opt.morph_tiles_per_launch > 0 ? c->opt.morph_tiles_per_launch : AUTO_TILES;
-    int64_t rounds = 0, visits = 0;
+    pnr::TileRounds::Tally done;
     c->morph_rounds = c->morph_visits = 0;
-    for (int cur = 0; call.ok(); cur ^= 1) {
-        c->tic();
-        call.fill(d_count, 0);
-        call.launch(morph_compact, dim3((unsigned)((tiles + MORPH_TPB - 1) / MORPH_TPB)), dim3(MORPH_TPB), flag[cur], (int)tiles, d_list.get(), d_count.get());
-        c->toc("morph_compact", 1);
-        call.down(h_count.get(), d_count);
-        if ((rc = call.finish())) return rc;
-        const int64_t count = (int64_t)*h_count.get();
-        if (count == 0) break;
-        // (a voxel rises at most 255 times, and a round without a rise is the last but one)
-        PNR_REQUIRE(count <= tiles && rounds < 256 * N + tiles + 16, PNR_E_HIP, "%s: the relaxation did not settle (round %lld, %lld tiles listed)", who, (long long)rounds,
-                    (long long)count);
-        rounds++, visits += count;
-        for (int64_t at = 0; at < count; at += per_launch) {
-            const int64_t n = std::min(per_launch, count - at);
-            call.timed("morph_relax", morph_relax, dim3((unsigned)n), dim3(RTPB),
-                       RelaxArgs{c->d_img, R, (const int *)d_list.get() + at, flag[cur ^ 1], d, iters, o.connectivity, cmpl});
-        }
-    }
-    if (!call.ok()) return call.finish();
-    c->morph_rounds = rounds, c->morph_visits = visits;
+    // (a voxel rises at most 255 times, and a round without a rise is the last but one)
+    rc = rounds.run(call, "morph_compact", pnr::tiles_per_launch(c->opt.morph_tiles_per_launch), 256 * N + tiles + 16, 0, [&](const int *list, int64_t n, int *flag_next) {
+        call.timed("morph_relax", morph_relax, dim3((unsigned)n), dim3(RTPB), RelaxArgs{c->d_img, R, list, flag_next, d, iters, o.connectivity, cmpl});
+    }, done);
+    if (rc) return rc;
+    c->morph_rounds = done.rounds, c->morph_visits = done.visits;
     const uintptr_t av = (uintptr_t)c->d_img, ar = (uintptr_t)R;
     const bool alike = (av & 3) == (ar & 3);
     const long long head = alike ? std::min<long long>(N, (long long)((4 - (av & 3)) & 3)) : (long long)N, nvec = (N - head) >> 2;
@@ -330,7 +270,7 @@ int pnr_morph_run(pnr_ctx *c, const char *who, const pnr_morph_opts &o, const ui
     if (out) call.down(out, (const uint8_t *)R, (size_t)N);
     if ((rc = call.finish())) return rc;
     if (info)
-        *info = pnr_morph_info{N, (int64_t)st[0], (int64_t)st[1], st[2], st[3], tiles, visits, (int32_t)st[4], o.connectivity, (int32_t)std::min<int64_t>(rounds, INT32_MAX), 0};
+        *info = pnr_morph_info{N, (int64_t)st[0], (int64_t)st[1], st[2], st[3], tiles, done.visits, (int32_t)st[4], o.connectivity, (int32_t)std::min<int64_t>(done.rounds, INT32_MAX), 0};
     if (keep) *keep = std::move(state);
     return PNR_OK;
 }

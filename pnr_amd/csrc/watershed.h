@@ -8,7 +8,7 @@ namespace pnr {
 constexpr int WS_TX = 32;
 constexpr int WS_TY = 8;
 constexpr int WS_TZ = 8;
-// voxels (threads) per work-group of the init, compaction and finish kernels
+// voxels (threads) per work-group of the init and finish kernels (= TILE_TPB: the extent check of tilework.h)
 constexpr int WS_TPB = 256;
 
 } // namespace pnr

@@ -13,24 +13,21 @@
 //               volume was filled with ones), the others are counted as dropped.  voxels: a thread per voxel -- the relief byte
 //               (255 - V without a caller's relief), the first key (a marker inside the mask: R << 24, else NONE), the label (0: none),
 //               the kept marker labels appended to a list a wave at a time (for n_regions), markers outside the mask counted.
-//   ws_compact  the marked tiles of the current flag array into a list (cleared as they are listed), and their count.
 //   ws_flood    pass 1, a work-group per listed tile.  It loads the keys of the tile and its halo of 1 and the relief of the tile into LDS
 //               (outside the mask or the volume: NONE, relief BLOCKED), then iterates in LDS: a thread owns a line and runs g forward and
 //               backward along it -- the x rows, the y columns, (C = 6, 26) the z columns, the halo cell in front of a line as the first
 //               source --, which carries a key any distance along an axis in one pass; with C = 8 or 26 one step over the full
 //               neighbourhood follows (g is monotone: g of the smallest neighbouring key), reads and writes separated by a barrier.  It
-//               stops when an iteration changed nothing or after `iters` iterations: then the tile marks itself for the next round.
-//               Changed keys are stored (only the owner tile ever writes a voxel), and every neighbouring tile whose halo holds a changed
-//               voxel is marked in the NEXT flag array.  No work-group waits for another, no atomic touches a voxel.
-//   ws_label    pass 2, the same with the keys read-only and the labels relaxed over the tight edges.
-//   host loop   per pass: compact -> the count through 8 bytes of pinned memory -> the tiles of the list in launches of at most
-//               tiles_per_launch -> swap the flag arrays; until the count is 0.  In round 1 every tile is listed.
+//               stops when an iteration changed nothing or after `iters` iterations.  Changed keys are stored; no atomic touches a voxel.
+//   ws_label    pass 2, the same with the keys read-only and the labels relaxed over the tight edges.  The rounds, the flags and who
+//               marks whom: tilework.h; in round 1 of either pass every tile is listed.
 //   ws_finish   the levels (M of the reached voxels, 0 elsewhere) over the relief bytes, and the statistics as block partials with one
 //               set of atomics per work-group.
 // The LDS rows are WS_TX + 3 cells apart: an odd pitch, so that the 32 lanes that each scan an x row meet 32 different banks.
 #include "watershed.h"
 #include "call.h"
 #include "grid.h"
+#include "tilework.h"
 #include "volume.h"
 #include <algorithm>
 #include <vector>
@@ -49,14 +46,9 @@ constexpr unsigned BLOCKED = 0x100u; // the staged relief of a cell that is not 
 constexpr int HX = WS_TX + 2, HY = WS_TY + 2, HZ = WS_TZ + 2, PX = HX + 1, SXY = PX * HY, CELLS = SXY * HZ;
 constexpr int RTPB = WS_TX * WS_TY; // threads of a relaxation work-group
 constexpr int AUTO_ITERS = 64;      // LDS iterations per tile visit (option ws_iters = 0)
-constexpr int AUTO_TILES = 1 << 20; // tiles per launch (option ws_tiles_per_launch = 0)
-static_assert(RTPB % 64 == 0 && RTPB <= 1024 && WS_TPB % 64 == 0, "whole waves");
-static_assert(WS_TX >= 2 && WS_TY >= 2 && WS_TZ >= 2, "a voxel is on at most one of the two faces of an axis");
+static_assert(pnr::tile_shape_ok<WS_TX, WS_TY, WS_TZ, WS_TPB>());
 static_assert(PX % 2 == 1, "an odd pitch");
-
-struct Dims {
-    int w, h, l, ntx, nty, ntz;
-};
+using Dims = pnr::TileDims;
 
 // g(K(s), t) for a mask voxel t of relief r
 __device__ inline unsigned step(unsigned ks, unsigned r)
@@ -116,14 +108,6 @@ __global__ __launch_bounds__(WS_TPB) void ws_init(InitArgs a)
         if (keep) a.mlist[base + __popcll(bk & ((1ull << lane) - 1ull))] = lab; // (at most as many as the host counted markers)
     }
     if (bd && lane == __ffsll((long long)bd) - 1) atomicAdd(&a.cnt[0], (u64)__popcll(bd));
-}
-
-__global__ __launch_bounds__(WS_TPB) void ws_compact(int *flag, int tiles, int *list, u64 *count)
-{
-    const int i = blockIdx.x * WS_TPB + threadIdx.x;
-    if (i >= tiles || !flag[i]) return;
-    flag[i] = 0;
-    list[atomicAdd(count, 1ull)] = i; // (at most `tiles` entries: every tile is listed once)
 }
 
 struct RelaxArgs {
@@ -192,34 +176,6 @@ __device__ inline int label_line(const unsigned *sk, unsigned *sl, const uint8_t
     return ch;
 }
 
-// the tiles whose halo holds the voxel (lx, ly, z) of this tile, as bits (az + 1) 9 + (ay + 1) 3 + (ax + 1)
-__device__ inline unsigned halo_bits(int lx, int ly, int z)
-{
-    const unsigned mx = 2u | (lx == 0 ? 1u : 0u) | (lx == WS_TX - 1 ? 4u : 0u), my = 2u | (ly == 0 ? 1u : 0u) | (ly == WS_TY - 1 ? 4u : 0u);
-    const unsigned mz = 2u | (z == 0 ? 1u : 0u) | (z == WS_TZ - 1 ? 4u : 0u);
-    unsigned bits = 0;
-#pragma unroll
-    for (int az = 0; az < 3; az++)
-#pragma unroll
-        for (int ay = 0; ay < 3; ay++)
-            if ((mz >> az & 1u) && (my >> ay & 1u)) bits |= mx << (az * 9 + ay * 3);
-    return bits;
-}
-
-// the first 27 threads mark the tiles named in `touched` (bit 13, the tile itself: when the iteration bound cut its convergence short)
-__device__ inline void mark_tiles(const RelaxArgs &a, const pnr::TileAt &o, int tile, unsigned touched, int again)
-{
-    if (threadIdx.x >= 27) return;
-    const Dims d = a.d;
-    const int ax = (int)threadIdx.x % 3 - 1, ay = (int)threadIdx.x / 3 % 3 - 1, az = (int)threadIdx.x / 9 - 1;
-    if (threadIdx.x == 13) {
-        if (again) a.flag_next[tile] = 1;
-    } else if (touched >> threadIdx.x & 1u) {
-        const int nx = o.tx + ax, ny = o.ty + ay, nz = o.tz + az;
-        if (nx >= 0 && nx < d.ntx && ny >= 0 && ny < d.nty && nz >= 0 && nz < d.ntz) a.flag_next[(nz * d.nty + ny) * d.ntx + nx] = 1;
-    }
-}
-
 __global__ __launch_bounds__(RTPB) void ws_flood(RelaxArgs a)
 {
     __shared__ unsigned sk[CELLS];       // the keys; NONE: outside the mask or the volume
@@ -229,20 +185,15 @@ __global__ __launch_bounds__(RTPB) void ws_flood(RelaxArgs a)
     const int tile = a.list[blockIdx.x];
     const pnr::TileAt o = pnr::tile_origin((unsigned)tile, d.ntx, d.nty, WS_TX, WS_TY, WS_TZ);
     if (threadIdx.x == 0) touched = 0;
-    for (int c = threadIdx.x; c < HX * HY * HZ; c += RTPB) {
-        const int cx = c % HX, cy = c / HX % HY, cz = c / (HX * HY);
-        const int gx = o.x0 + cx - 1, gy = o.y0 + cy - 1, gz = o.z0 + cz - 1;
+    pnr::stage_cells<WS_TX, WS_TY, WS_TZ>(d, o, [&](int cx, int cy, int cz, bool inside, long long g, bool own_cell) {
         unsigned k = NONE, r = BLOCKED;
-        if (gx >= 0 && gx < d.w && gy >= 0 && gy < d.h && gz >= 0 && gz < d.l) {
-            const long long g = pnr::voxel_index(d.w, d.h, gx, gy, gz);
-            if ((int)a.V[g] >= a.t) {
-                k = __hip_atomic_load(&a.key[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (another tile may be writing its keys)
-                if (cx >= 1 && cx <= WS_TX && cy >= 1 && cy <= WS_TY && cz >= 1 && cz <= WS_TZ) r = a.R[g];
-            }
+        if (inside && (int)a.V[g] >= a.t) {
+            k = __hip_atomic_load(&a.key[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (another tile may be writing its keys)
+            if (own_cell) r = a.R[g];
         }
         const int cell = cell_at(cx, cy, cz);
         sk[cell] = k, sr[cell] = (unsigned short)r;
-    }
+    });
     __syncthreads();
     const int lx = threadIdx.x % WS_TX, ly = threadIdx.x / WS_TX;
     const int own = cell_at(lx + 1, ly + 1, 1); // the cell of the thread's voxel z = 0; z + 1 is SXY further
@@ -297,12 +248,10 @@ __global__ __launch_bounds__(RTPB) void ws_flood(RelaxArgs a)
         if (cur != first[z]) { // (a mask voxel inside the volume: the others stay NONE)
             const long long g = pnr::voxel_index(d.w, d.h, o.x0 + lx, o.y0 + ly, o.z0 + z);
             __hip_atomic_store(&a.key[g], cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            mine |= halo_bits(lx, ly, z);
+            mine |= pnr::halo_bits<WS_TX, WS_TY, WS_TZ>(lx, ly, z);
         }
     }
-    if (mine) atomicOr(&touched, mine);
-    __syncthreads();
-    mark_tiles(a, o, tile, touched, again);
+    pnr::mark_tiles(a.flag_next, d, o, tile, touched, mine, again);
 }
 
 __global__ __launch_bounds__(RTPB) void ws_label(RelaxArgs a)
@@ -315,12 +264,9 @@ __global__ __launch_bounds__(RTPB) void ws_label(RelaxArgs a)
     const int tile = a.list[blockIdx.x];
     const pnr::TileAt o = pnr::tile_origin((unsigned)tile, d.ntx, d.nty, WS_TX, WS_TY, WS_TZ);
     if (threadIdx.x == 0) touched = 0;
-    for (int c = threadIdx.x; c < HX * HY * HZ; c += RTPB) {
-        const int cx = c % HX, cy = c / HX % HY, cz = c / (HX * HY);
-        const int gx = o.x0 + cx - 1, gy = o.y0 + cy - 1, gz = o.z0 + cz - 1;
+    pnr::stage_cells<WS_TX, WS_TY, WS_TZ>(d, o, [&](int cx, int cy, int cz, bool inside, long long g, bool) {
         unsigned k = NONE, lab = NONE, r = 0;
-        if (gx >= 0 && gx < d.w && gy >= 0 && gy < d.h && gz >= 0 && gz < d.l) {
-            const long long g = pnr::voxel_index(d.w, d.h, gx, gy, gz);
+        if (inside) {
             k = a.key[g]; // (NONE outside the mask)
             if (k != NONE) {
                 lab = __hip_atomic_load(&a.L[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (another tile may be writing its labels)
@@ -330,7 +276,7 @@ __global__ __launch_bounds__(RTPB) void ws_label(RelaxArgs a)
         }
         const int cell = cell_at(cx, cy, cz);
         sk[cell] = k, sl[cell] = lab, sr[cell] = (uint8_t)r;
-    }
+    });
     __syncthreads();
     const int lx = threadIdx.x % WS_TX, ly = threadIdx.x / WS_TX;
     const int own = cell_at(lx + 1, ly + 1, 1);
@@ -387,12 +333,10 @@ __global__ __launch_bounds__(RTPB) void ws_label(RelaxArgs a)
         if (cur != first[z]) { // (a reached voxel inside the volume: the others stay NONE)
             const long long g = pnr::voxel_index(d.w, d.h, o.x0 + lx, o.y0 + ly, o.z0 + z);
             __hip_atomic_store(&a.L[g], cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            mine |= halo_bits(lx, ly, z);
+            mine |= pnr::halo_bits<WS_TX, WS_TY, WS_TZ>(lx, ly, z);
         }
     }
-    if (mine) atomicOr(&touched, mine);
-    __syncthreads();
-    mark_tiles(a, o, tile, touched, again);
+    pnr::mark_tiles(a.flag_next, d, o, tile, touched, mine, again);
 }
 
 // st (zeroed by the host): n_mask | n_reached | m_max | d_max | 1 + the largest level with a saturated D (0: none).  level (nullable):
@@ -449,32 +393,25 @@ int pnr_watershed_run(pnr_ctx *c, const char *who, const pnr_watershed_opts &o, 
                       uint8_t *level_out)
 {
     const int64_t N = c->N;
-    const Dims d{(int)c->w, (int)c->h, (int)c->l, (int)((c->w + WS_TX - 1) / WS_TX), (int)((c->h + WS_TY - 1) / WS_TY), (int)((c->l + WS_TZ - 1) / WS_TZ)};
-    const int64_t tiles = (int64_t)d.ntx * d.nty * d.ntz, vblocks = (N + WS_TPB - 1) / WS_TPB;
-    PNR_REQUIRE(tiles < (1LL << 31) - WS_TPB && vblocks < (1LL << 31), PNR_E_ARG, "%s: volume extent too large", who);
+    Dims d;
+    int rc = pnr::tile_dims<WS_TX, WS_TY, WS_TZ>(c, who, d);
+    if (rc) return rc;
+    const int64_t tiles = d.tiles(), vblocks = (N + WS_TPB - 1) / WS_TPB;
     const bool points = m.vol == nullptr;
     const int64_t cap = points ? std::min(m.n_src, N) : m.n_pos; // the kept marker voxels at most
     pnr::CallBuf buf; // (freed when the call returns)
     const auto d_key = buf.add<unsigned>((size_t)N);
     const auto d_lab = buf.add<int>((size_t)N);
     const auto d_rel = buf.add<uint8_t>((size_t)N);
-    const auto d_flag = buf.add<int>((size_t)tiles * 2), d_list = buf.add<int>((size_t)tiles);
-    const auto d_word = buf.add<u64>(1), d_count = buf.add<u64>(1), d_cnt = buf.add<u64>(2), d_st = buf.add<u64>(5);
+    pnr::TileRounds rounds(c, who, buf, d);
+    const auto d_word = buf.add<u64>(1), d_cnt = buf.add<u64>(2), d_st = buf.add<u64>(5);
     const auto d_sxyz = buf.add<float>(points ? (size_t)m.n_src * 3 : 0);
     const auto d_slab = buf.add<int>(points && m.src_label ? (size_t)m.n_src : 0);
     const auto d_mlist = buf.add<int>((size_t)cap);
-    int rc = buf.alloc(who);
-    if (rc) return rc;
-    pnr::PinBuf<u64> h_count;
-    if (h_count.alloc(1) != hipSuccess) {
-        (void)hipGetLastError();
-        pnr::set_error("%s: pinned allocation of 8 B failed", who);
-        return PNR_E_NOMEM;
-    }
+    if ((rc = buf.alloc(who)) || (rc = rounds.pin())) return rc;
     int t = o.thr;
     if (o.thr < 0 && (rc = pnr_mean_threshold(c, who, "watershed_init", c->d_img, N, d_word, &t))) return rc; // the global mean
     pnr::Call call(c, who);
-    int *flag[2] = {d_flag.get(), d_flag.get() + tiles};
     call.fill(d_cnt, 0);
     if (relief) call.up(d_rel, relief);
     InitArgs ia{c->d_img, d_rel.get(), d_key.get(), d_lab.get(), nullptr, nullptr, 0, (long long)N, d.w, d.h, d.l, t, relief ? 1 : 0, d_mlist.get(), d_cnt.get()};
@@ -488,35 +425,19 @@ int pnr_watershed_run(pnr_ctx *c, const char *who, const pnr_watershed_opts &o, 
     } else call.up(d_lab, m.vol);
     call.timed("watershed_init", ws_init, dim3((unsigned)vblocks), dim3(WS_TPB), ia);
     const int iters = c->opt.ws_iters > 0 ? c->opt.ws_iters : AUTO_ITERS;
-    const int64_t per_launch = c->opt.ws_tiles_per_launch > 0 ? c->opt.ws_tiles_per_launch : AUTO_TILES;
-    int64_t rounds[2] = {0, 0}, visits[2] = {0, 0};
+    pnr::TileRounds::Tally done[2];
     c->ws_rounds = c->ws_visits = 0;
     for (int pass = 0; pass < 2; pass++) {
-        call.fill(flag[0], 1, (size_t)tiles); // round 1: every tile
-        call.fill(flag[1], 0, (size_t)tiles);
-        for (int cur = 0; call.ok(); cur ^= 1) {
-            c->tic();
-            call.fill(d_count, 0);
-            call.launch(ws_compact, dim3((unsigned)((tiles + WS_TPB - 1) / WS_TPB)), dim3(WS_TPB), flag[cur], (int)tiles, d_list.get(), d_count.get());
-            c->toc("watershed_compact", 1);
-            call.down(h_count.get(), d_count);
-            if ((rc = call.finish())) return rc;
-            const int64_t count = (int64_t)*h_count.get();
-            if (count == 0) break;
-            // (a key falls at most 2^32 times; the bound only ends a loop that a fault keeps alive)
-            PNR_REQUIRE(count <= tiles && rounds[pass] < 256 * N + tiles + 16, PNR_E_HIP, "%s: the relaxation did not settle (pass %d, round %lld, %lld tiles listed)", who,
-                        pass + 1, (long long)rounds[pass], (long long)count);
-            rounds[pass]++, visits[pass] += count;
-            for (int64_t at = 0; at < count; at += per_launch) {
-                const int64_t n = std::min(per_launch, count - at);
-                const RelaxArgs ra{c->d_img, d_rel.get(), d_key.get(), (unsigned *)d_lab.get(), (const int *)d_list.get() + at, flag[cur ^ 1], d, t, iters, o.connectivity};
-                if (pass == 0) call.timed("watershed_flood", ws_flood, dim3((unsigned)n), dim3(RTPB), ra);
-                else call.timed("watershed_label", ws_label, dim3((unsigned)n), dim3(RTPB), ra);
-            }
-        }
-        if (!call.ok()) return call.finish();
+        rounds.seed_all(call);
+        // (a key falls at most 2^32 times; the bound only ends a loop that a fault keeps alive)
+        rc = rounds.run(call, "watershed_compact", pnr::tiles_per_launch(c->opt.ws_tiles_per_launch), 256 * N + tiles + 16, pass + 1, [&](const int *list, int64_t n, int *flag_next) {
+            const RelaxArgs ra{c->d_img, d_rel.get(), d_key.get(), (unsigned *)d_lab.get(), list, flag_next, d, t, iters, o.connectivity};
+            if (pass == 0) call.timed("watershed_flood", ws_flood, dim3((unsigned)n), dim3(RTPB), ra);
+            else call.timed("watershed_label", ws_label, dim3((unsigned)n), dim3(RTPB), ra);
+        }, done[pass]);
+        if (rc) return rc;
     }
-    c->ws_rounds = rounds[0] + rounds[1], c->ws_visits = visits[0] + visits[1];
+    c->ws_rounds = done[0].rounds + done[1].rounds, c->ws_visits = done[0].visits + done[1].visits;
     u64 st[5] = {0, 0, 0, 0, 0}, cnt[2] = {0, 0};
     call.fill(d_st, 0);
     call.timed("watershed_finish", ws_finish, dim3(pnr::grid_blocks(vblocks)), dim3(WS_TPB), c->d_img, (const unsigned *)d_key.get(),
@@ -536,8 +457,8 @@ int pnr_watershed_run(pnr_ctx *c, const char *who, const pnr_watershed_opts &o, 
         const int64_t regions = (int64_t)(std::unique(labels.begin(), labels.end()) - labels.begin());
         auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, INT32_MAX); };
         *info = pnr_watershed_info{N,      (int64_t)st[0], (int64_t)cnt[1], (int64_t)cnt[0], (int64_t)st[1], (int64_t)(st[0] - st[1]), regions,
-                                   tiles,  visits[0],      visits[1],       (int32_t)st[2],  (int32_t)st[3], t,                        o.connectivity,
-                                   i32(rounds[0]), i32(rounds[1])};
+                                   tiles,  done[0].visits, done[1].visits,  (int32_t)st[2],  (int32_t)st[3], t,                        o.connectivity,
+                                   i32(done[0].rounds), i32(done[1].rounds)};
     }
     return PNR_OK;
 }

@@ -3,7 +3,7 @@ passable (thr = 0, dmax unbounded: the cost alone steers the front through the w
 the stack's mean), with the rounds, the tile visits, the voxels reached and the bytes the relaxation moves per round against the 8 N bytes
 of the keys.
 On an MI355X:   python scripts/geodesic_timing.py [size] > profiles/rNN_geodesic_SIZE.txt   (default size 1024; the committed records
-are profiles/r12_geodesic_256.txt and profiles/r12_geodesic_512.txt, 1024 has not been run)
+are profiles/r12_geodesic_256.txt, profiles/r12_geodesic_512.txt, profiles/r19_geodesic_512_*.txt and profiles/r19_geodesic_1024_*.txt)
 
 Device time: the library's "geodesic_*" kernel timers (HIP events on the context's stream around each launch of one call), warmed up
 first.  The stack is borrowed (pnr_set_volume_device); the call never writes it; D and L stay on the device (volume=False: summary only).

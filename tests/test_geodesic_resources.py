@@ -4,7 +4,7 @@ the relaxation -- LDS latency bound, hidden only by resident waves -- leaves roo
 import pytest
 from test_kernel_resources import compile_isa
 
-KERNELS = ("geo_sources", "geo_compact", "geo_relax", "geo_stats", "geo_split", "geo_sample", "geo_paths")
+KERNELS = ("geo_sources", "geo_relax", "geo_stats", "geo_split", "geo_sample", "geo_paths")  # (the compaction is tilework.hip's: test_tilework_resources.py)
 
 
 @pytest.fixture(scope="module")

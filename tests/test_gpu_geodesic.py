@@ -301,6 +301,21 @@ def test_scheduling_options_change_no_bit(ctx):
         ctx.set_option("geo_tiles_per_launch", 0)
 
 
+@pytest.mark.parametrize("shape", [(TZ, TY, TX), (TZ + 1, TY + 1, TX + 1), (1, 21, 33)], ids=sid)
+def test_scheduling_options_change_no_bit_at_the_tile_edges(ctx, shape):
+    """the re-queue path and a launch per tile where the tile arithmetic has no room: exactly one tile (no neighbour to mark, so one round
+    may do), one voxel more than a tile on every axis, and a stack with l = 1"""
+    xyz, labels = seeds(shape, "rand90")
+    ctx.set_volume(volume(shape, "rand90"))
+    try:
+        ctx.set_option("geo_iters", 1)
+        ctx.set_option("geo_tiles_per_launch", 1)
+        same(ctx.geodesic(xyz, labels, thr=128, targets=points(shape)), want(shape, "rand90", 2.0), shape)
+    finally:
+        ctx.set_option("geo_iters", 0)
+        ctx.set_option("geo_tiles_per_launch", 0)
+
+
 def _snake(shape):
     """a one-voxel corridor in the plane z = 0 that winds back and forth along x, two rows apart"""
     l, h, w = shape

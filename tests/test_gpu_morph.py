@@ -142,6 +142,22 @@ def test_scheduling_changes_no_bit(ctx, shape):
         ctx.set_option("morph_tiles_per_launch", 0)
 
 
+@pytest.mark.parametrize("shape", [(TZ, TY, TX), (1, 21, 33)], ids=sid)
+def test_scheduling_changes_no_bit_at_one_tile_and_one_slice(ctx, shape):
+    """the re-queue path and a launch per tile where the tile arithmetic has no room: exactly one tile (no neighbour to mark, so the
+    automatic bound needs one round only and test_scheduling_changes_no_bit cannot take the shape), and a stack with l = 1"""
+    ctx.set_volume(volume(shape, "snake"))
+    try:
+        ctx.set_option("morph_iters", 1)
+        ctx.set_option("morph_tiles_per_launch", 1)
+        for op, mname, h, C_ in (("hmax", None, 100, 26), ("fill", None, 0, 6), ("dilate", "rand", 0, 4)):
+            got = ctx.morph_reconstruct(marker(shape, "snake", mname) if mname else None, op, h, C_)
+            same(got, want(shape, "snake", op, mname, h, C_), (shape, op, C_))
+    finally:
+        ctx.set_option("morph_iters", 0)
+        ctx.set_option("morph_tiles_per_launch", 0)
+
+
 def test_a_tile_is_visited_again_after_its_neighbour_changed(ctx):
     shape = (5, 67, 131)
     ctx.set_volume(volume(shape, "snake"))

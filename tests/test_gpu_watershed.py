@@ -20,10 +20,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "pnr_amd", "host", "advantra_cli")
 TZ, TY, TX = ref.tile()
 # (l, h, w) around the 32 x 8 x 8 tile: two tiles per axis; three, three and two tiles of odd extents; a 2-D stack; the smallest stack a context
-# takes, 2 x 2 x 1 (pnr_set_volume refuses 1 x 1 x 1: test_a_single_voxel_is_no_volume); a single row of tiles
-SHAPES = [(TZ + 1, TY + 1, TX + 1), (10, 17, 70), (1, 7, 31), (1, 2, 2), (TZ, TY, 2 * TX)]
+# takes, 2 x 2 x 1 (pnr_set_volume refuses 1 x 1 x 1: test_a_single_voxel_is_no_volume); a single row of tiles; exactly one tile
+SHAPES = [(TZ + 1, TY + 1, TX + 1), (10, 17, 70), (1, 7, 31), (1, 2, 2), (TZ, TY, 2 * TX), (TZ, TY, TX)]
 # the connectivities of a shape: all four on the two-tiles-per-axis and the 2-D stack
-CONNS = {SHAPES[0]: (4, 8, 6, 26), SHAPES[1]: (6, 26), SHAPES[2]: (4, 8, 6, 26), SHAPES[3]: (26,), SHAPES[4]: (4, 26)}
+CONNS = {SHAPES[0]: (4, 8, 6, 26), SHAPES[1]: (6, 26), SHAPES[2]: (4, 8, 6, 26), SHAPES[3]: (26,), SHAPES[4]: (4, 26), SHAPES[5]: (6, 26)}
 KINDS = ("plateau", "ridge", "serpentine", "adjacent", "drops", "norelief", "rand3")
 BIG = 2**31 - 1
 

@@ -4,7 +4,7 @@ scratch, and the relaxation -- LDS latency bound, hidden only by resident waves 
 import pytest
 from test_kernel_resources import compile_isa
 
-KERNELS = ("morph_init", "morph_compact", "morph_relax", "morph_finish")
+KERNELS = ("morph_init", "morph_relax", "morph_finish")  # (the compaction is tilework.hip's: test_tilework_resources.py)
 
 
 @pytest.fixture(scope="module")

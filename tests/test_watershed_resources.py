@@ -5,7 +5,7 @@ LDS per 256 threads allow seven).  The occupancy of ws_label is recorded in DESI
 import pytest
 from test_kernel_resources import compile_isa
 
-KERNELS = ("ws_init", "ws_compact", "ws_flood", "ws_label", "ws_finish")
+KERNELS = ("ws_init", "ws_flood", "ws_label", "ws_finish")  # (the compaction is tilework.hip's: test_tilework_resources.py)
 
 
 @pytest.fixture(scope="module")
